@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — frames/s of the StreamFormer encoder forward on 16x224^2 clips (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1: launched by torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     (N>1: launched by torch.distributed.run)
 
 A "step" is one forward of the hot path over one batch of 8 synthetic clips per GPU
 (BASELINE.json configs[1]: "1xMI355X bf16 forward, batch 8x16x224^2, SigLIP-base"), inputs already
@@ -9,7 +9,13 @@ resident in HBM.  Clips are independent, so N GPUs run N data-parallel replicas 
 collective ("scaling": "weak"); the only collectives here are the start/stop barriers and the
 max-over-ranks reduction of the elapsed time.  Rank 0 prints ONE JSON line.
 
-Extra objects on that line:
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the outputs of the last step
+(--dump-outputs DIR: DIR/<name>.npy, float32, at most 64 MB; inputs and weights are seeded, so two builds can be
+compared output for output), and the line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step).
+
+Extra objects on that line, measured only with --full (--profile: host_enqueue_ms_per_step, roofline and attention):
+  host_enqueue_ms_per_step  wall time to enqueue one step with the GPU running behind
+  two_steps_in_flight / single_stream   the same K steps on two HIP streams / on one (with --streams > 1)
   roofline      the dominant kernel of the forward (sf_gemm_panel_kernel, the N = 768 residual projections: ~38 % of kernel
                 time, MFMA-bound at K = 3072, HBM-bound at K = 768): algorithmic FLOPs of its three launches per layer over
                 their launch times measured with HIP events on the launch stream; the 256^2 kernel's shapes under other_gemms
@@ -25,8 +31,9 @@ Extra objects on that line:
                 and `roofline_streaming` (its dominant kernel, HIP-event timed)
   latency_b1    README.md:55-71 is one clip per call: ms per call at 1 / 2 / 4 clips (bf16) and 1 clip (fp32-accurate)
   train_step    BASELINE configs[2]: frames/s of one multitask pre-training step (forward + loss + backward +
-                AdamW) on the same clip shape, with its own CPU baseline; `--mode train` makes that step THE
-                timed step (configs[2] at N=1, configs[3] with the gradient all-reduce at N>1)
+                AdamW) on the same clip shape, with its own CPU baseline; at N > 1 configs[3], the training leg with the
+                gradient all-reduce.  `--mode train` makes that step THE timed step (configs[2] at N=1, configs[3] with the
+                gradient all-reduce at N>1; its --dump-outputs: the last step's loss and a sample of the parameters after it)
 """
 from __future__ import annotations
 
@@ -67,7 +74,38 @@ def parse():
                     help="forward = BASELINE configs[1] (the headline metric); train = configs[2]/[3]: one multitask "
                          "pre-training step (forward + loss + backward + gradient all-reduce + AdamW) per GPU batch")
     ap.add_argument("--no-train", action="store_true", help="forward mode: skip the short training-step measurement")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (roofline, attention, accuracy, accurate mode, CPU baselines, "
+                         "H2D, latency, streaming, training step); a plain run times the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "an array too large for that is written as a fixed, seeded sample DIR/<name>_sample.npy)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET_BYTES = 64_000_000      # every file of --dump-outputs together, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one float32 DIR/<name>.npy per array, smallest first.  An array larger than what is left of the budget is
+    written as DIR/<name>_sample.npy: its elements at flat positions drawn (with replacement, ascending) from a CPU generator
+    seeded 0 — the same positions in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        t = t.detach().float()
+        left -= 128                                             # .npy header
+        if t.numel() * 4 > left:
+            flat = t.reshape(-1)
+            idx = torch.randint(0, flat.numel(), (left // 4,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = flat[idx.to(flat.device)], name + "_sample"
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def usable_cores() -> int:
@@ -99,14 +137,14 @@ def usable_cores() -> int:
 def timed_steps(model, x, steps, warmup, dist, world, nstreams=1):
     """K forwards over batches of clips.  With nstreams > 1, consecutive (independent) steps are issued
     round-robin on separate HIP streams, each with its own workspace: the HBM-bound phases of one batch
-    overlap the MFMA-bound phases of the other.  Still K steps of the same batch size."""
+    overlap the MFMA-bound phases of the other.  Still K steps of the same batch size.  Returns (seconds, output of the last step)."""
     streams = [torch.cuda.Stream() for _ in range(nstreams)] if nstreams > 1 else [torch.cuda.current_stream()]
     def step(i):
         if nstreams > 1:
             with torch.cuda.stream(streams[i % nstreams]):
-                model(x)
+                return model(x)
         else:
-            model(x)
+            return model(x)
     # settle (untimed, in front of the W warm-up steps): a device that comes out of idle — or out of a rocprofv3 counter pass, which leaves
     # it in the profiling power state for a few seconds — runs its first tenths of a second at a lower clock (a 9.6 ms headline was
     # measured that way right behind the PMC passes of profiles/collect_r06.sh, with 7.96 ms seconds later in the same process)
@@ -123,14 +161,15 @@ def timed_steps(model, x, steps, warmup, dist, world, nstreams=1):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for i in range(steps):
+    for i in range(steps - 1):
         step(i)
+    last = step(steps - 1)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return max_over_ranks(dt, dist)
+    return max_over_ranks(dt, dist), last
 
 
 def power_under_load(model, x, seconds=2.5):
@@ -263,9 +302,10 @@ def dp_consistency_check(tr, task, x, ti, dist, world):
                    "of the all-gathered local gradients on a strided sample"}
 
 
-def train_bench(args, dev, dist, world, rank, steps, warmup, with_cpu):
+def train_bench(args, dev, dist, world, rank, steps, warmup, with_cpu, dump=None):
     """Time `steps` training micro-steps (update_freq = 1) of the LoRA recipe: SigLIP-base, add_lora_spatial,
-    spatial base weights frozen, tasks alternating retrieval / localization, AdamW, gradients all-reduced."""
+    spatial base weights frozen, tasks alternating retrieval / localization, AdamW, gradients all-reduced.
+    dump: directory for the last timed step's loss and the parameter buffer after it (dump_outputs)."""
     import streamformer_amd as sa
     from streamformer_amd.training import StreamformerTrainer, scaled_lr
     cfg = sa.siglip_base(add_lora_spatial=True)
@@ -300,6 +340,8 @@ def train_bench(args, dev, dist, world, rank, steps, warmup, with_cpu):
         return max_over_ranks(time.perf_counter() - t0, dist), out
 
     dt, losses = run(steps, warmup)
+    if dump and rank == 0:
+        dump_outputs(dump, {"loss": losses[-1], "params": tr.params})
     value = world * B * T * steps / dt
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -567,7 +609,8 @@ def main():
     from streamformer_amd import _native as nat
 
     if args.mode == "train":
-        r = train_bench(args, dev, dist, world, rank, args.steps, args.warmup, with_cpu=(world == 1 and not args.no_cpu_baseline))
+        r = train_bench(args, dev, dist, world, rank, args.steps, args.warmup, with_cpu=(world == 1 and args.full and not args.no_cpu_baseline),
+                        dump=args.dump_outputs)
         if rank == 0:
             out = {"metric": "frames/s (multitask pre-training step, 16x224^2 clips)", "value": r["value"], "unit": "frames/s",
                    "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -596,17 +639,12 @@ def main():
     model = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype="bf16")
     model.load_state_dict(sd)
     model.to(dev).eval()
-    dt = timed_steps(model, x, args.steps, args.warmup, dist, world, args.streams)
+    dt, last = timed_steps(model, x, args.steps, args.warmup, dist, world, args.streams)
     frames = world * B * T * args.steps
     value = frames / dt
-    # host headroom (8 ranks = 8 Python processes on one host): wall time this process needs to ENQUEUE one step (~107 launches
-    # through ctypes), measured on a drained stream with the GPU running behind
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(4):
-        model(x)
-    host_ms = 1e3 * (time.perf_counter() - t0) / 4
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"last_hidden_state": last.last_hidden_state, "pooler_output": last.pooler_output})
+    del last
 
     out = {
         "metric": "frames/s (16x224^2 clips)", "value": round(value, 1), "unit": "frames/s",
@@ -620,22 +658,37 @@ def main():
                    "collective": "none on the data path (clips are independent); start/stop barriers and the max-over-ranks "
                                  "reduction of the elapsed time only" + (f" [{args.backend}]" if dist is not None else "")},
         "e2e_mfma_frac": round(value / world * GFLOP_PER_FRAME / 1e3 / PEAK_BF16_TFLOPS, 4),
-        "host_enqueue_ms_per_step": round(host_ms, 3),
         "streams_in_flight": args.streams,
     }
     if dist is not None:
         out["ranks_seen"] = seen
+    if not (args.full or args.profile):     # the plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None and dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    # host headroom (8 ranks = 8 Python processes on one host): wall time this process needs to ENQUEUE one step (~107 launches
+    # through ctypes), measured on a drained stream with the GPU running behind
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(4):
+        model(x)
+    host_ms = 1e3 * (time.perf_counter() - t0) / 4
+    torch.cuda.synchronize()
+    out["host_enqueue_ms_per_step"] = round(host_ms, 3)
     if args.streams > 1:
-        dt1 = timed_steps(model, x, args.steps, 2, dist, world, 1)
+        dt1, _ = timed_steps(model, x, args.steps, 2, dist, world, 1)
         out["single_stream"] = {"value": round(frames / dt1, 1), "ms_per_step": round(1e3 * dt1 / args.steps, 3)}
     elif not args.profile:
         # beside the headline (one step at a time), the same K steps with TWO batches in flight on two HIP streams (own workspaces):
         # one batch's HBM-bound phases and round tails run under the other's main loops.  Reported, not `value`: a step's latency doubles.
-        dt2 = timed_steps(model, x, args.steps, 2, dist, world, 2)
+        dt2, _ = timed_steps(model, x, args.steps, 2, dist, world, 2)
         out["two_steps_in_flight"] = {"value": round(frames / dt2, 1), "ms_per_step": round(1e3 * dt2 / args.steps, 3),
                                       "note": "consecutive steps alternate over two HIP streams; throughput only"}
 
-    # BASELINE configs[3] on the driver's standard command: at N > 1 every rank also runs a short training leg (6 micro-steps of the
+    # BASELINE configs[3] with --full: at N > 1 every rank also runs a short training leg (6 micro-steps of the
     # multitask step with the bucketed RCCL gradient all-reduce + the caption all-gather) right behind the headline forward timing,
     # while all ranks are still in lock step; the forward `value` above is untouched.  north_star scopes the xGMI traffic to exactly
     # this collective, and the forward alone would show an embarrassingly parallel curve.
@@ -858,7 +911,7 @@ def main():
                          "pooler_output": float((o.pooler_output.cpu() - want["pooler_output"]).abs().max())}
         out["accuracy_max_abs_vs_cpu_oracle"] = acc
         if world == 1:
-            dt2 = timed_steps(m2, x, max(args.steps // 2, 3), 2, None, 1)
+            dt2, _ = timed_steps(m2, x, max(args.steps // 2, 3), 2, None, 1)
             out["accurate_mode"] = {"value": round(B * T * max(args.steps // 2, 3) / dt2, 1), "unit": "frames/s",
                                     "dtype": "bf16x3 (fp32-accurate)", "max_abs_last_hidden_state": acc["bf16x3"]["last_hidden_state"]}
         del m2

@@ -31,5 +31,5 @@ python $R/profiles/summarize.py $(find /tmp/prof_a -name "*.db" | head -1) > $OU
 [ -x $R/tools/bin/mfma_shape_lab ] && $R/tools/bin/mfma_shape_lab 20000 > $OUT/${TAG}_mfma_shape_lab.txt 2>&1
 rocprofv3 --kernel-trace -d /tmp/prof_t -o t -- python $R/bench.py --mode train --steps 6 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_train_run_line.json 2>/dev/null
 python $R/profiles/summarize.py $(find /tmp/prof_t -name "*.db" | head -1) > $OUT/${TAG}_train_step_kernel_stats.txt
-cd $R && python bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.txt
+cd $R && python bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.txt
 tail -c 600 $OUT/${TAG}_bench_line.json

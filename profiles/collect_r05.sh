@@ -47,5 +47,5 @@ sq() {   # $1 = name, $2 = note, rest = command
 sq "" "rocprofv3 --pmc passes (GRBM_GUI_ACTIVE | SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU | SQ_INSTS_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY) over bench.py --profile --steps 2 --warmup 1: 8-clip bf16 forward; means per dispatch" $FWD2
 sq "_train" "same three passes over bench.py --mode train --steps 2 --warmup 1: the 8-clip multitask training step; means per dispatch" $TRN2
 sq "_accurate" "same three passes over tools/accurate_fwd.py 2: the 8-clip fp32-accurate (bf16x3) forward; means per dispatch" $ACC2
-cd $R && python bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.txt
+cd $R && python bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_err.txt
 tail -c 400 $OUT/${TAG}_bench_line.json

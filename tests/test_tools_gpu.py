@@ -86,14 +86,15 @@ def test_siglip_surgery_on_the_hip_path(golden_dir, mode, tol):
     assert maxabs(out.pooler_output, g["pooler_output"]) <= tol
 
 
-def test_train_bench_two_ranks_dry_run():
+def test_train_bench_two_ranks_dry_run(tmp_path):
     """bench.py --mode train as the driver launches it at N = 2 (torch.distributed.run, one rank per GPU), here with both
     ranks on cuda:0 over gloo: the bucketed gradient all-reduce, cross-rank retrieval negatives, barriers and the
-    max-over-ranks timing all execute; rank 0 prints the one JSON line of the contract."""
+    max-over-ranks timing all execute; rank 0 prints the one JSON line of the contract and dumps the last step's loss and
+    a sample of the parameters after it (--dump-outputs)."""
     port = 29500 + os.getpid() % 400
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--mode", "train",
-           "--backend", "gloo", "--same-device", "--batch", "2"]
+           "--backend", "gloo", "--same-device", "--batch", "2", "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -102,15 +103,20 @@ def test_train_bench_two_ranks_dry_run():
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["scaling"] == "weak" and out["value"] > 0
     assert out["config"]["parallelism"] == "dp2" and out["allreduce_buckets"] >= 2
     assert all(np.isfinite(v) for pair in out["losses_per_task_first_last"].values() for v in pair)
+    assert sorted(os.listdir(tmp_path)) == ["loss.npy", "params_sample.npy"]
+    loss, params = np.load(tmp_path / "loss.npy"), np.load(tmp_path / "params_sample.npy")
+    assert loss.dtype == np.float32 and loss.size == 1 and abs(float(loss.reshape(-1)[0]) - out["losses_per_task_first_last"]["localization"][-1]) < 1e-3
+    assert params.dtype == np.float32 and params.size > 10_000_000 and np.isfinite(params).all()
 
 
 def test_forward_bench_two_ranks_dry_run():
     """bench.py (the headline forward mode) as the driver launches it at N = 2, both ranks on cuda:0 over gloo: clips sharded with
-    no data-path collective, start / stop barriers, max-over-ranks time, whole-job frames/s on the one JSON line."""
+    no data-path collective, start / stop barriers, max-over-ranks time, whole-job frames/s on the one JSON line; with --full
+    also the roofline and the training leg."""
     port = 29900 + os.getpid() % 90
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--same-device"]
+           "--backend", "gloo", "--same-device", "--full"]
     r = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -131,6 +137,32 @@ def test_forward_bench_two_ranks_dry_run():
     dp = ts["dp_check"]
     assert dp["params_identical_on_all_ranks"], {k: v for k, v in dp.items() if k != "how"}
     assert dp["ways"] == 2 and dp["reduced_equals_sum_of_local_rel_err"] <= 1e-5, {k: v for k, v in dp.items() if k != "how"}
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W`: the headline line alone, K timed steps; --dump-outputs DIR holds what the
+    last step computed (float32, within 64 MB), equal to a forward of the same seeded weights and clips in this process."""
+    import streamformer_amd as sa
+    d = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+    out = _one_line(subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=300))
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1 and out["higher_is_better"] is True
+    assert out["unit"] == "frames/s" and out["dtype"] == "bf16" and out["metric"] == "frames/s (16x224^2 clips)"
+    assert out["value"] > 0 and abs(out["value"] - 8 * 16 / (out["ms_per_step"] / 1e3)) < 0.02 * out["value"]
+    assert not {"roofline", "attention", "cpu_baseline", "accuracy_max_abs_vs_cpu_oracle", "streaming", "train_step",
+                "two_steps_in_flight"} & set(out), sorted(out)
+    assert sorted(os.listdir(d)) == ["last_hidden_state_sample.npy", "pooler_output.npy"]
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64_000_000
+    pool, lhs = np.load(d / "pooler_output.npy"), np.load(d / "last_hidden_state_sample.npy")
+    assert pool.dtype == np.float32 and pool.shape == (8, 16, 768) and lhs.dtype == np.float32 and lhs.ndim == 1
+    cfg = sa.siglip_base()
+    m = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype="bf16")
+    m.load_state_dict(make_state_dict(cfg, seed=0))
+    x = torch.randn(8, 16, 3, 224, 224, generator=torch.Generator().manual_seed(1000))
+    o = m.to("cuda").eval()(x.cuda())
+    idx = torch.randint(0, o.last_hidden_state.numel(), (lhs.size,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert maxabs(torch.from_numpy(pool), o.pooler_output) <= 1e-3
+    assert maxabs(torch.from_numpy(lhs), o.last_hidden_state.reshape(-1)[idx.cuda()]) <= 1e-3
 
 
 def _one_line(r):

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 for i in $(seq 1 ${1:-5}); do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29700 + i)) bench.py --gpus 2 --steps 2 --warmup 1 --backend gloo --same-device 2>/dev/null \
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $((29700 + i)) bench.py --gpus 2 --steps 2 --warmup 1 --backend gloo --same-device --full 2>/dev/null \
     | python -c "
 import sys, json
 for ln in sys.stdin:

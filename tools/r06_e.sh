@@ -22,4 +22,4 @@ timeout 60 tools/platform/neighbor_lab neighbour 3 16 & NP=$!
 sleep 1; timeout 60 tools/platform/neighbor_lab victim 10 163840 | grep -v "^  launch"; wait $NP
 } 2>&1 | tee $OUT/e_device_sharing.txt
 timeout 900 python -m pytest tests -q -m gpu -x -k "hidden_states or tower or nonfinite or lora_with_unfrozen or small_model_gradients" > $OUT/e_tests.log 2>&1; tail -4 $OUT/e_tests.log
-timeout 600 python bench.py > $OUT/e_bench.json 2> $OUT/e_bench.err; tail -c 1500 $OUT/e_bench.json
+timeout 600 python bench.py --full > $OUT/e_bench.json 2> $OUT/e_bench.err; tail -c 1500 $OUT/e_bench.json
