@@ -306,6 +306,10 @@ int sf_op_wgrad(const void* dy_dev, int ldy, const void* x_dev, int ldx, int M, 
  * qkv/d_qkv bf16 [rows, 3D], o/d_o bf16 [rows, D].                                               */
 int sf_op_attention_bwd(const void* qkv_dev, const void* o_dev, const void* d_o_dev, void* d_qkv_dev, int layout,
                         int nseq, int L, int seq_rows, int heads, int causal, sf_stream stream);
+/* the same at any head_dim that is a multiple of 8 up to 128 (D = heads * head_dim, scale head_dim^-0.5): 64 runs the kernels of
+ * sf_op_attention_bwd (bit-identical results), other widths the generic fp32 kernel (spatial L <= 224, temporal L <= 32)          */
+int sf_op_attention_bwd_hd(const void* qkv_dev, const void* o_dev, const void* d_o_dev, void* d_qkv_dev, int layout,
+                           int nseq, int L, int seq_rows, int heads, int head_dim, int causal, sf_stream stream);
 /* LayerNorm backward: dx = g_in + dLN(x; dy), d_gamma/d_beta accumulated                          */
 int sf_op_layernorm_bwd(const float* x_dev, const float* dy_dev, const float* gamma_dev, const float* g_in_dev,
                         float* dx_dev, float* d_gamma_dev, float* d_beta_dev, int rows, int D, float eps,

@@ -560,6 +560,7 @@ __global__ __launch_bounds__(SB_THREADS) void sf_spatial_attn_bwd_kernel(SfAttnB
 }
 
 hipError_t sf_launch_spatial_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s) {
+  if (a.head_dim && a.head_dim != 64) return sf_launch_attention_generic_bwd(a, false, s);      // sf_attention_generic_bwd.hip
   if (a.L <= 0 || a.L > SB_ROWS || a.nseq <= 0 || a.D != a.heads * 64) return hipErrorInvalidValue;
   if ((a.ld_qkv % 8) || (a.ld_o % 8)) return hipErrorInvalidValue;
   const size_t lds = 4 * SB_IMG + 2 * SB_ROWS * 4 + SB_WAVES * SB_PATCH;
@@ -661,6 +662,7 @@ __global__ __launch_bounds__(64 * WPB) void sf_temporal_attn_bwd_kernel(SfAttnBw
 }
 
 hipError_t sf_launch_temporal_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s) {
+  if (a.head_dim && a.head_dim != 64) return sf_launch_attention_generic_bwd(a, true, s);       // sf_attention_generic_bwd.hip
   if (a.L <= 0 || a.L > 32 || a.nseq <= 0 || a.seq_rows <= 0 || a.D != a.heads * 64) return hipErrorInvalidValue;
   if ((a.ld_qkv % 8) || (a.ld_o % 8)) return hipErrorInvalidValue;
   const int nprob = a.nseq * a.heads;

@@ -79,3 +79,25 @@ struct SfPoolBwdArgs {
 hipError_t sf_launch_pool_probe_bwd(const SfPoolBwdArgs& a, hipStream_t s);
 // dWk += q dU^T (null: skipped), dq = Wk dU;  du [>= heads, D] fp32
 hipError_t sf_launch_pool_u_bwd(const float* du, const float* wk, const float* q, float* dwk, float* dq, int D, hipStream_t s);
+
+// Training-step pooling head at generic widths (sf_pool_generic_bwd.hip): forward by sf_launch_pool_generic (its scratch keeps the raw
+// scores and z for the backward), U in fp32 only.
+// U_h = Wk_h^T q_h: fp32 [16, D] (rows >= heads zero)
+hipError_t sf_launch_pool_u_generic(const float* wk, const float* q, float* u, int heads, int hd, int D, hipStream_t s);
+// backward of ctx = Wv z + bv from the fp32 value rows wv [D][ldw]: dz [F, heads, D] written; dwv / dbv accumulate (+=), either may be null
+hipError_t sf_launch_pool_ctx_bwd_generic(const float* dctx, const float* wv, int ldw, const float* z, float* dz, float* dwv, float* dbv, int F,
+                                          int heads, int hd, int D, hipStream_t s);
+struct SfPoolGenBwdArgs {
+  const bf16_t* x_bf;                      // [F * N, D] bf16 normalised tokens
+  const float* scores;                     // [F, heads, N] raw scores (sf_launch_pool_generic's scratch)
+  const float* z; const float* dz;         // [F, heads, D]
+  const float* u;                          // [16, D] fp32
+  const float* d_lhs;                      // optional [F * N, D]: gradient arriving through last_hidden_state, added to dx
+  float* dx;                               // [F * N, D] fp32 (written)
+  bf16_t* ds_bf;                           // [F * N, 32] bf16 score gradients (columns >= heads zero)
+  float* stats;                            // scratch [F, heads, 4]
+  int F, N, heads, D;
+};
+hipError_t sf_launch_pool_probe_bwd_generic(const SfPoolGenBwdArgs& a, hipStream_t s);
+// dWk += q dU^T (null: skipped), dq = Wk dU with head h = row / hd
+hipError_t sf_launch_pool_u_bwd_generic(const float* du, const float* wk, const float* q, float* dwk, float* dq, int hd, int D, hipStream_t s);

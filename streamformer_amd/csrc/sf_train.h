@@ -64,9 +64,11 @@ struct SfAttnBwdArgs {
                                    // without it the backward recomputes the row statistics (phase A)
   int lab;                         // timing lab (SF_ATTN_BWD_LAB): 1 no phase B, 2 no phase C, 4 no output stores
   SfDrop drop;                     // attention-probability dropout the forward applied (on = 0: none); element index ((seq * heads + h) * L + q) * L + k
+  int head_dim;                    // 0 or 64: the tuned kernels; any other multiple of 8 up to 128: sf_attention_generic_bwd.hip (no lse2, no drop)
 };
 hipError_t sf_launch_spatial_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s);    // L <= 224
 hipError_t sf_launch_temporal_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s);   // L <= 32
+hipError_t sf_launch_attention_generic_bwd(const SfAttnBwdArgs& a, bool temporal, hipStream_t s);
 // (pooling head backward: sf_pool_head.h)
 
 // ------------------------------------------------------------------------------------------------
@@ -113,6 +115,7 @@ struct SfPrepJob {
   bf16_t* w_bf; bf16_t* wT_bf; float* bias_out;
   int N, K, rank;
   int tile0;                 // first workgroup of this job (32x32 tiles, k fastest)
+  int ldw, ldt;              // row pitches of w_bf (>= K) and wT_bf (>= N): zero-padded working copies, the padding written once at creation
 };
 hipError_t sf_launch_prep_weights_batched(const float* base, const SfPrepJob* jobs_dev, int njobs, int total_tiles,
                                           hipStream_t s);

@@ -27,6 +27,8 @@ struct TParam {
 
 struct TLin {                    // y = x W^T + b over the flat buffer
   int N = 0, K = 0;
+  int Nw = 0, Kw = 0;               // extents of the bf16 working copies and activations: N / K, or zero-padded to multiples of 64
+                                    // (intermediate_size, C*P*P); gradients and parameters keep N x K
   int pw = -1; size_t pw_off = 0;   // weight: param index + float offset inside it
   int pb = -1; size_t pb_off = 0;   // bias (pb < 0: none)
   int pla = -1, plb = -1;           // LoRA factors (spatial qkv / output.dense)
@@ -35,7 +37,7 @@ struct TLin {                    // y = x W^T + b over the flat buffer
   bf16_t* wT = nullptr;             // [K,N] for the input-gradient GEMM
   bf16_t* la_bf = nullptr;          // LoRA A [r,K] and B^T [r,N] (factor gradients through skinny GEMMs)
   bf16_t* lbT_bf = nullptr;
-  float* bias_scaled = nullptr;     // tanh(gate) * b
+  float* bias_scaled = nullptr;     // tanh(gate) * b, or the bias zero-padded to Nw
   bool need_wT = true;
 };
 
@@ -52,6 +54,9 @@ struct sf_trainer {
   sf_config cfg;
   int device;
   int D, I, L, heads, N, Kp, C, P;
+  int hd;                           // head_dim: 64 runs the tuned attention / pooling kernels, other widths the generic ones
+  int Ip, Kpp;                      // I and Kp padded to multiples of 64 (working copies and activations only)
+  float scale;                      // head_dim^-0.5
   bool lora, freeze;
   std::vector<TParam> params;
   size_t total = 0, n_train = 0;
@@ -118,7 +123,7 @@ static int add_param(sf_trainer* t, const std::string& name, std::initializer_li
 }
 
 static void lin_params(sf_trainer* t, TLin* l, const std::string& prefix, int N, int K, bool bias, bool trainable) {
-  l->N = N; l->K = K;
+  l->N = N; l->K = K; l->Nw = N; l->Kw = K;
   l->pw = add_param(t, prefix + ".weight", {N, K}, trainable);
   l->pb = bias ? add_param(t, prefix + ".bias", {N}, trainable) : -1;
 }
@@ -136,8 +141,20 @@ static void free_trainer_device(sf_trainer* t) {
 extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_spatial, int n_extra, sf_trainer** out) {
   if (!cfg || !out) return sf_set_err(SF_ERR_INVALID, "sf_trainer_create: null argument");
   const sf_config& c = *cfg;
-  if (c.hidden_size % c.num_attention_heads || c.hidden_size / c.num_attention_heads != 64)
-    return sf_set_err(SF_ERR_INVALID, "head_dim must be 64 (hidden %d, heads %d)", c.hidden_size, c.num_attention_heads);
+  // the width rules of sf_create: head_dim 64 on the tuned kernels, any other multiple of 8 up to 128 on the generic ones
+  if (c.num_attention_heads <= 0 || c.hidden_size <= 0 || c.hidden_size % c.num_attention_heads)
+    return sf_set_err(SF_ERR_INVALID, "hidden_size %d not divisible by heads %d", c.hidden_size, c.num_attention_heads);
+  if (c.num_attention_heads > 16)
+    return sf_set_err(SF_ERR_INVALID, "%d attention heads unsupported: training handles at most 16 heads", c.num_attention_heads);
+  {
+    const int hd = c.hidden_size / c.num_attention_heads;
+    if (hd < 8 || hd > 128 || hd % 8) return sf_set_err(SF_ERR_INVALID, "head_dim %d unsupported: training takes multiples of 8 from 8 to 128", hd);
+  }
+  if (c.hidden_size % 64) return sf_set_err(SF_ERR_INVALID, "hidden_size %d unsupported: training needs a multiple of 64", c.hidden_size);
+  if (c.intermediate_size <= 0 || c.intermediate_size % 4 || c.patch_size <= 0 || c.num_channels <= 0 ||
+      (c.num_channels * c.patch_size * c.patch_size) % 4)
+    return sf_set_err(SF_ERR_INVALID, "intermediate_size %d / patch vector %d: training needs positive multiples of 4", c.intermediate_size,
+                      c.num_channels * c.patch_size * c.patch_size);
   if (c.hidden_act != 0) return sf_set_err(SF_ERR_INVALID, "training supports hidden_act=gelu only");
   if (c.image_size % c.patch_size) return sf_set_err(SF_ERR_INVALID, "image_size %% patch_size != 0");
   if (n_extra < 0 || n_extra > 64) return sf_set_err(SF_ERR_INVALID, "n_extra out of range");
@@ -148,16 +165,19 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
   t->C = c.num_channels; t->P = c.patch_size;
   t->N = (c.image_size / c.patch_size) * (c.image_size / c.patch_size);
   t->Kp = t->C * t->P * t->P;
+  t->hd = t->D / t->heads;
+  t->scale = 1.0f / sqrtf((float)t->hd);          // 0.125 exactly at head_dim 64
+  t->Ip = (t->I + 63) / 64 * 64;
+  t->Kpp = (t->Kp + 63) / 64 * 64;
   t->lora = c.add_lora_spatial != 0;
   t->freeze = freeze_spatial != 0;
   const int D = t->D, I = t->I;
   if (t->N > 224) { delete t; return sf_set_err(SF_ERR_INVALID, "%d patches per frame; kernels handle <= 224", t->N); }
-  if ((D % 64) || (I % 64) || (t->Kp % 64)) { delete t; return sf_set_err(SF_ERR_INVALID, "hidden/intermediate/patch sizes must be multiples of 64"); }
 
   // ---- parameter list in model order (names = reference state_dict keys) -----------
   t->p_pos = add_param(t, "embeddings.position_embeddings", {1, t->N, D}, true);
   t->p_time = add_param(t, "embeddings.time_embeddings", {1, c.num_frames, D}, true);
-  t->patch.N = D; t->patch.K = t->Kp; t->patch.need_wT = false;
+  t->patch.N = D; t->patch.K = t->Kp; t->patch.Nw = D; t->patch.Kw = t->Kpp; t->patch.need_wT = false;
   t->patch.pw = add_param(t, "embeddings.patch_embeddings.projection.weight", {D, t->C, t->P, t->P}, true);
   t->patch.pb = add_param(t, "embeddings.patch_embeddings.projection.bias", {D}, true);
   t->layers.resize(t->L);
@@ -194,7 +214,7 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
   t->p_probe = add_param(t, "head.probe", {1, 1, D}, true);
   t->p_inw = add_param(t, "head.attention.in_proj_weight", {3 * D, D}, true);
   t->p_inb = add_param(t, "head.attention.in_proj_bias", {3 * D}, true);
-  t->head_kv.N = 2 * D; t->head_kv.K = D;
+  t->head_kv.N = 2 * D; t->head_kv.K = D; t->head_kv.Nw = 2 * D; t->head_kv.Kw = D;
   t->head_kv.pw = t->p_inw; t->head_kv.pw_off = (size_t)D * D;
   t->head_kv.pb = t->p_inb; t->head_kv.pb_off = (size_t)D;
   lin_params(t, &t->head_out, "head.attention.out_proj", D, D, true, true);
@@ -203,6 +223,11 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
   lin_params(t, &t->fc1, "head.mlp.fc1", I, D, true, true);
   lin_params(t, &t->fc2, "head.mlp.fc2", D, I, true, true);
   for (int i = 0; i < n_extra; ++i) add_param(t, "extra." + std::to_string(i), {}, true);
+  // zero-padded working extents of the MLPs (intermediate_size) and the patch projection (C*P*P): gelu(0) = 0 and zero weight
+  // rows / columns make the padding exact; it never reaches the parameter / gradient layout
+  for (TLayer& l : t->layers) { l.up.Nw = t->Ip; l.down.Kw = t->Ip; }
+  t->fc1.Nw = t->Ip; t->fc2.Kw = t->Ip;
+  const bool padded = t->Ip != I || t->Kpp != t->Kp;
 
   // ---- offsets: trainable prefix in model order, frozen tail; 64-float alignment ---------------------
   size_t off = 0;
@@ -262,11 +287,12 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
     std::vector<TLin*> lins = {&t->patch, &t->head_kv, &t->head_out, &t->fc1, &t->fc2};
     for (TLayer& l : t->layers) for (TLin* x : {&l.t_qkv, &l.t_out, &l.t_dense, &l.s_qkv, &l.s_out, &l.up, &l.down}) lins.push_back(x);
     size_t nb = 0, nf = 0;
+    auto pad_bias = [](const TLin* x) { return x->pgate < 0 && x->Nw != x->N && x->pb >= 0; };
     for (TLin* x : lins) {
-      nb += ((size_t)x->N * x->K + 127) & ~(size_t)127;
-      if (x->need_wT) nb += ((size_t)x->N * x->K + 127) & ~(size_t)127;
+      nb += ((size_t)x->Nw * x->Kw + 127) & ~(size_t)127;
+      if (x->need_wT) nb += ((size_t)x->Nw * x->Kw + 127) & ~(size_t)127;
       if (x->pla >= 0) nb += (((size_t)kRank * x->K + 127) & ~(size_t)127) + (((size_t)kRank * x->N + 127) & ~(size_t)127);
-      if (x->pgate >= 0) nf += ((size_t)x->N + 63) & ~(size_t)63;
+      if (x->pgate >= 0 || pad_bias(x)) nf += ((size_t)x->Nw + 63) & ~(size_t)63;
     }
     nf += (size_t)D + 64 + 2048 + (size_t)16 * D;          // head query + reduction scratch + the head's folded key projection
     nb += (size_t)2 * 16 * D;
@@ -276,17 +302,21 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
       free_trainer_device(t); delete t;
       return sf_set_err(SF_ERR_HIP, "hipMalloc failed (working weights, %zu bytes)", nb * 2);
     }
+    if (padded && (hipMemset(t->arena, 0, nb * sizeof(bf16_t)) != hipSuccess || hipMemset(t->farena, 0, nf * sizeof(float)) != hipSuccess)) {
+      free_trainer_device(t); delete t;
+      return sf_set_err(SF_ERR_HIP, "hipMemset failed (padded working weights)");
+    }
     bf16_t* bp = t->arena;
     float* fp = t->farena;
     for (TLin* x : lins) {
-      const size_t n = ((size_t)x->N * x->K + 127) & ~(size_t)127;
+      const size_t n = ((size_t)x->Nw * x->Kw + 127) & ~(size_t)127;
       x->w = bp; bp += n;
       if (x->need_wT) { x->wT = bp; bp += n; }
       if (x->pla >= 0) {
         x->la_bf = bp; bp += ((size_t)kRank * x->K + 127) & ~(size_t)127;
         x->lbT_bf = bp; bp += ((size_t)kRank * x->N + 127) & ~(size_t)127;
       }
-      if (x->pgate >= 0) { x->bias_scaled = fp; fp += ((size_t)x->N + 63) & ~(size_t)63; }
+      if (x->pgate >= 0 || pad_bias(x)) { x->bias_scaled = fp; fp += ((size_t)x->Nw + 63) & ~(size_t)63; }
     }
     t->head_q = fp; fp += (size_t)D + 64;
     t->head_u = fp; fp += (size_t)16 * D;
@@ -301,20 +331,22 @@ extern "C" int sf_trainer_create(const sf_config* cfg, int device, int freeze_sp
     // one-launch weight refresh: job table with offsets into the flat parameter buffer
     std::vector<SfPrepJob> jobs;
     int tiles = 0;
-    auto push = [&](long w_off, long la, long lb, int rank, long gate, long bias, bf16_t* w_bf, bf16_t* wT_bf, float* bias_out, int N, int K) {
+    auto push = [&](long w_off, long la, long lb, int rank, long gate, long bias, bf16_t* w_bf, bf16_t* wT_bf, float* bias_out, int N, int K,
+                    int ldw, int ldt) {
       SfPrepJob j;
       j.w_off = w_off; j.la_off = la; j.lb_off = lb; j.gate_off = gate; j.bias_off = bias;
       j.w_bf = w_bf; j.wT_bf = wT_bf; j.bias_out = bias_out; j.N = N; j.K = K; j.rank = rank; j.tile0 = tiles;
+      j.ldw = ldw; j.ldt = ldt;
       tiles += ((N + SF_PREP_TILE - 1) / SF_PREP_TILE) * ((K + SF_PREP_TILE - 1) / SF_PREP_TILE);
       jobs.push_back(j);
     };
     auto off = [&](int idx, size_t extra = 0) -> long { return idx < 0 ? -1 : (long)(t->params[idx].off + extra); };
     for (TLin* x : lins) {
-      push(off(x->pw, x->pw_off), off(x->pla), off(x->plb), kRank, off(x->pgate), x->pgate >= 0 ? off(x->pb, x->pb_off) : -1, x->w, x->wT,
-           x->bias_scaled, x->N, x->K);
+      push(off(x->pw, x->pw_off), off(x->pla), off(x->plb), kRank, off(x->pgate), x->bias_scaled ? off(x->pb, x->pb_off) : -1, x->w, x->wT,
+           x->bias_scaled, x->N, x->K, x->Kw, x->Nw);
       if (x->pla >= 0) {
-        push(off(x->pla), -1, -1, 0, -1, -1, x->la_bf, nullptr, nullptr, kRank, x->K);
-        push(off(x->plb), -1, -1, 0, -1, -1, nullptr, x->lbT_bf, nullptr, x->N, kRank);
+        push(off(x->pla), -1, -1, 0, -1, -1, x->la_bf, nullptr, nullptr, kRank, x->K, x->K, kRank);
+        push(off(x->plb), -1, -1, 0, -1, -1, nullptr, x->lbT_bf, nullptr, x->N, kRank, kRank, x->N);
       }
     }
     t->n_prep_jobs = (int)jobs.size(); t->prep_tiles = tiles;
@@ -399,7 +431,7 @@ static inline float* GG(const sf_trainer* t, float* grads, int idx, size_t extra
   return (idx < 0 || !t->params[idx].trainable) ? nullptr : grads + t->params[idx].off + extra;
 }
 static inline const float* lin_bias(const sf_trainer* t, const TLin& l) {
-  return l.pgate >= 0 ? l.bias_scaled : PP(t, t->params_dev, l.pb, l.pb_off);
+  return l.bias_scaled ? l.bias_scaled : PP(t, t->params_dev, l.pb, l.pb_off);
 }
 
 extern "C" int sf_trainer_sync_weights(sf_trainer* t, const float* params_dev, sf_stream stream) {
@@ -409,12 +441,15 @@ extern "C" int sf_trainer_sync_weights(sf_trainer* t, const float* params_dev, s
   t->params_dev = params_dev;
   HIP_TRY(sf_launch_prep_weights_batched(params_dev, t->prep_jobs, t->n_prep_jobs, t->prep_tiles, s));
   // nn.MultiheadAttention scales q by head_dim^-0.5 after the in-projection (modeling:1145-1149)
-  HIP_TRY(sf_launch_head_query(PP(t, params_dev, t->p_probe), PP(t, params_dev, t->p_inw), PP(t, params_dev, t->p_inb), 0.125f,
+  HIP_TRY(sf_launch_head_query(PP(t, params_dev, t->p_probe), PP(t, params_dev, t->p_inw), PP(t, params_dev, t->p_inb), t->scale,
                                t->head_q, t->D, s));
   // the temporal branch's two projections as one (used by forwards without drop_path / hidden dropout): from the fresh bf16 copies
   HIP_TRY(sf_launch_fuse_temporal(params_dev, t->fuse_jobs, t->L, t->D, s));
   // the keys of the pooling head only meet that one query: U_h = Wk_h^T q_h (sf_pool_head.hip)
-  HIP_TRY(sf_launch_pool_u(PP(t, params_dev, t->p_inw, (size_t)t->D * t->D), t->head_q, t->head_u, t->head_u_hi, t->head_u_lo, t->heads, t->D, s));
+  if (t->hd == 64)
+    HIP_TRY(sf_launch_pool_u(PP(t, params_dev, t->p_inw, (size_t)t->D * t->D), t->head_q, t->head_u, t->head_u_hi, t->head_u_lo, t->heads, t->D, s));
+  else
+    HIP_TRY(sf_launch_pool_u_generic(PP(t, params_dev, t->p_inw, (size_t)t->D * t->D), t->head_q, t->head_u, t->heads, t->hd, t->D, s));
   return SF_OK;
 }
 
@@ -437,7 +472,7 @@ struct TCarver {
 struct TSavedLayer {
   float *h1, *h2;
   bf16_t *ln_t, *tqkv, *ctx_t, *t_out, *ln_b, *sqkv, *ctx_s, *ln_a, *pre, *act;
-  float* lse_s;      // spatial attention log-sum-exp [F, heads, N]
+  float* lse_s;      // spatial attention log-sum-exp [F, heads, N] (head_dim 64; the generic backward recomputes it)
 };
 struct TWs {
   // saved by the forward
@@ -459,6 +494,7 @@ struct TWs {
   float *gh, *d_hn, *d_pc, *dq_total, *pdz, *pdu;
   bf16_t* pds;                         // pooling head: score gradients [M, 32] (the dY operand of dU = ds^T x)
   bf16_t *gh_bf, *d_hm;
+  float *pgen, *pgstat;                // generic-width pooling head: raw scores [F, heads, N] + z [F, heads, D]; backward statistics [F, heads, 4]
   size_t bytes;
 };
 
@@ -467,9 +503,9 @@ static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 static TWs tcarve(const sf_trainer* t, void* base, int B, int T) {
   TWs w;
   TCarver c(base);
-  const size_t D = t->D, I = t->I, N = t->N;
+  const size_t D = t->D, I = t->Ip, N = t->N;     // activations carry the padded intermediate width
   const size_t M = (size_t)B * T * N, F = (size_t)B * T;
-  w.patches = c.take<bf16_t>(M * t->Kp);
+  w.patches = c.take<bf16_t>(M * t->Kpp);
   w.te_rows = c.take<float>((size_t)T * D);
   w.h.resize(t->L + 1);
   w.sl.resize(t->L);
@@ -502,6 +538,7 @@ static TWs tcarve(const sf_trainer* t, void* base, int B, int T) {
   size_t wp = 0;
   const int Mi = (int)M, Fi = (int)F, Di = t->D, Ii = t->I;
   wp = max_sz(wp, sf_wgrad_partial_floats(Mi, Di, Ii)); wp = max_sz(wp, sf_wgrad_partial_floats(Mi, Ii, Di));
+  if (t->Ip != t->I) { wp = max_sz(wp, sf_wgrad_partial_floats(Mi, Di, t->Ip)); wp = max_sz(wp, sf_wgrad_partial_floats(Mi, t->Ip, Di)); }
   wp = max_sz(wp, sf_wgrad_partial_floats(Mi, 3 * Di, Di)); wp = max_sz(wp, sf_wgrad_partial_floats(Mi, Di, Di));
   wp = max_sz(wp, sf_wgrad_partial_floats(Mi, 2 * Di, Di)); wp = max_sz(wp, sf_wgrad_partial_floats(Mi, Di, t->Kp));
   wp = max_sz(wp, sf_wgrad_partial_floats(Fi, Di, Ii)); wp = max_sz(wp, sf_wgrad_partial_floats(Fi, Ii, Di));
@@ -534,6 +571,11 @@ static TWs tcarve(const sf_trainer* t, void* base, int B, int T) {
   w.dq_total = c.take<float>(D);
   w.pdz = c.take<float>(F * (size_t)t->heads * D); w.pdu = c.take<float>((size_t)32 * D); w.pds = c.take<bf16_t>(M * 32);
   w.gh_bf = c.take<bf16_t>(F * D); w.d_hm = c.take<bf16_t>(F * I);
+  w.pgen = w.pgstat = nullptr;
+  if (t->hd != 64) {
+    w.pgen = c.take<float>(sf_pool_generic_scratch_floats((int)F, (int)N, t->heads, (int)D));
+    w.pgstat = c.take<float>(F * (size_t)t->heads * 4);
+  }
   w.bytes = (c.off + 255) & ~(size_t)255;
   return w;
 }
@@ -543,7 +585,7 @@ static int check_bt(const sf_trainer* t, int B, int T) {
   if (B <= 0 || T <= 0) return sf_set_err(SF_ERR_INVALID, "bad geometry B=%d T=%d", B, T);
   if (T > t->cfg.num_frames) return sf_set_err(SF_ERR_INVALID, "training needs T <= config.num_frames (%d > %d)", T, t->cfg.num_frames);
   if (T > 32) return sf_set_err(SF_ERR_INVALID, "temporal attention backward handles T <= 32 (got %d)", T);
-  if ((size_t)B * T * t->N * (size_t)(t->I > 3 * t->D ? t->I : 3 * t->D) * 2 >= ((size_t)1 << 32))
+  if ((size_t)B * T * t->N * (size_t)(t->Ip > 3 * t->D ? t->Ip : 3 * t->D) * 2 >= ((size_t)1 << 32))
     return sf_set_err(SF_ERR_INVALID, "batch too large for 32-bit buffer offsets");
   return SF_OK;
 }
@@ -579,28 +621,28 @@ static hipError_t lin_dgrad_dgelu(const TLin& l, const bf16_t* dy, int M, hipStr
 // y = x W^T + b
 static hipError_t lin_fwd(const sf_trainer* t, const TLin& l, const bf16_t* x, int M, int epi, hipStream_t s, float* out_f32,
                           bf16_t* out_bf, const float* resid = nullptr) {
-  return tgemm(x, l.w, lin_bias(t, l), M, l.N, l.K, epi, s, out_f32, out_bf, resid);
+  return tgemm(x, l.w, lin_bias(t, l), M, l.Nw, l.Kw, epi, s, out_f32, out_bf, resid);
 }
 // dx = dy W   (dy [M,N] -> dx [M,K]); the forward-scaled weight is used as is
 static hipError_t lin_dgrad(const TLin& l, const bf16_t* dy, int M, hipStream_t s, float* out_f32, bf16_t* out_bf) {
-  return tgemm(dy, l.wT, nullptr, M, l.K, l.N, out_f32 ? SF_EPI_F32 : SF_EPI_BF16, s, out_f32, out_bf);
+  return tgemm(dy, l.wT, nullptr, M, l.Kw, l.Nw, out_f32 ? SF_EPI_F32 : SF_EPI_BF16, s, out_f32, out_bf);
 }
 
 static hipError_t lin_fwd_gelu(const sf_trainer* t, const TLin& l, const bf16_t* x, int M, hipStream_t s, bf16_t* pre, bf16_t* act) {
-  SfGemmArgs g = tgemm_args(x, l.w, lin_bias(t, l), M, l.N, l.K, SF_EPI_BF16, nullptr, pre, nullptr);
+  SfGemmArgs g = tgemm_args(x, l.w, lin_bias(t, l), M, l.Nw, l.Kw, SF_EPI_BF16, nullptr, pre, nullptr);
   g.aux_mode = 1; g.aux = act;
   if (sf_gemm256_aux_supported(g)) return sf_launch_gemm(g, false, s);
   g.aux_mode = 0; g.aux = nullptr;
   hipError_t e = sf_launch_gemm(g, false, s);
-  return e != hipSuccess ? e : sf_launch_gelu_fwd(pre, act, (size_t)M * l.N, s);
+  return e != hipSuccess ? e : sf_launch_gelu_fwd(pre, act, (size_t)M * l.Nw, s);
 }
 static hipError_t lin_dgrad_dgelu(const TLin& l, const bf16_t* dy, int M, hipStream_t s, bf16_t* d_pre, const bf16_t* pre) {
-  SfGemmArgs g = tgemm_args(dy, l.wT, nullptr, M, l.K, l.N, SF_EPI_BF16, nullptr, d_pre, nullptr);
+  SfGemmArgs g = tgemm_args(dy, l.wT, nullptr, M, l.Kw, l.Nw, SF_EPI_BF16, nullptr, d_pre, nullptr);
   g.aux_mode = 2; g.aux = const_cast<bf16_t*>(pre);
   if (sf_gemm256_aux_supported(g)) return sf_launch_gemm(g, false, s);
   g.aux_mode = 0; g.aux = nullptr;
   hipError_t e = sf_launch_gemm(g, false, s);
-  return e != hipSuccess ? e : sf_launch_gelu_bwd(d_pre, pre, (size_t)M * l.K, s);
+  return e != hipSuccess ? e : sf_launch_gelu_bwd(d_pre, pre, (size_t)M * l.Kw, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -619,7 +661,7 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
   const TWs ws = tcarve(t, workspace, B, T);
   if (workspace_bytes < ws.bytes) return sf_set_err(SF_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, ws.bytes);
   const sf_config& c = t->cfg;
-  const int D = t->D, I = t->I, N = t->N, heads = t->heads;
+  const int D = t->D, N = t->N, heads = t->heads;
   const int M = B * T * N, F = B * T;
   const float eps = c.layer_norm_eps;
   const float* P0 = t->params_dev;
@@ -630,12 +672,12 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
   for (int i = 0; i < T; ++i) idx.idx[i] = i;             // modeling:436-439 (T <= num_frames)
   HIP_TRY(sf_launch_gather_rows(PP(t, P0, t->p_time), ws.te_rows, idx, D, s));
   HIP_TRY(sf_launch_patchify(pixels, pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0), ws.patches, nullptr, F, c.num_channels, c.image_size, c.image_size,
-                             c.patch_size, s));
+                             c.patch_size, s, nullptr, nullptr, nullptr, nullptr, t->Kpp));
   {
     SfGemmArgs g;
     memset(&g, 0, sizeof(g));
     g.a_hi = ws.patches; g.w_hi = t->patch.w; g.bias = PP(t, P0, t->patch.pb);
-    g.M = M; g.N = D; g.K = t->Kp; g.epi = SF_EPI_EMBED_F32;
+    g.M = M; g.N = D; g.K = t->Kpp; g.epi = SF_EPI_EMBED_F32;
     g.pos = PP(t, P0, t->p_pos); g.time_rows = ws.te_rows; g.Np = N; g.Tn = T;
     g.out_f32 = ws.h[0]; g.ldc = D;
     if (t->drop_hidden > 0.f) {
@@ -649,11 +691,13 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
       HIP_TRY(sf_launch_gemm(g, false, s));
     }
   }
-  const float scale = 0.125f;
+  const float scale = t->scale;
+  const int hdim = t->hd;
   const bool hd = t->drop_hidden > 0.f;
   auto site = [&](int li, int k) { return sf_drop_make(t->drop_hidden, t->drop_seed, (unsigned)(li * 8 + k)); };
   const bool ad = t->drop_attn > 0.f;
   if (ad && (T > 16 || N > 224)) return sf_set_err(SF_ERR_INVALID, "attention dropout needs clips of <= 16 frames and <= 224 patches per frame");
+  if (ad && hdim != 64) return sf_set_err(SF_ERR_INVALID, "attention dropout needs head_dim 64 (got %d)", hdim);
   auto asite = [&](int li, int k) { return sf_drop_make(t->drop_attn, t->drop_seed, (unsigned)(li * 8 + k)); };
   if (t->dp_scales && (t->dp_B != B || t->dp_T != T))
     return sf_set_err(SF_ERR_INVALID, "drop_path factors were set for B=%d T=%d, the forward runs B=%d T=%d", t->dp_B, t->dp_T, B, T);
@@ -675,7 +719,7 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
       a.q = sv.tqkv; a.k = sv.tqkv + D; a.v = sv.tqkv + 2 * D;
       a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = scale;
       a.N = N; a.B = B; a.Tq = T; a.Tk = T; a.Tcap = T; a.t_past = 0; a.causal = c.enable_causal_temporal;
-      a.Tq_cap = T; a.q_t0 = 0; a.ctx_hi = sv.ctx_t; a.D = D;
+      a.Tq_cap = T; a.q_t0 = 0; a.ctx_hi = sv.ctx_t; a.D = D; a.head_dim = hdim;
       if (ad) a.drop = asite(li, 4);
       HIP_TRY(sf_launch_temporal_attention(a, false, s));
     }
@@ -697,7 +741,8 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
       memset(&a, 0, sizeof(a));
       a.q = sv.sqkv; a.k = sv.sqkv + D; a.v = sv.sqkv + 2 * D;
       a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = scale;
-      a.N = N; a.frames = F; a.ctx_hi = sv.ctx_s; a.D = D; a.lse2_out = sv.lse_s;
+      a.N = N; a.frames = F; a.ctx_hi = sv.ctx_s; a.D = D; a.head_dim = hdim;
+      if (hdim == 64) a.lse2_out = sv.lse_s;      // the generic backward recomputes the row statistics
       if (ad) a.drop = asite(li, 5);
       HIP_TRY(sf_launch_spatial_attention(a, false, s));
     }
@@ -710,7 +755,7 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
     // MLP (modeling:997-1000)
     HIP_TRY(sf_launch_layernorm(sv.h2, PP(t, P0, l.ln_a_g), PP(t, P0, l.ln_a_b), nullptr, sv.ln_a, nullptr, M, D, eps, s));
     HIP_TRY(lin_fwd_gelu(t, l.up, sv.ln_a, M, s, sv.pre, sv.act));
-    if (hd) HIP_TRY(sf_launch_rowscale_bf16(sv.act, sv.act, nullptr, M, I, 0, T, N, s, site(li, 2)));      // dropout behind the activation (modeling:822): the saved act IS the dropped tensor
+    if (hd) HIP_TRY(sf_launch_rowscale_bf16(sv.act, sv.act, nullptr, M, t->Ip, 0, T, N, s, site(li, 2)));      // dropout behind the activation (modeling:822): the saved act IS the dropped tensor
     if (dp || hd) {     // out = h2 + drop_path(dropout(mlp)) (modeling:835, 1000)
       HIP_TRY(lin_fwd(t, l.down, sv.act, M, SF_EPI_F32, s, ws.g, nullptr));
       HIP_TRY(sf_launch_resid_rowscale(ws.h[li + 1], sv.h2, ws.g, dp ? dp + (size_t)li * dp_per_layer + (size_t)B * N + (size_t)B * T : nullptr, M, D, 2, T, N, s,
@@ -725,7 +770,14 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
   // backward itself works from the bf16 copy ws.xn, so the caller may do with its tensor what it likes.
   float* xf = last_hidden ? last_hidden : ws.g;
   HIP_TRY(sf_launch_layernorm(ws.h[t->L], PP(t, P0, t->post_g), PP(t, P0, t->post_b), xf, ws.xn, nullptr, M, D, eps, s));
-  {
+  if (hdim != 64) {
+    // generic widths: raw scores and z stay in ws.pgen for the backward (sf_pool_generic_bwd.hip)
+    SfPoolGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.x = xf; ga.u = t->head_u; ga.wv = PP(t, P0, t->p_inw, (size_t)2 * D * D); ga.ldw = D; ga.bv = PP(t, P0, t->p_inb, (size_t)2 * D);
+    ga.ctx_hi = ws.pc; ga.scratch = ws.pgen; ga.F = F; ga.N = N; ga.heads = heads; ga.hd = hdim; ga.D = D;
+    HIP_TRY(sf_launch_pool_generic(ga, s));
+  } else {
     SfPoolArgs pa;
     memset(&pa, 0, sizeof(pa));
     // token splits as in inference (a frame's tokens over S workgroups): the raw scores and {max, sum} per split are kept, the backward
@@ -744,7 +796,7 @@ extern "C" int sf_trainer_forward(sf_trainer* t, const void* pixels, int pixel_d
   HIP_TRY(lin_fwd(t, t->head_out, ws.pc, F, SF_EPI_F32, s, ws.attn_out, nullptr));
   HIP_TRY(sf_launch_layernorm(ws.attn_out, PP(t, P0, t->hln_g), PP(t, P0, t->hln_b), nullptr, ws.hn, nullptr, F, D, eps, s));
   HIP_TRY(lin_fwd(t, t->fc1, ws.hn, F, SF_EPI_BF16, s, nullptr, ws.hm_pre));
-  HIP_TRY(sf_launch_gelu_fwd(ws.hm_pre, ws.hm, (size_t)F * I, s));
+  HIP_TRY(sf_launch_gelu_fwd(ws.hm_pre, ws.hm, (size_t)F * t->Ip, s));
   HIP_TRY(lin_fwd(t, t->fc2, ws.hm, F, SF_EPI_RESID_F32, s, pooler, nullptr, ws.attn_out));
   t->fB = B; t->fT = T; t->f_dp = dp; t->f_tfuse = tfuse;
   t->f_drop_hidden = t->drop_hidden; t->f_drop_attn = t->drop_attn; t->f_drop_seed = t->drop_seed;
@@ -773,7 +825,7 @@ static hipError_t lin_wgrad(const BwdCtx& c, const TLin& l, const bf16_t* dy, co
   float* gb = GG(t, c.grads, l.pb, l.pb_off);
   SfWgradArgs a;
   memset(&a, 0, sizeof(a));
-  a.dy = dy; a.ldy = l.N; a.x = x; a.ldx = l.K; a.M = M; a.N1 = l.N; a.N2 = l.K; a.ldo = l.K; a.alpha = 1.f;
+  a.dy = dy; a.ldy = l.Nw; a.x = x; a.ldx = l.Kw; a.M = M; a.N1 = l.N; a.N2 = l.K; a.ldo = l.K; a.alpha = 1.f;
   a.partial = c.wg_partial();
   hipError_t e = hipSuccess;
   if (l.pla >= 0) {
@@ -794,7 +846,7 @@ static hipError_t lin_wgrad(const BwdCtx& c, const TLin& l, const bf16_t* dy, co
     a.dbias = gb; a.dbias_scratch = c.cs_partial();      // bias gradient rides on the same launch
     e = sf_launch_wgrad(a, c.s);
   } else if (gb) {
-    e = sf_launch_colsum_bf16(dy, M, l.N, l.N, 1.f, gb, 1, c.cs_partial(), c.s);
+    e = sf_launch_colsum_bf16(dy, M, l.N, l.Nw, 1.f, gb, 1, c.cs_partial(), c.s);
   }
   return e;
 }
@@ -803,7 +855,7 @@ static int backward_head(const BwdCtx& c, const float* d_pooler, const float* d_
   const sf_trainer* t = c.t;
   const TWs& ws = *c.ws;
   hipStream_t s = c.s;
-  const int D = t->D, I = t->I, N = t->N;
+  const int D = t->D, N = t->N;
   const int M = B * T * N, F = B * T;
   const float eps = t->cfg.layer_norm_eps;
   const float* P0 = t->params_dev;
@@ -811,7 +863,7 @@ static int backward_head(const BwdCtx& c, const float* d_pooler, const float* d_
   HIP_TRY(sf_launch_split(d_pooler, ws.gh_bf, nullptr, (size_t)F * D, s));
   HIP_TRY(lin_dgrad(t->fc2, ws.gh_bf, F, s, nullptr, ws.d_hm));
   HIP_TRY(lin_wgrad(c, t->fc2, ws.gh_bf, ws.hm, F));
-  HIP_TRY(sf_launch_gelu_bwd(ws.d_hm, ws.hm_pre, (size_t)F * I, s));
+  HIP_TRY(sf_launch_gelu_bwd(ws.d_hm, ws.hm_pre, (size_t)F * t->Ip, s));
   HIP_TRY(lin_dgrad(t->fc1, ws.d_hm, F, s, ws.d_hn, nullptr));
   HIP_TRY(lin_wgrad(c, t->fc1, ws.d_hm, ws.hn, F));
   HIP_TRY(sf_launch_ln_bwd(ws.attn_out, ws.d_hn, 0, PP(t, P0, t->hln_g), d_pooler, ws.gh, ws.gh_bf, GG(t, c.grads, t->hln_g), GG(t, c.grads, t->hln_b),
@@ -821,6 +873,17 @@ static int backward_head(const BwdCtx& c, const float* d_pooler, const float* d_
   HIP_TRY(lin_wgrad(c, t->head_out, ws.gh_bf, ws.pc, F));
   // probe attention over the N tokens of every frame
   // ctx_h = Wv_h z_h + bv_h: dz, dWv, dbv (the value rows are in_proj rows [2D, 3D))
+  const bool gen = t->hd != 64;
+  const float* pz = gen ? ws.pgen + (size_t)F * t->heads * N : ws.pz;
+  if (gen) {
+    HIP_TRY(sf_launch_pool_ctx_bwd_generic(ws.d_pc, PP(t, P0, t->p_inw, (size_t)2 * D * D), D, pz, ws.pdz, GG(t, c.grads, t->p_inw, (size_t)2 * D * D),
+                                           GG(t, c.grads, t->p_inb, (size_t)2 * D), F, t->heads, t->hd, D, s));
+    SfPoolGenBwdArgs pb;
+    memset(&pb, 0, sizeof(pb));
+    pb.x_bf = ws.xn; pb.scores = ws.pgen; pb.z = pz; pb.dz = ws.pdz; pb.u = t->head_u; pb.d_lhs = d_lhs; pb.dx = ws.d_ln; pb.ds_bf = ws.pds;
+    pb.stats = ws.pgstat; pb.F = F; pb.N = N; pb.heads = t->heads; pb.D = D;
+    HIP_TRY(sf_launch_pool_probe_bwd_generic(pb, s));
+  } else {
   HIP_TRY(sf_launch_pool_ctx_bwd(ws.d_pc, t->head_kv.wT, 2 * D, D, ws.pz, ws.pdz, GG(t, c.grads, t->p_inw, (size_t)2 * D * D), D,
                                  GG(t, c.grads, t->p_inb, (size_t)2 * D), F, t->heads, D, s));
   // p = softmax(x . U), z = p x: dx (+ the gradient that arrives through last_hidden_state) and the score gradients ds
@@ -831,6 +894,7 @@ static int backward_head(const BwdCtx& c, const float* d_pooler, const float* d_
     pb.F = F; pb.N = N; pb.heads = t->heads; pb.D = D;
     HIP_TRY(sf_launch_pool_probe_bwd(pb, s));
   }
+  }
   {   // dU = ds^T x over all token rows ([32, D], rows >= heads zero), then U_h = Wk_h^T q_h: dWk_h += q_h dU_h^T, dq_h = Wk_h dU_h.
       // The key bias gets no gradient: its term q_h . bk_h is constant over the keys and cancels in the softmax.
     SfWgradArgs a;
@@ -838,9 +902,13 @@ static int backward_head(const BwdCtx& c, const float* d_pooler, const float* d_
     a.dy = ws.pds; a.ldy = 32; a.x = ws.xn; a.ldx = D; a.M = M; a.N1 = 32; a.N2 = D; a.out = ws.pdu; a.ldo = D; a.alpha = 1.f;
     a.partial = ws.wg_partial;
     HIP_TRY(sf_launch_wgrad(a, s));
-    HIP_TRY(sf_launch_pool_u_bwd(ws.pdu, PP(t, P0, t->p_inw, (size_t)D * D), t->head_q, GG(t, c.grads, t->p_inw, (size_t)D * D), ws.dq_total, D, s));
+    if (gen)
+      HIP_TRY(sf_launch_pool_u_bwd_generic(ws.pdu, PP(t, P0, t->p_inw, (size_t)D * D), t->head_q, GG(t, c.grads, t->p_inw, (size_t)D * D), ws.dq_total,
+                                           t->hd, D, s));
+    else
+      HIP_TRY(sf_launch_pool_u_bwd(ws.pdu, PP(t, P0, t->p_inw, (size_t)D * D), t->head_q, GG(t, c.grads, t->p_inw, (size_t)D * D), ws.dq_total, D, s));
   }
-  HIP_TRY(sf_launch_head_query_bwd(ws.dq_total, PP(t, P0, t->p_probe), PP(t, P0, t->p_inw), 0.125f, GG(t, c.grads, t->p_inw),
+  HIP_TRY(sf_launch_head_query_bwd(ws.dq_total, PP(t, P0, t->p_probe), PP(t, P0, t->p_inw), t->scale, GG(t, c.grads, t->p_inw),
                                    GG(t, c.grads, t->p_inb), GG(t, c.grads, t->p_probe), D, s));
   // post_layernorm: g = dLN(h_L)
   HIP_TRY(sf_launch_ln_bwd(ws.h[t->L], ws.d_ln, 0, PP(t, P0, t->post_g), nullptr, ws.g, ws.g_bf, GG(t, c.grads, t->post_g), GG(t, c.grads, t->post_b),
@@ -859,7 +927,7 @@ static hipError_t lin_wgrad_queued(const BwdCtx& c, LayerWgrads& q, const TLin& 
   if (!q.on || l.pla >= 0 || !gw || !sf_wgrad_groupable(M, l.N, l.K) || q.g.njobs >= SF_WG_MAX_JOBS) return lin_wgrad(c, l, dy, x, M);
   SfWgradJob& J = q.g.job[q.g.njobs++];
   memset(&J, 0, sizeof(J));
-  J.dy = dy; J.x = x; J.ldy = l.N; J.ldx = l.K; J.N1 = l.N; J.N2 = l.K; J.ldo = l.K; J.alpha = 1.f; J.accumulate = 1;
+  J.dy = dy; J.x = x; J.ldy = l.Nw; J.ldx = l.Kw; J.N1 = l.N; J.N2 = l.K; J.ldo = l.K; J.alpha = 1.f; J.accumulate = 1;
   J.out = gw; J.dbias = GG(c.t, c.grads, l.pb, l.pb_off);
   return hipSuccess;
 }
@@ -944,7 +1012,6 @@ static int backward_layer(const BwdCtx& c, int li, int B, int T) {
   memset(&q.g, 0, sizeof(q.g));
   q.g.M = M; q.g.partial = ws.wg_partial;
   const bool hd = t->f_drop_hidden > 0.f;
-  const int I = t->I;
   auto site = [&](int k) { return sf_drop_make(t->f_drop_hidden, t->f_drop_seed, (unsigned)(li * 8 + k)); };
   q.on = !dp && !hd && !ungrouped;  // the drop_path / dropout copies reuse d_ctx / d_tout inside the layer: immediate launches there
   const bool side_ok = q.on;        // same condition: the side stream's operands must stay untouched until the end of the layer
@@ -956,7 +1023,7 @@ static int backward_layer(const BwdCtx& c, int li, int B, int T) {
   const bf16_t* gy = ws.g_bf;
   if (dp || hd) { HIP_TRY(sf_launch_rowscale_bf16(ws.g_bf, ws.d_ctx, dp ? dp + (size_t)B * N + (size_t)B * T : nullptr, M, D, 2, T, N, s, site(3))); gy = ws.d_ctx; }
   HIP_TRY(lin_dgrad_dgelu(l.down, gy, M, s, ws.d_wide, sv.pre));            // d pre = (g W_down) * gelu'(pre)  [M,I]
-  if (hd) HIP_TRY(sf_launch_rowscale_bf16(ws.d_wide, ws.d_wide, nullptr, M, I, 0, T, N, s, site(2)));      // ... through the activation's dropout mask (elementwise factors commute)
+  if (hd) HIP_TRY(sf_launch_rowscale_bf16(ws.d_wide, ws.d_wide, nullptr, M, t->Ip, 0, T, N, s, site(2)));      // ... through the activation's dropout mask (elementwise factors commute)
   HIP_TRY(lin_wgrad_queued(c, q, l.down, gy, sv.act, M));
   HIP_TRY(lin_dgrad(l.up, ws.d_wide, M, s, nullptr, ws.d_ln_bf));
   HIP_TRY(lin_wgrad_queued(c, q, l.up, ws.d_wide, sv.ln_a, M));
@@ -972,8 +1039,8 @@ static int backward_layer(const BwdCtx& c, int li, int B, int T) {
     SfAttnBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.qkv = sv.sqkv; a.ld_qkv = 3 * D; a.o = sv.ctx_s; a.ld_o = D; a.d_o = ws.d_ctx; a.d_qkv = ws.d_wide_s;
-    a.heads = t->heads; a.D = D; a.scale = 0.125f; a.L = N; a.nseq = F; a.seq_rows = 1; a.causal = 0;
-    a.lse2 = sv.lse_s;
+    a.heads = t->heads; a.D = D; a.scale = t->scale; a.L = N; a.nseq = F; a.seq_rows = 1; a.causal = 0; a.head_dim = t->hd;
+    if (t->hd == 64) a.lse2 = sv.lse_s;
     if (t->f_drop_attn > 0.f) a.drop = sf_drop_make(t->f_drop_attn, t->f_drop_seed, (unsigned)(li * 8 + 5));
     HIP_TRY(sf_launch_spatial_attention_bwd(a, s));
   }
@@ -1039,7 +1106,7 @@ static int backward_layer(const BwdCtx& c, int li, int B, int T) {
     SfAttnBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.qkv = sv.tqkv; a.ld_qkv = 3 * D; a.o = sv.ctx_t; a.ld_o = D; a.d_o = ws.d_ctx; a.d_qkv = ws.d_wide_t;
-    a.heads = t->heads; a.D = D; a.scale = 0.125f; a.L = T; a.nseq = B * N; a.seq_rows = N;
+    a.heads = t->heads; a.D = D; a.scale = t->scale; a.L = T; a.nseq = B * N; a.seq_rows = N; a.head_dim = t->hd;
     a.causal = t->cfg.enable_causal_temporal;
     if (t->f_drop_attn > 0.f) a.drop = sf_drop_make(t->f_drop_attn, t->f_drop_seed, (unsigned)(li * 8 + 4));
     HIP_TRY(sf_launch_temporal_attention_bwd(a, s));
@@ -1244,6 +1311,21 @@ extern "C" int sf_op_attention_bwd(const void* qkv, const void* o, const void* d
   a.qkv = (const bf16_t*)qkv; a.ld_qkv = 3 * D; a.o = (const bf16_t*)o; a.ld_o = D; a.d_o = (const bf16_t*)d_o;
   a.d_qkv = (bf16_t*)d_qkv; a.heads = heads; a.D = D; a.scale = 0.125f; a.L = L; a.nseq = nseq; a.seq_rows = seq_rows;
   a.causal = causal;
+  HIP_TRY(layout == 0 ? sf_launch_spatial_attention_bwd(a, (hipStream_t)stream) : sf_launch_temporal_attention_bwd(a, (hipStream_t)stream));
+  return SF_OK;
+}
+
+extern "C" int sf_op_attention_bwd_hd(const void* qkv, const void* o, const void* d_o, void* d_qkv, int layout, int nseq, int L,
+                                      int seq_rows, int heads, int head_dim, int causal, sf_stream stream) {
+  if (!qkv || !o || !d_o || !d_qkv) return sf_set_err(SF_ERR_INVALID, "null argument");
+  if (heads <= 0 || head_dim < 8 || head_dim > 128 || head_dim % 8)
+    return sf_set_err(SF_ERR_INVALID, "sf_op_attention_bwd_hd: head_dim %d (multiples of 8 up to 128), heads %d", head_dim, heads);
+  SfAttnBwdArgs a;
+  memset(&a, 0, sizeof(a));
+  const int D = heads * head_dim;
+  a.qkv = (const bf16_t*)qkv; a.ld_qkv = 3 * D; a.o = (const bf16_t*)o; a.ld_o = D; a.d_o = (const bf16_t*)d_o;
+  a.d_qkv = (bf16_t*)d_qkv; a.heads = heads; a.D = D; a.scale = 1.0f / sqrtf((float)head_dim); a.L = L; a.nseq = nseq; a.seq_rows = seq_rows;
+  a.causal = causal; a.head_dim = head_dim;
   HIP_TRY(layout == 0 ? sf_launch_spatial_attention_bwd(a, (hipStream_t)stream) : sf_launch_temporal_attention_bwd(a, (hipStream_t)stream));
   return SF_OK;
 }

@@ -446,7 +446,7 @@ hipError_t sf_launch_sum_rows(const float* in, float* out, int n_out, int n_a, l
 #define PREP_T SF_PREP_TILE
 SF_DEVICE void prep_tile(const float* __restrict__ w, const float* __restrict__ la, const float* __restrict__ lb, int rank,
                          const float* gate, bf16_t* w_bf, bf16_t* wT_bf, const float* bias, float* bias_out, int N, int K,
-                         int kt, int nt, float (*tile)[PREP_T + 1]) {
+                         int ldw, int ldt, int kt, int nt, float (*tile)[PREP_T + 1]) {
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;       // 16 x 16 threads, 4 consecutive k (or n) each
   const int k0 = kt * PREP_T, n0 = nt * PREP_T;
   const float scale = gate ? tanhf(*gate) : 1.0f;
@@ -492,10 +492,10 @@ SF_DEVICE void prep_tile(const float* __restrict__ w, const float* __restrict__ 
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] *= scale;
       if (w_bf) {
-        if (kvec) *reinterpret_cast<u32x2_t*>(w_bf + (size_t)n * K + k) = (u32x2_t){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
+        if (kvec && (ldw % 4) == 0) *reinterpret_cast<u32x2_t*>(w_bf + (size_t)n * ldw + k) = (u32x2_t){pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
         else {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) if (k + j < K) w_bf[(size_t)n * K + k + j] = (bf16_t)f2bf(v[j]);
+          for (int j = 0; j < 4; ++j) if (k + j < K) w_bf[(size_t)n * ldw + k + j] = (bf16_t)f2bf(v[j]);
         }
       }
     }
@@ -504,18 +504,18 @@ SF_DEVICE void prep_tile(const float* __restrict__ w, const float* __restrict__ 
   }
   __syncthreads();
   if (wT_bf) {
-    const bool nvec = (N % 4) == 0;
+    const bool nvec = (N % 4) == 0 && (ldt % 4) == 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int k = k0 + ty + 16 * i, n = n0 + tx * 4;
       if (k < K && n < N) {
         const float a0 = tile[tx * 4 + 0][ty + 16 * i], a1 = tile[tx * 4 + 1][ty + 16 * i];
         const float a2 = tile[tx * 4 + 2][ty + 16 * i], a3 = tile[tx * 4 + 3][ty + 16 * i];
-        if (nvec) *reinterpret_cast<u32x2_t*>(wT_bf + (size_t)k * N + n) = (u32x2_t){pack_bf2(a0, a1), pack_bf2(a2, a3)};
+        if (nvec) *reinterpret_cast<u32x2_t*>(wT_bf + (size_t)k * ldt + n) = (u32x2_t){pack_bf2(a0, a1), pack_bf2(a2, a3)};
         else {
           const float a[4] = {a0, a1, a2, a3};
 #pragma unroll
-          for (int j = 0; j < 4; ++j) if (n + j < N) wT_bf[(size_t)k * N + n + j] = (bf16_t)f2bf(a[j]);
+          for (int j = 0; j < 4; ++j) if (n + j < N) wT_bf[(size_t)k * ldt + n + j] = (bf16_t)f2bf(a[j]);
         }
       }
     }
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void sf_prep_weights_batched_kernel(const floa
   const int tiles_k = (j.K + PREP_T - 1) / PREP_T;
   prep_tile(base + j.w_off, j.la_off >= 0 ? base + j.la_off : nullptr, j.lb_off >= 0 ? base + j.lb_off : nullptr, j.rank,
             j.gate_off >= 0 ? base + j.gate_off : nullptr, j.w_bf, j.wT_bf, j.bias_off >= 0 ? base + j.bias_off : nullptr,
-            j.bias_out, j.N, j.K, t % tiles_k, t / tiles_k, tile);
+            j.bias_out, j.N, j.K, j.ldw, j.ldt, t % tiles_k, t / tiles_k, tile);
 }
 hipError_t sf_launch_prep_weights_batched(const float* base, const SfPrepJob* jobs_dev, int njobs, int total_tiles,
                                           hipStream_t s) {

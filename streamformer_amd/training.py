@@ -121,6 +121,10 @@ class StreamformerTrainer:
             if n_patches > 224 or config.num_frames > 16:
                 raise NotImplementedError(f"attention_probs_dropout_prob > 0 needs <= 224 patches per frame and <= 16 frames "
                                           f"(this config: {n_patches} patches, {config.num_frames} frames)")
+            head_dim = config.hidden_size // config.num_attention_heads
+            if head_dim != 64:
+                # the generic-width attention kernels (head_dim != 64) apply no probability dropout
+                raise NotImplementedError(f"attention_probs_dropout_prob > 0 needs head_dim 64 (this config: {head_dim})")
         self.dropout = True                         # False: forwards without dropout (evaluation through the trainer)
         self.last_dropout: Optional[Tuple[int, float, float]] = None    # (seed, hidden_p, attention_p) of the last forward, for replay in tests
         self.drop_path_rate = float(getattr(config, "drop_path_rate", 0.0) or 0.0)
