@@ -30,6 +30,13 @@ ACC_CEIL = 5e-4
 # projects the tokens to k / v at all (sf_pool_head.hip: scores and weighted sums on the fp32 tokens, bf16x3 / fp32 arithmetic in both
 # modes), so what is left is exactly what the encoder's tokens carry: back to SURVEY's 2e-2 for every fixture.
 BF16_LHS, BF16_POOL = 4e-2, 2e-2
+# Accurate mode, per forward schedule (sf_encoder.hip: ln_fold_acc_ok, ln_fold_small_ok and the predicates next to them decide which one
+# a call takes).  Each bound is about twice the largest max-abs against the oracle measured on an MI355X, written next to its test:
+#   xm      residual stream as hi + lo + lo2 bf16 planes, LayerNorm fold on the bf16x3 256^2 kernel: SigLIP-base from three clips
+#           (M > 6272), D = 1024 from 2048 rows.  Without the third plane (SF_ACC_TWO_PLANES) it measures 1.36e-4.
+#   fp32    fp32 residual stream + standalone LayerNorms: one or two SigLIP-base clips, hidden_states, N > 224, D % 256 != 0.
+#   sfold   small M (streamed frames, a few frames per call): LayerNorm statistics of hi + lo inside the consumer GEMMs.
+ACC_XM = 1e-4
 
 
 @pytest.fixture(scope="module")
@@ -308,13 +315,13 @@ def test_forward_small_vs_golden(sa, golden_dir, mode, fuse):
         x = frames(100 + T, (2, T, 3, 48, 48))
         out = m(x.cuda(), output_hidden_states=True)
         torch.cuda.synchronize()
-        lt, pt = (ACC_CEIL, ACC_CEIL) if mode == "fp32" else (BF16_LHS, BF16_POOL)
+        lt, pt = (2e-4, 2e-4) if mode == "fp32" else (BF16_LHS, BF16_POOL)      # fp32 + hidden_states: measured 7.3e-5
         assert out.last_hidden_state.shape == (2, T, 9, 128) and out.pooler_output.shape == (2, T, 128)
         assert maxabs(out.last_hidden_state, g[f"T{T}_last_hidden_state"]) <= lt
         assert maxabs(out.pooler_output, g[f"T{T}_pooler_output"]) <= pt
         hs = torch.stack([h.cpu() for h in out.hidden_states])            # patch-major like the reference
         assert hs.shape == (3, 2, 9 * T, 128)
-        assert maxabs(hs, g[f"T{T}_hidden_states"]) <= (ACC_CEIL if mode == "fp32" else 6e-2)      # pre-LayerNorm residual rows up to |7.4|: measured 3.9e-2 (tools/hs_err.py)
+        assert maxabs(hs, g[f"T{T}_hidden_states"]) <= (2e-4 if mode == "fp32" else 6e-2)      # pre-LayerNorm residual rows up to |7.4|: measured 3.9e-2 (tools/hs_err.py)
         tup = m(x.cuda(), return_dict=False)
         assert isinstance(tup, tuple) and torch.equal(tup[0], out.last_hidden_state)
 
@@ -389,7 +396,7 @@ def test_streaming_f4(sa, golden_dir, mode, tag, nf):
     m = build(sa, cfg, make_state_dict(cfg, seed=4), mode)
     x = frames(500 + nf, (1, nf, 3, 48, 48)).cuda()
     want = g[f"{tag}_last_hidden_state"]
-    lt = ACC_CEIL if mode == "fp32" else BF16_LHS
+    lt = 2e-4 if mode == "fp32" else BF16_LHS          # accurate: T = 64 full clip (fp32 stream) and sfold chunks, measured 5.8e-5
     full = m(x).last_hidden_state
     assert maxabs(full, want) <= lt
     for chunks in ([nf], [nf // 2, nf // 2], [1] * nf, [3, 1, nf - 4]):
@@ -423,6 +430,8 @@ class _TowerCfg:
 def test_vision_tower_streams_against_the_oracle(sa, tmp_path, mode, tol):
     """TimesformerVisionTower (vqa_enc:1462-1598) built the reference's way — checkpoint directory + config object — fed one
     frame per call; every returned window is compared with the ORACLE's full-clip forward (causal => identical)."""
+    if mode == "fp32":
+        tol = 2e-4          # accurate: measured 6.5e-5
     cfg = small_cfg(num_frames=16)
     sd = make_state_dict(cfg, seed=1)
     build(sa, cfg, sd, mode).save_pretrained(str(tmp_path))
@@ -669,8 +678,8 @@ def test_base_full_tensor_vs_oracle(sa, base_models, mode):
     out = base_models[mode](x.cuda())
     d_lhs, d_pool = maxabs(out.last_hidden_state, want["last_hidden_state"]), maxabs(out.pooler_output, want["pooler_output"])
     print(f"[{mode}] full-tensor max-abs lhs {d_lhs:.3e} pooler {d_pool:.3e} cosine {cosine(out.last_hidden_state, want['last_hidden_state']):.6f}")
-    if mode == "fp32":
-        assert d_lhs <= ACC_TOL and d_pool <= ACC_TOL
+    if mode == "fp32":          # one clip: fp32 residual stream + LayerNorm launches, measured 4.8e-5 / 4.3e-5
+        assert d_lhs <= 1e-4 and d_pool <= 1e-4
     else:
         assert d_lhs <= BF16_LHS and d_pool <= BF16_POOL
         assert cosine(out.last_hidden_state, want["last_hidden_state"]) >= 0.9995
@@ -691,7 +700,7 @@ def test_baseline_batch8_properties(sa, base_models, mode):
     out = m(x)
     assert out.last_hidden_state.shape == (8, 16, 196, 768) and out.pooler_output.shape == (8, 16, 768)
     assert torch.isfinite(out.last_hidden_state).all() and torch.isfinite(out.pooler_output).all()
-    lt, pt = (ACC_TOL, ACC_TOL) if mode == "fp32" else (BF16_LHS, BF16_POOL)
+    lt, pt = (ACC_XM, ACC_XM) if mode == "fp32" else (BF16_LHS, BF16_POOL)      # xm: measured 4.8e-5 / 4.5e-5
     for i in (0, 5):
         want = O.forward(sd, cfg, xc[i:i + 1])
         d1 = maxabs(out.last_hidden_state[i], want["last_hidden_state"][0])
@@ -788,6 +797,8 @@ def test_uint8_frames_fused_normalisation(golden_dir):
 def test_forward_more_than_224_patches(mode, tol):
     """384 x 384 frames = 576 patches per frame: spatial attention streams the keys (online softmax);
     full clip and streamed frame by frame, against the oracle."""
+    if mode == "fp32":
+        tol = 8e-5          # accurate (fp32 stream, N > 224): measured 3.7e-5
     import streamformer_amd as sa
     cfg = small_cfg(image_size=384, num_frames=4)
     sd = make_state_dict(cfg, seed=21)
@@ -925,6 +936,8 @@ def test_streaming_config5_full_size_vs_oracle(mode, tol_l, tol_p):
     identical in exact arithmetic; vqa_enc:491-560, 1316-1392).  The streamed path runs the small-M kernels (register-direct
     GEMM with the LayerNorm fold, the cache-append epilogue, temporal attention over the growing cache) inside hipGraph
     replays; a second pass over the same stream after cache.reset() must reproduce the first bit for bit."""
+    if mode == "fp32":
+        tol_l, tol_p = 1e-4, 7e-5          # accurate (streaming): measured 4.8e-5 / 3.4e-5
     import streamformer_amd as sa
     cfg = siglip_base(num_frames=64)
     sd = make_state_dict(cfg, seed=0)
@@ -942,6 +955,7 @@ def test_streaming_config5_full_size_vs_oracle(mode, tol_l, tol_p):
         passes.append((torch.cat([o.last_hidden_state for o in outs], 1), torch.cat([o.pooler_output for o in outs], 1)))
     lhs, pool = passes[0]
     per_frame = (lhs.cpu() - want["last_hidden_state"]).abs().amax(dim=(0, 2, 3))
+    print(f"[{mode}] 64 streamed frames: max-abs lhs {float(per_frame.max()):.3e} pooler {maxabs(pool, want['pooler_output']):.3e}")
     assert float(per_frame.max()) <= tol_l, per_frame.tolist()
     assert maxabs(pool, want["pooler_output"]) <= tol_p
     assert cosine(lhs, want["last_hidden_state"]) >= (0.9995 if mode == "bf16" else 0.999999)
@@ -956,6 +970,8 @@ def test_several_streams_per_call_vs_oracle(mode, tol_l, tol_p, streams, nframes
     per call (M = 784 / 1764 rows: the 64 x 64 GEMM tiles with the in-kernel LayerNorm fold in bf16 mode, the large split
     tiles in the accurate mode), against the oracle's full-clip forward of every stream; and the short-clip forward of the
     same frames outside streaming (same kernels, no cache)."""
+    if mode == "fp32":
+        tol_l, tol_p = 9e-5, 9e-5          # accurate (sfold): measured 4.5e-5
     import streamformer_amd as sa
     cfg = siglip_base(num_hidden_layers=3)
     sd = make_state_dict(cfg, seed=4)
@@ -987,6 +1003,8 @@ def test_forward_non_base_width_vs_oracle(mode, tol_l, tol_p):
     residual stream) and must still equal the oracle: whole clips at two batch sizes (M = 392 on the small-M kernels, M = 6272 on
     the generic 128^2 / 256^2 tiles), the pooling head at 16 heads, and three streamed frames through the KV-cache (the head's
     row-vector tail at K = 4096)."""
+    if mode == "fp32":
+        tol_l, tol_p = 9e-5, 9e-5          # accurate: measured 4.3e-5
     import streamformer_amd as sa
     from streamformer_amd.configuration import StreamformerConfig
     cfg = StreamformerConfig(image_size=224, patch_size=16, num_frames=16, hidden_size=1024, num_hidden_layers=2, num_attention_heads=16,
@@ -1019,6 +1037,8 @@ def test_forward_non_base_width_vs_oracle(mode, tol_l, tol_p):
 def test_forward_three_heads_vs_oracle(mode, tol_l, tol_p):
     """D = 192 / 3 heads: the ragged k-step splits of the pooling-head kernels (six k-steps over four waves) in whole clips (token splits
     S = 1 and S > 1) and streamed frames, against the oracle."""
+    if mode == "fp32":
+        tol_l, tol_p = 9e-5, 9e-5          # accurate: measured 4.3e-5
     import streamformer_amd as sa
     cfg = small_cfg(hidden_size=192, num_attention_heads=3, intermediate_size=384, image_size=96)      # 36 patches
     sd = make_state_dict(cfg, seed=31)
@@ -1069,6 +1089,8 @@ def test_forward_head_widths_other_than_64_vs_reference_fixture(golden_dir, mode
     oracle/make_golden_widths_hip.py / make_golden_variants.py): generic-width attention + pooling-head kernels, zero-padded MLP and
     patch-embedding weights, generic patch extraction.  Streamed frame by frame through the KV-cache the same frames must agree with
     the full clip, bit-reproducibly."""
+    if mode == "fp32":
+        tol_l, tol_p = 8e-5, 8e-5          # accurate (D % 256 != 0): measured 4.0e-5
     import streamformer_amd as sa
     from streamformer_amd.configuration import StreamformerConfig
     g = load_npz(os.path.join(golden_dir, fixture))
@@ -1131,7 +1153,7 @@ def test_so400m_shaped_layer_runs_and_matches_the_oracle():
     sd = make_state_dict(cfg, seed=16)
     x = frames(16, (1, 4, 3, 224, 224))
     want = O.forward(sd, cfg, x)
-    for mode, tl, tp in (("fp32", ACC_TOL, ACC_TOL), ("bf16", BF16_LHS, BF16_POOL)):
+    for mode, tl, tp in (("fp32", 7e-5, 7e-5), ("bf16", BF16_LHS, BF16_POOL)):      # accurate: measured 3.2e-5
         m = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype=mode)
         m.load_state_dict(sd)
         m.to("cuda").eval()
@@ -1196,9 +1218,24 @@ def test_plane_form_residual_stream_equals_the_fp32_one(sa, mode):
     assert d1 <= tol and d2 <= tol
     assert d1 > 0 or d2 > 0          # two different schedules ran
     want = O.forward(sd, cfg, xc[2:3])
-    lt, pt = (ACC_TOL, ACC_TOL) if mode == "fp32" else (BF16_LHS, BF16_POOL)
+    lt, pt = (ACC_XM, ACC_XM) if mode == "fp32" else (BF16_LHS, BF16_POOL)      # xm: measured 4.8e-5 / 4.0e-5
     assert maxabs(planes.last_hidden_state[2], want["last_hidden_state"][0]) <= lt
     assert maxabs(planes.pooler_output[2], want["pooler_output"][0]) <= pt
+
+
+def test_third_residual_plane_is_measurable(sa, switches):
+    """The accurate mode's plane-form residual stream (xm: three clips and more at SigLIP-base) keeps hi + lo + lo2 bf16 planes; without
+    lo2 (SF_ACC_TWO_PLANES) it rounds each residual row to 16 mantissa bits.  The schedule's ceiling must tell the two apart."""
+    cfg = siglip_base()
+    sd = make_state_dict(cfg, seed=2)
+    m = build(sa, cfg, sd, "fp32")
+    xc = torch.randn(3, 16, 3, 224, 224, generator=torch.Generator().manual_seed(78))
+    want = O.forward(sd, cfg, xc[1:2])["last_hidden_state"][0]
+    d3 = maxabs(m(xc.cuda()).last_hidden_state[1], want)
+    switches("SF_ACC_TWO_PLANES")
+    d2 = maxabs(m(xc.cuda()).last_hidden_state[1], want)
+    print(f"xm schedule vs oracle: three planes {d3:.3e}, two planes {d2:.3e}")      # measured 4.7e-5 and 1.36e-4
+    assert d3 <= ACC_XM < d2
 
 
 def test_two_clips_run_statistics_producing_tiles(sa, switches):
