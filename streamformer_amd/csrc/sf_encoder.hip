@@ -641,145 +641,102 @@ static Workspace carve(const sf_encoder* e, void* base, int B, int T, int N, boo
 // ------------------------------------------------------------------------------------------------
 // the launch schedule
 // ------------------------------------------------------------------------------------------------
-static hipError_t run_linear(const sf_encoder* e, const DevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo,
-                             int M, int epi, hipStream_t s, float* out_f32, bf16_t* out_hi, bf16_t* out_lo,
-                             const float* resid = nullptr, float alpha = 1.f, int ldc = 0, int grp_rows = 0,
-                             int grp_stride = 0, int grp_off = 0, const float* ln_stats = nullptr,
-                             float* ln_stats_out = nullptr, bool ln_inkernel = false, const int* grp_off_dev = nullptr,
-                             int grp_off_scale = 0, const bf16_t* resid_hi = nullptr, const bf16_t* resid_lo = nullptr,
-                             bf16_t* resid_lo2 = nullptr, bool force_split = false) {
+// The fields every Linear of the forward shares; a call site then sets what is special about it (outputs, residual, LayerNorm
+// fold, row remap) by field name and launches with the same `split`.
+static SfGemmArgs linear_args(const sf_encoder* e, const DevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, bool split) {
   SfGemmArgs g;
   memset(&g, 0, sizeof(g));
-  const bool split = force_split || e->compute == SF_COMPUTE_BF16X3;
   g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr;
   g.w_hi = lin.w_hi; g.w_lo = split ? lin.w_lo : nullptr;
   g.bias = lin.bias;
-  g.M = M; g.N = lin.N; g.K = lin.K;
-  g.epi = epi; g.act = e->cfg.hidden_act; g.alpha = alpha; g.resid = resid;
-  g.out_f32 = out_f32; g.out_hi = out_hi; g.out_lo = (split || resid_hi) ? out_lo : nullptr;
-  g.resid_hi = resid_hi; g.resid_lo = resid_lo; g.resid_lo2 = resid_lo2; g.out_lo2 = resid_lo2;     // third plane: in place
-  g.ldc = ldc ? ldc : lin.N;
-  g.grp_rows = grp_rows; g.grp_stride = grp_stride; g.grp_off = grp_off;
-  g.grp_off_dev = grp_off_dev; g.grp_off_scale = grp_off_scale;
-  if (grp_rows > 0 && grp_stride == grp_rows && grp_off == 0 && !grp_off_dev) g.grp_rows = 0;   // identity remap (full clip)
-  g.ln_stats = ln_stats; g.ln_s = ln_stats ? lin.ln_s : nullptr; g.ln_eps = e->cfg.layer_norm_eps;
-  g.ln_stats_out = ln_stats_out;
-  g.ln_stats_wide = 1;
-  if (ln_inkernel) { g.ln_inkernel = 1; g.ln_s = lin.ln_s; }
-  if (epi == SF_EPI_RESID_F32) g.out_hi = out_hi;     // LN-fold producer: bf16 copy of the new residual rows
-  return sf_launch_gemm(g, split, s);
+  g.M = M; g.N = lin.N; g.K = lin.K; g.ldc = lin.N;
+  g.epi = epi; g.act = e->cfg.hidden_act; g.alpha = 1.f;
+  g.ln_eps = e->cfg.layer_norm_eps; g.ln_stats_wide = 1;
+  return g;
 }
 
-static bool ln_fold_small_ok(const sf_encoder* e, int M);
+// ---- which LayerNorm fold a shape can take: each predicate asks the kernels' own *_supported functions with the shapes of a layer's
+// residual producers (N = D, K = D and K = I) and folded consumers (qkv: N = 3 D, MLP-up: N = I; K = D).  The operand pointers of
+// such a probe only say "present".
+static bf16_t* const kSetB = (bf16_t*)1;
+static float* const kSetF = (float*)1;
+static SfGemmArgs probe_args(const sf_encoder* e, int M, int N, int K, int epi) {
+  SfGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.M = M; g.N = N; g.K = K; g.ldc = N; g.epi = epi; g.act = e->cfg.hidden_act; g.ln_stats_wide = 1;
+  return g;
+}
+template <typename Takes>
+static bool takes_both_k(const sf_encoder* e, SfGemmArgs producer, Takes&& takes) {      // a residual producer at K = D and at K = I
+  producer.K = e->D;
+  if (!takes(producer)) return false;
+  producer.K = e->I;
+  return takes(producer);
+}
+static bool bf16_consumers_on_g256(const sf_encoder* e, int M) {
+  return sf_gemm256_supported(probe_args(e, M, 3 * e->D, e->D, SF_EPI_BF16), false) && sf_gemm256_supported(probe_args(e, M, e->I, e->D, SF_EPI_ACT_BF16), false);
+}
 
-// LayerNorm folding needs the panel kernel as every residual producer (it emits the row statistics)
-// and the 256^2 kernel as every consumer (it applies them): true for the BASELINE shape.
-// Two clips per call (sf_tile_fold_min_rows() <= M <= sf_tile_max_rows()): the narrow tile kernel stays the residual producer (it beats
-// the panel kernel there) but emits the row statistics, so that the folded consumers can run on the 256^2 kernel (which beats the wide tiles there)
+// bf16 mode, two clips per call (sf_tile_fold_min_rows() <= M <= sf_tile_max_rows()): the narrow tile kernel stays the residual producer (it
+// beats the panel kernel there) but emits the row statistics, so that the folded consumers can run on the 256^2 kernel (which beats the
+// wide tiles there)
 static bool ln_fold_tile_ok(const sf_encoder* e, int M) {
   if (e->compute != SF_COMPUTE_BF16 || sf_sw(SW_DISABLE_LN_FOLD)) return false;
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ln_stats_wide = 1;
-  g.M = M; g.N = e->D; g.ldc = e->D; g.epi = SF_EPI_RESID_F32; g.out_f32 = (float*)1; g.resid = (const float*)1; g.out_hi = (bf16_t*)1;
-  g.ln_stats_out = (float*)1;
-  g.K = e->D;
-  if (!sf_gemm_tile_supported(g, false)) return false;
-  g.K = e->I;
-  if (!sf_gemm_tile_supported(g, false)) return false;
-  memset(&g, 0, sizeof(g));
-  g.ln_stats_wide = 1;
-  g.M = M; g.epi = SF_EPI_BF16; g.K = e->D; g.N = 3 * e->D;
-  if (!sf_gemm256_supported(g, false)) return false;
-  g.epi = SF_EPI_ACT_BF16; g.N = e->I; g.act = e->cfg.hidden_act;
-  return sf_gemm256_supported(g, false);
+  SfGemmArgs g = probe_args(e, M, e->D, e->D, SF_EPI_RESID_F32);
+  g.out_f32 = kSetF; g.resid = kSetF; g.out_hi = kSetB; g.ln_stats_out = kSetF;
+  return takes_both_k(e, g, [](const SfGemmArgs& a) { return sf_gemm_tile_supported(a, false); }) && bf16_consumers_on_g256(e, M);
 }
 
-static bool ln_fold_ok(const sf_encoder* e, int M) {
-  if (e->compute != SF_COMPUTE_BF16) return false;
-  if (sf_sw(SW_DISABLE_LN_FOLD)) return false;        // A/B switch for measurements
-  if (ln_fold_tile_ok(e, M)) return true;
-  if (ln_fold_small_ok(e, M)) return false;              // the small-M fold (in-kernel statistics: skinny / 64 x 64 / tile kernels) takes these
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.M = M; g.N = e->D; g.epi = SF_EPI_RESID_F32;
-  g.K = e->D;
-  if (!sf_gemm_panel_supported(g, false)) return false;
-  g.K = e->I;
-  if (!sf_gemm_panel_supported(g, false)) return false;
-  g.epi = SF_EPI_BF16; g.K = e->D; g.N = 3 * e->D;
-  if (!sf_gemm256_supported(g, false)) return false;
-  g.epi = SF_EPI_ACT_BF16; g.N = e->I; g.act = e->cfg.hidden_act;
-  return sf_gemm256_supported(g, false);
+// bf16 mode, BASELINE-sized M: the panel kernel as every residual producer (it emits the row statistics) and the 256^2 kernel as
+// every consumer (it applies them).  SF_DISABLE_LN_FOLD is the A/B switch of this fold and of the two next to it.
+static bool ln_fold_panel_ok(const sf_encoder* e, int M) {
+  if (e->compute != SF_COMPUTE_BF16 || sf_sw(SW_DISABLE_LN_FOLD)) return false;
+  return takes_both_k(e, probe_args(e, M, e->D, e->D, SF_EPI_RESID_F32), [](const SfGemmArgs& a) { return sf_gemm_panel_supported(a, false); }) &&
+         bf16_consumers_on_g256(e, M);
 }
 
-// fp32-accurate mode: the fold on the bf16x3 256^2 kernel, with the residual stream itself carried as the hi + lo bf16 planes
-// that are the folded Linears' operands (xn_hi / xn_lo): a residual producer reads and writes the planes and emits one
-// {sum x, sum x^2} pair per 256-column tile; no fp32 residual, no LayerNorm launch.  The planes hold x to 2^-18 relative, the
-// precision every bf16x3 operand has anyway.  SF_DISABLE_ACC_FOLD restores fp32 residual + standalone LayerNorm (A/B).
+// The plane-form fold on the 256^2 kernel as producer (hi + lo planes in / out + one {sum x, sum x^2} pair per 256-column tile, four per
+// row) and consumer (its LNF instances sum the pairs): D a multiple of 256 up to 1024.
+//   accurate mode (split): the residual stream itself is the hi + lo planes that are the folded Linears' operands (xn_hi / xn_lo); they
+//     hold x to 2^-18 relative, the precision every bf16x3 operand has anyway.  SF_DISABLE_ACC_FOLD restores fp32 residual + LayerNorm (A/B).
+//   bf16 mode: widths the panel kernel does not take (D = 1024, a ViT-L-shaped encoder), which would otherwise pay three standalone
+//     LayerNorm launches per layer (9.7 % of the ViT-L forward).
+static bool ln_fold_planes_g256_ok(const sf_encoder* e, int M, bool split) {
+  if ((e->D % 256) || e->D > 1024) return false;
+  SfGemmArgs g = probe_args(e, M, e->D, e->D, SF_EPI_RESID_F32);
+  if (split) { g.a_lo = kSetB; g.w_lo = kSetB; }
+  g.out_hi = kSetB; g.out_lo = kSetB; g.ln_stats_out = kSetF; g.resid_hi = kSetB; g.resid_lo = kSetB;
+  if (!takes_both_k(e, g, [split](const SfGemmArgs& a) { return sf_gemm256_supported(a, split); })) return false;
+  g.ln_stats_out = nullptr; g.resid_hi = g.resid_lo = nullptr; g.ln_stats = kSetF; g.ln_s = kSetF;
+  if (split) g.out_hi = nullptr; else g.out_lo = nullptr;      // (the probes name one output plane: lo in the accurate mode, hi in bf16 mode)
+  g.epi = SF_EPI_BF16; g.K = e->D; g.N = g.ldc = 3 * e->D;
+  if (!sf_gemm256_supported(g, split)) return false;
+  g.epi = SF_EPI_ACT_BF16; g.N = g.ldc = e->I;
+  return sf_gemm256_supported(g, split);
+}
 static bool ln_fold_acc_ok(const sf_encoder* e, int M) {
-  if (e->compute != SF_COMPUTE_BF16X3 || (e->D % 256) || e->D > 1024) return false;      // one statistics pair per 256-column producer tile, four per row
-  const bool off = sf_sw(SW_DISABLE_ACC_FOLD) != nullptr;
-  if (off) return false;
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a_lo = (const bf16_t*)1; g.w_lo = (const bf16_t*)1; g.ln_stats_wide = 1;
-  g.M = M; g.N = e->D; g.K = e->D; g.epi = SF_EPI_RESID_F32;
-  g.out_hi = (bf16_t*)1; g.out_lo = (bf16_t*)1; g.ln_stats_out = (float*)1; g.resid_hi = (const bf16_t*)1; g.resid_lo = (const bf16_t*)1;
-  if (!sf_gemm256_supported(g, true)) return false;
-  g.K = e->I;
-  if (!sf_gemm256_supported(g, true)) return false;
-  g.ln_stats_out = nullptr; g.out_hi = nullptr; g.resid_hi = g.resid_lo = nullptr; g.ln_stats = (const float*)1; g.ln_s = (const float*)1;
-  g.epi = SF_EPI_BF16; g.K = e->D; g.N = 3 * e->D;
-  if (!sf_gemm256_supported(g, true)) return false;
-  g.epi = SF_EPI_ACT_BF16; g.N = e->I; g.act = e->cfg.hidden_act;
-  return sf_gemm256_supported(g, true);
+  return e->compute == SF_COMPUTE_BF16X3 && !sf_sw(SW_DISABLE_ACC_FOLD) && ln_fold_planes_g256_ok(e, M, true);
 }
-
-// bf16 mode at widths the panel kernel does not take (D = 1024: a ViT-L-shaped encoder): the same plane-form residual stream + fold with
-// the 256^2 kernel as producer (planes in / out + one statistics pair per 256-column tile) and consumer (its bf16 LNF instance sums
-// the four pairs).  Without it those widths pay three standalone LayerNorm launches per layer (9.7 % of the ViT-L forward).
 static bool ln_fold_g256_ok(const sf_encoder* e, int M) {
-  if (e->compute != SF_COMPUTE_BF16 || (e->D % 256) || e->D > 1024) return false;
-  if (sf_sw(SW_DISABLE_LN_FOLD)) return false;
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.ln_stats_wide = 1;
-  g.M = M; g.N = e->D; g.K = e->D; g.epi = SF_EPI_RESID_F32;
-  g.out_hi = (bf16_t*)1; g.out_lo = (bf16_t*)1; g.ln_stats_out = (float*)1; g.resid_hi = (const bf16_t*)1; g.resid_lo = (const bf16_t*)1;
-  if (!sf_gemm256_supported(g, false)) return false;
-  g.K = e->I;
-  if (!sf_gemm256_supported(g, false)) return false;
-  g.ln_stats_out = nullptr; g.out_hi = (bf16_t*)1; g.out_lo = nullptr; g.resid_hi = g.resid_lo = nullptr; g.ln_stats = (const float*)1; g.ln_s = (const float*)1;
-  g.epi = SF_EPI_BF16; g.K = e->D; g.N = 3 * e->D;
-  if (!sf_gemm256_supported(g, false)) return false;
-  g.epi = SF_EPI_ACT_BF16; g.N = e->I; g.act = e->cfg.hidden_act;
-  return sf_gemm256_supported(g, false);
+  return e->compute == SF_COMPUTE_BF16 && !sf_sw(SW_DISABLE_LN_FOLD) && ln_fold_planes_g256_ok(e, M, false);
 }
 
-// Small-M variant (the per-frame streaming step): the skinny GEMM derives the row statistics itself from the A fragments
-// it reads anyway, every residual producer only adds the bf16 copy of its output rows.
+// Small M (the per-frame streaming step): the skinny GEMM derives the row statistics itself from the A fragments it reads anyway,
+// every residual producer only adds the bf16 copy of its output rows.  Accurate mode: the consumers take x as hi + lo planes and sum
+// the statistics of hi + lo (32 x 32 skinny kernel only).  SF_DISABLE_STREAM_FOLD: A/B.
 static bool ln_fold_small_ok(const sf_encoder* e, int M) {
-  if (M > sf_infold_max_rows()) return false;
-  const bool off = sf_sw(SW_DISABLE_STREAM_FOLD) != nullptr;
-  if (off) return false;
-  // accurate mode (round 6): the consumers take x as hi + lo planes and sum the statistics of hi + lo (32 x 32 skinny kernel only)
+  if (M > sf_infold_max_rows() || sf_sw(SW_DISABLE_STREAM_FOLD)) return false;
   const bool acc = e->compute == SF_COMPUTE_BF16X3;
   auto takes = [acc](const SfGemmArgs& g) { return sf_gemm_skinny_supported(g, acc) || (!acc && sf_gemm_tile_supported(g, false)); };
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  if (acc) { g.a_lo = (const bf16_t*)1; g.w_lo = (const bf16_t*)1; g.out_lo = (bf16_t*)1; }
-  g.M = M; g.K = e->D; g.ldc = 3 * e->D; g.ln_inkernel = 1; g.ln_s = (const float*)1; g.out_hi = (bf16_t*)1;
-  g.epi = acc ? SF_EPI_F32 : SF_EPI_BF16; g.N = 3 * e->D;
-  if (acc) g.out_f32 = (float*)1;
+  SfGemmArgs g = probe_args(e, M, 3 * e->D, e->D, acc ? SF_EPI_F32 : SF_EPI_BF16);
+  if (acc) { g.a_lo = kSetB; g.w_lo = kSetB; g.out_lo = kSetB; g.out_f32 = kSetF; }
+  g.ln_inkernel = 1; g.ln_s = kSetF; g.out_hi = kSetB;
   if (!takes(g)) return false;
-  g.epi = SF_EPI_ACT_BF16; g.N = e->I; g.ldc = e->I;
+  g.epi = SF_EPI_ACT_BF16; g.N = g.ldc = e->I;
   if (!takes(g)) return false;
-  g.ln_inkernel = 0; g.ln_s = nullptr; g.epi = SF_EPI_RESID_F32; g.N = e->D; g.ldc = e->D; g.out_hi = (bf16_t*)1;
-  g.out_f32 = (float*)1; g.resid = (const float*)1;
-  if (!takes(g)) return false;                                // producers (they add the bf16 copy): K = D ...
-  g.K = e->I;
-  return takes(g);                                            // ... and K = I
+  g.ln_inkernel = 0; g.ln_s = nullptr; g.epi = SF_EPI_RESID_F32; g.N = g.ldc = e->D;      // producers (they add the bf16 copy)
+  g.out_f32 = kSetF; g.resid = kSetF;
+  return takes_both_k(e, g, takes);
 }
 
 // the head's per-frame tail on one to four rows runs as row-vector launches (sf_launch_rowlin)
@@ -788,9 +745,9 @@ static bool sf_head_rows_ok(const sf_encoder* e, int F) {
          sf_rowlin_supported(F, e->D, e->I);
 }
 
+// T <= 256 (SfRowIndex): every entry point has checked it (the streaming entry through the cache capacity)
 static int time_rows(const sf_encoder* e, int t_past, int T, bool streaming, SfRowIndex* idx) {
   const int nf = e->cfg.num_frames;
-  if (T > 256) return set_err(SF_ERR_INVALID, "at most 256 frames per call (got %d)", T);
   idx->n = T;
   if (streaming) {
     // vqa_enc:328-369: direct rows; the reference raises past num_frames rows
@@ -810,73 +767,117 @@ static int time_rows(const sf_encoder* e, int t_past, int T, bool streaming, SfR
   return SF_OK;
 }
 
-// One call of the encoder over T new frames.  tq = per-layer temporal qkv buffers ([B,cap,N,3D]).
-static int run_forward(sf_encoder* e, const void* pixels, int pixel_dtype, int B, int T, int H, int W,
-                       float* last_hidden, float* pooler, float* hidden_states, const float* pos_dev,
-                       const Workspace& ws, void* const* layer_tqkv, int cap, int t_past, bool streaming,
-                       hipStream_t s, float* attentions = nullptr, int stages = 7, int la = 0, int lb = -1,
-                       int ready = 0, const SfStreamParams* sp = nullptr, const int* pos3 = nullptr) {
-  // pos3 (streaming, T == 1): {time-embedding row, cache slot, keys seen} when they differ from (t_past, t_past, t_past + 1):
-  // the sliding-window policy of a full cache
-  const int t_row = pos3 ? pos3[0] : t_past, slot = pos3 ? pos3[1] : t_past, tk = pos3 ? pos3[2] : t_past + T;
-  // sp (streaming, T == 1, graph capture): the cache position is read on the DEVICE from sp->t_past by the kernels that need
-  // it (time-embedding row, KV-cache append row, single-query attention); t_past here only selects kernel variants
-  // ready: 1 = the patch matrix is already in the workspace (the streaming entry extracts it outside its graph),
-  //        2 = ws.res_bf already holds bf16(residual) (a later layer range of the same call)
-  const bool patches_ready = (ready & 1) != 0;
+// What one call of the encoder over T new frames is asked to do (filled by name at the entry points).
+struct ForwardRequest {
+  const void* pixels = nullptr; int pixel_dtype = SF_F32;
+  int B = 0, T = 0, H = 0, W = 0;
+  float* last_hidden = nullptr; float* pooler = nullptr; float* hidden_states = nullptr; float* attentions = nullptr;
+  const float* pos_dev = nullptr;        // resized position table, or null for the encoder's own
+  void* const* layer_tqkv = nullptr;     // streaming: per-layer temporal qkv caches [B, cap, N, 3D]; null: ws.tqkv, rewritten by every layer
+  int cap = 0, t_past = 0;               // frames a cache row holds (T without a cache), frames already in it
+  bool streaming = false;
   // stages: 1 = embeddings -> ws.resid, 2 = layers [la, lb) on ws.resid, 4 = post-LayerNorm + pooling head,
   // 8 = pooling head alone on already-normalised tokens in ws.resid
   // (the sub-module entry points run them one at a time on a caller-owned residual stream)
-  if (lb < 0) lb = e->L;
-  const sf_config& c = e->cfg;
-  const int P = c.patch_size, D = e->D, heads = c.num_attention_heads;
-  const int N = (H / P) * (W / P);
-  const int M = B * T * N, F = B * T;
-  const bool acc = e->compute == SF_COMPUTE_BF16X3;
-  const int qkv_epi = acc ? SF_EPI_F32 : SF_EPI_BF16;
-  const size_t esz = acc ? 4 : 2;
-  const float scale = 1.0f / sqrtf((float)e->hd);
+  int stages = 7, la = 0, lb = -1;       // lb < 0: to the last layer
+  // ready: 1 = the patch matrix is already in the workspace (the streaming entry extracts it outside its graph),
+  //        2 = ws.res_bf already holds bf16(residual) (a later layer range of the same call)
+  int ready = 0;
+  // sp (streaming, T == 1, graph capture): the cache position is read on the DEVICE from sp->t_past by the kernels that need
+  // it (time-embedding row, KV-cache append row, single-query attention); t_past here only selects kernel variants
+  const SfStreamParams* sp = nullptr;
+  // pos3 (streaming, T == 1): {time-embedding row, cache slot, keys seen} when they differ from (t_past, t_past, t_past + 1):
+  // the sliding-window policy of a full cache
+  const int* pos3 = nullptr;
+};
 
-  bool embed_emitted_stats = false;
-  // statistics rows of the bf16 fold are 8 floats = four pairs; the 384-column panel kernel fills pairs 0 and 2 only
-  if (e->compute == SF_COMPUTE_BF16 && !streaming && (stages & 3) && ln_fold_ok(e, B * T * ((H / e->cfg.patch_size) * (W / e->cfg.patch_size))))
-    HIP_TRY(hipMemsetAsync(ws.ln_stats, 0, (size_t)B * T * ((H / e->cfg.patch_size) * (W / e->cfg.patch_size)) * 8 * sizeof(float), s));
-  // pm: the residual stream of a whole bf16 forward at BASELINE-sized M travels as hi + lo bf16 planes (hi = xn_hi, the A operand
-  // of the folded Linears; lo = res_lo) instead of fp32: every residual producer moves 154 MB instead of 192 (no separate bf16
-  // copy).  Only for complete forwards without hidden_states (the fp32 tensor is the interface of the stage-wise entry points).
-  const bool planes_off = sf_sw(SW_DISABLE_RESID_PLANES) != nullptr;
-  bool pm = !planes_off && !acc && !streaming && ws.res_lo && !hidden_states && (stages & 7) == 7 && ln_fold_ok(e, M) && !ln_fold_tile_ok(e, M) && ws.embed_tab &&
-            ws.patch_buf && e->Kp % 32 == 0 && e->Kp >= 128 && D == 768 && !sf_sw(SW_EMBED_VIA_GEMM128);
+enum EmbedRoute { EMBED_NONE, EMBED_TILE, EMBED_PANEL, EMBED_GEMM };
+
+// Every schedule decision of one forward, made by plan_forward() before the first launch and only read afterwards.
+//
+// The residual stream x and the LayerNorms in front of the three folded Linears of a layer (temporal qkv, spatial qkv, MLP-up: weights
+// W' = W gamma, ln_s = row sums of W') take one of these forms; `M` = B T N token rows:
+//
+//   schedule   taken when                                                      residual stream             LayerNorm of the consumers
+//   ---------  --------------------------------------------------------------  --------------------------  ------------------------------------
+//   fold       bf16, whole clips (not streaming), ln_fold_panel_ok (BASELINE-   fp32 ws.resid + bf16 copy   statistics rows ws.ln_stats written by
+//              sized M, D = 768) and not sfold-sized                            in ws.xn_hi                 the panel producers, applied by the
+//                                                                                                           256^2 consumers
+//   fold + pm  fold, and: complete forward (stages 1|2|4) without               hi = ws.xn_hi, lo =         as fold (every producer moves 154 MB
+//              hidden_states, panel embedding route with plane outputs,         ws.res_lo (no fp32)         instead of 192)
+//              no SF_DISABLE_RESID_PLANES
+//   tile-fold  bf16, whole clips, ln_fold_tile_ok (two clips per call)          as fold                     as fold, narrow tile kernel as producer
+//   sfold      not fold; M <= sf_infold_max_rows() (streamed frames, a few      fp32 ws.resid + bf16 copy   inside the skinny / tile consumers
+//              frames per call), ln_fold_small_ok, ws.res_bf carved             ws.res_bf (accurate: + lo   (ln_inkernel), no statistics buffer
+//                                                                               plane ws.res_lo)
+//   xm         accurate, complete forward of whole clips without hidden_states  hi = ws.xn_hi, lo =         ws.ln_stats: one pair per 256-column
+//              or cache, temporal + spatial attention on planes, ln_fold_acc_ok ws.xn_lo, lo2 = ws.res_lo2  tile of the bf16x3 256^2 producer
+//              (M > 6272, or D = 1024 from 2048 rows)                           (SF_ACC_TWO_PLANES: no lo2)
+//   gm         bf16, neither fold nor sfold, complete forward of whole clips    hi = ws.xn_hi, lo =         as xm, bf16 256^2 kernel
+//              without hidden_states, ln_fold_g256_ok (D = 1024)                ws.res_lo
+//   plain      everything else                                                  fp32 ws.resid               three sf_launch_layernorm per layer
+//                                                                                                           into ws.xn_hi (/ xn_lo)
+//
+// In the plane forms (pm, xm, gm) ws.resid is written by the embeddings only; the post-LayerNorm reads the planes.
+struct ForwardPlan {
+  ForwardRequest rq;                     // lb resolved
+  int N, M, F;                           // patches per frame, token rows, frames
+  bool acc;                              // fp32-accurate mode: every GEMM operand as hi + lo planes
+  int qkv_epi; size_t esz;               // qkv tensors: bf16, or fp32 in the accurate mode
+  float scale;
+  int t_row, slot, tk;                   // time-embedding row, cache slot of the first new frame, keys the new frames see
+  // embeddings
+  bool zero_stats;                       // statistics rows of the bf16 fold are four pairs; the 384-column panel kernel fills pairs 0 and 2 only
+  bool time_folded;                      // the embedding GEMM reads its time row from the table (row index in the device block): no gather
+  EmbedRoute embed_route;                // EMBED_TILE / EMBED_PANEL also emit bf16(x) + row statistics; EMBED_GEMM: sf_launch_gemm's choice
+  bf16_t* patches;                       // the patch matrix: ws.patch_buf in front of the tile / panel routes (their bf16 output goes to xn_hi)
+  SfGemmArgs embed;
+  // the schedule (table above)
+  bool fold, sfold, xm, gm, pm;
+  bool anyfold;                          // fold || sfold || xm || gm: folded weights, no LayerNorm launch
+  bool rplanes;                          // pm || xm || gm
+  bool seed_stats;                       // fold, embeddings without statistics (generic route, or sf_layers on the caller's tensor)
+  bool seed_split;                       // sfold entered through sf_layers: ws.res_bf (+ lo) from the caller's tensor
+  float* resid;                          // fp32 residual stream, null in the plane forms
+  bf16_t* fold_hi;                       // what a producer writes next to (or instead of) it: the consumers' A operand
+  bf16_t* plo; bf16_t* plo2;             // lo / third plane
+  float* fold_st;                        // statistics rows, null when no buffer carries them
+  const bf16_t* ln_in; const bf16_t* ln_in_lo;      // A operand of the three LayerNorm'd Linears
+  // attention inputs of the accurate mode as hi + lo bf16 planes in the bytes of the fp32 tensor (DMA kernels) instead of fp32
+  bool tplanes, planes;                  // temporal: whole short clip without a cache; spatial: <= 224 tokens, no probabilities wanted
+  size_t tsz, sesz;                      // element size of the temporal / spatial qkv tensor
+  // head
+  bool head_generic;                     // widths the MFMA probe kernels do not cover
+  bool head_rows;                        // one to four frames: row-vector tail, pooler_output written by its last launch
+};
+
+static ForwardPlan plan_forward(const sf_encoder* e, const ForwardRequest& rq, const Workspace& ws) {
+  ForwardPlan p = {};
+  p.rq = rq;
+  if (p.rq.lb < 0) p.rq.lb = e->L;
+  const int D = e->D, T = rq.T, stages = rq.stages;
+  const int N = (rq.H / e->cfg.patch_size) * (rq.W / e->cfg.patch_size), M = rq.B * T * N;
+  const bool acc = e->compute == SF_COMPUTE_BF16X3, streaming = rq.streaming;
+  const bool complete = (stages & 7) == 7 && !rq.hidden_states;      // the fp32 tensor is the interface of the stage-wise entry points
+  p.N = N; p.M = M; p.F = rq.B * T; p.acc = acc;
+  p.qkv_epi = acc ? SF_EPI_F32 : SF_EPI_BF16; p.esz = acc ? 4 : 2;
+  p.scale = 1.0f / sqrtf((float)e->hd);
+  p.t_row = rq.pos3 ? rq.pos3[0] : rq.t_past; p.slot = rq.pos3 ? rq.pos3[1] : rq.t_past; p.tk = rq.pos3 ? rq.pos3[2] : rq.t_past + T;
+
+  const bool tile_fold = ln_fold_tile_ok(e, M), small_fold = ln_fold_small_ok(e, M);
+  const bool stats_fold = tile_fold || (!small_fold && ln_fold_panel_ok(e, M));      // bf16 mode: a fold with a statistics buffer
+  const bool small_bufs = ws.res_bf && (!acc || ws.res_lo) && small_fold;
+  p.zero_stats = stats_fold && !streaming && (stages & 3);
+
+  // ---- embeddings.  Panel route: out = table[m % (T N)] + patches W^T + b with table = pos + time rows; pm asks it for plane outputs
+  const bool panel_embed = stats_fold && !streaming && (stages & 2) && ws.embed_tab && ws.patch_buf && e->Kp % 32 == 0 && e->Kp >= 128 && D == 768 &&
+                           !sf_sw(SW_EMBED_VIA_GEMM128);
+  const bool pm_wanted = panel_embed && !tile_fold && !acc && complete && ws.res_lo && !sf_sw(SW_DISABLE_RESID_PLANES);
   if (stages & 1) {
-  SfRowIndex idx;
-  int rc = time_rows(e, t_row, T, streaming, &idx);
-  if (rc) return rc;
-  if (sp) { for (int t = 0; t < T; ++t) idx.idx[t] = t; }
-  // streamed frame inside the position-free graph: the embedding GEMM reads its time-embedding row straight from the table
-  // (row index from the device block) when the skinny kernel takes the shape — no gather launch
-  bool time_folded = false;
-  if (sp && T == 1) {
-    SfGemmArgs gt;
-    memset(&gt, 0, sizeof(gt));
-    gt.a_hi = ws.xn_hi; gt.a_lo = acc ? ws.xn_lo : nullptr; gt.w_hi = e->patch.w_hi; gt.w_lo = acc ? e->patch.w_lo : nullptr;
-    gt.M = M; gt.N = D; gt.K = e->Kp; gt.ldc = D; gt.epi = SF_EPI_EMBED_F32; gt.out_f32 = ws.resid;
-    time_folded = sf_gemm_skinny_supported(gt, acc) && !sf_sw(SW_DISABLE_SKINNY) && !ln_fold_ok(e, M);      // exactly when sf_launch_gemm takes the skinny kernel
-  }
-  if (!time_folded) HIP_TRY(sf_launch_gather_rows(e->time_tab, ws.te_rows, idx, D, s, sp ? &sp->t_row : nullptr));
-  // LN folding (decided here because the folded path lets the embedding GEMM emit bf16(x) + row statistics itself:
-  // panel kernel, out = table[m % (T N)] + patches W^T + b with table = pos + time rows)
-  bool embed_panel = false;
-  if (ln_fold_ok(e, M) && !streaming && (stages & 2) && ws.embed_tab && ws.patch_buf && e->Kp % 32 == 0 && e->Kp >= 128 && D == 768 &&
-      !sf_sw(SW_EMBED_VIA_GEMM128))
-    embed_panel = true;
-  bf16_t* patches = embed_panel ? ws.patch_buf : ws.xn_hi;
-  if (!patches_ready)
-    HIP_TRY(sf_launch_patchify(pixels, pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0), patches, ws.xn_lo, F, c.num_channels, H, W, P, s,
-                               &e->pixel_norm, nullptr, nullptr, nullptr, e->Kp));
-  {
+    p.patches = panel_embed ? ws.patch_buf : ws.xn_hi;
     SfGemmArgs g;
     memset(&g, 0, sizeof(g));
-    g.a_hi = patches; g.a_lo = acc ? ws.xn_lo : nullptr;
+    g.a_hi = p.patches; g.a_lo = acc ? ws.xn_lo : nullptr;
     g.w_hi = e->patch.w_hi; g.w_lo = acc ? e->patch.w_lo : nullptr;
     g.bias = e->patch.bias;
     g.M = M; g.N = D; g.K = e->Kp;
@@ -884,238 +885,318 @@ static int run_forward(sf_encoder* e, const void* pixels, int pixel_dtype, int B
     SfGemmArgs gp = g;
     gp.epi = SF_EPI_RESID_F32; gp.alpha = 1.f; gp.resid = ws.embed_tab; gp.resid_mod = T * N;
     gp.out_hi = ws.xn_hi; gp.ln_stats_out = ws.ln_stats; gp.ln_stats_wide = 1;
-    if (pm) {
+    if (pm_wanted) {
       SfGemmArgs gq = gp;
       gq.out_f32 = nullptr; gq.out_lo = ws.res_lo;
-      if (embed_panel && sf_gemm_panel_supported(gq, false)) gp = gq; else pm = false;
+      p.pm = sf_gemm_panel_supported(gq, false);
+      if (p.pm) gp = gq;
     }
-    // two clips per call (ln_fold_tile_ok): the embedding GEMM on the statistics-producing narrow tile (table add in its epilogue)
+    // pos + time rows added in the epilogue: the statistics-producing narrow tile (tile-fold), or whatever sf_launch_gemm picks
+    g.epi = SF_EPI_EMBED_F32; g.pos = rq.pos_dev ? rq.pos_dev : e->pos; g.time_rows = ws.te_rows; g.Np = N; g.Tn = T;
     SfGemmArgs gt = g;
-    gt.epi = SF_EPI_EMBED_F32; gt.pos = pos_dev ? pos_dev : e->pos; gt.time_rows = ws.te_rows; gt.Np = N; gt.Tn = T;
     gt.out_hi = ws.xn_hi; gt.ln_stats_out = ws.ln_stats; gt.ln_stats_wide = 1;
-    if (!acc && !streaming && (stages & 2) && patches != ws.xn_hi && ln_fold_tile_ok(e, M) && sf_gemm_tile_supported(gt, false)) {      // (A must not alias out_hi)
-      HIP_TRY(sf_launch_gemm_tile(gt, s));
-      embed_emitted_stats = true;
-    } else
-    if (embed_panel && sf_gemm_panel_supported(gp, false)) {
-      HIP_TRY(sf_launch_pos_time_table(pos_dev ? pos_dev : e->pos, ws.te_rows, ws.embed_tab, T, N, D, s));
-      HIP_TRY(sf_launch_gemm_panel(gp, s));
-      embed_emitted_stats = true;
+    if (!acc && !streaming && (stages & 2) && p.patches != ws.xn_hi && tile_fold && sf_gemm_tile_supported(gt, false)) {      // (A must not alias out_hi)
+      p.embed_route = EMBED_TILE; p.embed = gt;
+    } else if (panel_embed && sf_gemm_panel_supported(gp, false)) {
+      p.embed_route = EMBED_PANEL; p.embed = gp;
     } else {
-      g.epi = SF_EPI_EMBED_F32;
-      g.pos = pos_dev ? pos_dev : e->pos; g.time_rows = ws.te_rows; g.Np = N; g.Tn = T;
-      if (time_folded) { g.time_rows = e->time_tab; g.time_base_dev = &sp->t_row; }
-      if (ws.res_bf && (!acc || ws.res_lo) && ln_fold_small_ok(e, M) && (stages & 2)) { g.out_hi = ws.res_bf; if (acc) g.out_lo = ws.res_lo; }   // layer 0's folded qkv reads bf16(x) (accurate: hi + lo)
-      HIP_TRY(sf_launch_gemm(g, acc, s));
+      // streamed frame inside the position-free graph: the time-embedding row straight from the table — exactly when sf_launch_gemm
+      // takes the skinny kernel
+      p.time_folded = rq.sp && T == 1 && !stats_fold && !sf_sw(SW_DISABLE_SKINNY) && sf_gemm_skinny_supported(g, acc);
+      if (p.time_folded) { g.time_rows = e->time_tab; g.time_base_dev = &rq.sp->t_row; }
+      if (small_bufs && (stages & 2)) { g.out_hi = ws.res_bf; if (acc) g.out_lo = ws.res_lo; }   // layer 0's folded qkv reads bf16(x) (accurate: hi + lo)
+      p.embed_route = EMBED_GEMM; p.embed = g;
     }
   }
-  }
-  const size_t hs_stride = (size_t)M * D;
-  // LN folding (bf16 mode, BASELINE-sized M): xn_hi holds bf16(residual), ln_stats the row sums; the
-  // three per-layer LayerNorm launches disappear into the neighbouring GEMM epilogues.
-  const bool fold = ln_fold_ok(e, M) && !streaming;
-  // sfold: the same algebra at small M (streamed frames), statistics computed inside the consumer GEMM
-  const bool sfold = !fold && ws.res_bf && (!acc || ws.res_lo) && ln_fold_small_ok(e, M);
-  // xm: the accurate mode's counterpart of fold + pm (ln_fold_acc_ok): whole clips on the plane-fed attention kernels
-  const bool two_planes = sf_sw(SW_ACC_TWO_PLANES) != nullptr;      // A/B: drop the third plane (max-abs 1.4e-4 instead of 5e-5)
-  bf16_t* plo2 = two_planes ? nullptr : ws.res_lo2;
-  const bool xm = acc && !streaming && !hidden_states && (stages & 7) == 7 && !layer_tqkv && cap == T && t_past == 0 &&
-                  sf_temporal_planes_ok(T, T) && sf_spatial_planes_ok(N, attentions != nullptr) && ln_fold_acc_ok(e, M);
-  // gm: the bf16 mode's counterpart at widths without a panel kernel (ln_fold_g256_ok): lo plane = res_lo, two planes
-  const bool gm = !acc && !fold && !sfold && !streaming && !hidden_states && (stages & 7) == 7 && ws.res_lo != nullptr && ln_fold_g256_ok(e, M);
-  bf16_t* fold_hi = (fold || xm || gm) ? ws.xn_hi : (sfold ? ws.res_bf : nullptr);
-  float* fold_st = (fold || xm || gm) ? ws.ln_stats : nullptr;
-  const bf16_t* ln_in = sfold ? ws.res_bf : ws.xn_hi;       // A operand of the three LayerNorm'd Linears
-  const bf16_t* ln_in_lo = (sfold && acc) ? ws.res_lo : ws.xn_lo;      // its lo plane (accurate mode)
-  const bool anyfold = fold || sfold || xm || gm;
-  const bool rplanes = pm || xm || gm;                       // residual stream as two bf16 planes: hi = xn_hi, lo = plo
-  bf16_t* plo = (pm || gm) ? ws.res_lo : (xm ? ws.xn_lo : ((sfold && acc) ? ws.res_lo : nullptr));      // sfold in the accurate mode: lo plane of the residual for the folded consumers
-  if (fold && (stages & 2) && !embed_emitted_stats) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, M, D, s, nullptr, nullptr, 1));
-  if (!xm) plo2 = nullptr;
-  if (xm) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, M, D, s, ws.xn_lo, plo2));      // embeddings -> planes + wide statistics
-  if (gm) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, M, D, s, ws.res_lo, nullptr));
-  if (sfold && (stages & 2) && !(stages & 1) && !(ready & 2)) HIP_TRY(sf_launch_split(ws.resid, ws.res_bf, acc ? ws.res_lo : nullptr, (size_t)M * D, s));   // sf_layers entry
-  for (int li = la; li < lb && (stages & 2); ++li) {
-    const DevLayer& l = e->layers[li];
-    if (hidden_states)
-      HIP_TRY(hipMemcpyAsync(hidden_states + li * hs_stride, ws.resid, hs_stride * 4, hipMemcpyDeviceToDevice, s));
-    // ---- temporal attention (modeling:937-958) ---------------------------------------------------
-    if (!anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_t.g, l.ln_t.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
-    void* tq = layer_tqkv ? layer_tqkv[li] : ws.tqkv;
-    // accurate mode, whole short clip (no cache): hi + lo bf16 planes for the DMA kernel, like the spatial attention below
-    const bool tplanes = acc && !layer_tqkv && cap == T && t_past == 0 && sf_temporal_planes_ok(T, T);
-    const size_t tsz = tplanes ? 2 : esz;
-    // lab library, SF_QKV_FUSED=1 (bf16 mode, whole 16-frame clips, no cache): qkv projection + temporal attention in ONE launch
-    // (sf_gemm_qkv.hip; bit-identical, -0.27 ms of kernel time per forward under rocprof, +0.07 ms on the wall clock: docs/history.md H.4)
-    bool t_fused_attn = false;
-#ifdef SF_LAB
-    if (fold && !acc && !layer_tqkv && cap == T && t_past == 0 && tk == T && !sp && l.t_qkv_fp.w_hi) {
-      SfQkvArgs q;
-      memset(&q, 0, sizeof(q));
-      q.a = ln_in; q.w = l.t_qkv_fp.w_hi; q.bias = l.t_qkv_fp.bias; q.ln_s = l.t_qkv_fp.ln_s; q.ln_stats = fold_st; q.ln_eps = c.layer_norm_eps;
-      q.M = M; q.K = D; q.D = D; q.B = B; q.T = T; q.NP = N; q.out = ws.ctx_hi; q.scale = scale; q.causal = c.enable_causal_temporal;
-      if (sf_gemm_qkv_supported(q, true)) {
-        HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_gemm_qkv(q, true, s); }));
-        t_fused_attn = true;
-      }
-    }
-#endif
-#ifdef SF_LAB
-    // lab library, SF_STREAM_QKV_FUSE=1 (one streamed frame per stream, bf16 mode, cache of <= 64 frames): projection + cache append +
-    // single-query attention in one launch (tools/lab/sf_stream_fused.hip; bit-identical, 15.0 against 6.1 + 7.4 us: a CU's ingest)
-    if (!t_fused_attn && sfold && !acc && T == 1 && layer_tqkv && l.t_qkv_f.ln_s) {
-      SfStreamQkvArgs q;
-      memset(&q, 0, sizeof(q));
-      q.a = ln_in; q.w_frag = l.t_qkv_f.w_frag; q.bias = l.t_qkv_f.bias; q.ln_s = l.t_qkv_f.ln_s; q.ln_eps = c.layer_norm_eps;
-      q.M = M; q.K = l.t_qkv_f.K; q.D = D; q.heads = heads; q.N = N;
-      q.cache = (bf16_t*)tq; q.cap = cap; q.slot = slot; q.Tk = tk; q.pos_dev = sp ? &sp->slot : nullptr;
-      q.ctx = ws.ctx_hi; q.scale = scale;
-      if (l.t_qkv_f.N == 3 * D && sf_stream_qkv_decode_supported(q)) {
-        HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_stream_qkv_decode(q, s); }));
-        t_fused_attn = true;
-      }
-    }
-#endif
-    if (!t_fused_attn)
-    HIP_TRY(run_linear(e, anyfold ? l.t_qkv_f : l.t_qkv, ln_in, ln_in_lo, M, tplanes ? (int)SF_EPI_BF16 : qkv_epi, s, (float*)tq, (bf16_t*)tq,
-                       tplanes ? (bf16_t*)tq + (size_t)M * 3 * D : nullptr, nullptr, 1.f,
-                       3 * D, T * N, cap * N, sp ? 0 : slot * N, fold_st, nullptr, sfold, sp ? &sp->slot : nullptr, N));
-    if (!t_fused_attn) {
-      SfAttnArgs a;
-      memset(&a, 0, sizeof(a));
-      a.q = tq; a.k = (char*)tq + (size_t)D * tsz; a.v = (char*)tq + (size_t)2 * D * tsz;
-      a.in_is_f32 = acc && !tplanes; a.lo_plane_off = tplanes ? (long long)M * 3 * D : 0;
-      a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = scale; a.head_dim = e->hd;
-      a.N = N; a.B = B; a.Tq = T; a.Tk = tk; a.Tcap = cap; a.t_past = tk - T;
-      a.causal = c.enable_causal_temporal; a.Tq_cap = cap; a.q_t0 = slot;
-      a.pos_dev = sp ? &sp->slot : nullptr;
-      a.ctx_hi = ws.ctx_hi; a.ctx_lo = ws.ctx_lo; a.D = D;
-      HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_temporal_attention(a, acc, s); }));
-    }
-    if (e->fused_temporal) {
-      HIP_TRY(prof_span(e, 0, s, [&]() {
-        return run_linear(e, l.t_fused, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_RESID_F32, s, rplanes ? nullptr : ws.resid, fold_hi, plo, rplanes ? nullptr : ws.resid, l.gate_tanh,
-                          0, 0, 0, 0, nullptr, fold_st, false, nullptr, 0, rplanes ? fold_hi : nullptr, plo, plo2); }));
-    } else {
-      HIP_TRY(run_linear(e, l.t_out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_BF16, s, nullptr, ws.tmp_hi, ws.tmp_lo));
-      HIP_TRY(run_linear(e, l.t_dense, ws.tmp_hi, ws.tmp_lo, M, SF_EPI_RESID_F32, s, rplanes ? nullptr : ws.resid, fold_hi, plo, rplanes ? nullptr : ws.resid, l.gate_tanh,
-                         0, 0, 0, 0, nullptr, fold_st, false, nullptr, 0, rplanes ? fold_hi : nullptr, plo, plo2));
-    }
-    // ---- spatial attention (modeling:962-996) ------------------------------------------------------
-    if (!anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_b.g, l.ln_b.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
-    // accurate mode: q / k / v leave the GEMM as hi + lo bf16 planes (the bytes of the fp32 tensor) when the DMA attention
-    // kernel can take them; fp32 otherwise (probabilities requested, more than 224 tokens per frame)
-    const bool planes = acc && sf_spatial_planes_ok(N, attentions != nullptr);
-    const size_t sesz = planes ? 2 : esz;
-    // lab library, SF_SQKV_PANEL=1: the folded spatial qkv projection on the panel tile (768 tiles of 196 x 384 = three whole rounds)
-    bool s_qkv_panel = false;
-#ifdef SF_LAB
-    static const bool s_panel_on = SF_LAB_SWITCH("SF_SQKV_PANEL") != 0;
-    if (s_panel_on && fold && !acc && qkv_epi == SF_EPI_BF16 && l.s_qkv_f.ln_s) {
-      SfQkvArgs q;
-      memset(&q, 0, sizeof(q));
-      q.a = ln_in; q.w = l.s_qkv_f.w_hi; q.bias = l.s_qkv_f.bias; q.ln_s = l.s_qkv_f.ln_s; q.ln_stats = fold_st; q.ln_eps = c.layer_norm_eps;
-      q.M = M; q.K = D; q.D = D; q.out = (bf16_t*)ws.qkv;
-      if (sf_gemm_qkv_supported(q, false)) {
-        HIP_TRY(sf_launch_gemm_qkv(q, false, s));
-        s_qkv_panel = true;
-      }
-    }
-#endif
-    if (!s_qkv_panel)
-    HIP_TRY(run_linear(e, anyfold ? l.s_qkv_f : l.s_qkv, ln_in, ln_in_lo, M, planes ? (int)SF_EPI_BF16 : qkv_epi, s, (float*)ws.qkv, (bf16_t*)ws.qkv,
-                       planes ? (bf16_t*)ws.qkv + (size_t)M * 3 * D : nullptr, nullptr, 1.f, 0, 0, 0, 0, fold_st, nullptr, sfold));
-    {
-      SfAttnArgs a;
-      memset(&a, 0, sizeof(a));
-      a.q = ws.qkv; a.k = (char*)ws.qkv + (size_t)D * sesz; a.v = (char*)ws.qkv + (size_t)2 * D * sesz;
-      a.in_is_f32 = acc && !planes; a.lo_plane_off = planes ? (long long)M * 3 * D : 0;
-      a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = scale; a.head_dim = e->hd;
-      a.N = N; a.frames = F; a.ctx_hi = ws.ctx_hi; a.ctx_lo = ws.ctx_lo; a.D = D;
-      a.probs = attentions ? attentions + (size_t)(li - la) * F * heads * N * N : nullptr;
-      HIP_TRY(prof_span(e, 2, s, [&]() { return sf_launch_spatial_attention(a, acc, s); }));
-    }
-    HIP_TRY(prof_span(e, 0, s, [&]() {
-      return run_linear(e, l.s_out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_RESID_F32, s, rplanes ? nullptr : ws.resid, fold_hi, plo, rplanes ? nullptr : ws.resid, 1.f,
-                        0, 0, 0, 0, nullptr, fold_st, false, nullptr, 0, rplanes ? fold_hi : nullptr, plo, plo2); }));
-    // ---- MLP (modeling:997-1000) ---------------------------------------------------------------------
-    if (!anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_a.g, l.ln_a.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
-    HIP_TRY(run_linear(e, anyfold ? l.up_f : l.up, ln_in, ln_in_lo, M, SF_EPI_ACT_BF16, s, nullptr, ws.mid_hi, ws.mid_lo, nullptr, 1.f,
-                       0, 0, 0, 0, fold_st, nullptr, sfold));
-    HIP_TRY(prof_span(e, 1, s, [&]() {
-      return run_linear(e, l.down, ws.mid_hi, ws.mid_lo, M, SF_EPI_RESID_F32, s, rplanes ? nullptr : ws.resid, fold_hi, plo, rplanes ? nullptr : ws.resid, 1.f,
-                        0, 0, 0, 0, nullptr, fold_st, false, nullptr, 0, rplanes ? fold_hi : nullptr, plo, plo2); }));
-  }
-  if (hidden_states && (stages & 2) && lb == e->L)
-    HIP_TRY(hipMemcpyAsync(hidden_states + (size_t)e->L * hs_stride, ws.resid, hs_stride * 4, hipMemcpyDeviceToDevice, s));
-  if (!(stages & 12)) return SF_OK;
-  // ---- post LayerNorm + pooling head (modeling:1330-1340, 1141-1154) -------------------------------
-  // (the head reads the fp32 tokens: no bf16 copy of the normalised rows is written any more)
-  if (stages & 4)       // pm: the rows arrive as the two planes of the residual stream
-    HIP_TRY(sf_launch_layernorm(ws.resid, e->post_ln.g, e->post_ln.b, last_hidden, nullptr, nullptr, M, D, c.layer_norm_eps, s,
-                                rplanes ? ws.xn_hi : nullptr, plo, plo2, sp ? &sp->lhs : nullptr));   // sp: straight into the caller's tensor
-  // stage 8: the head alone on tokens the caller has already normalised (model.head(x)): they sit in ws.resid
-  if (pooler) {
-    // The probe attention without projecting the tokens (sf_pool_head.hip): scores = x . U, z_h = sum_n p_hn x_n on the fp32
-    // tokens, ctx_h = Wv_h z_h + bv_h — bf16x3 / fp32 arithmetic in BOTH modes (the [M, 2D] k / v tensor and its 59 GFLOP are gone).
-    const bool hacc = !acc;          // the head's one-row-per-frame tensors keep hi + lo planes in both modes (force_split in bf16 mode)
-    {
-      const float* tok = (stages & 4) ? last_hidden : ws.resid;
-      const bool rows = sf_head_rows_ok(e, F);
-      if (e->hd != 64 || D > 1024) {      // widths the MFMA probe kernels do not cover: the whole probe attention of a frame in one fp32 workgroup
-        SfPoolGenArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.x = tok; ga.x_ind = (sp && (stages & 4)) ? reinterpret_cast<const float* const*>(&sp->lhs) : nullptr;
-        ga.u = e->head_u; ga.wv = e->head_wv; ga.ldw = D; ga.bv = e->head_bv;
-        ga.F = F; ga.N = N; ga.heads = heads; ga.hd = e->hd; ga.D = D;
-        ga.scratch = ws.pool_z;
-        if (rows) ga.ctx_f32 = ws.head_ctx; else { ga.ctx_hi = ws.pc_hi; ga.ctx_lo = ws.pc_lo; }
-        HIP_TRY(sf_launch_pool_generic(ga, s));
-      } else {
-      SfPoolArgs pa;
-      memset(&pa, 0, sizeof(pa));
-      pa.x = tok; pa.x_ind = (sp && (stages & 4)) ? reinterpret_cast<const float* const*>(&sp->lhs) : nullptr;
-      pa.u_hi = e->head_u_hi; pa.u_lo = e->head_u_lo; pa.zpart = ws.pool_z; pa.ml = ws.pool_ml;
-      pa.F = F; pa.N = N; pa.heads = heads; pa.D = D; pa.S = sf_pool_splits(F, N, heads); pa.normalize = pa.S == 1;
-      HIP_TRY(sf_launch_pool_probe(pa, s));
-      SfPoolCtxArgs ca;
-      memset(&ca, 0, sizeof(ca));
-      ca.zpart = ws.pool_z; ca.ml = ws.pool_ml; ca.wv = e->head_wv; ca.ldw = D; ca.bv = e->head_bv;
-      ca.ctx_hi = ws.pc_hi; ca.ctx_lo = ws.pc_lo; ca.F = F; ca.heads = heads; ca.D = D; ca.S = pa.S;
-      if (rows) { ca.ctx_hi = ca.ctx_lo = nullptr; ca.ctx_f32 = ws.head_ctx; }
-      HIP_TRY(sf_launch_pool_ctx(ca, s));
-      }
-      if (rows) {
-        // One to four rows (streamed frames): the per-frame tail as three row-vector launches with fp32 activations — out_proj,
-        // LayerNorm + fc1 + GELU, fc2 + residual (written straight into the caller's pooler_output inside the position-free graph)
-        SfRowLinArgs r;
-        memset(&r, 0, sizeof(r));
-        r.F = F; r.act = -1;
-        r.x = ws.head_ctx; r.ldx = D; r.K = D; r.N = D; r.w_hi = e->head_out.w_hi; r.w_lo = e->head_out.w_lo; r.bias = e->head_out.bias;
-        r.out = ws.attn_out; r.ldo = D;
-        HIP_TRY(sf_launch_rowlin(r, s));
-        r.x = ws.attn_out; r.ln_g = e->head_ln.g; r.ln_b = e->head_ln.b; r.ln_eps = c.layer_norm_eps; r.N = e->I; r.act = c.hidden_act;
-        r.w_hi = e->head_fc1.w_hi; r.w_lo = e->head_fc1.w_lo; r.bias = e->head_fc1.bias; r.out = ws.head_mid; r.ldo = e->I;
-        HIP_TRY(sf_launch_rowlin(r, s));
-        r.x = ws.head_mid; r.ldx = e->I; r.K = e->I; r.N = D; r.ln_g = r.ln_b = nullptr; r.act = -1;
-        r.w_hi = e->head_fc2.w_hi; r.w_lo = e->head_fc2.w_lo; r.bias = e->head_fc2.bias; r.resid = ws.attn_out; r.ldr = D;
-        r.out = pooler; r.ldo = D; r.out_ind = sp ? &sp->pooler : nullptr;
-        HIP_TRY(sf_launch_rowlin(r, s));
-        return SF_OK;
-      }
-    }
-    // one row per frame from here on (F rows: 0.03 % of the forward's FLOPs): three bf16 products per operand pair in BOTH modes —
-    // pooler_output is the product both loss heads and the feature dumps consume, and the bf16 mode's own head added 1.5e-2 of
-    // max-abs error to it on top of what the encoder's tokens carry (tools/pool_err.py)
-    HIP_TRY(run_linear(e, e->head_out, ws.pc_hi, ws.pc_lo, F, SF_EPI_F32, s, ws.attn_out, nullptr, nullptr, nullptr, 1.f, 0, 0, 0, 0, nullptr, nullptr,
-                       false, nullptr, 0, nullptr, nullptr, nullptr, hacc));
-    HIP_TRY(sf_launch_layernorm(ws.attn_out, e->head_ln.g, e->head_ln.b, nullptr, ws.hn_hi, (acc || hacc) ? ws.hn_lo : nullptr, F, D, c.layer_norm_eps, s));
-    HIP_TRY(run_linear(e, e->head_fc1, ws.hn_hi, ws.hn_lo, F, SF_EPI_ACT_BF16, s, nullptr, ws.hm_hi, ws.hm_lo, nullptr, 1.f, 0, 0, 0, 0, nullptr, nullptr,
-                       false, nullptr, 0, nullptr, nullptr, nullptr, hacc));
-    HIP_TRY(run_linear(e, e->head_fc2, ws.hm_hi, ws.hm_lo, F, SF_EPI_RESID_F32, s, pooler, nullptr, nullptr, ws.attn_out, 1.f, 0, 0, 0, 0, nullptr, nullptr,
-                       false, nullptr, 0, nullptr, nullptr, nullptr, hacc));
+
+  // ---- the schedule of the layers
+  p.tplanes = acc && !rq.layer_tqkv && rq.cap == T && rq.t_past == 0 && sf_temporal_planes_ok(T, T);
+  p.planes = acc && sf_spatial_planes_ok(N, rq.attentions != nullptr);
+  p.tsz = p.tplanes ? 2 : p.esz; p.sesz = p.planes ? 2 : p.esz;
+  p.fold = stats_fold && !streaming;
+  p.sfold = !p.fold && small_bufs;
+  p.xm = p.tplanes && p.planes && !streaming && complete && ln_fold_acc_ok(e, M);
+  p.gm = !acc && !p.fold && !p.sfold && !streaming && complete && ws.res_lo != nullptr && ln_fold_g256_ok(e, M);
+  p.anyfold = p.fold || p.sfold || p.xm || p.gm;
+  p.rplanes = p.pm || p.xm || p.gm;
+  p.seed_stats = p.fold && (stages & 2) && p.embed_route != EMBED_TILE && p.embed_route != EMBED_PANEL;
+  p.seed_split = p.sfold && (stages & 2) && !(stages & 1) && !(rq.ready & 2);
+  p.resid = p.rplanes ? nullptr : ws.resid;
+  p.fold_hi = (p.fold || p.xm || p.gm) ? ws.xn_hi : (p.sfold ? ws.res_bf : nullptr);
+  p.fold_st = (p.fold || p.xm || p.gm) ? ws.ln_stats : nullptr;
+  p.plo = (p.pm || p.gm) ? ws.res_lo : (p.xm ? ws.xn_lo : ((p.sfold && acc) ? ws.res_lo : nullptr));
+  p.plo2 = (p.xm && !sf_sw(SW_ACC_TWO_PLANES)) ? ws.res_lo2 : nullptr;      // A/B: drop the third plane (max-abs 1.4e-4 instead of 5e-5)
+  p.ln_in = p.sfold ? ws.res_bf : ws.xn_hi;
+  p.ln_in_lo = (p.sfold && acc) ? ws.res_lo : ws.xn_lo;
+
+  p.head_generic = e->hd != 64 || D > 1024;
+  p.head_rows = rq.pooler && sf_head_rows_ok(e, p.F);
+  return p;
+}
+
+// a residual producer: x += alpha (A W^T + b) in the plan's form of the residual stream, with what the next folded consumer needs
+static hipError_t launch_resid_linear(const sf_encoder* e, const ForwardPlan& p, const DevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo,
+                                      float alpha, hipStream_t s) {
+  SfGemmArgs g = linear_args(e, lin, a_hi, a_lo, p.M, SF_EPI_RESID_F32, p.acc);
+  g.alpha = alpha;
+  g.resid = p.resid; g.out_f32 = p.resid;
+  g.resid_hi = p.rplanes ? p.fold_hi : nullptr; g.resid_lo = p.plo; g.resid_lo2 = p.plo2;
+  g.out_hi = p.fold_hi; g.out_lo = p.plo; g.out_lo2 = p.plo2;       // planes: in place; otherwise the bf16 copy of the new rows
+  g.ln_stats_out = p.fold_st;
+  return sf_launch_gemm(g, p.acc, s);
+}
+
+// one of the three Linears behind a LayerNorm: the folded weights on the plan's operand, or the plain ones on LayerNorm's output
+static SfGemmArgs ln_linear_args(const sf_encoder* e, const ForwardPlan& p, const DevLinear& plain, const DevLinear& folded, int epi) {
+  const DevLinear& lin = p.anyfold ? folded : plain;
+  SfGemmArgs g = linear_args(e, lin, p.ln_in, p.ln_in_lo, p.M, epi, p.acc);
+  g.ln_stats = p.fold_st; g.ln_inkernel = p.sfold;
+  g.ln_s = (p.fold_st || p.sfold) ? lin.ln_s : nullptr;
+  return g;
+}
+// q / k / v leave their GEMM as bf16, fp32 (accurate), or hi + lo bf16 planes in the bytes of the fp32 tensor
+static void set_qkv_out(SfGemmArgs& g, void* qkv, bool planes, const ForwardPlan& p) {
+  if (planes) g.epi = SF_EPI_BF16;
+  g.out_f32 = (float*)qkv; g.out_hi = (bf16_t*)qkv;
+  g.out_lo = planes ? (bf16_t*)qkv + (size_t)p.M * g.N : nullptr;
+}
+static void set_qkv_in(SfAttnArgs& a, const sf_encoder* e, void* qkv, bool planes, size_t esz, const ForwardPlan& p, const Workspace& ws) {
+  const int D = e->D;
+  a.q = qkv; a.k = (char*)qkv + (size_t)D * esz; a.v = (char*)qkv + (size_t)2 * D * esz;
+  a.in_is_f32 = p.acc && !planes; a.lo_plane_off = planes ? (long long)p.M * 3 * D : 0;
+  a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = e->cfg.num_attention_heads; a.scale = p.scale; a.head_dim = e->hd;
+  a.N = p.N; a.ctx_hi = ws.ctx_hi; a.ctx_lo = ws.ctx_lo; a.D = D;
+}
+
+// ---- stage 1: patch + position + time embeddings -> ws.resid (pm: -> the planes)
+static int forward_embeddings(sf_encoder* e, const ForwardPlan& p, const Workspace& ws, hipStream_t s) {
+  const ForwardRequest& rq = p.rq;
+  const sf_config& c = e->cfg;
+  SfRowIndex idx;
+  int rc = time_rows(e, p.t_row, rq.T, rq.streaming, &idx);
+  if (rc) return rc;
+  if (rq.sp) { for (int t = 0; t < rq.T; ++t) idx.idx[t] = t; }
+  if (!p.time_folded) HIP_TRY(sf_launch_gather_rows(e->time_tab, ws.te_rows, idx, e->D, s, rq.sp ? &rq.sp->t_row : nullptr));
+  if (!(rq.ready & 1))
+    HIP_TRY(sf_launch_patchify(rq.pixels, rq.pixel_dtype == SF_U8 ? 2 : (rq.pixel_dtype == SF_BF16 ? 1 : 0), p.patches, ws.xn_lo, p.F, c.num_channels, rq.H, rq.W,
+                               c.patch_size, s, &e->pixel_norm, nullptr, nullptr, nullptr, e->Kp));
+  if (p.embed_route == EMBED_TILE) {
+    HIP_TRY(sf_launch_gemm_tile(p.embed, s));
+  } else if (p.embed_route == EMBED_PANEL) {
+    HIP_TRY(sf_launch_pos_time_table(rq.pos_dev ? rq.pos_dev : e->pos, ws.te_rows, ws.embed_tab, rq.T, p.N, e->D, s));
+    HIP_TRY(sf_launch_gemm_panel(p.embed, s));
+  } else {
+    HIP_TRY(sf_launch_gemm(p.embed, p.acc, s));
   }
   return SF_OK;
+}
+
+// ---- stage 2: one layer on the residual stream
+static int forward_layer(sf_encoder* e, const ForwardPlan& p, const Workspace& ws, int li, hipStream_t s) {
+  const ForwardRequest& rq = p.rq;
+  const sf_config& c = e->cfg;
+  const DevLayer& l = e->layers[li];
+  const int D = e->D, M = p.M, N = p.N, T = rq.T, heads = c.num_attention_heads;
+  const bool acc = p.acc;
+  const SfStreamParams* sp = rq.sp;
+  if (rq.hidden_states)
+    HIP_TRY(hipMemcpyAsync(rq.hidden_states + (size_t)li * M * D, ws.resid, (size_t)M * D * 4, hipMemcpyDeviceToDevice, s));
+  // ---- temporal attention (modeling:937-958) ---------------------------------------------------
+  if (!p.anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_t.g, l.ln_t.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
+  void* tq = rq.layer_tqkv ? rq.layer_tqkv[li] : ws.tqkv;
+  // lab library, SF_QKV_FUSED=1 (bf16 mode, whole 16-frame clips, no cache): qkv projection + temporal attention in ONE launch
+  // (sf_gemm_qkv.hip; bit-identical, -0.27 ms of kernel time per forward under rocprof, +0.07 ms on the wall clock: docs/history.md H.4)
+  bool t_fused_attn = false;
+#ifdef SF_LAB
+  if (p.fold && !acc && !rq.layer_tqkv && rq.cap == T && rq.t_past == 0 && p.tk == T && !sp && l.t_qkv_fp.w_hi) {
+    SfQkvArgs q;
+    memset(&q, 0, sizeof(q));
+    q.a = p.ln_in; q.w = l.t_qkv_fp.w_hi; q.bias = l.t_qkv_fp.bias; q.ln_s = l.t_qkv_fp.ln_s; q.ln_stats = p.fold_st; q.ln_eps = c.layer_norm_eps;
+    q.M = M; q.K = D; q.D = D; q.B = rq.B; q.T = T; q.NP = N; q.out = ws.ctx_hi; q.scale = p.scale; q.causal = c.enable_causal_temporal;
+    if (sf_gemm_qkv_supported(q, true)) {
+      HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_gemm_qkv(q, true, s); }));
+      t_fused_attn = true;
+    }
+  }
+#endif
+#ifdef SF_LAB
+  // lab library, SF_STREAM_QKV_FUSE=1 (one streamed frame per stream, bf16 mode, cache of <= 64 frames): projection + cache append +
+  // single-query attention in one launch (tools/lab/sf_stream_fused.hip; bit-identical, 15.0 against 6.1 + 7.4 us: a CU's ingest)
+  if (!t_fused_attn && p.sfold && !acc && T == 1 && rq.layer_tqkv && l.t_qkv_f.ln_s) {
+    SfStreamQkvArgs q;
+    memset(&q, 0, sizeof(q));
+    q.a = p.ln_in; q.w_frag = l.t_qkv_f.w_frag; q.bias = l.t_qkv_f.bias; q.ln_s = l.t_qkv_f.ln_s; q.ln_eps = c.layer_norm_eps;
+    q.M = M; q.K = l.t_qkv_f.K; q.D = D; q.heads = heads; q.N = N;
+    q.cache = (bf16_t*)tq; q.cap = rq.cap; q.slot = p.slot; q.Tk = p.tk; q.pos_dev = sp ? &sp->slot : nullptr;
+    q.ctx = ws.ctx_hi; q.scale = p.scale;
+    if (l.t_qkv_f.N == 3 * D && sf_stream_qkv_decode_supported(q)) {
+      HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_stream_qkv_decode(q, s); }));
+      t_fused_attn = true;
+    }
+  }
+#endif
+  if (!t_fused_attn) {
+    SfGemmArgs g = ln_linear_args(e, p, l.t_qkv, l.t_qkv_f, p.qkv_epi);
+    set_qkv_out(g, tq, p.tplanes, p);
+    // the new frames' rows go to their slots of the [B, cap, N, 3D] cache (position from the device block inside the position-free graph)
+    g.grp_rows = T * N; g.grp_stride = rq.cap * N; g.grp_off = sp ? 0 : p.slot * N;
+    g.grp_off_dev = sp ? &sp->slot : nullptr; g.grp_off_scale = N;
+    if (g.grp_stride == g.grp_rows && g.grp_off == 0 && !g.grp_off_dev) g.grp_rows = 0;   // identity remap (full clip)
+    HIP_TRY(sf_launch_gemm(g, acc, s));
+    SfAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    set_qkv_in(a, e, tq, p.tplanes, p.tsz, p, ws);
+    a.B = rq.B; a.Tq = T; a.Tk = p.tk; a.Tcap = rq.cap; a.t_past = p.tk - T;
+    a.causal = c.enable_causal_temporal; a.Tq_cap = rq.cap; a.q_t0 = p.slot;
+    a.pos_dev = sp ? &sp->slot : nullptr;
+    HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_temporal_attention(a, acc, s); }));
+  }
+  if (e->fused_temporal) {
+    HIP_TRY(prof_span(e, 0, s, [&]() { return launch_resid_linear(e, p, l.t_fused, ws.ctx_hi, ws.ctx_lo, l.gate_tanh, s); }));
+  } else {
+    SfGemmArgs g = linear_args(e, l.t_out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_BF16, acc);
+    g.out_hi = ws.tmp_hi; g.out_lo = ws.tmp_lo;
+    HIP_TRY(sf_launch_gemm(g, acc, s));
+    HIP_TRY(launch_resid_linear(e, p, l.t_dense, ws.tmp_hi, ws.tmp_lo, l.gate_tanh, s));
+  }
+  // ---- spatial attention (modeling:962-996) ------------------------------------------------------
+  if (!p.anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_b.g, l.ln_b.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
+  // lab library, SF_SQKV_PANEL=1: the folded spatial qkv projection on the panel tile (768 tiles of 196 x 384 = three whole rounds)
+  bool s_qkv_panel = false;
+#ifdef SF_LAB
+  static const bool s_panel_on = SF_LAB_SWITCH("SF_SQKV_PANEL") != 0;
+  if (s_panel_on && p.fold && !acc && p.qkv_epi == SF_EPI_BF16 && l.s_qkv_f.ln_s) {
+    SfQkvArgs q;
+    memset(&q, 0, sizeof(q));
+    q.a = p.ln_in; q.w = l.s_qkv_f.w_hi; q.bias = l.s_qkv_f.bias; q.ln_s = l.s_qkv_f.ln_s; q.ln_stats = p.fold_st; q.ln_eps = c.layer_norm_eps;
+    q.M = M; q.K = D; q.D = D; q.out = (bf16_t*)ws.qkv;
+    if (sf_gemm_qkv_supported(q, false)) {
+      HIP_TRY(sf_launch_gemm_qkv(q, false, s));
+      s_qkv_panel = true;
+    }
+  }
+#endif
+  if (!s_qkv_panel) {
+    SfGemmArgs g = ln_linear_args(e, p, l.s_qkv, l.s_qkv_f, p.qkv_epi);
+    set_qkv_out(g, ws.qkv, p.planes, p);
+    HIP_TRY(sf_launch_gemm(g, acc, s));
+  }
+  {
+    SfAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    set_qkv_in(a, e, ws.qkv, p.planes, p.sesz, p, ws);
+    a.frames = p.F;
+    a.probs = rq.attentions ? rq.attentions + (size_t)(li - rq.la) * p.F * heads * N * N : nullptr;
+    HIP_TRY(prof_span(e, 2, s, [&]() { return sf_launch_spatial_attention(a, acc, s); }));
+  }
+  HIP_TRY(prof_span(e, 0, s, [&]() { return launch_resid_linear(e, p, l.s_out, ws.ctx_hi, ws.ctx_lo, 1.f, s); }));
+  // ---- MLP (modeling:997-1000) ---------------------------------------------------------------------
+  if (!p.anyfold) HIP_TRY(sf_launch_layernorm(ws.resid, l.ln_a.g, l.ln_a.b, nullptr, ws.xn_hi, ws.xn_lo, M, D, c.layer_norm_eps, s));
+  {
+    SfGemmArgs g = ln_linear_args(e, p, l.up, l.up_f, SF_EPI_ACT_BF16);
+    g.out_hi = ws.mid_hi; g.out_lo = ws.mid_lo;
+    HIP_TRY(sf_launch_gemm(g, acc, s));
+  }
+  HIP_TRY(prof_span(e, 1, s, [&]() { return launch_resid_linear(e, p, l.down, ws.mid_hi, ws.mid_lo, 1.f, s); }));
+  return SF_OK;
+}
+
+// ---- stages 4 / 8: post LayerNorm + pooling head (modeling:1330-1340, 1141-1154)
+// (the head reads the fp32 tokens: no bf16 copy of the normalised rows is written)
+static int forward_post_head(sf_encoder* e, const ForwardPlan& p, const Workspace& ws, hipStream_t s) {
+  const ForwardRequest& rq = p.rq;
+  const sf_config& c = e->cfg;
+  const int D = e->D, F = p.F, N = p.N, heads = c.num_attention_heads;
+  const SfStreamParams* sp = rq.sp;
+  if (rq.stages & 4)       // plane forms: the rows arrive as the planes of the residual stream
+    HIP_TRY(sf_launch_layernorm(ws.resid, e->post_ln.g, e->post_ln.b, rq.last_hidden, nullptr, nullptr, p.M, D, c.layer_norm_eps, s,
+                                p.rplanes ? ws.xn_hi : nullptr, p.plo, p.plo2, sp ? &sp->lhs : nullptr));   // sp: straight into the caller's tensor
+  if (!rq.pooler) return SF_OK;
+  // The probe attention without projecting the tokens (sf_pool_head.hip): scores = x . U, z_h = sum_n p_hn x_n on the fp32
+  // tokens, ctx_h = Wv_h z_h + bv_h — bf16x3 / fp32 arithmetic in BOTH modes (the [M, 2D] k / v tensor and its 59 GFLOP are gone).
+  // stage 8: the head alone on tokens the caller has already normalised (model.head(x)): they sit in ws.resid
+  const float* tok = (rq.stages & 4) ? rq.last_hidden : ws.resid;
+  const float* const* tok_ind = (sp && (rq.stages & 4)) ? reinterpret_cast<const float* const*>(&sp->lhs) : nullptr;
+  if (p.head_generic) {      // the whole probe attention of a frame in one fp32 workgroup
+    SfPoolGenArgs ga;
+    memset(&ga, 0, sizeof(ga));
+    ga.x = tok; ga.x_ind = tok_ind;
+    ga.u = e->head_u; ga.wv = e->head_wv; ga.ldw = D; ga.bv = e->head_bv;
+    ga.F = F; ga.N = N; ga.heads = heads; ga.hd = e->hd; ga.D = D;
+    ga.scratch = ws.pool_z;
+    if (p.head_rows) ga.ctx_f32 = ws.head_ctx; else { ga.ctx_hi = ws.pc_hi; ga.ctx_lo = ws.pc_lo; }
+    HIP_TRY(sf_launch_pool_generic(ga, s));
+  } else {
+    SfPoolArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.x = tok; pa.x_ind = tok_ind;
+    pa.u_hi = e->head_u_hi; pa.u_lo = e->head_u_lo; pa.zpart = ws.pool_z; pa.ml = ws.pool_ml;
+    pa.F = F; pa.N = N; pa.heads = heads; pa.D = D; pa.S = sf_pool_splits(F, N, heads); pa.normalize = pa.S == 1;
+    HIP_TRY(sf_launch_pool_probe(pa, s));
+    SfPoolCtxArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.zpart = ws.pool_z; ca.ml = ws.pool_ml; ca.wv = e->head_wv; ca.ldw = D; ca.bv = e->head_bv;
+    ca.ctx_hi = ws.pc_hi; ca.ctx_lo = ws.pc_lo; ca.F = F; ca.heads = heads; ca.D = D; ca.S = pa.S;
+    if (p.head_rows) { ca.ctx_hi = ca.ctx_lo = nullptr; ca.ctx_f32 = ws.head_ctx; }
+    HIP_TRY(sf_launch_pool_ctx(ca, s));
+  }
+  if (p.head_rows) {
+    // One to four rows (streamed frames): the per-frame tail as three row-vector launches with fp32 activations — out_proj,
+    // LayerNorm + fc1 + GELU, fc2 + residual (written straight into the caller's pooler_output inside the position-free graph)
+    SfRowLinArgs r;
+    memset(&r, 0, sizeof(r));
+    r.F = F; r.act = -1;
+    r.x = ws.head_ctx; r.ldx = D; r.K = D; r.N = D; r.w_hi = e->head_out.w_hi; r.w_lo = e->head_out.w_lo; r.bias = e->head_out.bias;
+    r.out = ws.attn_out; r.ldo = D;
+    HIP_TRY(sf_launch_rowlin(r, s));
+    r.x = ws.attn_out; r.ln_g = e->head_ln.g; r.ln_b = e->head_ln.b; r.ln_eps = c.layer_norm_eps; r.N = e->I; r.act = c.hidden_act;
+    r.w_hi = e->head_fc1.w_hi; r.w_lo = e->head_fc1.w_lo; r.bias = e->head_fc1.bias; r.out = ws.head_mid; r.ldo = e->I;
+    HIP_TRY(sf_launch_rowlin(r, s));
+    r.x = ws.head_mid; r.ldx = e->I; r.K = e->I; r.N = D; r.ln_g = r.ln_b = nullptr; r.act = -1;
+    r.w_hi = e->head_fc2.w_hi; r.w_lo = e->head_fc2.w_lo; r.bias = e->head_fc2.bias; r.resid = ws.attn_out; r.ldr = D;
+    r.out = rq.pooler; r.ldo = D; r.out_ind = sp ? &sp->pooler : nullptr;
+    HIP_TRY(sf_launch_rowlin(r, s));
+    return SF_OK;
+  }
+  // one row per frame from here on (F rows: 0.03 % of the forward's FLOPs): hi + lo planes and three bf16 products per operand pair in
+  // BOTH modes (the head's Linears keep their lo plane in bf16 mode too) — pooler_output is the product both loss heads and the feature
+  // dumps consume, and the bf16 mode's own head added 1.5e-2 of max-abs error to it on top of what the encoder's tokens carry
+  // (tools/pool_err.py)
+  SfGemmArgs g = linear_args(e, e->head_out, ws.pc_hi, ws.pc_lo, F, SF_EPI_F32, true);
+  g.out_f32 = ws.attn_out;
+  HIP_TRY(sf_launch_gemm(g, true, s));
+  HIP_TRY(sf_launch_layernorm(ws.attn_out, e->head_ln.g, e->head_ln.b, nullptr, ws.hn_hi, ws.hn_lo, F, D, c.layer_norm_eps, s));
+  g = linear_args(e, e->head_fc1, ws.hn_hi, ws.hn_lo, F, SF_EPI_ACT_BF16, true);
+  g.out_hi = ws.hm_hi; g.out_lo = ws.hm_lo;
+  HIP_TRY(sf_launch_gemm(g, true, s));
+  g = linear_args(e, e->head_fc2, ws.hm_hi, ws.hm_lo, F, SF_EPI_RESID_F32, true);
+  g.out_f32 = rq.pooler; g.resid = ws.attn_out;
+  HIP_TRY(sf_launch_gemm(g, true, s));
+  return SF_OK;
+}
+
+// One call of the encoder over T new frames, as planned.
+static int run_plan(sf_encoder* e, const ForwardPlan& p, const Workspace& ws, hipStream_t s) {
+  const ForwardRequest& rq = p.rq;
+  const size_t hs_stride = (size_t)p.M * e->D;
+  int rc;
+  if (p.zero_stats) HIP_TRY(hipMemsetAsync(ws.ln_stats, 0, (size_t)p.M * 8 * sizeof(float), s));
+  if ((rq.stages & 1) && (rc = forward_embeddings(e, p, ws, s))) return rc;
+  // what the schedule reads that the embeddings (or the caller of sf_layers) left as fp32 rows only
+  if (p.seed_stats) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, p.M, e->D, s, nullptr, nullptr, 1));
+  if (p.xm) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, p.M, e->D, s, ws.xn_lo, p.plo2));      // embeddings -> planes + wide statistics
+  if (p.gm) HIP_TRY(sf_launch_rowstats_cast(ws.resid, ws.xn_hi, ws.ln_stats, p.M, e->D, s, ws.res_lo, nullptr));
+  if (p.seed_split) HIP_TRY(sf_launch_split(ws.resid, ws.res_bf, p.acc ? ws.res_lo : nullptr, hs_stride, s));
+  if (rq.stages & 2) {
+    for (int li = rq.la; li < rq.lb; ++li)
+      if ((rc = forward_layer(e, p, ws, li, s))) return rc;
+    if (rq.hidden_states && rq.lb == e->L)
+      HIP_TRY(hipMemcpyAsync(rq.hidden_states + (size_t)e->L * hs_stride, ws.resid, hs_stride * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return (rq.stages & 12) ? forward_post_head(e, p, ws, s) : SF_OK;
+}
+static int run_forward(sf_encoder* e, const ForwardRequest& rq, const Workspace& ws, hipStream_t s) {
+  return run_plan(e, plan_forward(e, rq, ws), ws, s);
 }
 
 static int check_geometry(const sf_encoder* e, int B, int T, int H, int W, const float* pos_dev, int* N_out) {
@@ -1154,8 +1235,11 @@ static int forward_common(sf_encoder* e, const void* pixels, int pixel_dtype, in
   if (T > 256) return set_err(SF_ERR_INVALID, "at most 256 frames per clip");
   Workspace ws = carve(e, workspace, B, T, N, true);
   if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
-  return run_forward(e, pixels, pixel_dtype, B, T, H, W, last_hidden, pooler, hidden_states, pos_dev, ws, nullptr, T, 0,
-                     false, (hipStream_t)stream, attentions);
+  ForwardRequest rq;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = B; rq.T = T; rq.H = H; rq.W = W; rq.pos_dev = pos_dev;
+  rq.last_hidden = last_hidden; rq.pooler = pooler; rq.hidden_states = hidden_states; rq.attentions = attentions;
+  rq.cap = T;
+  return run_forward(e, rq, ws, (hipStream_t)stream);
 }
 
 extern "C" int sf_forward(sf_encoder* e, const void* pixels, int pixel_dtype, int B, int T, int H, int W,
@@ -1215,8 +1299,12 @@ static int stage_common(sf_encoder* e, const void* pixels, int pixel_dtype, int 
   Workspace ws = carve(e, workspace, B, T, N, true);
   if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
   ws.resid = hidden;                       // the caller's tensor IS the residual stream
-  return run_forward(e, pixels, pixel_dtype, B, T, H, W, last_hidden, pooler, nullptr, pos_dev, ws, nullptr, T, 0, false,
-                     (hipStream_t)stream, attentions, stages, la, lb);
+  ForwardRequest rq;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = B; rq.T = T; rq.H = H; rq.W = W; rq.pos_dev = pos_dev;
+  rq.last_hidden = last_hidden; rq.pooler = pooler; rq.attentions = attentions;
+  rq.cap = T;
+  rq.stages = stages; rq.la = la; rq.lb = lb;
+  return run_forward(e, rq, ws, (hipStream_t)stream);
 }
 
 extern "C" int sf_embed(sf_encoder* e, const void* pixels, int pixel_dtype, int B, int T, int H, int W, float* hidden_out,
@@ -1350,9 +1438,14 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
   (void)hipStreamIsCapturing(s, &cap);
   const bool graphs_off = sf_sw(SW_DISABLE_STREAM_GRAPH) != nullptr;
   const bool use_graph = !graphs_off && !hidden_states && !attentions && cap == hipStreamCaptureStatusNone && T_new < 256 && c->len < 65536;
+  // what the four forwards below share; each sets its outputs and its position
+  ForwardRequest rq;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = c->B; rq.T = T_new; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
+  rq.layer_tqkv = c->qkv.data(); rq.cap = c->cap; rq.streaming = true;
   if (!use_graph) {
-    rc = run_forward(e, pixels, pixel_dtype, c->B, T_new, c->H, c->W, last_hidden, pooler, hidden_states, pos_dev, ws,
-                     c->qkv.data(), c->cap, c->len, true, s, attentions, 7, 0, -1, 0, nullptr, pos);
+    rq.last_hidden = last_hidden; rq.pooler = pooler; rq.hidden_states = hidden_states; rq.attentions = attentions;
+    rq.t_past = c->len; rq.pos3 = pos;
+    rc = run_forward(e, rq, ws, s);
     if (rc == SF_OK) c->len += T_new;
     return rc;
   }
@@ -1377,8 +1470,9 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
   if (!c->warmed) {
     // first call of this cache: run eagerly once so that every lazy per-kernel set-up (hipFuncSetAttribute, device
     // queries) has happened before a capture is opened
-    rc = run_forward(e, pixels, pixel_dtype, c->B, T_new, c->H, c->W, last_hidden, pooler, nullptr, pos_dev, ws, c->qkv.data(),
-                     c->cap, c->len, true, s, nullptr, 7, 0, -1, 0, nullptr, pos);
+    rq.last_hidden = last_hidden; rq.pooler = pooler;
+    rq.t_past = c->len; rq.pos3 = pos;
+    rc = run_forward(e, rq, ws, s);
     if (rc == SF_OK) { c->len += T_new; c->warmed = true; }
     if (!g.exec) c->graphs.erase(key);
     return rc;
@@ -1393,6 +1487,9 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
     if (!c->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
     hipError_t pe = hipSuccess;
+    // the graph's forward: patch matrix already extracted, graph-owned outputs
+    rq.last_hidden = ws.lhs_stage; rq.pooler = pooler ? ws.pool_stage : nullptr;
+    rq.ready = 1;
     if (posfree) {
       // representative position of the class: selects the 64-key pass count; the kernels read the live one from dparams.
       // The patch extraction stays OUTSIDE the graph (it also delivers the parameter block, below); last_hidden_state is written
@@ -1402,13 +1499,14 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
       if (rep_tk > c->cap) rep_tk = c->cap;
       if (c->policy != 1 && rep_tk > nf) rep_tk = nf;
       const int rep3[3] = {0, 0, rep_tk};
-      rc = run_forward(e, pixels, pixel_dtype, c->B, T_new, c->H, c->W, ws.lhs_stage, pooler ? ws.pool_stage : nullptr, nullptr, pos_dev,
-                       ws, c->qkv.data(), c->cap, 0, true, c->cap_stream, nullptr, 7, 0, -1, 1, c->dparams, rep3);
-      if (rc == SF_OK && pooler && !sf_head_rows_ok(e, F))
+      rq.t_past = 0; rq.sp = c->dparams; rq.pos3 = rep3;
+      const ForwardPlan plan = plan_forward(e, rq, ws);
+      rc = run_plan(e, plan, ws, c->cap_stream);
+      if (rc == SF_OK && pooler && !plan.head_rows)      // the F-row tail left pooler_output in the workspace
         pe = sf_launch_copy2(nullptr, nullptr, 0, ws.pool_stage, nullptr, (size_t)F * e->D, c->cap_stream, c->dparams);
     } else {
-      rc = run_forward(e, pixels, pixel_dtype, c->B, T_new, c->H, c->W, ws.lhs_stage, pooler ? ws.pool_stage : nullptr, nullptr, pos_dev,
-                       ws, c->qkv.data(), c->cap, c->len, true, c->cap_stream, nullptr, 7, 0, -1, 1);
+      rq.t_past = c->len;
+      rc = run_forward(e, rq, ws, c->cap_stream);
     }
     hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
     if (rc != SF_OK || pe != hipSuccess || ce != hipSuccess || !graph) {
@@ -1612,16 +1710,17 @@ extern "C" int sf_bench_gemm(sf_encoder* e, int M, int which, int iters, void* w
   HIP_TRY(hipEventCreate(&e1));
   if (acc && epi == SF_EPI_RESID_F32) oh = nullptr;     // the accurate mode keeps no bf16 copy of the residual (no LayerNorm fold)
   // bf16 mode at BASELINE-sized M: the residual projections as the forward launches them — hi + lo planes in and out, LayerNorm
-  // row sums of the next Linear (run_forward's `pm`); fp32 residual + bf16 copy otherwise
-  const bool planes_off = sf_sw(SW_DISABLE_RESID_PLANES) != nullptr;
-  const bool pm = !planes_off && !acc && epi == SF_EPI_RESID_F32 && ln_fold_ok(e, M) && !ln_fold_tile_ok(e, M);
+  // row sums of the next Linear (ForwardPlan's `fold + pm`); fp32 residual + bf16 copy otherwise
+  const bool pm = !sf_sw(SW_DISABLE_RESID_PLANES) && !acc && epi == SF_EPI_RESID_F32 && !ln_fold_tile_ok(e, M) && !ln_fold_small_ok(e, M) &&
+                  ln_fold_panel_ok(e, M);
   float* st = pm ? c.take<float>((size_t)M * 8) : nullptr;
   if (c.off > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, c.off);
   if (st) HIP_TRY(hipMemsetAsync(st, 0, (size_t)M * 8 * sizeof(float), (hipStream_t)stream));
-  auto go = [&]() {
-    return pm ? run_linear(e, *lin, ah, al, M, epi, s, nullptr, oh, ol, nullptr, 0.f, 0, 0, 0, 0, nullptr, st, false, nullptr, 0, oh, ol)
-              : run_linear(e, *lin, ah, al, M, epi, s, of, oh, ol, of, 0.f);
-  };
+  SfGemmArgs g = linear_args(e, *lin, ah, al, M, epi, acc);
+  g.alpha = 0.f; g.out_hi = oh;
+  if (pm) { g.out_lo = ol; g.resid_hi = oh; g.resid_lo = ol; g.ln_stats_out = st; }
+  else { g.out_f32 = of; g.resid = of; g.out_lo = acc ? ol : nullptr; }
+  auto go = [&]() { return sf_launch_gemm(g, acc, s); };
   HIP_TRY(go());   // warm
   HIP_TRY(hipEventRecord(e0, s));
   for (int i = 0; i < iters; ++i) HIP_TRY(go());

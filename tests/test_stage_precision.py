@@ -67,7 +67,7 @@ def pool_splits(F, N):
     return S
 
 
-# (F, N, large-magnitude tokens).  F <= 4: the row-vector tail (sf_rowlin), F >= 5: the F-row run_linear tail.
+# (F, N, large-magnitude tokens).  F <= 4: the row-vector tail (sf_rowlin), F >= 5: the F-row GEMM tail.
 HEAD_CASES = [(1, 196, False), (2, 9, False), (3, 36, False), (4, 729, False), (4, 81, True),
               (7, 9, False), (9, 36, False), (6, 81, False), (5, 256, False), (64, 196, False), (8, 196, True)]
 # every split count meets both tails
