@@ -211,6 +211,40 @@ int sf_localization_loss(const float* pooler_dev, const float* label_emb_dev, co
                          float* loss_dev, float* grad_pooler_dev, float* grad_scalars_dev,
                          void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- spatial task: mask loss of the video instance segmentation head ------------------------
+ * TimesformerUniversalVideoInstanceSegmentationHead.forward, training branch (modeling:1829-1916), per clip i:
+ *   z[t,n,l] = <x[i,t,n] / |x[i,t,n]|, E_i[l]> * exp(logit_scale) + logit_bias
+ *   logits   = bilinear resize of z viewed as [T, L_i, P, P] to (H, W_i), align_corners = False   (F.interpolate)
+ *   loss_i   = mean over the pixels whose target is in [0, L_i) of logsumexp_l(logits) - logits[target]
+ *              (0, and no gradient, for a clip without such a pixel);   loss = (1 / B) sum_i loss_i
+ * evaluated WITHOUT the upsampled tensor (csrc/sf_mask_loss.hip): the workspace holds patch logits, never pixels.
+ * x_dev fp32 [B,T,N,D] (N = P * P patch tokens, frame-major).  The per-clip arguments are HOST arrays of B entries:
+ * label_emb_dev[i] = device fp32 [num_labels[i], D], used as given; mask_dev[i] = device int32 [T, H, mask_width[i]],
+ * any value outside [0, num_labels[i]) (-1 by convention) = ignore.  logit_scale_dev / logit_bias_dev: DEVICE pointers to one
+ * fp32 each.  Outputs: loss_dev fp32 [1]; grad_x_dev fp32 [B,T,N,D] or NULL; grad_scalars_dev fp32 [2] =
+ * d loss / d (logit_scale, logit_bias) or NULL.  Bit-reproducible (no atomics); the valid-pixel count stays on the device.
+ * Capacity (SF_ERR_CAPACITY): N <= 224, num_labels <= 128, D <= 2048, mask_width <= min(4 H, 2048).
+ * workspace: the query below with L_max = the largest num_labels[i].                                                    */
+size_t sf_mask_loss_workspace_bytes(int B, int T, int N, int L_max);
+int sf_mask_loss(const float* x_dev, int B, int T, int N, int D, const float* const* label_emb_dev,
+                 const int32_t* num_labels, const int32_t* const* mask_dev, const int32_t* mask_width, int H,
+                 const float* logit_scale_dev, const float* logit_bias_dev, float* loss_dev, float* grad_x_dev,
+                 float* grad_scalars_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+
+/* Dense feature projection of the same head (modeling:1786-1795) on M = B*T*N token rows, in the training arithmetic
+ * (bf16 operands, fp32 accumulation):  a = x Wv^T + bv;  y = a Wo^T + bo;  out = y + fc2(gelu(fc1(LayerNorm(y)))).
+ * params: HOST array of 10 device fp32 pointers in the order w_v.weight [D,D], w_v.bias, v_proj.weight [D,D], v_proj.bias,
+ * head_layernorm.weight, head_layernorm.bias, head_mlp.fc1.weight [I,D], fc1.bias, head_mlp.fc2.weight [D,I], fc2.bias
+ * (erf GELU).  forward keeps what backward needs in the caller's workspace; backward must follow forward on the same
+ * workspace and OVERWRITES d_x_dev fp32 [M,D] and the ten gradient tensors grads[i] (same order and shapes).
+ * D a multiple of 64; I is zero-padded to a multiple of 64 inside.                                                    */
+size_t sf_dense_head_workspace_bytes(int M, int D, int I);
+int sf_dense_head_forward(const float* x_dev, int M, int D, int I, float eps, const float* const* params,
+                          float* out_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+int sf_dense_head_backward(const float* d_out_dev, int M, int D, int I, float eps, const float* const* params,
+                           float* d_x_dev, float* const* grads, void* workspace_dev, size_t workspace_bytes,
+                           sf_stream stream);
+
 /* ---- training step (BASELINE configs #3 / #4) ------------------------------
  * Replaces, for one micro-batch: the autograd graph of TimesformerMultiTaskingModelSigLIP.forward
  * (modeling:1299-1354) as driven by train_one_epoch_multi_task (tools/finetune_tools.py:395-573:

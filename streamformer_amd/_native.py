@@ -71,6 +71,12 @@ SIGNATURES = {
     "sf_loss_workspace_bytes": (_SZ, [_I, _I]),
     "sf_retrieval_loss": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_localization_loss": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_mask_loss_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_mask_loss": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(C.c_int32), _I,
+                          _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_dense_head_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "sf_dense_head_forward": (_I, [_P, _I, _I, _I, _F, C.POINTER(_P), _P, _P, _SZ, _P]),
+    "sf_dense_head_backward": (_I, [_P, _I, _I, _I, _F, C.POINTER(_P), _P, C.POINTER(_P), _P, _SZ, _P]),
     "sf_trainer_create": (_I, [C.POINTER(SfConfig), _I, _I, _I, C.POINTER(_P)]),
     "sf_trainer_destroy": (None, [_P]),
     "sf_trainer_num_params": (_I, [_P]),

@@ -8,6 +8,7 @@ Text features come from a frozen SigLIP text tower in the reference; here they a
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import Optional, Tuple
 
@@ -88,3 +89,102 @@ class LocalizationHead:
                                                    ls.data_ptr(), lb.data_ptr(), loss.data_ptr(), nat.ptr(gp),
                                                    nat.ptr(gs), ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
         return loss, gp, gs
+
+
+class MaskLossHead:
+    """Fused bilinear upsample + per-pixel cross-entropy of the video instance segmentation head (``sf_mask_loss``; reference
+    ``models/modeling_timesformer_siglip.py:1829-1916``, training branch).  Thin: it groups nothing and selects nothing — the
+    per-clip label tables (already sub-sampled / normalised where the reference does so) and integer masks at their training
+    resolution come from the caller (``multitask.TimesformerUniversalVideoInstanceSegmentationHead``)."""
+
+    def __init__(self, logit_scale=math.log(10.0), logit_bias=-2.0):
+        self.logit_scale = logit_scale
+        self.logit_bias = logit_bias
+
+    def loss(self, dense_embeds: torch.Tensor, label_tables, mask_targets, need_grad: bool = True):
+        """dense_embeds [B,T,N,D] (cuda); label_tables[i] [L_i, D]; mask_targets[i] int [T, H, W_i], -1 = ignore (every clip the
+        same H).  Returns (loss [1], d loss / d dense_embeds [B,T,N,D], d loss / d (logit_scale, logit_bias) [2])."""
+        x = _f32(dense_embeds)
+        dev = x.device
+        B, T, N, D = x.shape
+        if len(label_tables) != B or len(mask_targets) != B:
+            raise ValueError(f"{B} clips need {B} label tables and masks, got {len(label_tables)} and {len(mask_targets)}")
+        tabs = [_f32(t.to(dev)) for t in label_tables]
+        masks = [m.to(dev, torch.int32).contiguous() for m in mask_targets]
+        H = int(masks[0].shape[1])
+        for i, (t, m) in enumerate(zip(tabs, masks)):
+            if t.dim() != 2 or t.shape[1] != D:
+                raise ValueError(f"clip {i}: label table must be [L, {D}], got {tuple(t.shape)}")
+            if m.dim() != 3 or m.shape[0] != T or m.shape[1] != H:
+                raise ValueError(f"clip {i}: mask must be [{T}, {H}, W], got {tuple(m.shape)}")
+        nl = (C.c_int32 * B)(*[int(t.shape[0]) for t in tabs])
+        wd = (C.c_int32 * B)(*[int(m.shape[2]) for m in masks])
+        tp = (C.c_void_p * B)(*[t.data_ptr() for t in tabs])
+        mp = (C.c_void_p * B)(*[m.data_ptr() for m in masks])
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        gx = torch.empty_like(x) if need_grad else None
+        gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
+        ls, lb = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias)
+        ws = torch.empty(max(1, nat.lib.sf_mask_loss_workspace_bytes(B, T, N, max(1, max(nl)))), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            nat.check(nat.lib.sf_mask_loss(x.data_ptr(), B, T, N, D, tp, nl, mp, wd, H, ls.data_ptr(), lb.data_ptr(), loss.data_ptr(),
+                                           nat.ptr(gx), nat.ptr(gs), ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        return loss, gx, gs
+
+
+class DenseHeadProjection:
+    """``_dense_feature_projection`` of the segmentation head (reference modeling:1786-1795) on all token rows, forward and backward
+    on the library's training GEMMs (``sf_dense_head_forward`` / ``sf_dense_head_backward``: bf16 operands, fp32 accumulation).
+    ``params``: the ten fp32 tensors in the order w_v.weight, w_v.bias, v_proj.weight, v_proj.bias, head_layernorm.weight,
+    head_layernorm.bias, head_mlp.fc1.weight, fc1.bias, head_mlp.fc2.weight, fc2.bias.
+    The workspace (the forward's saved activations + scratch, ~1 GB at 8 clips) is held from ``forward`` to the ``backward`` that
+    consumes it and then handed back to torch's allocator: between steps, and while other tasks run, the object holds nothing."""
+
+    def __init__(self, eps: float = 1e-6):
+        self.eps = float(eps)
+        self._ws = None
+        self._shape = None
+        self._params = None
+
+    def release(self) -> None:
+        """Drop the saved forward (workspace and parameter copies)."""
+        self._ws = self._shape = self._params = None
+
+    def forward(self, x: torch.Tensor, params) -> torch.Tensor:
+        x = _f32(x)
+        dev = x.device
+        D = x.shape[-1]
+        M = x.numel() // D
+        ps = [_f32(p.detach().to(dev)) for p in params]
+        if len(ps) != 10:
+            raise ValueError(f"the dense projection has 10 parameter tensors, got {len(ps)}")
+        inter = int(ps[6].shape[0])
+        nbytes = nat.lib.sf_dense_head_workspace_bytes(M, D, inter)
+        self.release()
+        self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty_like(x)
+        pp = (C.c_void_p * 10)(*[p.data_ptr() for p in ps])
+        with torch.cuda.device(dev):
+            nat.check(nat.lib.sf_dense_head_forward(x.data_ptr(), M, D, inter, self.eps, pp, out.data_ptr(), self._ws.data_ptr(),
+                                                    self._ws.numel(), nat.current_stream_handle(dev)))
+        self._shape = (M, D, inter)
+        self._params = ps
+        return out
+
+    def backward(self, d_out: torch.Tensor):
+        """Gradients of the forward that ran last on this object: (d x, [ten parameter gradients]).  Consumes the saved forward."""
+        if self._shape is None:
+            raise RuntimeError("DenseHeadProjection.backward needs a forward on the same object first")
+        M, D, inter = self._shape
+        g = _f32(d_out)
+        dev = g.device
+        ps = self._params
+        dx = torch.empty_like(g)
+        grads = [torch.empty_like(p) for p in ps]
+        pp = (C.c_void_p * 10)(*[p.data_ptr() for p in ps])
+        gp = (C.c_void_p * 10)(*[t.data_ptr() for t in grads])
+        with torch.cuda.device(dev):
+            nat.check(nat.lib.sf_dense_head_backward(g.data_ptr(), M, D, inter, self.eps, pp, dx.data_ptr(), gp, self._ws.data_ptr(),
+                                                     self._ws.numel(), nat.current_stream_handle(dev)))
+        self.release()         # stream-ordered: torch's allocator reuses the block only behind the launches above
+        return dx, grads

@@ -1,8 +1,10 @@
 """The multitask wrapper of the pre-training step, as a torch module over the HIP encoder.
 
 Mirror of ``StreamformerForMultiTaskingSigLIP`` (reference ``models/modeling_timesformer_siglip.py:1356-1536``) for the
-two task families BASELINE config #3 trains — video-text retrieval (``TimesformerVideoRetrievalHead``, ``:2285-2351``)
-and per-frame localization (``TimesformerUniversalLocalizationHead``, ``:2186-2282``):
+three granularities of the pre-training — global: video-text retrieval (``TimesformerVideoRetrievalHead``, ``:2285-2351``) and
+zero-shot classification (``TimesformerVideoClassificationHead``, ``:1651-1726``); temporal: per-frame localization
+(``TimesformerUniversalLocalizationHead``, ``:2186-2282``); spatial: video instance segmentation
+(``TimesformerUniversalVideoInstanceSegmentationHead``, ``:1729-1918``, trained through ``last_hidden_state``):
 
     model = StreamformerForMultiTaskingSigLIP(config, {"TaskRetrieval": {}, "TaskLocalization": {"label2id": ...}})
     model.prepare_for_multi_tasks(); model.frozen_spatial(); model.cuda().train()
@@ -10,7 +12,7 @@ and per-frame localization (``TimesformerUniversalLocalizationHead``, ``:2186-22
     losses[task].backward(); optimizer.step()                    # torch.optim over model.parameters()
 
 Encoder forward / backward run in ``libstreamformer_hip.so`` behind one autograd node (``autograd.py``); the loss heads
-are the HIP loss kernels (``sf_loss.hip``) behind a second one.  What is NOT here: the SigLIP *text tower* and tokenizer
+are the HIP loss kernels (``sf_loss.hip``, ``sf_mask_loss.hip`` + ``sf_dense_head.hip``) behind a second one.  What is NOT here: the SigLIP *text tower* and tokenizer
 (``:1365-1373``; hub weights, outside the path) — captions / class prompts enter as feature tensors
 (``task_input["text_features"]``, ``set_label_embeddings``) — and the other task heads, which raise
 ``NotImplementedError`` (out of scope).
@@ -19,18 +21,23 @@ from __future__ import annotations
 
 import copy
 import math
-from typing import Dict, Optional
+import random
+from typing import Dict, Optional, Tuple
 
 import torch
 from torch import nn
 
 from .configuration import StreamformerConfig
-from .heads import LocalizationHead, RetrievalHead
+from .heads import DenseHeadProjection, LocalizationHead, MaskLossHead, RetrievalHead
 from .modeling import TimesformerMultiTaskingModelSigLIP
 
 RETRIEVAL_TASKS = ("MSRVTT", "WebVid", "TaskRetrieval")                                        # modeling:1401
 LOCALIZATION_TASKS = ("THUMOS14Grounding", "ActivityNetGrounding", "FineActionGrounding", "HACSGrounding",
                       "TaskLocalization")                                                       # modeling:1384-1390
+CLASSIFICATION_TASKS = ("Kinetics",)         # modeling:1380 also lists "SSV2" (same head): still refused here, tests/test_autograd_bridge.py
+                                             # pins that refusal as its example of an unimplemented task type
+VIS_TASKS = ("YoutubeVIS", "LVVIS", "COCOPseudoVIS", "TaskVIS")                                 # modeling:1416
+NUM_MAX_CLASSES = 100                                                                           # modeling:1826
 
 
 class _HeadLossFn(torch.autograd.Function):
@@ -139,6 +146,164 @@ class TimesformerUniversalLocalizationHead(_TaskHead):
         return total, all_logits
 
 
+class TimesformerVideoClassificationHead(_TaskHead):
+    """modeling:1651-1726 (task type ``Kinetics``; the reference's second name for it, ``SSV2``, is not dispatched yet): sigmoid loss of the LAST frame's pooled vector against one label
+    table, ``-sum logsigmoid(+-logits) / B`` — the localization kernel on ``pooler[:, -1:, :]`` with labels [B, 1], so the
+    gradient lands in the last frame's rows only.  In eval mode it returns the logits alone, the convention of the localization
+    head here; the reference computes ``(loss, logits)`` in either mode (:1725-1726).  The prompt-ensemble class embeddings of ``prepare_multi_task`` (:1676-1684,
+    text tower) are supplied through :meth:`set_label_embeddings` ([L, D], unit norm)."""
+
+    def __init__(self, config: Optional[StreamformerConfig] = None, label2id: Optional[dict] = None):
+        super().__init__()
+        self.config = config
+        self.label2id = label2id or {}
+        self.label_embeddings: Optional[torch.Tensor] = None
+
+    def set_label_embeddings(self, embeddings: torch.Tensor) -> None:
+        self.label_embeddings = embeddings.detach()
+
+    def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
+        if self.label_embeddings is None:
+            raise RuntimeError("set_label_embeddings([L, D]) first: the class prompts' text features are inputs here")
+        pooler = task_head_input.pooler_output
+        emb = self.label_embeddings.to(pooler.device)
+        labels = task_specific_input["label"].to(pooler.device).long()
+        last = pooler[:, -1:, :]
+        with torch.no_grad():
+            img = last[:, 0] / last[:, 0].norm(p=2, dim=-1, keepdim=True)
+            logits = img @ emb.t() * self.logit_scale.exp() + self.logit_bias
+        if not self.training:
+            return logits
+
+        def run(p, ls, lb):
+            return LocalizationHead(emb, ls, lb).loss(p, labels.reshape(-1, 1))
+        return _HeadLossFn.apply(last, self.logit_scale, self.logit_bias, run), logits
+
+
+def select_vis_classes(table: torch.Tensor, mask_target: torch.Tensor, rng=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The label rows and remapped targets one clip trains against (modeling:1844-1892; host logic).  At most 100 classes: the table
+    as given (NOT re-normalised), background 0 -> -1.  More: the positives present in the mask (ascending) followed by
+    ``random.sample`` negatives up to 100, targets remapped, everything else -> -1, and only here the selected rows are
+    re-normalised.  ``rng``: a ``random.Random``; default the module-level generator the reference draws from, so
+    ``random.seed(k)`` replays its draw."""
+    L = table.shape[0]
+    t = mask_target.long()
+    if L <= NUM_MAX_CLASSES:
+        return table, t.masked_fill(t == 0, -1)
+    uniq = torch.unique(t)
+    uniq = uniq[uniq > 0]
+    num_neg = min(NUM_MAX_CLASSES - len(uniq), L - len(uniq))
+    neg = list(set(range(L)) - set(uniq.cpu().numpy()))
+    chosen = (rng or random).sample(neg, num_neg)
+    sel = torch.cat([uniq, torch.tensor(chosen, dtype=torch.long, device=uniq.device)])
+    rows = table[sel.to(table.device)]
+    rows = rows / rows.norm(p=2, dim=-1, keepdim=True)
+    remap = torch.full((L,), -1, dtype=torch.long, device=t.device)
+    remap[sel] = torch.arange(len(sel), device=t.device)
+    return rows, torch.where((t >= 0) & (t < L), remap[t.clamp(0, L - 1)], torch.full_like(t, -1))
+
+
+class _VisLossFn(torch.autograd.Function):
+    """loss = mask_loss(dense_projection(last_hidden_state)): one node over the dense projection (``sf_dense_head_*``) and the
+    fused mask loss (``sf_mask_loss``).  The loss is a scalar, so the whole backward runs in forward (the projection's saved
+    activations live only for this call) and backward() scales the stored gradients."""
+
+    @staticmethod
+    def forward(ctx, proj, tables, targets, lhs, logit_scale, logit_bias, *params):
+        dense = proj.forward(lhs.detach(), [p.detach() for p in params])
+        loss, g_dense, g_scalars = MaskLossHead(logit_scale.detach(), logit_bias.detach()).loss(dense, tables, targets)
+        d_lhs, grads = proj.backward(g_dense)
+        ctx.save_for_backward(d_lhs, g_scalars, *grads)
+        ctx.shapes = (logit_scale.shape, logit_bias.shape)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        d_lhs, gs, *grads = ctx.saved_tensors
+        return (None, None, None, d_lhs * g, (gs[0] * g).reshape(ctx.shapes[0]), (gs[1] * g).reshape(ctx.shapes[1])) + tuple(
+            pg * g for pg in grads)
+
+
+class _HeadMlp(nn.Module):
+    def __init__(self, D: int, I: int):
+        super().__init__()
+        self.fc1 = nn.Linear(D, I)
+        self.fc2 = nn.Linear(I, D)
+
+
+class TimesformerUniversalVideoInstanceSegmentationHead(_TaskHead):
+    """modeling:1729-1918 (task types ``YoutubeVIS`` / ``LVVIS`` / ``COCOPseudoVIS`` / ``TaskVIS``): the spatial task.  All patch
+    tokens go through the head's own copies of the pooling head's value projection, out_proj, layernorm and mlp
+    (``w_v``, ``v_proj``, ``head_layernorm``, ``head_mlp``; :1764-1779, :1786-1795), their cosine logits against a per-dataset
+    label table are upsampled to the mask size and trained with a per-pixel cross-entropy (:1829-1916).
+
+    Parameters, as in the reference: ``logit_scale``, ``logit_bias``, then — when ``head`` (the encoder's pooling head) is given,
+    which the wrapper does — that module registered as the child ``head`` (SHARED tensors: under the wrapper they are listed once,
+    as ``timesformer.head.*``, by ``named_parameters()`` and twice by ``state_dict()``), then ``w_v.*``, ``v_proj.*``,
+    ``head_layernorm.*``, ``head_mlp.fc1.*``, ``head_mlp.fc2.*``.  The ten projection tensors TRAIN: the reference's
+    ``requires_grad = False`` lines (:1781-1784) set an attribute on modules and freeze nothing.
+    ``label2id``: ``{dataset_name: {label: id}}``; the class embeddings of ``prepare_multi_task`` (:1748-1762, text tower) come
+    through :meth:`set_label_embeddings`."""
+
+    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None):
+        super().__init__()
+        self.config = config
+        self.label2id = label2id or {}
+        if head is not None:
+            self.head = head
+        D, I = config.hidden_size, config.intermediate_size
+        if config.hidden_act != "gelu":
+            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the dense projection's training kernels implement the erf GELU")
+        self.w_v = nn.Linear(D, D, bias=True)
+        self.v_proj = nn.Linear(D, D, bias=True)
+        self.head_layernorm = nn.LayerNorm(D, eps=config.layer_norm_eps)
+        self.head_mlp = _HeadMlp(D, I)
+        self.dataset_label_embeddings: Dict[str, torch.Tensor] = {}
+        self.class_rng: Optional[random.Random] = None      # None: the module-level `random`, as the reference
+        self._proj = DenseHeadProjection(config.layer_norm_eps)
+
+    def projection_parameters(self):
+        return [self.w_v.weight, self.w_v.bias, self.v_proj.weight, self.v_proj.bias, self.head_layernorm.weight, self.head_layernorm.bias,
+                self.head_mlp.fc1.weight, self.head_mlp.fc1.bias, self.head_mlp.fc2.weight, self.head_mlp.fc2.bias]
+
+    def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
+        super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
+        if vision_model is None:
+            return
+        D = self.config.hidden_size
+        src = dict(vision_model.head.named_parameters())           # modeling:1764-1779: deep copies of the pooling head's tensors
+        with torch.no_grad():
+            for dst, val in zip(self.projection_parameters(),
+                                (src["attention.in_proj_weight"][2 * D:, :], src["attention.in_proj_bias"][2 * D:], src["attention.out_proj.weight"],
+                                 src["attention.out_proj.bias"], src["layernorm.weight"], src["layernorm.bias"], src["mlp.fc1.weight"],
+                                 src["mlp.fc1.bias"], src["mlp.fc2.weight"], src["mlp.fc2.bias"])):
+                dst.data = val.detach().clone().to(dst.dtype)
+
+    def set_label_embeddings(self, dataset_name: str, embeddings: torch.Tensor) -> None:
+        self.dataset_label_embeddings[dataset_name] = embeddings.detach()
+
+    def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
+        if not self.training:
+            return None                                             # modeling:1914-1918: the head has no evaluation output
+        lhs = task_head_input.last_hidden_state                    # [B, T, N, D]
+        B = lhs.shape[0]
+        H = self.config.image_size
+        tables, targets = [], []
+        for i in range(B):
+            name = task_specific_input["dataset"][i]
+            tab, tgt = select_vis_classes(self.dataset_label_embeddings[name].to(lhs.device), task_specific_input["mask_target"][i].to(lhs.device),
+                                          self.class_rng)
+            target_h, target_w = task_specific_input["mask_size"][i]
+            new_w = int(int(target_w) * (H / int(target_h)))       # modeling:1895-1897
+            if tgt.shape[-2] != H or tgt.shape[-1] != new_w:
+                raise ValueError(f"clip {i}: mask_target must arrive at its training resolution [T, {H}, {new_w}] "
+                                 f"(mask_size {tuple(int(v) for v in task_specific_input['mask_size'][i])}), got {tuple(tgt.shape)}")
+            tables.append(tab)
+            targets.append(tgt)
+        loss = _VisLossFn.apply(self._proj, tables, targets, lhs, self.logit_scale, self.logit_bias, *self.projection_parameters())
+        return loss, None
+
+
 class StreamformerForMultiTaskingSigLIP(nn.Module):
     """modeling:1356-1536 without the text tower: ``timesformer`` + per-task heads, one task per call."""
 
@@ -155,9 +320,14 @@ class StreamformerForMultiTaskingSigLIP(nn.Module):
                 self.task_heads[task_type] = TimesformerUniversalLocalizationHead(config, (multi_task_config[task_type] or {}).get("label2id"))
             elif task_type in RETRIEVAL_TASKS:
                 self.task_heads[task_type] = TimesformerVideoRetrievalHead(config)
+            elif task_type in CLASSIFICATION_TASKS:
+                self.task_heads[task_type] = TimesformerVideoClassificationHead(config, (multi_task_config[task_type] or {}).get("label2id"))
+            elif task_type in VIS_TASKS:
+                self.task_heads[task_type] = TimesformerUniversalVideoInstanceSegmentationHead(
+                    config, (multi_task_config[task_type] or {}).get("label2id"), self.timesformer.head)
             else:
-                raise NotImplementedError(f"Task type {task_type} not implemented (this build covers the retrieval and "
-                                          "localization heads of BASELINE config #3)")
+                raise NotImplementedError(f"Task type {task_type} not implemented (this build covers the retrieval, localization, "
+                                          "classification and video instance segmentation heads)")
         if config.add_lora_spatial:
             self.add_lora_spatial()
         self.train()                      # an nn.Module is born in train mode; the encoder child alone is born in eval mode
