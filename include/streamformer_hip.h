@@ -211,6 +211,26 @@ int sf_localization_loss(const float* pooler_dev, const float* label_emb_dev, co
                          float* loss_dev, float* grad_pooler_dev, float* grad_scalars_dev,
                          void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- caption-driven heads ---------------------------------------------------------------------
+ * Temporal grounding, TimesformerTemporalGroundingHead.forward (modeling:2373-2397): ONE caption per clip supervises every frame.
+ *   logit[b,t] = exp(logit_scale) * <p[b,t] / |p[b,t]|, c[b] / |c[b]|> + logit_bias
+ *   y[b,t]     = -1 where labels[b,t] == 0, else labels[b,t] as given (the reference's masked_fill; no host check)
+ *   loss       = -sum_{b,t} logsigmoid(y * logit) / B
+ * pooler_dev fp32 [B,T,D]; text_dev fp32 [B,D] (un-normalised, no gradient: frozen text tower); labels_dev fp32 [B,T].
+ * Conventions of sf_localization_loss: DEVICE scalars, workspace of sf_loss_workspace_bytes(B, T), bit-reproducible.
+ * Outputs: loss_dev fp32 [1]; grad_pooler_dev fp32 [B,T,D] or NULL; grad_scalars_dev fp32 [2] or NULL; logits_out_dev fp32 [B,T] or NULL. */
+int sf_grounding_loss(const float* pooler_dev, const float* text_dev, const float* labels_dev, int B, int T, int D,
+                      const float* logit_scale_dev, const float* logit_bias_dev, float* loss_dev, float* grad_pooler_dev,
+                      float* grad_scalars_dev, float* logits_out_dev, void* workspace_dev, size_t workspace_bytes,
+                      sf_stream stream);
+/* Evaluation output of the referring segmentation head (modeling:2004-2018): dense caption-to-patch logits
+ *   out[m, j] = exp(logit_scale) * <x[m] / |x[m]|, text[j] / |text[j]|> + logit_bias
+ * x_dev fp32 [M,D] (the dense projection's output rows, 16-byte aligned), text_dev fp32 [n,D] (un-normalised), out_dev fp32 [M,n].
+ * fp32 arithmetic throughout, one pass over x for tables of up to 128 KB (42 captions at D = 768), no workspace, bit-reproducible.
+ * D a multiple of 4; capacity (SF_ERR_CAPACITY): n <= 64, D <= 2048.                                                              */
+int sf_dense_text_logits(const float* x_dev, const float* text_dev, int M, int D, int n, const float* logit_scale_dev,
+                         const float* logit_bias_dev, float* out_dev, sf_stream stream);
+
 /* ---- spatial task: mask loss of the video instance segmentation head ------------------------
  * TimesformerUniversalVideoInstanceSegmentationHead.forward, training branch (modeling:1829-1916), per clip i:
  *   z[t,n,l] = <x[i,t,n] / |x[i,t,n]|, E_i[l]> * exp(logit_scale) + logit_bias

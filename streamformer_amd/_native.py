@@ -71,6 +71,8 @@ SIGNATURES = {
     "sf_loss_workspace_bytes": (_SZ, [_I, _I]),
     "sf_retrieval_loss": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_localization_loss": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_grounding_loss": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_dense_text_logits": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "sf_mask_loss_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_mask_loss": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(_P), C.POINTER(C.c_int32), _I,
                           _P, _P, _P, _P, _P, _P, _SZ, _P]),

@@ -441,3 +441,7 @@ hipError_t sf_launch_retrieval_loss(const float* pooler, const float* text, int 
 hipError_t sf_launch_localization_loss(const float* pooler, const float* label_emb, const int* labels,
                                        int B, int T, int D, int L, const float* logit_scale, const float* logit_bias,
                                        float* loss, float* grad_pooler, float* grad_scalars, float* partial, hipStream_t s);
+// labels fp32 [B,T] (0 -> -1, anything else as given); text [B,D]: one caption per clip; logits_out [B,T] or null
+hipError_t sf_launch_grounding_loss(const float* pooler, const float* text, const float* labels, int B, int T, int D,
+                                    const float* logit_scale, const float* logit_bias, float* loss, float* grad_pooler,
+                                    float* grad_scalars, float* logits_out, float* partial, hipStream_t s);

@@ -180,6 +180,49 @@ __global__ __launch_bounds__(256) void sf_localization_loss_kernel(const float* 
   }
 }
 
+// temporal grounding (TimesformerTemporalGroundingHead.forward, modeling:2373-2397): per frame (b,t) ONE logit against the
+// clip's own caption,  z = s * <p/|p|, c_b/|c_b|> + bias ;  y = -1 where label == 0, else the label as given (the
+// reference's masked_fill on a numeric tensor) ;  loss = -sum_{b,t} logsigmoid(y z) / B.
+// One workgroup per frame row writes {loss, d scale, d bias} partials for the finish kernel below (fixed order).
+__global__ __launch_bounds__(256) void sf_grounding_loss_kernel(const float* __restrict__ pooler,
+                                                                const float* __restrict__ text,
+                                                                const float* __restrict__ labels, int B, int T, int D,
+                                                                const float* __restrict__ logit_scale_p,
+                                                                const float* __restrict__ logit_bias_p,
+                                                                float* __restrict__ partial,
+                                                                float* __restrict__ grad_pooler,
+                                                                float* __restrict__ logits_out) {
+  __shared__ float red[4];
+  const int row = blockIdx.x;
+  const float* x = pooler + (size_t)row * D;
+  const float* c = text + (size_t)(row / T) * D;
+  const float s = expf(logit_scale_p[0]), bias = logit_bias_p[0];
+  float xx = 0.f, cc = 0.f, xc = 0.f;
+  for (int d = threadIdx.x; d < D; d += 256) {
+    const float xv = x[d], cv = c[d];
+    xx = fmaf(xv, xv, xx);
+    cc = fmaf(cv, cv, cc);
+    xc = fmaf(xv, cv, xc);
+  }
+  const float xn = sqrtf(block_sum(xx, red)), cn = sqrtf(block_sum(cc, red));
+  const float cosv = block_sum(xc, red) / (xn * cn);
+  const float z = fmaf(s, cosv, bias);
+  const float lab = labels[row];
+  const float y = lab == 0.f ? -1.f : lab;
+  const float gz = -y * sigmoidf(-y * z) / (float)B;
+  if (grad_pooler) {
+    // dL/dx = gz s (chat - xhat cos) / |x|
+    const float f = gz * s / xn;
+    for (int d = threadIdx.x; d < D; d += 256) grad_pooler[(size_t)row * D + d] = f * (c[d] / cn - x[d] / xn * cosv);
+  }
+  if (threadIdx.x == 0) {
+    if (logits_out) logits_out[row] = z;
+    partial[row * 3 + 0] = -log_sigmoid(y * z) / (float)B;
+    partial[row * 3 + 1] = gz * s * cosv;
+    partial[row * 3 + 2] = gz;
+  }
+}
+
 // one wave adds the row partials in a fixed order (lane-strided sums, then the DPP tree): deterministic
 __global__ __launch_bounds__(64) void sf_loss_finish_kernel(const float* __restrict__ partial, int rows,
                                                             float* __restrict__ loss,
@@ -217,6 +260,15 @@ hipError_t sf_launch_localization_loss(const float* pooler, const float* label_e
   const size_t lds = (size_t)(2 * L + 8) * sizeof(float);
   hipLaunchKernelGGL(sf_localization_loss_kernel, dim3(B * T), dim3(256), lds, s, pooler, label_emb, labels, B, T, D, L,
                      logit_scale, logit_bias, partial, grad_pooler);
+  hipLaunchKernelGGL(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
+  return hipGetLastError();
+}
+
+hipError_t sf_launch_grounding_loss(const float* pooler, const float* text, const float* labels, int B, int T, int D,
+                                    const float* logit_scale, const float* logit_bias, float* loss, float* grad_pooler,
+                                    float* grad_scalars, float* logits_out, float* partial, hipStream_t s) {
+  hipLaunchKernelGGL(sf_grounding_loss_kernel, dim3(B * T), dim3(256), 0, s, pooler, text, labels, B, T, D, logit_scale,
+                     logit_bias, partial, grad_pooler, logits_out);
   hipLaunchKernelGGL(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
   return hipGetLastError();
 }

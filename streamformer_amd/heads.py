@@ -5,6 +5,8 @@ Mirrors ``TimesformerVideoRetrievalHead.forward`` + ``SigLipLoss._loss`` (refere
 ``TimesformerUniversalLocalizationHead.forward`` (``:2238-2282``).  Each head owns its
 ``logit_scale = log 10`` / ``logit_bias = -2`` pair (``:1363-1364, 2204-2205, 2300-2301``).
 Text features come from a frozen SigLIP text tower in the reference; here they are inputs.
+The caption-driven heads sit on the same conventions: ``GroundingHead`` (``TimesformerTemporalGroundingHead.forward``,
+``:2373-2397``) and ``DenseTextLogits`` (evaluation output of the referring segmentation head, ``:2004-2018``).
 """
 from __future__ import annotations
 
@@ -188,3 +190,76 @@ class DenseHeadProjection:
                                                      self._ws.numel(), nat.current_stream_handle(dev)))
         self.release()         # stream-ordered: torch's allocator reuses the block only behind the launches above
         return dx, grads
+
+
+class GroundingHead:
+    """Temporal grounding (``sf_grounding_loss``; reference ``TimesformerTemporalGroundingHead.forward``, ``:2373-2397``): ONE caption
+    per clip against every frame's pooled vector, ``-sum logsigmoid(y * logits) / B`` with ``y = -1`` where the label is 0 and the
+    label itself elsewhere (the reference's ``masked_fill``; the rule is applied by the kernel on fp32 labels, no host check)."""
+
+    def __init__(self, logit_scale=math.log(10.0), logit_bias=-2.0):
+        self.logit_scale = logit_scale
+        self.logit_bias = logit_bias
+
+    def loss(self, pooler_output: torch.Tensor, text_features: torch.Tensor, labels: torch.Tensor, need_grad: bool = True,
+             return_logits: bool = False):
+        """pooler_output [B,T,D] (cuda), text_features [B,D] (this rank's captions: the reference gathers nothing for this head),
+        labels [B,T] numbers.  Returns (loss [1], d loss/d pooler [B,T,D], d loss/d (logit_scale, logit_bias) [2]), followed by the
+        logits [B,T] when ``return_logits``."""
+        p = _f32(pooler_output)
+        dev = p.device
+        if p.dim() != 3:
+            raise ValueError(f"pooler_output must be [B, T, D], got {tuple(p.shape)}")
+        B, T, D = p.shape
+        t = _f32(text_features.to(dev))
+        if tuple(t.shape) != (B, D):
+            raise ValueError(f"text_features must be [{B}, {D}] (one caption per clip), got {tuple(t.shape)}")
+        if tuple(labels.shape) != (B, T):
+            raise ValueError(f"labels must be [{B}, {T}], got {tuple(labels.shape)}")
+        lab = _f32(labels.to(dev))
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        gp = torch.empty_like(p) if need_grad else None
+        gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
+        logits = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logits else None
+        ls, lb, ws = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias), _workspace(dev, B, T)
+        with torch.cuda.device(dev):
+            nat.check(nat.lib.sf_grounding_loss(p.data_ptr(), t.data_ptr(), lab.data_ptr(), B, T, D, ls.data_ptr(), lb.data_ptr(),
+                                                loss.data_ptr(), nat.ptr(gp), nat.ptr(gs), nat.ptr(logits), ws.data_ptr(), ws.numel(),
+                                                nat.current_stream_handle(dev)))
+        return (loss, gp, gs, logits) if return_logits else (loss, gp, gs)
+
+    def logits(self, pooler_output: torch.Tensor, text_features: torch.Tensor) -> torch.Tensor:
+        """The logits [B,T] alone (labels play no part in them)."""
+        B, T = pooler_output.shape[:2]
+        return self.loss(pooler_output, text_features, torch.zeros(B, T, device=pooler_output.device), need_grad=False, return_logits=True)[3]
+
+
+class DenseTextLogits:
+    """Dense caption-to-patch logits of the referring segmentation head's evaluation branch (``sf_dense_text_logits``; reference
+    ``:2004-2018``): ``exp(logit_scale) * <x / |x|, text_j / |text_j|> + logit_bias`` for every row of ``x``, fp32 throughout."""
+    MAX_CAPTIONS = 64
+
+    def __init__(self, logit_scale=math.log(10.0), logit_bias=-2.0):
+        self.logit_scale = logit_scale
+        self.logit_bias = logit_bias
+
+    def forward(self, x: torch.Tensor, text_features: torch.Tensor) -> torch.Tensor:
+        """x [..., D] (cuda), text_features [n, D] (un-normalised) -> [..., n]."""
+        x = _f32(x)
+        dev = x.device
+        D = x.shape[-1]
+        t = _f32(text_features.to(dev))
+        if t.dim() != 2 or t.shape[1] != D:
+            raise ValueError(f"text_features must be [n, {D}], got {tuple(t.shape)}")
+        n = int(t.shape[0])
+        if n > self.MAX_CAPTIONS:
+            raise ValueError(f"{n} captions: the dense text logits kernel takes at most {self.MAX_CAPTIONS} per call")
+        if x.data_ptr() % 16:
+            x = x.clone()
+        M = x.numel() // D
+        out = torch.empty(tuple(x.shape[:-1]) + (n,), dtype=torch.float32, device=dev)
+        ls, lb = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias)
+        with torch.cuda.device(dev):
+            nat.check(nat.lib.sf_dense_text_logits(x.data_ptr(), t.data_ptr(), M, D, n, ls.data_ptr(), lb.data_ptr(), out.data_ptr(),
+                                                   nat.current_stream_handle(dev)))
+        return out

@@ -3,8 +3,10 @@
 Mirror of ``StreamformerForMultiTaskingSigLIP`` (reference ``models/modeling_timesformer_siglip.py:1356-1536``) for the
 three granularities of the pre-training — global: video-text retrieval (``TimesformerVideoRetrievalHead``, ``:2285-2351``) and
 zero-shot classification (``TimesformerVideoClassificationHead``, ``:1651-1726``); temporal: per-frame localization
-(``TimesformerUniversalLocalizationHead``, ``:2186-2282``); spatial: video instance segmentation
-(``TimesformerUniversalVideoInstanceSegmentationHead``, ``:1729-1918``, trained through ``last_hidden_state``):
+(``TimesformerUniversalLocalizationHead``, ``:2186-2282``) and caption-driven temporal grounding (``TimesformerTemporalGroundingHead``,
+``:2354-2397``); spatial: video instance segmentation (``TimesformerUniversalVideoInstanceSegmentationHead``, ``:1729-1918``) and
+referring segmentation (``TimesformerVideoContrastiveCrossEntropySegmentationHead``, ``:1921-2078``), both trained through
+``last_hidden_state``:
 
     model = StreamformerForMultiTaskingSigLIP(config, {"TaskRetrieval": {}, "TaskLocalization": {"label2id": ...}})
     model.prepare_for_multi_tasks(); model.frozen_spatial(); model.cuda().train()
@@ -12,10 +14,12 @@ zero-shot classification (``TimesformerVideoClassificationHead``, ``:1651-1726``
     losses[task].backward(); optimizer.step()                    # torch.optim over model.parameters()
 
 Encoder forward / backward run in ``libstreamformer_hip.so`` behind one autograd node (``autograd.py``); the loss heads
-are the HIP loss kernels (``sf_loss.hip``, ``sf_mask_loss.hip`` + ``sf_dense_head.hip``) behind a second one.  What is NOT here: the SigLIP *text tower* and tokenizer
-(``:1365-1373``; hub weights, outside the path) — captions / class prompts enter as feature tensors
-(``task_input["text_features"]``, ``set_label_embeddings``) — and the other task heads, which raise
-``NotImplementedError`` (out of scope).
+are the HIP loss kernels (``sf_loss.hip``, ``sf_mask_loss.hip`` + ``sf_dense_head.hip``, ``sf_text_heads.hip``) behind a second one.
+What is NOT here: the SigLIP *text tower* and tokenizer (``:1365-1373``; hub weights, outside the path) — captions / class prompts
+enter as feature tensors (``task_input["text_features"]``, ``set_label_embeddings``) — and two dispatches of the reference, which
+raise ``NotImplementedError``: ``SSV2`` (the ``Kinetics`` head under a second name) and the naive localization head
+(``THUMOS14`` / ``ActivityNet`` / ``FineAction`` / ``HACS``, ``:2081-2185``: window bookkeeping over pre-extracted features, not in
+the shipped recipe).  With those two exceptions every task entry of the shipped recipe (``scripts/dataset_metadata/all.yaml``) builds.
 """
 from __future__ import annotations
 
@@ -28,7 +32,7 @@ import torch
 from torch import nn
 
 from .configuration import StreamformerConfig
-from .heads import DenseHeadProjection, LocalizationHead, MaskLossHead, RetrievalHead
+from .heads import DenseHeadProjection, DenseTextLogits, GroundingHead, LocalizationHead, MaskLossHead, RetrievalHead
 from .modeling import TimesformerMultiTaskingModelSigLIP
 
 RETRIEVAL_TASKS = ("MSRVTT", "WebVid", "TaskRetrieval")                                        # modeling:1401
@@ -37,6 +41,9 @@ LOCALIZATION_TASKS = ("THUMOS14Grounding", "ActivityNetGrounding", "FineActionGr
 CLASSIFICATION_TASKS = ("Kinetics",)         # modeling:1380 also lists "SSV2" (same head): still refused here, tests/test_autograd_bridge.py
                                              # pins that refusal as its example of an unimplemented task type
 VIS_TASKS = ("YoutubeVIS", "LVVIS", "COCOPseudoVIS", "TaskVIS")                                 # modeling:1416
+GROUNDING_TASKS = ("CharadesSTA", "QVHighlights", "TaCoS", "TVSum", "ActivityNetCaptions", "DiDeMo", "QuerYD",
+                   "TaskGrounding")                                                             # modeling:1404-1413
+REFER_VOS_TASKS = ("MEVIS", "ReferYoutubeVOS", "RefCOCOPseudo", "TaskReferVOS")                 # modeling:1423-1428
 NUM_MAX_CLASSES = 100                                                                           # modeling:1826
 
 
@@ -180,6 +187,34 @@ class TimesformerVideoClassificationHead(_TaskHead):
         return _HeadLossFn.apply(last, self.logit_scale, self.logit_bias, run), logits
 
 
+class TimesformerTemporalGroundingHead(_TaskHead):
+    """modeling:2354-2397 (task types ``CharadesSTA`` / ``QVHighlights`` / ``TaCoS`` / ``TVSum`` / ``ActivityNetCaptions`` / ``DiDeMo`` /
+    ``QuerYD`` / ``TaskGrounding``): the one task where a caption supervises EVERY frame — sigmoid loss of each frame's pooled vector
+    against the clip's own caption, ``-sum logsigmoid(y * logits) / B`` with ``y = -1`` where ``label`` is 0 (``sf_grounding_loss``).
+    ``task_input["text_features"]`` [B, D] stands in for the tokenizer + text tower (:2378-2386), ``task_input["label"]`` is [B, T].
+    Local captions only: the reference gathers nothing across ranks for this head.  In eval mode it returns the logits [B, T] alone,
+    the convention of the localization / classification heads here; the reference computes ``(loss, logits)`` in either mode (:2396-2397)."""
+
+    def __init__(self, config: Optional[StreamformerConfig] = None):
+        super().__init__()
+        self.config = config
+
+    def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
+        pooler = task_head_input.pooler_output                     # [B, T, D]
+        text = task_specific_input["text_features"].to(pooler.device).detach()      # frozen text tower (:1372-1373)
+        if not self.training:
+            with torch.no_grad():
+                return GroundingHead(self.logit_scale, self.logit_bias).logits(pooler, text)
+        labels = task_specific_input["label"].to(pooler.device)
+        kept = {}
+
+        def run(p, ls, lb):
+            loss, gp, gs, kept["logits"] = GroundingHead(ls, lb).loss(p, text, labels, return_logits=True)
+            return loss, gp, gs
+        loss = _HeadLossFn.apply(pooler, self.logit_scale, self.logit_bias, run)
+        return loss, kept["logits"]
+
+
 def select_vis_classes(table: torch.Tensor, mask_target: torch.Tensor, rng=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The label rows and remapped targets one clip trains against (modeling:1844-1892; host logic).  At most 100 classes: the table
     as given (NOT re-normalised), background 0 -> -1.  More: the positives present in the mask (ascending) followed by
@@ -231,7 +266,53 @@ class _HeadMlp(nn.Module):
         self.fc2 = nn.Linear(I, D)
 
 
-class TimesformerUniversalVideoInstanceSegmentationHead(_TaskHead):
+class _DenseProjectionHead(_TaskHead):
+    """What the two segmentation heads share (modeling:1764-1795 and, the same lines again, :1940-1971): the pooling head registered as
+    the child ``head`` and the head's own copies of its value projection, out_proj, layernorm and mlp, applied to every patch token
+    by ``DenseHeadProjection``."""
+
+    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None):
+        super().__init__()
+        self.config = config
+        self.label2id = label2id or {}
+        if head is not None:
+            self.head = head
+        if config.hidden_act != "gelu":
+            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the dense projection's training kernels implement the erf GELU")
+        self._proj = DenseHeadProjection(config.layer_norm_eps)
+
+    def _build_projection(self) -> None:
+        D, I = self.config.hidden_size, self.config.intermediate_size
+        self.w_v = nn.Linear(D, D, bias=True)
+        self.v_proj = nn.Linear(D, D, bias=True)
+        self.head_layernorm = nn.LayerNorm(D, eps=self.config.layer_norm_eps)
+        self.head_mlp = _HeadMlp(D, I)
+
+    def projection_parameters(self):
+        return [self.w_v.weight, self.w_v.bias, self.v_proj.weight, self.v_proj.bias, self.head_layernorm.weight, self.head_layernorm.bias,
+                self.head_mlp.fc1.weight, self.head_mlp.fc1.bias, self.head_mlp.fc2.weight, self.head_mlp.fc2.bias]
+
+    def _copy_projection(self, vision_model) -> None:
+        D = self.config.hidden_size
+        src = dict(vision_model.head.named_parameters())           # modeling:1764-1779: deep copies of the pooling head's tensors
+        with torch.no_grad():
+            for dst, val in zip(self.projection_parameters(),
+                                (src["attention.in_proj_weight"][2 * D:, :], src["attention.in_proj_bias"][2 * D:], src["attention.out_proj.weight"],
+                                 src["attention.out_proj.bias"], src["layernorm.weight"], src["layernorm.bias"], src["mlp.fc1.weight"],
+                                 src["mlp.fc1.bias"], src["mlp.fc2.weight"], src["mlp.fc2.bias"])):
+                dst.data = val.detach().clone().to(dst.dtype)
+
+    def _check_mask(self, i: int, target: torch.Tensor, mask_size) -> None:
+        """modeling:1895-1897 / :2029-2030: masks arrive at their training resolution, height = image size, width scaled with it."""
+        H = self.config.image_size
+        target_h, target_w = mask_size
+        new_w = int(int(target_w) * (H / int(target_h)))
+        if target.shape[-2] != H or target.shape[-1] != new_w:
+            raise ValueError(f"clip {i}: mask_target must arrive at its training resolution [T, {H}, {new_w}] "
+                             f"(mask_size {tuple(int(v) for v in mask_size)}), got {tuple(target.shape)}")
+
+
+class TimesformerUniversalVideoInstanceSegmentationHead(_DenseProjectionHead):
     """modeling:1729-1918 (task types ``YoutubeVIS`` / ``LVVIS`` / ``COCOPseudoVIS`` / ``TaskVIS``): the spatial task.  All patch
     tokens go through the head's own copies of the pooling head's value projection, out_proj, layernorm and mlp
     (``w_v``, ``v_proj``, ``head_layernorm``, ``head_mlp``; :1764-1779, :1786-1795), their cosine logits against a per-dataset
@@ -246,38 +327,15 @@ class TimesformerUniversalVideoInstanceSegmentationHead(_TaskHead):
     through :meth:`set_label_embeddings`."""
 
     def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None):
-        super().__init__()
-        self.config = config
-        self.label2id = label2id or {}
-        if head is not None:
-            self.head = head
-        D, I = config.hidden_size, config.intermediate_size
-        if config.hidden_act != "gelu":
-            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the dense projection's training kernels implement the erf GELU")
-        self.w_v = nn.Linear(D, D, bias=True)
-        self.v_proj = nn.Linear(D, D, bias=True)
-        self.head_layernorm = nn.LayerNorm(D, eps=config.layer_norm_eps)
-        self.head_mlp = _HeadMlp(D, I)
+        super().__init__(config, label2id, head)
+        self._build_projection()
         self.dataset_label_embeddings: Dict[str, torch.Tensor] = {}
         self.class_rng: Optional[random.Random] = None      # None: the module-level `random`, as the reference
-        self._proj = DenseHeadProjection(config.layer_norm_eps)
-
-    def projection_parameters(self):
-        return [self.w_v.weight, self.w_v.bias, self.v_proj.weight, self.v_proj.bias, self.head_layernorm.weight, self.head_layernorm.bias,
-                self.head_mlp.fc1.weight, self.head_mlp.fc1.bias, self.head_mlp.fc2.weight, self.head_mlp.fc2.bias]
 
     def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
         super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
-        if vision_model is None:
-            return
-        D = self.config.hidden_size
-        src = dict(vision_model.head.named_parameters())           # modeling:1764-1779: deep copies of the pooling head's tensors
-        with torch.no_grad():
-            for dst, val in zip(self.projection_parameters(),
-                                (src["attention.in_proj_weight"][2 * D:, :], src["attention.in_proj_bias"][2 * D:], src["attention.out_proj.weight"],
-                                 src["attention.out_proj.bias"], src["layernorm.weight"], src["layernorm.bias"], src["mlp.fc1.weight"],
-                                 src["mlp.fc1.bias"], src["mlp.fc2.weight"], src["mlp.fc2.bias"])):
-                dst.data = val.detach().clone().to(dst.dtype)
+        if vision_model is not None:
+            self._copy_projection(vision_model)
 
     def set_label_embeddings(self, dataset_name: str, embeddings: torch.Tensor) -> None:
         self.dataset_label_embeddings[dataset_name] = embeddings.detach()
@@ -287,20 +345,91 @@ class TimesformerUniversalVideoInstanceSegmentationHead(_TaskHead):
             return None                                             # modeling:1914-1918: the head has no evaluation output
         lhs = task_head_input.last_hidden_state                    # [B, T, N, D]
         B = lhs.shape[0]
-        H = self.config.image_size
         tables, targets = [], []
         for i in range(B):
             name = task_specific_input["dataset"][i]
             tab, tgt = select_vis_classes(self.dataset_label_embeddings[name].to(lhs.device), task_specific_input["mask_target"][i].to(lhs.device),
                                           self.class_rng)
-            target_h, target_w = task_specific_input["mask_size"][i]
-            new_w = int(int(target_w) * (H / int(target_h)))       # modeling:1895-1897
-            if tgt.shape[-2] != H or tgt.shape[-1] != new_w:
-                raise ValueError(f"clip {i}: mask_target must arrive at its training resolution [T, {H}, {new_w}] "
-                                 f"(mask_size {tuple(int(v) for v in task_specific_input['mask_size'][i])}), got {tuple(tgt.shape)}")
+            self._check_mask(i, tgt, task_specific_input["mask_size"][i])
             tables.append(tab)
             targets.append(tgt)
         loss = _VisLossFn.apply(self._proj, tables, targets, lhs, self.logit_scale, self.logit_bias, *self.projection_parameters())
+        return loss, None
+
+
+def refer_mask_targets(mask_targets, rank: int, batch: int):
+    """modeling:2045-2060: clip i trains against the WHOLE gathered caption table; its pixels equal to 1 get the class
+    ``rank * batch + i`` (this clip's own caption), every other pixel -1 (ignored)."""
+    out = []
+    for i, m in enumerate(mask_targets):
+        m = m.long()
+        out.append(torch.where(m == 1, torch.full_like(m, rank * batch + i), torch.full_like(m, -1)))
+    return out
+
+
+class TimesformerVideoContrastiveCrossEntropySegmentationHead(_DenseProjectionHead):
+    """modeling:1921-2078 (task types ``MEVIS`` / ``ReferYoutubeVOS`` / ``RefCOCOPseudo`` / ``TaskReferVOS``): referring segmentation,
+    the per-pixel counterpart of the grounding head.  The dense projection and the upsample + per-pixel cross-entropy are the VIS
+    head's (``sf_dense_head_*``, ``sf_mask_loss``); the class table is the captions of the whole (gathered) batch.
+
+    ``task_input["text_features"]`` [B, D] stands in for the tokenizer + text tower (:1989-1998).  With ``torch.distributed``
+    initialised the rows are all-gathered over ranks into [W * B, D] (:2000-2002), normalised row-wise and detached.  Clip ``i``
+    trains against that whole table with target ``rank * B + i`` where ``mask_target[i] == 1`` and -1 elsewhere; the masks arrive at
+    height ``config.image_size`` and width ``int(target_w * (image_size / target_h))`` (:2029-2030 — the reference hard-codes 224 and
+    a 14 x 14 patch grid; here the grid is ``sqrt(N)`` and the height the configured image size, as in the VIS head).  The loss is the
+    mean over clips of the per-clip mean cross-entropy over non-ignored pixels.  A clip whose mask has no pixel equal to 1 makes the
+    reference's ``cross_entropy`` return NaN; here it contributes loss 0 and no gradient and is still counted in the mean (the
+    convention of ``sf_mask_loss``).  At most 128 gathered captions (the mask loss's class capacity).
+
+    Training returns ``(loss, None)``: the reference also hands back its [B, T, N, W * B] similarity tensor, which nothing consumes.
+    Evaluation returns the dense caption-to-patch logits against the LOCAL captions, [B, T, N, B] (:2016-2018, no gather), from
+    ``sf_dense_text_logits``; the dense projection's saved activations are released right after.
+
+    Parameters, as in the reference: ``logit_scale``, ``logit_bias``, the shared pooling head as the child ``head``, and — created by
+    :meth:`prepare_multi_task`, not by the constructor (:1940-1955) — ``w_v.*``, ``v_proj.*``, ``head_layernorm.*``, ``head_mlp.fc1.*``,
+    ``head_mlp.fc2.*``; all ten train (:1957-1960 set an attribute on modules and freeze nothing)."""
+
+    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None, process_group=None):
+        super().__init__(config, label2id, head)
+        self.group = process_group
+
+    def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
+        super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
+        if vision_model is None:
+            return
+        if not hasattr(self, "w_v"):          # a second call refills the SAME tensors: an optimizer built in between keeps training them
+            self._build_projection()          # (the reference creates new modules on every call and orphans the optimizer's)
+        self._copy_projection(vision_model)
+
+    def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
+        if not hasattr(self, "w_v"):
+            raise RuntimeError("prepare_multi_task(vision_model=...) first: it creates this head's dense projection (modeling:1940-1955)")
+        lhs = task_head_input.last_hidden_state                    # [B, T, N, D]
+        B, T, N, D = lhs.shape
+        text = task_specific_input["text_features"].to(lhs.device).detach().float()      # frozen text tower (:1372-1373)
+        if tuple(text.shape) != (B, D):
+            raise ValueError(f"text_features must be [{B}, {D}] (one caption per clip), got {tuple(text.shape)}")
+        if not self.training:
+            with torch.no_grad():
+                try:
+                    dense = self._proj.forward(lhs, self.projection_parameters())
+                    return DenseTextLogits(self.logit_scale, self.logit_bias).forward(dense, text)
+                finally:
+                    self._proj.release()                           # ~1 GB of saved activations at 8 clips: no backward follows
+        from .parallel import all_gather_rows, world
+        rank, ws = world(self.group)
+        if ws > 1:
+            text = all_gather_rows(text.contiguous(), group=self.group)
+        else:
+            rank = 0
+        table = text / text.norm(p=2, dim=-1, keepdim=True)
+        masks = [m.to(lhs.device) for m in task_specific_input["mask_target"]]
+        if len(masks) != B:
+            raise ValueError(f"{B} clips need {B} masks, got {len(masks)}")
+        for i, m in enumerate(masks):
+            self._check_mask(i, m, task_specific_input["mask_size"][i])
+        targets = refer_mask_targets(masks, rank, B)
+        loss = _VisLossFn.apply(self._proj, [table] * B, targets, lhs, self.logit_scale, self.logit_bias, *self.projection_parameters())
         return loss, None
 
 
@@ -325,9 +454,15 @@ class StreamformerForMultiTaskingSigLIP(nn.Module):
             elif task_type in VIS_TASKS:
                 self.task_heads[task_type] = TimesformerUniversalVideoInstanceSegmentationHead(
                     config, (multi_task_config[task_type] or {}).get("label2id"), self.timesformer.head)
+            elif task_type in GROUNDING_TASKS:
+                self.task_heads[task_type] = TimesformerTemporalGroundingHead(config)
+            elif task_type in REFER_VOS_TASKS:
+                self.task_heads[task_type] = TimesformerVideoContrastiveCrossEntropySegmentationHead(
+                    config, (multi_task_config[task_type] or {}).get("label2id"), self.timesformer.head)
             else:
-                raise NotImplementedError(f"Task type {task_type} not implemented (this build covers the retrieval, localization, "
-                                          "classification and video instance segmentation heads)")
+                raise NotImplementedError(f"Task type {task_type} not implemented (this build covers the retrieval, localization, classification, "
+                                          "temporal grounding, video instance segmentation and referring segmentation heads; still refused: "
+                                          "SSV2, and the naive localization head of THUMOS14 / ActivityNet / FineAction / HACS)")
         if config.add_lora_spatial:
             self.add_lora_spatial()
         self.train()                      # an nn.Module is born in train mode; the encoder child alone is born in eval mode

@@ -665,9 +665,13 @@ class StreamformerTrainer:
         Retrieval with world > 1 uses every rank's captions as negatives (the reference's distributed SigLipLoss,
         modeling:239-297) unless ``task_input["gather_negatives"]`` is False.
         Localization takes either one table for the whole batch (``label_emb`` [L, D]) or, as the reference head does, a dataset
-        name per clip (``datasets``: B names, ``label_embs``: {name: [L_name, D]}) with tables of different sizes."""
-        from .heads import LocalizationHead, RetrievalHead
+        name per clip (``datasets``: B names, ``label_embs``: {name: [L_name, D]}) with tables of different sizes.
+        Grounding (``kind == "grounding"``) takes ``text`` [B, D], one caption per clip, and ``labels`` [B, T]; no cross-rank gather."""
+        from .heads import GroundingHead, LocalizationHead, RetrievalHead
         ls, lb = self._view(f"task_heads.{task}.logit_scale"), self._view(f"task_heads.{task}.logit_bias")
+        if task_input["kind"] == "grounding":
+            # one caption per clip against every frame (modeling:2373-2397); local captions only: the reference gathers nothing here
+            return GroundingHead(ls, lb).loss(pooler, task_input["text"].to(self.device), task_input["labels"])
         if task_input["kind"] == "retrieval":
             text = task_input["text"].to(self.device)
             rank = 0
