@@ -167,6 +167,26 @@ int sf_forward_stream_attentions(sf_encoder* enc, sf_cache* cache, const void* p
                                  float* last_hidden_dev, float* pooler_dev, float* hidden_states_dev, float* attentions_dev,
                                  const float* pos_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- independent stream positions in one batched cache --------------------------------------------
+ * Each of the B streams (slabs) of a cache keeps its own position, so sessions may join, skip calls, restart and leave on their
+ * own while sharing calls.  The entry points above advance ALL streams together and need them level: sf_cache_length is the
+ * longest stream's count, sf_forward_stream on a cache whose streams differ returns SF_ERR_STATE, sf_cache_reset clears all.   */
+int sf_cache_stream_length(const sf_cache* cache, int stream);      /* frames seen by one stream (0 for an id out of range) */
+int sf_cache_reset_stream(sf_cache* cache, int stream);             /* that stream starts over; the others keep their positions */
+/* Advances the `n_streams` DISTINCT streams named in the HOST array `streams` (slab indices of the cache), each from its own
+ * position.  pixels_dev [n_streams, T_new, C, H, W]; last_hidden_dev [n_streams, T_new, N, D] and pooler_dev [n_streams, T_new, D]
+ * (or NULL) come back in the order of `streams`.
+ *   T_new == 1: any subset.  Same launch sequence as the lockstep call of n_streams rows, replayed from one captured graph per
+ *     (n_streams, 64-key pass class of the longest stream, pooler, pixel type) whatever the positions are; at most 64 streams
+ *     per call.  Under the sliding-window policy wrapped and fresh streams may share a call.
+ *   T_new  > 1: n_streams == 1 only — the prefill of a stream that joins.
+ * Capacity and the time-embedding table are checked for every named stream before anything is launched (SF_ERR_CAPACITY names
+ * the stream; the cache is unchanged).  A workspace of sf_stream_workspace_bytes(enc, cache, T_new) — sized for the cache's full
+ * batch — is sufficient for any subset.                                                                                          */
+int sf_forward_stream_slots(sf_encoder* enc, sf_cache* cache, const void* pixels_dev, int pixel_dtype, int T_new,
+                            const int* streams, int n_streams, float* last_hidden_dev, float* pooler_dev,
+                            const float* pos_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+
 /* ---- single operators (each is one kernel of the path; used by the parity tests) ----------- */
 /* nn.LayerNorm(D, eps) rows (modeling:860-865,878-880,1251): x fp32 [rows,D] -> y fp32 [rows,D] */
 int sf_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev,

@@ -57,11 +57,14 @@ SIGNATURES = {
     "sf_cache_create": (_I, [_P, _I, _I, _I, _I, C.POINTER(_P)]),
     "sf_cache_reset": (_I, [_P]),
     "sf_cache_length": (_I, [_P]),
+    "sf_cache_stream_length": (_I, [_P, _I]),
+    "sf_cache_reset_stream": (_I, [_P, _I]),
     "sf_cache_bytes": (_SZ, [_P]),
     "sf_cache_set_policy": (_I, [_P, _I]),
     "sf_cache_destroy": (None, [_P]),
     "sf_stream_workspace_bytes": (_I, [_P, _P, _I, C.POINTER(_SZ)]),
     "sf_forward_stream": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_forward_stream_slots": (_I, [_P, _P, _P, _I, _I, C.POINTER(_I), _I, _P, _P, _P, _P, _SZ, _P]),
     "sf_forward_stream_attentions": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sf_op_linear": (_I, [_P, _P, _P, _P, _F, _I, _P, _I, _I, _I, _I, _P, _SZ, _P]),

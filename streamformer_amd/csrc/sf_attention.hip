@@ -1282,15 +1282,21 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_kernel(SfAttnArgs p, i
   const int h = task % p.heads, bn = task / p.heads;
   const int b = bn / p.N, n = bn % p.N;
   // the cache position by value, or (streamed frame replayed from the position-free graph) from device memory
-  const int q_t0 = p.pos_dev ? p.pos_dev[0] : p.q_t0;
-  const int Tk = p.pos_dev ? min(p.pos_dev[1], KP * 64) : p.Tk;
-  const int t_past = p.pos_dev ? Tk - 1 : p.t_past;         // absolute index of the query among the keys (causal: keys <= it)
+  // (ragged call: this sequence's own entry of the call's table, and its cache slab bs; the context row stays row b)
+  int q_t0 = p.q_t0, Tk = p.Tk, bs = b;
+  if (p.tab) {
+    const SfStreamSlot e = p.tab[b];
+    bs = e.stream; q_t0 = e.slot; Tk = min(e.tk, KP * 64);
+  } else if (p.pos_dev) {
+    q_t0 = p.pos_dev[0]; Tk = min(p.pos_dev[1], KP * 64);
+  }
+  const int t_past = (p.tab || p.pos_dev) ? Tk - 1 : p.t_past;         // absolute index of the query among the keys (causal: keys <= it)
   constexpr int ESZ = F32 ? 4 : 2;
   constexpr int QL = F32 ? 16 : 8;                 // 16-byte loads per 64-dim row
   const char* qb = reinterpret_cast<const char*>(p.q);
   const char* kb = reinterpret_cast<const char*>(p.k);
   const char* vb = reinterpret_cast<const char*>(p.v);
-  const size_t qoff = ((((size_t)b * p.Tq_cap + q_t0) * p.N + n) * p.row_pitch_q + h * HD) * ESZ;
+  const size_t qoff = ((((size_t)bs * p.Tq_cap + q_t0) * p.N + n) * p.row_pitch_q + h * HD) * ESZ;
 
   // ---- issue: q (same 128 / 256 bytes for every lane), this lane's key rows, this lane's V chunks -------------------
   u32x4_t qv[QL], kv[KP][QL], vv[KP][8][F32 ? 2 : 1];
@@ -1300,7 +1306,7 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_kernel(SfAttnArgs p, i
   for (int kp = 0; kp < KP; ++kp) {
     int key = kp * 64 + lane;
     key = key < Tk ? key : Tk - 1;                 // clamped rows are masked below
-    const size_t off = ((((size_t)b * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD) * ESZ;
+    const size_t off = ((((size_t)bs * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD) * ESZ;
 #pragma unroll
     for (int c = 0; c < QL; ++c) kv[kp][c] = *reinterpret_cast<const u32x4_t*>(kb + off + c * 16);
   }
@@ -1315,7 +1321,7 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_kernel(SfAttnArgs p, i
       for (int i = 0; i < 8; ++i) {
         int key = kp * 64 + i * 8 + tsub;
         key = key < Tk ? key : Tk - 1;
-        const size_t off = ((((size_t)b * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD + ch * 8) * ESZ;
+        const size_t off = ((((size_t)bs * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD + ch * 8) * ESZ;
         vv[kp][i][0] = *reinterpret_cast<const u32x4_t*>(vb + off);
         if (F32) vv[kp][i][F32 ? 1 : 0] = *reinterpret_cast<const u32x4_t*>(vb + off + 16);
       }
@@ -1418,8 +1424,13 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_lines_kernel(SfAttnArg
   if (task >= ntasks) return;
   const int h = task % p.heads, bn = task / p.heads;
   const int b = bn / p.N, n = bn % p.N;
-  int q_t0 = p.q_t0, Tk = p.Tk, t_past = p.t_past;
-  if (p.pos_dev) {                                 // streamed frame replayed from the position-free graph: {slot, keys} in one scalar load
+  int q_t0 = p.q_t0, Tk = p.Tk, t_past = p.t_past, bs = b;
+  if (p.tab) {                                     // ragged call: this sequence's own {slab, slot, keys}
+    const SfStreamSlot e = p.tab[b];
+    bs = e.stream; q_t0 = e.slot;
+    Tk = min(e.tk, KP * 64);
+    t_past = Tk - 1;
+  } else if (p.pos_dev) {                                 // streamed frame replayed from the position-free graph: {slot, keys} in one scalar load
     struct __attribute__((aligned(4))) SlotKeys { int slot, tk; };
     const SlotKeys sk = *reinterpret_cast<const SlotKeys*>(p.pos_dev);
     q_t0 = sk.slot;
@@ -1429,7 +1440,7 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_lines_kernel(SfAttnArg
   const int tsub = lane >> 3, ch = lane & 7;       // key = 64 kp + 8 i + tsub, dims 8 ch .. 8 ch + 7
   const char* kb = reinterpret_cast<const char*>(p.k);
   const char* vb = reinterpret_cast<const char*>(p.v);
-  const size_t qoff = ((((size_t)b * p.Tq_cap + q_t0) * p.N + n) * p.row_pitch_q + h * HD + ch * 8) * 2;
+  const size_t qoff = ((((size_t)bs * p.Tq_cap + q_t0) * p.N + n) * p.row_pitch_q + h * HD + ch * 8) * 2;
   const u32x4_t qv = *reinterpret_cast<const u32x4_t*>(reinterpret_cast<const char*>(p.q) + qoff);
   u32x4_t kv[KP][8], vv[KP][8];
 #pragma unroll
@@ -1438,7 +1449,7 @@ __global__ __launch_bounds__(256) void sf_temporal_decode_lines_kernel(SfAttnArg
     for (int i = 0; i < 8; ++i) {
       int key = kp * 64 + i * 8 + tsub;
       key = key < Tk ? key : Tk - 1;               // clamped rows (one line, already in the cache) are masked below
-      const size_t off = ((((size_t)b * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD + ch * 8) * 2;
+      const size_t off = ((((size_t)bs * p.Tcap + key) * p.N + n) * p.row_pitch_kv + h * HD + ch * 8) * 2;
       kv[kp][i] = *reinterpret_cast<const u32x4_t*>(kb + off);
       vv[kp][i] = *reinterpret_cast<const u32x4_t*>(vb + off);
     }

@@ -83,8 +83,14 @@ __global__ __launch_bounds__(256) void sf_attention_generic_kernel(SfGenAttn p) 
     t_past = Lk - 1;
   }
   const int b = p.temporal ? seq / a.N : 0, n = p.temporal ? seq % a.N : 0;
-  auto qrow = [&](int t) -> size_t { return p.temporal ? ((size_t)b * a.Tq_cap + q_t0 + t) * a.N + n : (size_t)seq * a.N + t; };
-  auto krow = [&](int t) -> size_t { return p.temporal ? ((size_t)b * a.Tcap + t) * a.N + n : (size_t)seq * a.N + t; };
+  int bs = b;
+  if (p.temporal && a.tab) {                       // ragged streaming call: the sequence's own {slab, slot, keys} (Tq = 1)
+    const SfStreamSlot e = a.tab[b];
+    bs = e.stream; q_t0 = e.slot; Lk = e.tk;
+    t_past = Lk - 1;
+  }
+  auto qrow = [&](int t) -> size_t { return p.temporal ? ((size_t)bs * a.Tq_cap + q_t0 + t) * a.N + n : (size_t)seq * a.N + t; };
+  auto krow = [&](int t) -> size_t { return p.temporal ? ((size_t)bs * a.Tcap + t) * a.N + n : (size_t)seq * a.N + t; };
   auto orow = [&](int t) -> size_t { return p.temporal ? ((size_t)b * a.Tq + t) * a.N + n : (size_t)seq * a.N + t; };
 
   // this lane's query (l15 of the tile) and its HDQ contiguous dims

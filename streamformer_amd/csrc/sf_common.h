@@ -223,6 +223,13 @@ enum SfEpilogue {
   SF_EPI_EMBED_F32 = 4,  // out_f32 = acc + bias + pos[row % Np] + time[(row / Np) % Tn]
 };
 
+// One row group of a ragged streaming call (streams of one batched cache at different positions, any subset of them advanced by one
+// frame): group g of the call belongs to cache slab `stream`; t_row / slot / tk as in SfStreamParams below.  The table of a call
+// lives in DEVICE memory next to the parameter block and is written by the same launch (sf_launch_patchify).
+struct __attribute__((aligned(16))) SfStreamSlot { int stream, t_row, slot, tk; };
+#define SF_MAX_CALL_STREAMS 64                 // the table travels as a kernel argument of the patch extraction
+struct SfStreamTable { int n; int pad[3]; SfStreamSlot e[SF_MAX_CALL_STREAMS]; };
+
 struct SfGemmArgs {
   const bf16_t* a_hi; const bf16_t* a_lo;   // [M,K]   (a_lo == nullptr unless split)
   const bf16_t* w_hi; const bf16_t* w_lo;   // [N,K]
@@ -252,6 +259,9 @@ struct SfGemmArgs {
   // streaming: the cache position comes from DEVICE memory (one hipGraph serves every position):
   //   grp_off += *grp_off_dev * grp_off_scale
   const int* grp_off_dev; int grp_off_scale;
+  // ragged streaming call: group g = m / grp_rows goes to slab grp_tab[g].stream at row grp_tab[g].slot * grp_off_scale (instead of
+  // slab g at the one position above); the skinny kernel's folded time row of group m / Np is grp_tab[m / Np].t_row
+  const SfStreamSlot* grp_tab;
   int w_nt;                                 // skinny kernels: non-temporal policy on the weight loads (lab switch SF_SKINNY_NT)
   // LayerNorm folded into the NEXT Linear (bf16 mode): a residual producer also emits bf16(x) in out_hi
   // and per-row partial sums {sum x, sum x^2} per 384-column half in ln_stats_out [M][4]; the consumer
@@ -273,6 +283,11 @@ struct SfGemmArgs {
 };
 SF_DEVICE size_t sf_out_row(const SfGemmArgs& p, int m) {
   if (p.grp_rows <= 0) return (size_t)m;
+  if (p.grp_tab) {
+    const int g = m / p.grp_rows;
+    const SfStreamSlot e = p.grp_tab[g];
+    return (size_t)e.stream * p.grp_stride + e.slot * p.grp_off_scale + (m - g * p.grp_rows);
+  }
   const int off = p.grp_off + (p.grp_off_dev ? *p.grp_off_dev * p.grp_off_scale : 0);
   return (size_t)(m / p.grp_rows) * p.grp_stride + off + (m % p.grp_rows);
 }
@@ -351,9 +366,11 @@ hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi
                               int F, int C, int H, int W, int P, hipStream_t s, const SfPixelNorm* norm = nullptr,
                               const SfStreamParams* sp = nullptr,      // sp != nullptr: pixels = sp->pixels (device read)
                               SfStreamParams* sp_write = nullptr, const SfStreamParams* sp_value = nullptr,
-                              int Kpad = 0);       // > C * P * P: row pitch of the patch matrix, zero-filled past the patch vector
+                              int Kpad = 0,        // > C * P * P: row pitch of the patch matrix, zero-filled past the patch vector
+                              SfStreamSlot* tab_write = nullptr, const SfStreamTable* tab_value = nullptr);
                               // sp_write: the launch also stores *sp_value there (the streamed frame's parameter block rides on the
-                              // patch extraction instead of a launch of its own)
+                              // patch extraction instead of a launch of its own); tab_write: and the tab_value->n entries of a
+                              // ragged call's table
 // fp32 [n] -> bf16 hi (+lo)
 hipError_t sf_launch_split(const float* x, bf16_t* hi, bf16_t* lo, size_t n, hipStream_t s);
 // two fp32 copies in one launch (b may be null): the streaming path's hand-over of graph-owned outputs to the caller's tensors
@@ -367,7 +384,8 @@ hipError_t sf_launch_pos_time_table(const float* pos, const float* time_rows, fl
 // gather rows: out[t,:] = table[idx[t],:]   (idx passed by value, T <= 256)
 struct SfRowIndex { int n; int idx[256]; };
 hipError_t sf_launch_gather_rows(const float* table, float* out, const SfRowIndex& idx, int D, hipStream_t s,
-                                 const int* base_dev = nullptr);       // row = idx[t] + *base_dev
+                                 const int* base_dev = nullptr,        // row = idx[t] + *base_dev
+                                 const SfStreamSlot* tab = nullptr);   // row = tab[t].t_row (one row per group of a ragged call)
 
 // ------------------------------------------------------------------------------------------------
 // attention
@@ -413,6 +431,8 @@ struct SfAttnArgs {
   int B, Tq, Tk, Tcap, t_past, causal, Tq_cap, q_t0;
   const int* pos_dev;                 // single-query decode kernel only: {slot, tk} from device memory (position-free graph): q row = slot,
                                       // tk keys, all of them visible
+  const SfStreamSlot* tab;            // single-query kernels, ragged call: sequence b reads tab[b].{slot, tk} and the q / k / v rows of slab
+                                      // tab[b].stream; its context row stays row b of the call
   bf16_t* ctx_hi; bf16_t* ctx_lo;     // [rows, D] output (lo only in accurate mode)
   int D;
   int head_dim;                       // 0 or 64: the tuned kernels of sf_attention.hip; any other multiple of 8 up to 128: sf_attention_generic.hip

@@ -123,7 +123,11 @@ static hipError_t prof_span(const sf_encoder* ce, int cls, hipStream_t s, F&& la
 struct sf_cache {
   sf_encoder* enc = nullptr;
   uint64_t enc_generation = 0;   // packing of the encoder this cache was sized for (element size, device, weights)
-  int B = 0, cap = 0, H = 0, W = 0, N = 0, len = 0;
+  int B = 0, cap = 0, H = 0, W = 0, N = 0;
+  std::vector<int> lens;    // frames seen per stream; the lockstep entry points need them level
+  int len() const { int m = 0; for (int v : lens) m = v > m ? v : m; return m; }      // the largest (every stream's, when level)
+  bool level() const { for (int v : lens) if (v != lens[0]) return false; return true; }
+  void advance(int T) { for (int& v : lens) v += T; }
   bool warmed = false;      // one eager call has run on this cache (lazy kernel set-up done) -> captures may start
   std::vector<void*> qkv;   // per layer [B, cap, N, 3D] (bf16 or fp32 by compute mode)
   size_t bytes = 0;
@@ -141,6 +145,8 @@ struct sf_cache {
                                       // cannot capture) and replayed on the caller's
   int policy = 0;                     // 0 = stop at capacity (the reference raises there), 1 = sliding window over the last `cap` frames
   SfStreamParams* dparams = nullptr;  // device block {pixels, outputs, position} of the single-frame graph (one graph for all positions)
+  SfStreamSlot* dtable = nullptr;     // behind it: the stream table of a ragged call, SF_MAX_CALL_STREAMS entries (sf_forward_stream_slots)
+  std::map<uint32_t, bool> ragged_seen;      // ragged call shapes that have run eagerly once (lazy kernel set-up done) -> their capture may start
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -595,7 +601,7 @@ static Workspace carve(const sf_encoder* e, void* base, int B, int T, int N, boo
   const bool acc = e->compute == SF_COMPUTE_BF16X3;
   const size_t wide = D > (size_t)e->Kp ? D : (size_t)e->Kp;
   w.resid = c.take<float>(M * D);
-  w.te_rows = c.take<float>((size_t)T * D);
+  w.te_rows = c.take<float>((size_t)((!need_tqkv && B > T) ? B : T) * D);      // streaming: a ragged call gathers one time row per stream
   w.ln_stats = c.take<float>(M * 8);                  // rows of 8 floats in both modes (SfGemmArgs::ln_stats_wide)
   w.embed_tab = (!acc && M >= 2048) ? c.take<float>((size_t)T * N * D) : nullptr;
   w.patch_buf = (!acc && M >= 2048) ? c.take<bf16_t>(M * (size_t)e->Kp) : nullptr;
@@ -789,6 +795,9 @@ struct ForwardRequest {
   // pos3 (streaming, T == 1): {time-embedding row, cache slot, keys seen} when they differ from (t_past, t_past, t_past + 1):
   // the sliding-window policy of a full cache
   const int* pos3 = nullptr;
+  // tab (streaming, T == 1, with sp): the call is ragged — row group g is one frame of cache slab tab[g].stream at that entry's own
+  // position (device table); B counts the groups of the call, pos3 carries the largest tk (kernel variants only)
+  const SfStreamSlot* tab = nullptr;
 };
 
 enum EmbedRoute { EMBED_NONE, EMBED_TILE, EMBED_PANEL, EMBED_GEMM };
@@ -892,7 +901,7 @@ static ForwardPlan plan_forward(const sf_encoder* e, const ForwardRequest& rq, c
       if (p.pm) gp = gq;
     }
     // pos + time rows added in the epilogue: the statistics-producing narrow tile (tile-fold), or whatever sf_launch_gemm picks
-    g.epi = SF_EPI_EMBED_F32; g.pos = rq.pos_dev ? rq.pos_dev : e->pos; g.time_rows = ws.te_rows; g.Np = N; g.Tn = T;
+    g.epi = SF_EPI_EMBED_F32; g.pos = rq.pos_dev ? rq.pos_dev : e->pos; g.time_rows = ws.te_rows; g.Np = N; g.Tn = rq.tab ? rq.B : T;      // ragged call: one gathered time row per group
     SfGemmArgs gt = g;
     gt.out_hi = ws.xn_hi; gt.ln_stats_out = ws.ln_stats; gt.ln_stats_wide = 1;
     if (!acc && !streaming && (stages & 2) && p.patches != ws.xn_hi && tile_fold && sf_gemm_tile_supported(gt, false)) {      // (A must not alias out_hi)
@@ -903,7 +912,7 @@ static ForwardPlan plan_forward(const sf_encoder* e, const ForwardRequest& rq, c
       // streamed frame inside the position-free graph: the time-embedding row straight from the table — exactly when sf_launch_gemm
       // takes the skinny kernel
       p.time_folded = rq.sp && T == 1 && !stats_fold && !sf_sw(SW_DISABLE_SKINNY) && sf_gemm_skinny_supported(g, acc);
-      if (p.time_folded) { g.time_rows = e->time_tab; g.time_base_dev = &rq.sp->t_row; }
+      if (p.time_folded) { g.time_rows = e->time_tab; g.time_base_dev = &rq.sp->t_row; g.grp_tab = rq.tab; }
       if (small_bufs && (stages & 2)) { g.out_hi = ws.res_bf; if (acc) g.out_lo = ws.res_lo; }   // layer 0's folded qkv reads bf16(x) (accurate: hi + lo)
       p.embed_route = EMBED_GEMM; p.embed = g;
     }
@@ -973,10 +982,11 @@ static int forward_embeddings(sf_encoder* e, const ForwardPlan& p, const Workspa
   const ForwardRequest& rq = p.rq;
   const sf_config& c = e->cfg;
   SfRowIndex idx;
-  int rc = time_rows(e, p.t_row, rq.T, rq.streaming, &idx);
+  int rc = rq.tab ? SF_OK : time_rows(e, p.t_row, rq.T, rq.streaming, &idx);      // (ragged call: the entry point has checked every stream's row)
   if (rc) return rc;
   if (rq.sp) { for (int t = 0; t < rq.T; ++t) idx.idx[t] = t; }
-  if (!p.time_folded) HIP_TRY(sf_launch_gather_rows(e->time_tab, ws.te_rows, idx, e->D, s, rq.sp ? &rq.sp->t_row : nullptr));
+  if (rq.tab) idx.n = rq.B;
+  if (!p.time_folded) HIP_TRY(sf_launch_gather_rows(e->time_tab, ws.te_rows, idx, e->D, s, rq.sp ? &rq.sp->t_row : nullptr, rq.tab));
   if (!(rq.ready & 1))
     HIP_TRY(sf_launch_patchify(rq.pixels, rq.pixel_dtype == SF_U8 ? 2 : (rq.pixel_dtype == SF_BF16 ? 1 : 0), p.patches, ws.xn_lo, p.F, c.num_channels, rq.H, rq.W,
                                c.patch_size, s, &e->pixel_norm, nullptr, nullptr, nullptr, e->Kp));
@@ -1022,7 +1032,7 @@ static int forward_layer(sf_encoder* e, const ForwardPlan& p, const Workspace& w
 #ifdef SF_LAB
   // lab library, SF_STREAM_QKV_FUSE=1 (one streamed frame per stream, bf16 mode, cache of <= 64 frames): projection + cache append +
   // single-query attention in one launch (tools/lab/sf_stream_fused.hip; bit-identical, 15.0 against 6.1 + 7.4 us: a CU's ingest)
-  if (!t_fused_attn && p.sfold && !acc && T == 1 && rq.layer_tqkv && l.t_qkv_f.ln_s) {
+  if (!t_fused_attn && p.sfold && !acc && T == 1 && rq.layer_tqkv && l.t_qkv_f.ln_s && !rq.tab) {
     SfStreamQkvArgs q;
     memset(&q, 0, sizeof(q));
     q.a = p.ln_in; q.w_frag = l.t_qkv_f.w_frag; q.bias = l.t_qkv_f.bias; q.ln_s = l.t_qkv_f.ln_s; q.ln_eps = c.layer_norm_eps;
@@ -1041,6 +1051,7 @@ static int forward_layer(sf_encoder* e, const ForwardPlan& p, const Workspace& w
     // the new frames' rows go to their slots of the [B, cap, N, 3D] cache (position from the device block inside the position-free graph)
     g.grp_rows = T * N; g.grp_stride = rq.cap * N; g.grp_off = sp ? 0 : p.slot * N;
     g.grp_off_dev = sp ? &sp->slot : nullptr; g.grp_off_scale = N;
+    g.grp_tab = rq.tab;                                                                    // ragged call: slab and slot per row group
     if (g.grp_stride == g.grp_rows && g.grp_off == 0 && !g.grp_off_dev) g.grp_rows = 0;   // identity remap (full clip)
     HIP_TRY(sf_launch_gemm(g, acc, s));
     SfAttnArgs a;
@@ -1048,7 +1059,7 @@ static int forward_layer(sf_encoder* e, const ForwardPlan& p, const Workspace& w
     set_qkv_in(a, e, tq, p.tplanes, p.tsz, p, ws);
     a.B = rq.B; a.Tq = T; a.Tk = p.tk; a.Tcap = rq.cap; a.t_past = p.tk - T;
     a.causal = c.enable_causal_temporal; a.Tq_cap = rq.cap; a.q_t0 = p.slot;
-    a.pos_dev = sp ? &sp->slot : nullptr;
+    a.pos_dev = sp ? &sp->slot : nullptr; a.tab = rq.tab;
     HIP_TRY(prof_span(e, 3, s, [&]() { return sf_launch_temporal_attention(a, acc, s); }));
   }
   if (e->fused_temporal) {
@@ -1345,6 +1356,7 @@ extern "C" int sf_cache_create(sf_encoder* e, int B, int max_frames, int H, int 
   HIP_TRY(hipSetDevice(e->device));
   sf_cache* c = new sf_cache();
   c->enc = e; c->enc_generation = e->generation; c->B = B; c->cap = max_frames; c->H = H; c->W = W; c->N = N;
+  c->lens.assign(B, 0);
   const size_t per = (size_t)B * max_frames * N * 3 * e->D * (e->compute == SF_COMPUTE_BF16X3 ? 4 : 2);
   for (int i = 0; i < e->L; ++i) {
     void* p = nullptr;
@@ -1357,23 +1369,33 @@ extern "C" int sf_cache_create(sf_encoder* e, int B, int max_frames, int H, int 
     c->qkv.push_back(p);
   }
   c->bytes = per * e->L;
-  if (hipMalloc((void**)&c->dparams, sizeof(SfStreamParams)) != hipSuccess) {
+  // the parameter block, and behind it (256-byte aligned) the stream table of a ragged call
+  if (hipMalloc((void**)&c->dparams, 256 + sizeof(SfStreamSlot) * SF_MAX_CALL_STREAMS) != hipSuccess) {
     for (void* q : c->qkv) (void)hipFree(q);
     delete c;
     return set_err(SF_ERR_HIP, "hipMalloc for the stream parameter block failed");
   }
+  static_assert(sizeof(SfStreamParams) <= 256, "the stream table sits 256 bytes behind the parameter block");
+  c->dtable = reinterpret_cast<SfStreamSlot*>(reinterpret_cast<char*>(c->dparams) + 256);
   *out = c;
   return SF_OK;
 }
 extern "C" int sf_cache_reset(sf_cache* c) {
   if (!c) return set_err(SF_ERR_INVALID, "null cache");
-  c->len = 0;
+  c->lens.assign(c->B, 0);
   return SF_OK;
 }
-extern "C" int sf_cache_length(const sf_cache* c) { return c ? c->len : 0; }
+extern "C" int sf_cache_reset_stream(sf_cache* c, int stream) {
+  if (!c) return set_err(SF_ERR_INVALID, "null cache");
+  if (stream < 0 || stream >= c->B) return set_err(SF_ERR_INVALID, "stream %d outside this cache's %d streams", stream, c->B);
+  c->lens[stream] = 0;
+  return SF_OK;
+}
+extern "C" int sf_cache_length(const sf_cache* c) { return c ? c->len() : 0; }
+extern "C" int sf_cache_stream_length(const sf_cache* c, int stream) { return (c && stream >= 0 && stream < c->B) ? c->lens[stream] : 0; }
 extern "C" int sf_cache_set_policy(sf_cache* c, int policy) {
   if (!c || (policy != 0 && policy != 1)) return set_err(SF_ERR_INVALID, "policy must be 0 (stop at capacity) or 1 (sliding window)");
-  if (c->len != 0) return set_err(SF_ERR_STATE, "the policy of a cache is chosen while it is empty");
+  if (c->len() != 0) return set_err(SF_ERR_STATE, "the policy of a cache is chosen while it is empty");
   c->policy = policy;
   return SF_OK;
 }
@@ -1397,38 +1419,52 @@ extern "C" int sf_stream_workspace_bytes(sf_encoder* e, const sf_cache* c, int T
   *out = carve(e, nullptr, c->B, T_new, c->N, false).bytes;
   return SF_OK;
 }
+// slab < 0: every stream of the cache advances T_new frames from the one position they share (the lockstep call).
+// slab >= 0: that stream alone, as a B = 1 call on its slab of every layer's cache (the prefill of a stream that joins a ragged cache);
+// always eager — a prefill happens once per stream, and its position-keyed graph would be captured for a single replay.
 static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, int pixel_dtype, int T_new,
                                float* last_hidden, float* pooler, float* hidden_states, float* attentions, const float* pos_dev,
-                               void* workspace, size_t workspace_bytes, sf_stream stream) {
+                               void* workspace, size_t workspace_bytes, sf_stream stream, int slab = -1) {
   if (!e || !c || c->enc != e) return set_err(SF_ERR_INVALID, "cache does not belong to this encoder");
   // a handle address can be reused after sf_destroy, and sf_finalize_weights may have changed the compute mode (cache element
   // size) or the device: the generation stamp tells a cache of an earlier packing from a current one
   if (c->enc_generation != e->generation)
     return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
   int N;
-  int rc = check_geometry(e, c->B, T_new, c->H, c->W, pos_dev, &N);
+  const int B = slab < 0 ? c->B : 1;
+  int rc = check_geometry(e, B, T_new, c->H, c->W, pos_dev, &N);
   if (rc) return rc;
+  if (slab < 0 && !c->level())
+    return set_err(SF_ERR_STATE, "the streams of this cache are at different positions (longest %d frames): advance them with sf_forward_stream_slots "
+                   "(stream_ids= in Python), or level them with sf_cache_reset", c->len());
+  const int len = slab < 0 ? c->len() : c->lens[slab];
   if (!pixels || !last_hidden || !workspace) return set_err(SF_ERR_INVALID, "null buffer");
   if (pixel_dtype != SF_F32 && pixel_dtype != SF_BF16 && pixel_dtype != SF_U8) return set_err(SF_ERR_INVALID, "pixels must be fp32, bf16 or uint8");
   // Positions of the call.  Sliding window (policy 1, beyond the reference, which raises at num_frames): once the cache is
   // full the new frame overwrites the oldest slot, its query sees the last `cap` frames, and frames past the time-embedding
   // table reuse its last row (the nearest-neighbour extension modeling:441-447 applies to long clips).
   const int nf = e->cfg.num_frames;
-  const bool slide = c->policy == 1 && c->len + T_new > (c->cap < nf ? c->cap : nf);
+  const bool slide = c->policy == 1 && len + T_new > (c->cap < nf ? c->cap : nf);
   if (slide && T_new != 1)
-    return set_err(SF_ERR_CAPACITY, "a sliding-window cache that is full (%d of %d frames) advances one frame per call, got %d", c->len, c->cap, T_new);
-  if (!slide && c->len + T_new > c->cap)
-    return set_err(SF_ERR_CAPACITY, "cache holds %d of %d frames; %d more do not fit", c->len, c->cap, T_new);
-  if (!slide && c->len + T_new > nf)
-    return set_err(SF_ERR_CAPACITY, "streaming needs time-embedding row %d but config.num_frames is %d", c->len + T_new - 1, nf);
-  int pos3[3] = {c->len, c->len, c->len + T_new};
+    return set_err(SF_ERR_CAPACITY, "a sliding-window cache that is full (%d of %d frames) advances one frame per call, got %d", len, c->cap, T_new);
+  if (!slide && len + T_new > c->cap)
+    return set_err(SF_ERR_CAPACITY, "cache holds %d of %d frames; %d more do not fit", len, c->cap, T_new);
+  if (!slide && len + T_new > nf)
+    return set_err(SF_ERR_CAPACITY, "streaming needs time-embedding row %d but config.num_frames is %d", len + T_new - 1, nf);
+  int pos3[3] = {len, len, len + T_new};
   if (c->policy == 1 && T_new == 1) {
-    pos3[0] = c->len < nf ? c->len : nf - 1;
-    pos3[1] = c->len % c->cap;
-    pos3[2] = c->len + 1 < c->cap ? c->len + 1 : c->cap;
+    pos3[0] = len < nf ? len : nf - 1;
+    pos3[1] = len % c->cap;
+    pos3[2] = len + 1 < c->cap ? len + 1 : c->cap;
   }
   const int* pos = (c->policy == 1 && T_new == 1) ? pos3 : nullptr;
-  Workspace ws = carve(e, workspace, c->B, T_new, N, false);
+  auto advance = [&](int T) { if (slab < 0) c->advance(T); else c->lens[slab] += T; };
+  std::vector<void*> slab_qkv;
+  if (slab >= 0) {
+    const size_t per = (size_t)c->cap * N * 3 * e->D * (e->compute == SF_COMPUTE_BF16X3 ? 4 : 2);
+    for (void* q : c->qkv) slab_qkv.push_back((char*)q + (size_t)slab * per);
+  }
+  Workspace ws = carve(e, workspace, B, T_new, N, false);
   if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
   hipStream_t s = (hipStream_t)stream;
   // ---- graph replay (the per-frame sequence is ~100 dependent launches of a few microseconds) -----------------
@@ -1437,16 +1473,16 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(s, &cap);
   const bool graphs_off = sf_sw(SW_DISABLE_STREAM_GRAPH) != nullptr;
-  const bool use_graph = !graphs_off && !hidden_states && !attentions && cap == hipStreamCaptureStatusNone && T_new < 256 && c->len < 65536;
+  const bool use_graph = slab < 0 && !graphs_off && !hidden_states && !attentions && cap == hipStreamCaptureStatusNone && T_new < 256 && len < 65536;
   // what the four forwards below share; each sets its outputs and its position
   ForwardRequest rq;
-  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = c->B; rq.T = T_new; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
-  rq.layer_tqkv = c->qkv.data(); rq.cap = c->cap; rq.streaming = true;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = B; rq.T = T_new; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
+  rq.layer_tqkv = slab < 0 ? c->qkv.data() : slab_qkv.data(); rq.cap = c->cap; rq.streaming = true;
   if (!use_graph) {
     rq.last_hidden = last_hidden; rq.pooler = pooler; rq.hidden_states = hidden_states; rq.attentions = attentions;
-    rq.t_past = c->len; rq.pos3 = pos;
+    rq.t_past = len; rq.pos3 = pos;
     rc = run_forward(e, rq, ws, s);
-    if (rc == SF_OK) c->len += T_new;
+    if (rc == SF_OK) advance(T_new);
     return rc;
   }
   const int F = c->B * T_new, M = F * N;
@@ -1458,7 +1494,7 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
   const bool posfree = T_new == 1 && !posfree_off && c->dparams != nullptr;
   const int kp = (pos3[2] + 63) >> 6;
   const int kcls = kp <= 1 ? 1 : (kp <= 2 ? 2 : 4);
-  const uint32_t key = posfree ? (0x80000000u | (uint32_t)kcls) : (((uint32_t)c->len << 8) | (uint32_t)T_new);
+  const uint32_t key = posfree ? (0x80000000u | (uint32_t)kcls) : (((uint32_t)len << 8) | (uint32_t)T_new);
   if (!posfree && pos) return set_err(SF_ERR_STATE, "SF_STREAM_GRAPH_PER_POSITION cannot serve a sliding-window cache");
   sf_cache::GraphEntry& g = c->graphs[key];
   if (g.exec && (g.ws != workspace || g.pos != pos_dev || g.pooler != (pooler != nullptr))) {
@@ -1471,9 +1507,9 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
     // first call of this cache: run eagerly once so that every lazy per-kernel set-up (hipFuncSetAttribute, device
     // queries) has happened before a capture is opened
     rq.last_hidden = last_hidden; rq.pooler = pooler;
-    rq.t_past = c->len; rq.pos3 = pos;
+    rq.t_past = len; rq.pos3 = pos;
     rc = run_forward(e, rq, ws, s);
-    if (rc == SF_OK) { c->len += T_new; c->warmed = true; }
+    if (rc == SF_OK) { advance(T_new); c->warmed = true; }
     if (!g.exec) c->graphs.erase(key);
     return rc;
   }
@@ -1505,7 +1541,7 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
       if (rc == SF_OK && pooler && !plan.head_rows)      // the F-row tail left pooler_output in the workspace
         pe = sf_launch_copy2(nullptr, nullptr, 0, ws.pool_stage, nullptr, (size_t)F * e->D, c->cap_stream, c->dparams);
     } else {
-      rq.t_past = c->len;
+      rq.t_past = len;
       rc = run_forward(e, rq, ws, c->cap_stream);
     }
     hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
@@ -1534,7 +1570,7 @@ static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, i
     HIP_TRY(hipGraphLaunch(g.exec, s));
     HIP_TRY(sf_launch_copy2(ws.lhs_stage, last_hidden, (size_t)M * e->D, pooler ? ws.pool_stage : nullptr, pooler, (size_t)F * e->D, s));
   }
-  c->len += T_new;
+  advance(T_new);
   return SF_OK;
 }
 
@@ -1552,6 +1588,138 @@ extern "C" int sf_forward_stream_attentions(sf_encoder* e, sf_cache* c, const vo
   if (!attentions) return set_err(SF_ERR_INVALID, "null attentions buffer");
   return forward_stream_impl(e, c, pixels, pixel_dtype, T_new, last_hidden, pooler, hidden_states, attentions, pos_dev, workspace,
                              workspace_bytes, stream);
+}
+
+// Ragged streaming: the named streams of one batched cache advance, each from its own position.  One frame per stream (the streaming
+// step proper): the same launch sequence as the lockstep call of n_streams rows, with {slab, time row, slot, keys} of every row group
+// read from a device table that the patch extraction writes next to the parameter block — so one captured graph per (rows, key-pass
+// class, pooler, pixel kind) serves every combination of positions.  The key-pass class comes from the longest stream of the call;
+// shorter ones are masked by the kernels' own key < tk test.
+extern "C" int sf_forward_stream_slots(sf_encoder* e, sf_cache* c, const void* pixels, int pixel_dtype, int T_new, const int* streams,
+                                       int n_streams, float* last_hidden, float* pooler, const float* pos_dev, void* workspace,
+                                       size_t workspace_bytes, sf_stream stream) {
+  if (!e || !c || c->enc != e) return set_err(SF_ERR_INVALID, "cache does not belong to this encoder");
+  if (c->enc_generation != e->generation)
+    return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
+  if (!streams || n_streams <= 0) return set_err(SF_ERR_INVALID, "name at least one stream");
+  if (T_new <= 0) return set_err(SF_ERR_INVALID, "T_new must be positive");
+  {
+    std::vector<char> named(c->B, 0);
+    for (int i = 0; i < n_streams; ++i) {
+      const int st = streams[i];
+      if (st < 0 || st >= c->B) return set_err(SF_ERR_INVALID, "stream %d outside this cache's %d streams (ids are 0 .. %d)", st, c->B, c->B - 1);
+      if (named[st]) return set_err(SF_ERR_INVALID, "stream %d named twice: a stream advances once per call, pass several frames of one stream as T_new > 1", st);
+      named[st] = 1;
+    }
+  }
+  if (T_new > 1) {
+    if (n_streams != 1)
+      return set_err(SF_ERR_INVALID, "T_new = %d with %d streams: several frames per call are the prefill of ONE stream — call once per stream with "
+                     "n_streams = 1, then advance the streams together one frame per call", T_new, n_streams);
+    return forward_stream_impl(e, c, pixels, pixel_dtype, T_new, last_hidden, pooler, nullptr, nullptr, pos_dev, workspace, workspace_bytes, stream,
+                               streams[0]);
+  }
+  if (n_streams > SF_MAX_CALL_STREAMS)
+    return set_err(SF_ERR_INVALID, "%d streams in one call; the stream table holds %d: split the call", n_streams, SF_MAX_CALL_STREAMS);
+  const int n = n_streams;
+  int N;
+  int rc = check_geometry(e, n, 1, c->H, c->W, pos_dev, &N);
+  if (rc) return rc;
+  if (!pixels || !last_hidden || !workspace) return set_err(SF_ERR_INVALID, "null buffer");
+  if (pixel_dtype != SF_F32 && pixel_dtype != SF_BF16 && pixel_dtype != SF_U8) return set_err(SF_ERR_INVALID, "pixels must be fp32, bf16 or uint8");
+  // every stream's position, checked before anything is launched (sliding window: SfStreamParams in sf_common.h)
+  const int nf = e->cfg.num_frames;
+  SfStreamTable tv;
+  memset(&tv, 0, sizeof(tv));
+  tv.n = n;
+  int max_tk = 0;
+  for (int i = 0; i < n; ++i) {
+    const int st = streams[i], len = c->lens[st];
+    SfStreamSlot& t = tv.e[i];
+    t.stream = st;
+    if (c->policy == 1) {
+      t.t_row = len < nf ? len : nf - 1; t.slot = len % c->cap; t.tk = len + 1 < c->cap ? len + 1 : c->cap;
+    } else {
+      if (len + 1 > c->cap)
+        return set_err(SF_ERR_CAPACITY, "stream %d holds %d of %d frames; one more does not fit: leave it out of the call, or restart it with "
+                       "sf_cache_reset_stream", st, len, c->cap);
+      if (len + 1 > nf)
+        return set_err(SF_ERR_CAPACITY, "stream %d needs time-embedding row %d but config.num_frames is %d: leave it out of the call, or restart it "
+                       "with sf_cache_reset_stream", st, len, nf);
+      t.t_row = len; t.slot = len; t.tk = len + 1;
+    }
+    max_tk = t.tk > max_tk ? t.tk : max_tk;
+  }
+  Workspace ws = carve(e, workspace, n, 1, N, false);
+  if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
+  hipStream_t s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(s, &cap);
+  const bool use_graph = !sf_sw(SW_DISABLE_STREAM_GRAPH) && cap == hipStreamCaptureStatusNone && c->dparams != nullptr;
+  const int kp = (max_tk + 63) >> 6;
+  const int kcls = kp <= 1 ? 1 : (kp <= 2 ? 2 : 4);
+  const int pk = pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0);
+  const uint32_t key = 0x40000000u | ((uint32_t)n << 8) | ((uint32_t)kcls << 4) | (pooler ? 4u : 0u) | (uint32_t)pk;
+  // the call's forward: patch matrix extracted by the launch that delivers the block and the table, a representative key count of the
+  // class (it selects the 64-key pass count; the kernels read every stream's own from the table), outputs through the block
+  int rep_tk = kcls * 64;
+  if (rep_tk > c->cap) rep_tk = c->cap;
+  if (c->policy != 1 && rep_tk > nf) rep_tk = nf;
+  const int rep3[3] = {0, 0, rep_tk};
+  ForwardRequest rq;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = n; rq.T = 1; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
+  rq.layer_tqkv = c->qkv.data(); rq.cap = c->cap; rq.streaming = true;
+  rq.last_hidden = ws.lhs_stage; rq.pooler = pooler ? ws.pool_stage : nullptr;
+  rq.ready = 1; rq.t_past = 0; rq.sp = c->dparams; rq.tab = c->dtable; rq.pos3 = rep3;
+  const ForwardPlan plan = plan_forward(e, rq, ws);
+  auto run = [&](hipStream_t on) -> int {
+    int r = run_plan(e, plan, ws, on);
+    if (r == SF_OK && pooler && !plan.head_rows)       // the F-row tail left pooler_output in the workspace
+      HIP_TRY(sf_launch_copy2(nullptr, nullptr, 0, ws.pool_stage, nullptr, (size_t)n * e->D, on, c->dparams));
+    return r;
+  };
+  SfStreamParams v;
+  v.pixels = pixels; v.lhs = last_hidden; v.pooler = pooler; v.t_row = tv.e[0].t_row; v.slot = tv.e[0].slot; v.tk = max_tk;
+  auto deliver = [&]() -> hipError_t {
+    return sf_launch_patchify(pixels, pk, ws.xn_hi, ws.xn_lo, n, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr,
+                              c->dparams, &v, e->Kp, c->dtable, &tv);
+  };
+  // The first call of a shape runs eagerly, so that every lazy per-kernel set-up has happened before its capture is opened
+  // (the lockstep entry's `warmed`, per shape: another row count selects other GEMM kernels).
+  if (!use_graph || !c->ragged_seen[key]) {
+    HIP_TRY(deliver());
+    rc = run(s);
+    if (rc != SF_OK) return rc;
+    if (use_graph) c->ragged_seen[key] = true;
+    for (int i = 0; i < n; ++i) c->lens[streams[i]] += 1;
+    return SF_OK;
+  }
+  sf_cache::GraphEntry& g = c->graphs[key];
+  if (g.exec && (g.ws != workspace || g.pos != pos_dev)) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+  if (!g.exec) {
+    hipGraph_t graph = nullptr;
+    if (!c->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
+    rc = run(c->cap_stream);
+    hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
+    if (rc != SF_OK || ce != hipSuccess || !graph) {
+      if (graph) (void)hipGraphDestroy(graph);
+      c->graphs.erase(key);
+      if (rc != SF_OK) return rc;
+      return set_err(SF_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce));
+    }
+    hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) {
+      c->graphs.erase(key);
+      return set_err(SF_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+    }
+    g.ws = workspace; g.pos = pos_dev; g.pooler = pooler != nullptr; g.pixel_kind = pk;
+  }
+  HIP_TRY(deliver());
+  HIP_TRY(hipGraphLaunch(g.exec, s));
+  for (int i = 0; i < n; ++i) c->lens[streams[i]] += 1;
+  return SF_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

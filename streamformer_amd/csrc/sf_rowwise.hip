@@ -107,14 +107,8 @@ hipError_t sf_launch_layernorm(const float* x, const float* gamma, const float* 
 // one FMA per pixel, so frames cross PCIe / HBM as bytes.
 // ------------------------------------------------------------------------------------------------
 template <int IN>
-__global__ __launch_bounds__(256) void sf_patchify_kernel(const void* __restrict__ pixels,
-                                                          bf16_t* __restrict__ out_hi,
-                                                          bf16_t* __restrict__ out_lo, int F, int C, int H,
-                                                          int W, int P, int gh, int gw, SfPixelNorm norm,
-                                                          const SfStreamParams* __restrict__ sp, SfStreamParams* sp_write,
-                                                          SfStreamParams sp_value) {
-  if (sp) pixels = sp->pixels;
-  if (sp_write && blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+SF_DEVICE void sf_patchify_body(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi, bf16_t* __restrict__ out_lo, int F, int C, int H,
+                                int W, int P, int gh, int gw, const SfPixelNorm& norm) {
   const int Kp = C * P * P;
   const int chunks_per_row = Kp >> 3;
   const size_t total = (size_t)F * gh * gw * chunks_per_row;
@@ -154,16 +148,33 @@ __global__ __launch_bounds__(256) void sf_patchify_kernel(const void* __restrict
           (u32x4_t){l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16)};
   }
 }
+template <int IN>
+__global__ __launch_bounds__(256) void sf_patchify_kernel(const void* __restrict__ pixels,
+                                                          bf16_t* __restrict__ out_hi,
+                                                          bf16_t* __restrict__ out_lo, int F, int C, int H,
+                                                          int W, int P, int gh, int gw, SfPixelNorm norm,
+                                                          const SfStreamParams* __restrict__ sp, SfStreamParams* sp_write,
+                                                          SfStreamParams sp_value) {
+  if (sp) pixels = sp->pixels;
+  if (sp_write && blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+  sf_patchify_body<IN>(pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm);
+}
+// Ragged streaming call: the launch also stores the call's stream table (one entry per row group, by thread = entry of workgroup 0)
+template <int IN>
+__global__ __launch_bounds__(256) void sf_patchify_tab_kernel(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi,
+                                                              bf16_t* __restrict__ out_lo, int F, int C, int H, int W, int P, int gh, int gw,
+                                                              SfPixelNorm norm, SfStreamParams* sp_write, SfStreamParams sp_value,
+                                                              SfStreamSlot* tab_write, SfStreamTable tab_value) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+  if (blockIdx.x == 0 && (int)threadIdx.x < tab_value.n) tab_write[threadIdx.x] = tab_value.e[threadIdx.x];
+  sf_patchify_body<IN>(pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm);
+}
 
 // Any patch size / padded patch vectors (14 x 14 patches: K = 588 -> 640): one thread per 8 output columns, element by element;
 // columns past C * P * P are zeros (the patch-embedding weight is zero-padded to the same width at upload).
 template <int IN>
-__global__ __launch_bounds__(256) void sf_patchify_generic_kernel(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi,
-                                                                  bf16_t* __restrict__ out_lo, int F, int C, int H, int W, int P, int gh, int gw,
-                                                                  int Kpad, SfPixelNorm norm, const SfStreamParams* __restrict__ sp,
-                                                                  SfStreamParams* sp_write, SfStreamParams sp_value) {
-  if (sp) pixels = sp->pixels;
-  if (sp_write && blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+SF_DEVICE void sf_patchify_generic_body(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi, bf16_t* __restrict__ out_lo, int F, int C,
+                                        int H, int W, int P, int gh, int gw, int Kpad, const SfPixelNorm& norm) {
   const int Kr = C * P * P, chunks_per_row = Kpad >> 3;
   const size_t total = (size_t)F * gh * gw * chunks_per_row;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -189,12 +200,33 @@ __global__ __launch_bounds__(256) void sf_patchify_generic_kernel(const void* __
     if (out_lo) *reinterpret_cast<u32x4_t*>(out_lo + o) = (u32x4_t){l[0] | (l[1] << 16), l[2] | (l[3] << 16), l[4] | (l[5] << 16), l[6] | (l[7] << 16)};
   }
 }
+template <int IN>
+__global__ __launch_bounds__(256) void sf_patchify_generic_kernel(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi,
+                                                                  bf16_t* __restrict__ out_lo, int F, int C, int H, int W, int P, int gh, int gw,
+                                                                  int Kpad, SfPixelNorm norm, const SfStreamParams* __restrict__ sp,
+                                                                  SfStreamParams* sp_write, SfStreamParams sp_value) {
+  if (sp) pixels = sp->pixels;
+  if (sp_write && blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+  sf_patchify_generic_body<IN>(pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm);
+}
+template <int IN>
+__global__ __launch_bounds__(256) void sf_patchify_generic_tab_kernel(const void* __restrict__ pixels, bf16_t* __restrict__ out_hi,
+                                                                      bf16_t* __restrict__ out_lo, int F, int C, int H, int W, int P, int gh,
+                                                                      int gw, int Kpad, SfPixelNorm norm, SfStreamParams* sp_write,
+                                                                      SfStreamParams sp_value, SfStreamSlot* tab_write, SfStreamTable tab_value) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *sp_write = sp_value;
+  if (blockIdx.x == 0 && (int)threadIdx.x < tab_value.n) tab_write[threadIdx.x] = tab_value.e[threadIdx.x];
+  sf_patchify_generic_body<IN>(pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm);
+}
 
 hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi, bf16_t* out_lo,
                               int F, int C, int H, int W, int P, hipStream_t s, const SfPixelNorm* pnorm, const SfStreamParams* sp,
-                              SfStreamParams* sp_write, const SfStreamParams* sp_value, int Kpad) {
+                              SfStreamParams* sp_write, const SfStreamParams* sp_value, int Kpad, SfStreamSlot* tab_write,
+                              const SfStreamTable* tab_value) {
   SfStreamParams spv = {};
   if (sp_write) { if (!sp_value) return hipErrorInvalidValue; spv = *sp_value; }
+  // the table rides with the parameter block, on the caller's pixels
+  if (tab_write && (!tab_value || !sp_write || sp || tab_value->n <= 0 || tab_value->n > SF_MAX_CALL_STREAMS)) return hipErrorInvalidValue;
   SfPixelNorm norm;
   for (int i = 0; i < 4; ++i) { norm.scale[i] = 1.0f / 127.5f; norm.shift[i] = -1.0f; }    // mean = std = 0.5, rescale 1/255
   if (pnorm) norm = *pnorm;
@@ -205,6 +237,12 @@ hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi
     const size_t total = (size_t)F * gh * gw * (Kpad / 8);
     if (!total) return hipSuccess;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (tab_write) {
+#define SF_PG_TAB(IN) hipLaunchKernelGGL(sf_patchify_generic_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp_write, spv, tab_write, *tab_value)
+      if (pixel_kind == 2) SF_PG_TAB(2); else if (pixel_kind == 1) SF_PG_TAB(1); else SF_PG_TAB(0);
+#undef SF_PG_TAB
+      return hipGetLastError();
+    }
     if (pixel_kind == 2) hipLaunchKernelGGL(sf_patchify_generic_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
     else if (pixel_kind == 1) hipLaunchKernelGGL(sf_patchify_generic_kernel<1>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
     else hipLaunchKernelGGL(sf_patchify_generic_kernel<0>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
@@ -215,6 +253,12 @@ hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi
   const size_t total = (size_t)F * gh * gw * (C * P * P / 8);
   if (!total) return hipSuccess;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  if (tab_write) {
+#define SF_P_TAB(IN) hipLaunchKernelGGL(sf_patchify_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp_write, spv, tab_write, *tab_value)
+    if (pixel_kind == 2) SF_P_TAB(2); else if (pixel_kind == 1) SF_P_TAB(1); else SF_P_TAB(0);
+#undef SF_P_TAB
+    return hipGetLastError();
+  }
   if (pixel_kind == 2)
     hipLaunchKernelGGL(sf_patchify_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
   else if (pixel_kind == 1)
@@ -288,15 +332,16 @@ hipError_t sf_launch_rowstats_cast(const float* x, bf16_t* xb, float* stats, int
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sf_gather_rows_kernel(const float* __restrict__ table,
                                                              float* __restrict__ out, SfRowIndex idx, int D,
-                                                             const int* __restrict__ base_dev) {
+                                                             const int* __restrict__ base_dev, const SfStreamSlot* __restrict__ tab) {
   const int t = blockIdx.x;
-  const float* src = table + (size_t)(idx.idx[t] + (base_dev ? *base_dev : 0)) * D;
+  const float* src = table + (size_t)(tab ? tab[t].t_row : idx.idx[t] + (base_dev ? *base_dev : 0)) * D;
   for (int i = threadIdx.x; i < D; i += blockDim.x) out[(size_t)t * D + i] = src[i];
 }
 
-hipError_t sf_launch_gather_rows(const float* table, float* out, const SfRowIndex& idx, int D, hipStream_t s, const int* base_dev) {
+hipError_t sf_launch_gather_rows(const float* table, float* out, const SfRowIndex& idx, int D, hipStream_t s, const int* base_dev,
+                                 const SfStreamSlot* tab) {
   if (idx.n <= 0 || idx.n > 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_gather_rows_kernel, dim3(idx.n), dim3(256), 0, s, table, out, idx, D, base_dev);
+  hipLaunchKernelGGL(sf_gather_rows_kernel, dim3(idx.n), dim3(256), 0, s, table, out, idx, D, base_dev, tab);
   return hipGetLastError();
 }
 

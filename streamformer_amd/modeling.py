@@ -29,7 +29,7 @@ from __future__ import annotations
 import os
 import weakref
 from collections import OrderedDict
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -78,12 +78,16 @@ def BaseModelOutputWithPast(last_hidden_state, past_key_values=None, hidden_stat
 
 
 class StreamCache:
-    """Temporal KV-cache of one stream: the ``past_key_values`` object of the streaming forward.
+    """Temporal KV-cache of ``batch`` streams: the ``past_key_values`` object of the streaming forward.
 
     Library-owned device memory (``sf_cache``); mirrors the two things the reference uses of HF's
     ``DynamicCache``: ``get_seq_length()`` (vqa_enc:328-331) and being threaded through calls.
     A cache belongs to the packed weights it was created against: when the model re-packs (new weights, another
-    compute mode, another device) the cache is invalidated and the next use raises instead of reading freed memory."""
+    compute mode, another device) the cache is invalidated and the next use raises instead of reading freed memory.
+
+    Every stream (slab) of a batched cache keeps its own position.  The plain call advances all of them together and needs them
+    level; ``forward(..., stream_ids=[...])`` advances any subset, each from where it stands.  ``acquire()`` / ``release()`` hand
+    slabs out to sessions that come and go."""
 
     def __init__(self, model: "TimesformerMultiTaskingModelSigLIP", batch: int, max_frames: int, H: int, W: int,
                  policy: str = "stop"):
@@ -93,6 +97,7 @@ class StreamCache:
         self._h = nat.C.c_void_p()
         nat.check(nat.lib.sf_cache_create(model._handle, batch, max_frames, H, W, nat.C.byref(self._h)))
         self.batch, self.max_frames, self.H, self.W, self.policy = batch, max_frames, H, W, policy
+        self._free = list(range(batch))      # slabs no session holds, lowest first (acquire / release)
         if policy == "slide":
             nat.check(nat.lib.sf_cache_set_policy(self._h, 1))
         model._caches.add(self)
@@ -107,17 +112,42 @@ class StreamCache:
                                "left (load_state_dict, set_compute_dtype or .to() re-packed it): start a new cache")
         return self._h
 
-    def get_seq_length(self, layer_idx: int = 0) -> int:
-        """Frames the cache holds (HF ``DynamicCache`` semantics): never more than ``max_frames`` under the sliding window."""
-        return min(self.frames_seen, self.max_frames)
+    def get_seq_length(self, layer_idx: int = 0, stream: Optional[int] = None) -> int:
+        """Frames the cache holds (HF ``DynamicCache`` semantics): never more than ``max_frames`` under the sliding window.
+        ``stream``: of that stream; otherwise of the longest one."""
+        seen = self.frames_seen if stream is None else self.frames_seen_per_stream[self._check_stream(stream)]
+        return min(seen, self.max_frames)
 
     @property
     def frames_seen(self) -> int:
-        """Frames streamed through this cache since its creation / last ``reset()``."""
+        """Frames streamed through this cache since its creation / last ``reset()`` (the longest stream's count)."""
         return nat.lib.sf_cache_length(self._require())
 
-    def reset(self) -> None:
-        nat.check(nat.lib.sf_cache_reset(self._require()))
+    @property
+    def frames_seen_per_stream(self) -> List[int]:
+        h = self._require()
+        return [nat.lib.sf_cache_stream_length(h, i) for i in range(self.batch)]
+
+    def _check_stream(self, stream: int) -> int:
+        if not isinstance(stream, int) or isinstance(stream, bool) or not 0 <= stream < self.batch:
+            raise ValueError(f"stream must be an int in 0..{self.batch - 1} (this cache holds {self.batch} streams), got {stream!r}")
+        return stream
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        """Forget every stream's frames, or those of ``stream`` alone (the others keep their positions)."""
+        if stream is None:
+            nat.check(nat.lib.sf_cache_reset(self._require()))
+        else:
+            nat.check(nat.lib.sf_cache_reset_stream(self._require(), self._check_stream(stream)))
+
+    def acquire(self) -> int:
+        """A free slab for a new session (the lowest free index).  Raises when every slab is held."""
+        return _slab_acquire(self._free, self.batch)
+
+    def release(self, stream: int) -> None:
+        """Return a slab: it is reset and may be handed out again."""
+        _slab_release(self._free, self._check_stream(stream))
+        self.reset(stream)
 
     @property
     def nbytes(self) -> int:
@@ -133,6 +163,20 @@ class StreamCache:
             self._invalidate()
         except Exception:
             pass
+
+
+def _slab_acquire(free: List[int], batch: int) -> int:
+    if not free:
+        raise RuntimeError(f"all {batch} streams of this cache are in use: release() one, or create the cache with a larger "
+                           "batch_size")
+    return free.pop(0)
+
+
+def _slab_release(free: List[int], stream: int) -> None:
+    if stream in free:
+        raise ValueError(f"stream {stream} is not acquired (released twice?)")
+    free.append(stream)
+    free.sort()
 
 
 def expected_keys(cfg: StreamformerConfig, lora: Optional[bool] = None) -> "OrderedDict[str, Tuple[int, ...]]":
@@ -768,7 +812,10 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
     def forward(self, pixel_values: torch.Tensor, output_attentions: Optional[bool] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None,
                 past_key_values: Optional[StreamCache] = None, use_cache: bool = False,
-                cache_position: Optional[torch.Tensor] = None):
+                cache_position: Optional[torch.Tensor] = None, stream_ids: Optional[Sequence[int]] = None):
+        """``stream_ids`` (with ``past_key_values``): row ``i`` of ``pixel_values`` is the next frame of stream ``stream_ids[i]`` of a
+        batched cache; any subset of its streams, each continuing from its own position, outputs in the same order.  Several
+        frames per call (``T > 1``) are the prefill of one stream."""
         c = self.config
         output_attentions = c.output_attentions if output_attentions is None else output_attentions
         output_hidden_states = c.output_hidden_states if output_hidden_states is None else output_hidden_states
@@ -779,6 +826,15 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         if C_ != c.num_channels:
             raise ValueError(f"expected {c.num_channels} channels, got {C_}")
         streaming = bool(use_cache) or past_key_values is not None
+        if stream_ids is not None:
+            if not isinstance(past_key_values, StreamCache):
+                raise ValueError("stream_ids names streams of a batched cache: pass past_key_values=model.new_cache(batch_size=...)")
+            if output_attentions or output_hidden_states:
+                raise NotImplementedError("output_attentions / output_hidden_states are not available together with stream_ids: "
+                                          "use a lockstep call (all streams, no stream_ids) for them")
+            stream_ids = [int(i) for i in stream_ids]
+            if len(stream_ids) != B:
+                raise ValueError(f"pixel_values carries {B} streams but stream_ids names {len(stream_ids)}")
         if self.training and torch.is_grad_enabled() and not streaming and any(p.requires_grad for p in self._plist):
             # the reference wrapper's training forward (modeling:1506-1511): outputs carry a grad_fn (autograd.py)
             if output_attentions or output_hidden_states:
@@ -827,6 +883,26 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
                     raise ValueError("past_key_values belongs to another model")
                 # a sliding-window cache saturates get_seq_length() at its capacity while frames_seen keeps counting: an HF-style
                 # caller that derives cache_position from get_seq_length() is as right as one that counts frames
+                if stream_ids is not None:
+                    if cache_position is not None:
+                        # one start position per named stream ([B] or [B, T]); checked for the ids the library will accept
+                        cp = torch.as_tensor(cache_position)
+                        cp = (cp[:, 0] if cp.dim() == 2 else cp.reshape(-1)).tolist()
+                        if len(cp) != B:
+                            raise ValueError(f"cache_position must give one start position per named stream ({B}), got {len(cp)}")
+                        seen = cache.frames_seen_per_stream
+                        for sid, pos0 in zip(stream_ids, cp):
+                            if 0 <= sid < cache.batch and int(pos0) not in (seen[sid], min(seen[sid], cache.max_frames)):
+                                raise ValueError(f"cache_position {int(pos0)} does not continue stream {sid} ({seen[sid]} frames seen)")
+                    if (cache.H, cache.W) != (H, W):
+                        raise ValueError("past_key_values was created for a different resolution")
+                    nat.check(nat.lib.sf_stream_workspace_bytes(self._handle, ch, T, nat.C.byref(nbytes)))
+                    ws = self._workspace(("s", cache.batch, T, H, W, skey), nbytes.value)
+                    ids = (nat.C.c_int * max(B, 1))(*stream_ids)
+                    nat.check(nat.lib.sf_forward_stream_slots(self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T, ids, B,
+                                                              lhs.data_ptr(), pool.data_ptr(), nat.ptr(pos), ws.data_ptr(),
+                                                              ws.numel(), stream))
+                    return self._stream_output(cast(lhs), cast(pool), None, None, cache, True, return_dict)
                 if cache_position is not None and int(cache_position[0]) not in (cache.frames_seen, cache.get_seq_length()):
                     raise ValueError("cache_position must continue the cache (vqa_enc:1340-1349)")
                 if (cache.batch, cache.H, cache.W) != (B, H, W):
@@ -863,14 +939,18 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         lhs, pool = cast(lhs), cast(pool)
         if streaming:
             attentions = tuple(att[i] for i in range(L)) if att is not None else None
-            if not return_dict:
-                return (lhs,) + ((hidden,) if hidden is not None else ()) + ((attentions,) if attentions is not None else ()) + (cache,)
-            return BaseModelOutputWithPast(lhs, past_key_values=cache if use_cache or past_key_values is not None else None,
-                                           hidden_states=hidden, attentions=attentions, pooler_output=pool)
+            return self._stream_output(lhs, pool, hidden, attentions, cache, use_cache or past_key_values is not None, return_dict)
         attentions = tuple(att[i] for i in range(L)) if att is not None else None    # spatial probabilities per layer
         if not return_dict:
             return (lhs,) + ((hidden,) if hidden is not None else ()) + ((attentions,) if attentions is not None else ())
         return BaseModelOutputWithPooling(lhs, pool, hidden_states=hidden, attentions=attentions)
+
+    @staticmethod
+    def _stream_output(lhs, pool, hidden, attentions, cache, keep_cache, return_dict):
+        if not return_dict:
+            return (lhs,) + ((hidden,) if hidden is not None else ()) + ((attentions,) if attentions is not None else ()) + (cache,)
+        return BaseModelOutputWithPast(lhs, past_key_values=cache if keep_cache else None,
+                                       hidden_states=hidden, attentions=attentions, pooler_output=pool)
 
     # -------------------------------------------------------------------------------- sub-modules
     # The reference's users that drive the encoder piecewise (ViT-Adapter interaction blocks:
