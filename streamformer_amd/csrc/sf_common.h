@@ -354,14 +354,13 @@ hipError_t sf_launch_layernorm(const float* x, const float* gamma, const float* 
 // pixels [F,C,H,W] -> patch matrix [F*N, C*P*P] bf16 (+lo), columns (c,ph,pw).
 // pixel_kind 0 fp32, 1 bf16, 2 uint8 raw frames normalised on the fly: y = x * scale[c] + shift[c]
 struct SfPixelNorm { float scale[4]; float shift[4]; };
-// Per-call parameters of a streamed frame, in DEVICE memory (written by one tiny launch in front of the graph replay): the
+// Per-call parameters of a streamed frame, in DEVICE memory (written by the patch extraction in front of the graph replay): the
 // caller's input / output tensors and the cache position.  Kernels of the captured sequence read them through this block, so
 // ONE graph serves every call (no per-position capture, no staging copy of the outputs).
 // t_row = time-embedding row of the new frame, slot = its row in the KV-cache, tk = keys its query sees (cached + itself).
 // Plain streaming: t_row = slot = frames cached, tk = slot + 1.  Sliding window (cache full): slot = t mod capacity,
 // tk = capacity, t_row = min(t, num_frames - 1).
 struct SfStreamParams { const void* pixels; float* lhs; float* pooler; int t_row; int slot; int tk; };
-hipError_t sf_launch_stream_params(SfStreamParams* dst, const SfStreamParams& v, hipStream_t s);
 hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi, bf16_t* out_lo,
                               int F, int C, int H, int W, int P, hipStream_t s, const SfPixelNorm* norm = nullptr,
                               const SfStreamParams* sp = nullptr,      // sp != nullptr: pixels = sp->pixels (device read)

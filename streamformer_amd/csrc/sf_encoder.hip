@@ -12,7 +12,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #define SF_ABI_VERSION 5
@@ -128,25 +130,36 @@ struct sf_cache {
   int len() const { int m = 0; for (int v : lens) m = v > m ? v : m; return m; }      // the largest (every stream's, when level)
   bool level() const { for (int v : lens) if (v != lens[0]) return false; return true; }
   void advance(int T) { for (int& v : lens) v += T; }
-  bool warmed = false;      // one eager call has run on this cache (lazy kernel set-up done) -> captures may start
   std::vector<void*> qkv;   // per layer [B, cap, N, 3D] (bf16 or fp32 by compute mode)
   size_t bytes = 0;
-  // hipGraph of the per-call launch sequence, one per (frames cached, frames added): everything between the patch
-  // extraction (reads the caller's pixels) and the copy-out (writes the caller's outputs) is replayed as one graph launch
+  // hipGraph of the per-call launch sequence: everything between the patch extraction (reads the caller's pixels) and the
+  // copy-out (writes the caller's outputs) is replayed as one graph launch.  The key names what is compiled into a capture;
+  // the entry holds what else it is valid for (the addresses its nodes carry).
+  enum GraphKind { PER_POSITION, POSITION_FREE, RAGGED };      // lockstep, several frames per call / lockstep, one frame / named streams
+  struct GraphKey {
+    int kind = PER_POSITION;
+    int rows = 0, T_new = 0;          // row groups (streams) and frames per stream of the call
+    int at = 0;                       // PER_POSITION: frames cached; otherwise the key-pass class (key_pass_class)
+    int pooler = 0, pixel_kind = 0;   // pooler_output wanted; 0 fp32, 1 bf16, 2 uint8 frames
+    bool operator<(const GraphKey& o) const {
+      return std::tie(kind, rows, T_new, at, pooler, pixel_kind) < std::tie(o.kind, o.rows, o.T_new, o.at, o.pooler, o.pixel_kind);
+    }
+  };
   struct GraphEntry {
     hipGraphExec_t exec = nullptr;
     void* ws = nullptr;
     const float* pos = nullptr;
-    bool pooler = false;
-    int pixel_kind = 0;
   };
-  std::map<uint32_t, GraphEntry> graphs;
+  std::map<GraphKey, GraphEntry> graphs;
+  // Keys that have run eagerly once, so that every lazy per-kernel set-up (hipFuncSetAttribute, device queries) has happened
+  // before a capture is opened.  The lockstep entry warms once per cache, under kLockstepWarm; the ragged entry once per key
+  // (another row count selects other GEMM kernels).
+  std::set<GraphKey> warmed;
   hipStream_t cap_stream = nullptr;   // captures are recorded on a private stream (the caller's may be the null stream, which
                                       // cannot capture) and replayed on the caller's
   int policy = 0;                     // 0 = stop at capacity (the reference raises there), 1 = sliding window over the last `cap` frames
   SfStreamParams* dparams = nullptr;  // device block {pixels, outputs, position} of the single-frame graph (one graph for all positions)
   SfStreamSlot* dtable = nullptr;     // behind it: the stream table of a ragged call, SF_MAX_CALL_STREAMS entries (sf_forward_stream_slots)
-  std::map<uint32_t, bool> ragged_seen;      // ragged call shapes that have run eagerly once (lazy kernel set-up done) -> their capture may start
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -773,6 +786,9 @@ static int time_rows(const sf_encoder* e, int t_past, int T, bool streaming, SfR
   return SF_OK;
 }
 
+// Where a streamed frame goes: its time-embedding row, its slot in the KV-cache, and the keys its query sees (cached + itself).
+struct StreamPos { int t_row, slot, tk; };
+
 // What one call of the encoder over T new frames is asked to do (filled by name at the entry points).
 struct ForwardRequest {
   const void* pixels = nullptr; int pixel_dtype = SF_F32;
@@ -792,11 +808,10 @@ struct ForwardRequest {
   // sp (streaming, T == 1, graph capture): the cache position is read on the DEVICE from sp->t_past by the kernels that need
   // it (time-embedding row, KV-cache append row, single-query attention); t_past here only selects kernel variants
   const SfStreamParams* sp = nullptr;
-  // pos3 (streaming, T == 1): {time-embedding row, cache slot, keys seen} when they differ from (t_past, t_past, t_past + 1):
-  // the sliding-window policy of a full cache
-  const int* pos3 = nullptr;
+  // pos (streaming): the position of the first new frame, from stream_position(); null: (t_past, t_past, t_past + T)
+  const StreamPos* pos = nullptr;
   // tab (streaming, T == 1, with sp): the call is ragged — row group g is one frame of cache slab tab[g].stream at that entry's own
-  // position (device table); B counts the groups of the call, pos3 carries the largest tk (kernel variants only)
+  // position (device table); B counts the groups of the call, pos carries the largest tk (kernel variants only)
   const SfStreamSlot* tab = nullptr;
 };
 
@@ -871,7 +886,7 @@ static ForwardPlan plan_forward(const sf_encoder* e, const ForwardRequest& rq, c
   p.N = N; p.M = M; p.F = rq.B * T; p.acc = acc;
   p.qkv_epi = acc ? SF_EPI_F32 : SF_EPI_BF16; p.esz = acc ? 4 : 2;
   p.scale = 1.0f / sqrtf((float)e->hd);
-  p.t_row = rq.pos3 ? rq.pos3[0] : rq.t_past; p.slot = rq.pos3 ? rq.pos3[1] : rq.t_past; p.tk = rq.pos3 ? rq.pos3[2] : rq.t_past + T;
+  p.t_row = rq.pos ? rq.pos->t_row : rq.t_past; p.slot = rq.pos ? rq.pos->slot : rq.t_past; p.tk = rq.pos ? rq.pos->tk : rq.t_past + T;
 
   const bool tile_fold = ln_fold_tile_ok(e, M), small_fold = ln_fold_small_ok(e, M);
   const bool stats_fold = tile_fold || (!small_fold && ln_fold_panel_ok(e, M));      // bf16 mode: a fold with a statistics buffer
@@ -1419,158 +1434,210 @@ extern "C" int sf_stream_workspace_bytes(sf_encoder* e, const sf_cache* c, int T
   *out = carve(e, nullptr, c->B, T_new, c->N, false).bytes;
   return SF_OK;
 }
+// What the lockstep entry records in sf_cache::warmed: no key of a call equals it, a call has rows >= 1.
+static const sf_cache::GraphKey kLockstepWarm = {};
+
+// The cache was created by this encoder, as it is packed now.
+static int check_cache_owner(const sf_encoder* e, const sf_cache* c) {
+  if (!e || !c || c->enc != e) return set_err(SF_ERR_INVALID, "cache does not belong to this encoder");
+  // a handle address can be reused after sf_destroy, and sf_finalize_weights may have changed the compute mode (cache element
+  // size) or the device: the generation stamp tells a cache of an earlier packing from a current one (ADVICE r1)
+  if (c->enc_generation != e->generation)
+    return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
+  return SF_OK;
+}
+
+// What the streaming entries share once the cache is known to be the encoder's: the checked arguments of a call of `rows` streams.
+struct StreamCall {
+  Workspace ws;
+  ForwardRequest rq;      // input, geometry and cache filled in; the entry sets the outputs and the position
+  hipStream_t s = nullptr;
+  int pk = 0;             // pixel kind of sf_launch_patchify
+  bool graph_ok = false;  // graphs are not switched off and the caller is not capturing the stream itself
+};
+// lockstep: the call advances every stream of the cache, which must be level.  positions(): the entry's position refusals; they come
+// before the workspace refusal.
+template <typename Positions>
+static int open_stream_call(sf_encoder* e, sf_cache* c, int rows, int T_new, bool lockstep, const void* pixels, int pixel_dtype,
+                            const float* last_hidden, const float* pos_dev, void* workspace, size_t workspace_bytes, sf_stream stream,
+                            Positions&& positions, StreamCall* call) {
+  int N;
+  int rc = check_geometry(e, rows, T_new, c->H, c->W, pos_dev, &N);
+  if (rc) return rc;
+  if (lockstep && !c->level())
+    return set_err(SF_ERR_STATE, "the streams of this cache are at different positions (longest %d frames): advance them with sf_forward_stream_slots "
+                   "(stream_ids= in Python), or level them with sf_cache_reset", c->len());
+  if (!pixels || !last_hidden || !workspace) return set_err(SF_ERR_INVALID, "null buffer");
+  if (pixel_dtype != SF_F32 && pixel_dtype != SF_BF16 && pixel_dtype != SF_U8) return set_err(SF_ERR_INVALID, "pixels must be fp32, bf16 or uint8");
+  if ((rc = positions())) return rc;
+  call->ws = carve(e, workspace, rows, T_new, N, false);
+  if (call->ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, call->ws.bytes);
+  call->pk = pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0);
+  call->s = (hipStream_t)stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(call->s, &cap);
+  call->graph_ok = !sf_sw(SW_DISABLE_STREAM_GRAPH) && cap == hipStreamCaptureStatusNone;
+  ForwardRequest& rq = call->rq;
+  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = rows; rq.T = T_new; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
+  rq.layer_tqkv = c->qkv.data(); rq.cap = c->cap; rq.streaming = true;
+  return SF_OK;
+}
+
+// Position of the first of T_new frames that follow `len` cached ones, or the refusal (stream: the id a ragged call names, -1 for a
+// lockstep call).  Sliding window (policy 1, beyond the reference, which raises at num_frames): once the cache is full the new
+// frame overwrites the oldest slot, its query sees the last `cap` frames, and frames past the time-embedding table reuse its
+// last row (the nearest-neighbour extension modeling:441-447 applies to long clips).
+static int stream_position(const sf_cache* c, int len, int T_new, int stream, StreamPos* out) {
+  const int nf = c->enc->cfg.num_frames, cap = c->cap;
+  if (c->policy == 1 && T_new == 1) {
+    *out = {len < nf ? len : nf - 1, len % cap, len + 1 < cap ? len + 1 : cap};
+    return SF_OK;
+  }
+  if (c->policy == 1 && len + T_new > (cap < nf ? cap : nf))
+    return set_err(SF_ERR_CAPACITY, "a sliding-window cache that is full (%d of %d frames) advances one frame per call, got %d", len, cap, T_new);
+  if (len + T_new > cap)
+    return stream < 0 ? set_err(SF_ERR_CAPACITY, "cache holds %d of %d frames; %d more do not fit", len, cap, T_new)
+                      : set_err(SF_ERR_CAPACITY, "stream %d holds %d of %d frames; one more does not fit: leave it out of the call, or restart it with "
+                                "sf_cache_reset_stream", stream, len, cap);
+  if (len + T_new > nf)
+    return stream < 0 ? set_err(SF_ERR_CAPACITY, "streaming needs time-embedding row %d but config.num_frames is %d", len + T_new - 1, nf)
+                      : set_err(SF_ERR_CAPACITY, "stream %d needs time-embedding row %d but config.num_frames is %d: leave it out of the call, or restart it "
+                                "with sf_cache_reset_stream", stream, len + T_new - 1, nf);
+  *out = {len, len, len + T_new};
+  return SF_OK;
+}
+
+// The single-query attention compiles in its number of 64-key passes, 1 / 2 / 4: the only thing about a position that a
+// position-free capture fixes (at most three graphs per call shape).
+static int key_pass_class(int tk) {
+  const int kp = (tk + 63) >> 6;
+  return kp <= 1 ? 1 : (kp <= 2 ? 2 : 4);
+}
+// A key count of the class that this cache can reach: it selects the kernels, which read the live position from the device.
+static StreamPos class_position(const sf_cache* c, int kcls) {
+  const int nf = c->enc->cfg.num_frames;
+  int tk = kcls * 64;
+  if (tk > c->cap) tk = c->cap;
+  if (c->policy != 1 && tk > nf) tk = nf;
+  return {0, 0, tk};
+}
+
+// The forward of a position-free call (one frame per stream; ragged: the named streams through the device table): patch matrix
+// already extracted by the launch that delivered the parameter block, last_hidden_state written straight into the caller's tensor
+// through the block, pooler_output too when the head's row-vector tail runs (<= 4 rows): no staging copy at the end.
+static int run_position_free(sf_encoder* e, sf_cache* c, const StreamCall& call, int kcls, bool ragged, bool pooler, hipStream_t on) {
+  const StreamPos rep = class_position(c, kcls);
+  ForwardRequest rq = call.rq;
+  rq.last_hidden = call.ws.lhs_stage; rq.pooler = pooler ? call.ws.pool_stage : nullptr;
+  rq.ready = 1; rq.sp = c->dparams; rq.tab = ragged ? c->dtable : nullptr; rq.pos = &rep;
+  const ForwardPlan plan = plan_forward(e, rq, call.ws);
+  int rc = run_plan(e, plan, call.ws, on);
+  if (rc == SF_OK && pooler && !plan.head_rows)      // the F-row tail left pooler_output in the workspace
+    HIP_TRY(sf_launch_copy2(nullptr, nullptr, 0, call.ws.pool_stage, nullptr, (size_t)plan.F * e->D, on, c->dparams));
+  return rc;
+}
+
+// The graph of `key`, valid for this workspace and position table: the cached one, or a capture of run(cap_stream).
+template <typename Run>
+static int stream_graph(sf_cache* c, const sf_cache::GraphKey& key, void* workspace, const float* pos_dev, Run&& run, hipGraphExec_t* exec) {
+  sf_cache::GraphEntry& g = c->graphs[key];
+  if (g.exec && (g.ws != workspace || g.pos != pos_dev)) {      // its nodes carry addresses of another workspace
+    (void)hipGraphExecDestroy(g.exec);
+    g.exec = nullptr;
+  }
+  if (!g.exec) {
+    hipGraph_t graph = nullptr;
+    if (!c->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
+    const int rc = run(c->cap_stream);
+    const hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
+    hipError_t ie = hipSuccess;
+    if (rc == SF_OK && ce == hipSuccess && graph) ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (!g.exec) {
+      c->graphs.erase(key);
+      if (rc != SF_OK) return rc;
+      if (ie != hipSuccess) return set_err(SF_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+      return set_err(SF_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce));
+    }
+    g.ws = workspace; g.pos = pos_dev;
+  }
+  *exec = g.exec;
+  return SF_OK;
+}
+
 // slab < 0: every stream of the cache advances T_new frames from the one position they share (the lockstep call).
 // slab >= 0: that stream alone, as a B = 1 call on its slab of every layer's cache (the prefill of a stream that joins a ragged cache);
 // always eager — a prefill happens once per stream, and its position-keyed graph would be captured for a single replay.
 static int forward_stream_impl(sf_encoder* e, sf_cache* c, const void* pixels, int pixel_dtype, int T_new,
                                float* last_hidden, float* pooler, float* hidden_states, float* attentions, const float* pos_dev,
                                void* workspace, size_t workspace_bytes, sf_stream stream, int slab = -1) {
-  if (!e || !c || c->enc != e) return set_err(SF_ERR_INVALID, "cache does not belong to this encoder");
-  // a handle address can be reused after sf_destroy, and sf_finalize_weights may have changed the compute mode (cache element
-  // size) or the device: the generation stamp tells a cache of an earlier packing from a current one (ADVICE r1)
-  if (c->enc_generation != e->generation)
-    return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
-  int N;
-  const int B = slab < 0 ? c->B : 1;
-  int rc = check_geometry(e, B, T_new, c->H, c->W, pos_dev, &N);
+  int rc = check_cache_owner(e, c);
   if (rc) return rc;
-  if (slab < 0 && !c->level())
-    return set_err(SF_ERR_STATE, "the streams of this cache are at different positions (longest %d frames): advance them with sf_forward_stream_slots "
-                   "(stream_ids= in Python), or level them with sf_cache_reset", c->len());
   const int len = slab < 0 ? c->len() : c->lens[slab];
-  if (!pixels || !last_hidden || !workspace) return set_err(SF_ERR_INVALID, "null buffer");
-  if (pixel_dtype != SF_F32 && pixel_dtype != SF_BF16 && pixel_dtype != SF_U8) return set_err(SF_ERR_INVALID, "pixels must be fp32, bf16 or uint8");
-  // Positions of the call.  Sliding window (policy 1, beyond the reference, which raises at num_frames): once the cache is
-  // full the new frame overwrites the oldest slot, its query sees the last `cap` frames, and frames past the time-embedding
-  // table reuse its last row (the nearest-neighbour extension modeling:441-447 applies to long clips).
-  const int nf = e->cfg.num_frames;
-  const bool slide = c->policy == 1 && len + T_new > (c->cap < nf ? c->cap : nf);
-  if (slide && T_new != 1)
-    return set_err(SF_ERR_CAPACITY, "a sliding-window cache that is full (%d of %d frames) advances one frame per call, got %d", len, c->cap, T_new);
-  if (!slide && len + T_new > c->cap)
-    return set_err(SF_ERR_CAPACITY, "cache holds %d of %d frames; %d more do not fit", len, c->cap, T_new);
-  if (!slide && len + T_new > nf)
-    return set_err(SF_ERR_CAPACITY, "streaming needs time-embedding row %d but config.num_frames is %d", len + T_new - 1, nf);
-  int pos3[3] = {len, len, len + T_new};
-  if (c->policy == 1 && T_new == 1) {
-    pos3[0] = len < nf ? len : nf - 1;
-    pos3[1] = len % c->cap;
-    pos3[2] = len + 1 < c->cap ? len + 1 : c->cap;
-  }
-  const int* pos = (c->policy == 1 && T_new == 1) ? pos3 : nullptr;
-  auto advance = [&](int T) { if (slab < 0) c->advance(T); else c->lens[slab] += T; };
+  StreamCall call;
+  StreamPos pos;
+  if ((rc = open_stream_call(e, c, slab < 0 ? c->B : 1, T_new, slab < 0, pixels, pixel_dtype, last_hidden, pos_dev, workspace, workspace_bytes, stream,
+                             [&]() { return stream_position(c, len, T_new, -1, &pos); }, &call))) return rc;
+  const Workspace& ws = call.ws;
+  ForwardRequest& rq = call.rq;
+  hipStream_t s = call.s;
+  rq.pos = &pos;
   std::vector<void*> slab_qkv;
   if (slab >= 0) {
-    const size_t per = (size_t)c->cap * N * 3 * e->D * (e->compute == SF_COMPUTE_BF16X3 ? 4 : 2);
+    const size_t per = (size_t)c->cap * c->N * 3 * e->D * (e->compute == SF_COMPUTE_BF16X3 ? 4 : 2);
     for (void* q : c->qkv) slab_qkv.push_back((char*)q + (size_t)slab * per);
+    rq.layer_tqkv = slab_qkv.data();
   }
-  Workspace ws = carve(e, workspace, B, T_new, N, false);
-  if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
-  hipStream_t s = (hipStream_t)stream;
+  auto eager = [&]() -> int {
+    ForwardRequest q = rq;
+    q.last_hidden = last_hidden; q.pooler = pooler; q.hidden_states = hidden_states; q.attentions = attentions;
+    const int r = run_forward(e, q, ws, s);
+    if (r == SF_OK) { if (slab < 0) c->advance(T_new); else c->lens[slab] += T_new; }
+    return r;
+  };
   // ---- graph replay (the per-frame sequence is ~100 dependent launches of a few microseconds) -----------------
   // Not when the caller wants the per-layer hidden states (memcpy nodes to caller memory), is capturing the stream
   // itself, or asked for eager launches.
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  const bool graphs_off = sf_sw(SW_DISABLE_STREAM_GRAPH) != nullptr;
-  const bool use_graph = slab < 0 && !graphs_off && !hidden_states && !attentions && cap == hipStreamCaptureStatusNone && T_new < 256 && len < 65536;
-  // what the four forwards below share; each sets its outputs and its position
-  ForwardRequest rq;
-  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = B; rq.T = T_new; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
-  rq.layer_tqkv = slab < 0 ? c->qkv.data() : slab_qkv.data(); rq.cap = c->cap; rq.streaming = true;
-  if (!use_graph) {
-    rq.last_hidden = last_hidden; rq.pooler = pooler; rq.hidden_states = hidden_states; rq.attentions = attentions;
-    rq.t_past = len; rq.pos3 = pos;
-    rc = run_forward(e, rq, ws, s);
-    if (rc == SF_OK) advance(T_new);
-    return rc;
-  }
-  const int F = c->B * T_new, M = F * N;
+  if (slab >= 0 || !call.graph_ok || hidden_states || attentions) return eager();
   // One new frame per call (the streaming step proper): ONE graph per cache serves every position.  The caller's tensors
-  // and the position reach the kernels through a small device block written by one tiny launch in front of the replay;
-  // only the number of 64-key passes of the single-query attention is compiled in (1 / 2 / 4 -> at most three graphs).
+  // and the position reach the kernels through a small device block that the patch extraction writes in front of the replay;
+  // only the key-pass class is compiled in.
   // Several frames per call keep one graph per (position, count): their attention kernels take the position by value.
-  const bool posfree_off = sf_sw(SW_STREAM_GRAPH_PER_POSITION) != nullptr;
-  const bool posfree = T_new == 1 && !posfree_off && c->dparams != nullptr;
-  const int kp = (pos3[2] + 63) >> 6;
-  const int kcls = kp <= 1 ? 1 : (kp <= 2 ? 2 : 4);
-  const uint32_t key = posfree ? (0x80000000u | (uint32_t)kcls) : (((uint32_t)len << 8) | (uint32_t)T_new);
-  if (!posfree && pos) return set_err(SF_ERR_STATE, "SF_STREAM_GRAPH_PER_POSITION cannot serve a sliding-window cache");
-  sf_cache::GraphEntry& g = c->graphs[key];
-  if (g.exec && (g.ws != workspace || g.pos != pos_dev || g.pooler != (pooler != nullptr))) {
-    (void)hipGraphExecDestroy(g.exec);
-    g.exec = nullptr;
-  }
-  const int pk = pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0);
-  if (posfree && g.exec && g.pixel_kind != pk) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-  if (!c->warmed) {
-    // first call of this cache: run eagerly once so that every lazy per-kernel set-up (hipFuncSetAttribute, device
-    // queries) has happened before a capture is opened
-    rq.last_hidden = last_hidden; rq.pooler = pooler;
-    rq.t_past = len; rq.pos3 = pos;
-    rc = run_forward(e, rq, ws, s);
-    if (rc == SF_OK) { advance(T_new); c->warmed = true; }
-    if (!g.exec) c->graphs.erase(key);
+  const bool posfree = T_new == 1 && !sf_sw(SW_STREAM_GRAPH_PER_POSITION);
+  if (!posfree && T_new == 1 && c->policy == 1) return set_err(SF_ERR_STATE, "SF_STREAM_GRAPH_PER_POSITION cannot serve a sliding-window cache");
+  if (!c->warmed.count(kLockstepWarm)) {      // first graph-eligible call of this cache
+    rc = eager();
+    if (rc == SF_OK) c->warmed.insert(kLockstepWarm);
     return rc;
   }
+  const int F = c->B * T_new, kcls = key_pass_class(pos.tk);
+  sf_cache::GraphKey key;
+  key.kind = posfree ? sf_cache::POSITION_FREE : sf_cache::PER_POSITION; key.rows = c->B; key.T_new = T_new; key.at = posfree ? kcls : len;
+  key.pooler = pooler != nullptr; key.pixel_kind = posfree ? call.pk : 0;      // (per position: the patch extraction stays outside the graph)
   // patch extraction reads the caller's frames: outside the graphs.  For the position-free graph the same launch stores the call's
-  // parameter block {pixels, outputs, position} that the graph's kernels read (it used to be a launch of its own)
+  // parameter block {pixels, outputs, position} that the graph's kernels read, after the graph is there
+  SfStreamParams v;
+  v.pixels = pixels; v.lhs = last_hidden; v.pooler = pooler; v.t_row = pos.t_row; v.slot = pos.slot; v.tk = pos.tk;
+  auto patchify = [&](bool deliver) {
+    return sf_launch_patchify(pixels, call.pk, ws.xn_hi, ws.xn_lo, F, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr,
+                              deliver ? c->dparams : nullptr, deliver ? &v : nullptr, e->Kp);
+  };
+  if (!posfree) HIP_TRY(patchify(false));
+  hipGraphExec_t exec = nullptr;
+  rc = stream_graph(c, key, workspace, pos_dev, [&](hipStream_t on) -> int {
+    if (posfree) return run_position_free(e, c, call, kcls, false, pooler != nullptr, on);
+    ForwardRequest q = rq;      // at this position, into graph-owned outputs
+    q.last_hidden = ws.lhs_stage; q.pooler = pooler ? ws.pool_stage : nullptr; q.ready = 1;
+    return run_forward(e, q, ws, on);
+  }, &exec);
+  if (rc) return rc;
+  if (posfree) HIP_TRY(patchify(true));
+  // (Launching the embedding + first layers eagerly to cover the replay's host-side submit time measured no gain: 0.78 vs 0.77 ms.)
+  HIP_TRY(hipGraphLaunch(exec, s));
   if (!posfree)
-    HIP_TRY(sf_launch_patchify(pixels, pk, ws.xn_hi, ws.xn_lo, F, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr, nullptr, nullptr,
-                               e->Kp));
-  if (!g.exec) {
-    hipGraph_t graph = nullptr;
-    if (!c->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-    hipError_t pe = hipSuccess;
-    // the graph's forward: patch matrix already extracted, graph-owned outputs
-    rq.last_hidden = ws.lhs_stage; rq.pooler = pooler ? ws.pool_stage : nullptr;
-    rq.ready = 1;
-    if (posfree) {
-      // representative position of the class: selects the 64-key pass count; the kernels read the live one from dparams.
-      // The patch extraction stays OUTSIDE the graph (it also delivers the parameter block, below); last_hidden_state is written
-      // straight into the caller's tensor through the block, pooler_output too when the head's row-vector tail runs (<= 4 streams):
-      // no staging copy at the end of the graph.
-      int rep_tk = kcls * 64;
-      if (rep_tk > c->cap) rep_tk = c->cap;
-      if (c->policy != 1 && rep_tk > nf) rep_tk = nf;
-      const int rep3[3] = {0, 0, rep_tk};
-      rq.t_past = 0; rq.sp = c->dparams; rq.pos3 = rep3;
-      const ForwardPlan plan = plan_forward(e, rq, ws);
-      rc = run_plan(e, plan, ws, c->cap_stream);
-      if (rc == SF_OK && pooler && !plan.head_rows)      // the F-row tail left pooler_output in the workspace
-        pe = sf_launch_copy2(nullptr, nullptr, 0, ws.pool_stage, nullptr, (size_t)F * e->D, c->cap_stream, c->dparams);
-    } else {
-      rq.t_past = len;
-      rc = run_forward(e, rq, ws, c->cap_stream);
-    }
-    hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
-    if (rc != SF_OK || pe != hipSuccess || ce != hipSuccess || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      c->graphs.erase(key);
-      if (rc != SF_OK && rc != SF_ERR_HIP) return rc;
-      return set_err(SF_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce != hipSuccess ? ce : pe));
-    }
-    hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-      c->graphs.erase(key);
-      return set_err(SF_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-    }
-    g.ws = workspace; g.pos = pos_dev; g.pooler = pooler != nullptr; g.pixel_kind = pk;
-  }
-  if (posfree) {
-    SfStreamParams v;
-    v.pixels = pixels; v.lhs = last_hidden; v.pooler = pooler; v.t_row = pos3[0]; v.slot = pos3[1]; v.tk = pos3[2];
-    HIP_TRY(sf_launch_patchify(pixels, pk, ws.xn_hi, ws.xn_lo, F, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr,
-                               c->dparams, &v, e->Kp));
-    HIP_TRY(hipGraphLaunch(g.exec, s));
-  } else {
-    // (Launching the embedding + first layers eagerly to cover the replay's host-side submit time measured no gain: 0.78 vs 0.77 ms.)
-    HIP_TRY(hipGraphLaunch(g.exec, s));
-    HIP_TRY(sf_launch_copy2(ws.lhs_stage, last_hidden, (size_t)M * e->D, pooler ? ws.pool_stage : nullptr, pooler, (size_t)F * e->D, s));
-  }
-  advance(T_new);
+    HIP_TRY(sf_launch_copy2(ws.lhs_stage, last_hidden, (size_t)F * c->N * e->D, pooler ? ws.pool_stage : nullptr, pooler, (size_t)F * e->D, s));
+  c->advance(T_new);
   return SF_OK;
 }
 
@@ -1598,9 +1665,8 @@ extern "C" int sf_forward_stream_attentions(sf_encoder* e, sf_cache* c, const vo
 extern "C" int sf_forward_stream_slots(sf_encoder* e, sf_cache* c, const void* pixels, int pixel_dtype, int T_new, const int* streams,
                                        int n_streams, float* last_hidden, float* pooler, const float* pos_dev, void* workspace,
                                        size_t workspace_bytes, sf_stream stream) {
-  if (!e || !c || c->enc != e) return set_err(SF_ERR_INVALID, "cache does not belong to this encoder");
-  if (c->enc_generation != e->generation)
-    return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
+  int rc = check_cache_owner(e, c);
+  if (rc) return rc;
   if (!streams || n_streams <= 0) return set_err(SF_ERR_INVALID, "name at least one stream");
   if (T_new <= 0) return set_err(SF_ERR_INVALID, "T_new must be positive");
   {
@@ -1622,102 +1688,45 @@ extern "C" int sf_forward_stream_slots(sf_encoder* e, sf_cache* c, const void* p
   if (n_streams > SF_MAX_CALL_STREAMS)
     return set_err(SF_ERR_INVALID, "%d streams in one call; the stream table holds %d: split the call", n_streams, SF_MAX_CALL_STREAMS);
   const int n = n_streams;
-  int N;
-  int rc = check_geometry(e, n, 1, c->H, c->W, pos_dev, &N);
-  if (rc) return rc;
-  if (!pixels || !last_hidden || !workspace) return set_err(SF_ERR_INVALID, "null buffer");
-  if (pixel_dtype != SF_F32 && pixel_dtype != SF_BF16 && pixel_dtype != SF_U8) return set_err(SF_ERR_INVALID, "pixels must be fp32, bf16 or uint8");
-  // every stream's position, checked before anything is launched (sliding window: SfStreamParams in sf_common.h)
-  const int nf = e->cfg.num_frames;
+  // every stream's position, checked before anything is launched
   SfStreamTable tv;
   memset(&tv, 0, sizeof(tv));
   tv.n = n;
   int max_tk = 0;
-  for (int i = 0; i < n; ++i) {
-    const int st = streams[i], len = c->lens[st];
-    SfStreamSlot& t = tv.e[i];
-    t.stream = st;
-    if (c->policy == 1) {
-      t.t_row = len < nf ? len : nf - 1; t.slot = len % c->cap; t.tk = len + 1 < c->cap ? len + 1 : c->cap;
-    } else {
-      if (len + 1 > c->cap)
-        return set_err(SF_ERR_CAPACITY, "stream %d holds %d of %d frames; one more does not fit: leave it out of the call, or restart it with "
-                       "sf_cache_reset_stream", st, len, c->cap);
-      if (len + 1 > nf)
-        return set_err(SF_ERR_CAPACITY, "stream %d needs time-embedding row %d but config.num_frames is %d: leave it out of the call, or restart it "
-                       "with sf_cache_reset_stream", st, len, nf);
-      t.t_row = len; t.slot = len; t.tk = len + 1;
+  auto positions = [&]() -> int {
+    for (int i = 0; i < n; ++i) {
+      StreamPos p;
+      if (int r = stream_position(c, c->lens[streams[i]], 1, streams[i], &p)) return r;
+      tv.e[i] = {streams[i], p.t_row, p.slot, p.tk};
+      max_tk = p.tk > max_tk ? p.tk : max_tk;
     }
-    max_tk = t.tk > max_tk ? t.tk : max_tk;
-  }
-  Workspace ws = carve(e, workspace, n, 1, N, false);
-  if (ws.bytes > workspace_bytes) return set_err(SF_ERR_WORKSPACE, "workspace %zu < required %zu bytes", workspace_bytes, ws.bytes);
-  hipStream_t s = (hipStream_t)stream;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(s, &cap);
-  const bool use_graph = !sf_sw(SW_DISABLE_STREAM_GRAPH) && cap == hipStreamCaptureStatusNone && c->dparams != nullptr;
-  const int kp = (max_tk + 63) >> 6;
-  const int kcls = kp <= 1 ? 1 : (kp <= 2 ? 2 : 4);
-  const int pk = pixel_dtype == SF_U8 ? 2 : (pixel_dtype == SF_BF16 ? 1 : 0);
-  const uint32_t key = 0x40000000u | ((uint32_t)n << 8) | ((uint32_t)kcls << 4) | (pooler ? 4u : 0u) | (uint32_t)pk;
-  // the call's forward: patch matrix extracted by the launch that delivers the block and the table, a representative key count of the
-  // class (it selects the 64-key pass count; the kernels read every stream's own from the table), outputs through the block
-  int rep_tk = kcls * 64;
-  if (rep_tk > c->cap) rep_tk = c->cap;
-  if (c->policy != 1 && rep_tk > nf) rep_tk = nf;
-  const int rep3[3] = {0, 0, rep_tk};
-  ForwardRequest rq;
-  rq.pixels = pixels; rq.pixel_dtype = pixel_dtype; rq.B = n; rq.T = 1; rq.H = c->H; rq.W = c->W; rq.pos_dev = pos_dev;
-  rq.layer_tqkv = c->qkv.data(); rq.cap = c->cap; rq.streaming = true;
-  rq.last_hidden = ws.lhs_stage; rq.pooler = pooler ? ws.pool_stage : nullptr;
-  rq.ready = 1; rq.t_past = 0; rq.sp = c->dparams; rq.tab = c->dtable; rq.pos3 = rep3;
-  const ForwardPlan plan = plan_forward(e, rq, ws);
-  auto run = [&](hipStream_t on) -> int {
-    int r = run_plan(e, plan, ws, on);
-    if (r == SF_OK && pooler && !plan.head_rows)       // the F-row tail left pooler_output in the workspace
-      HIP_TRY(sf_launch_copy2(nullptr, nullptr, 0, ws.pool_stage, nullptr, (size_t)n * e->D, on, c->dparams));
-    return r;
+    return SF_OK;
   };
+  StreamCall call;
+  if ((rc = open_stream_call(e, c, n, 1, false, pixels, pixel_dtype, last_hidden, pos_dev, workspace, workspace_bytes, stream, positions, &call))) return rc;
+  const int kcls = key_pass_class(max_tk);
+  sf_cache::GraphKey key;
+  key.kind = sf_cache::RAGGED; key.rows = n; key.T_new = 1; key.at = kcls; key.pooler = pooler != nullptr; key.pixel_kind = call.pk;
+  // the launch that extracts the patch matrix delivers the parameter block and the table
+  const Workspace& ws = call.ws;
+  hipStream_t s = call.s;
   SfStreamParams v;
   v.pixels = pixels; v.lhs = last_hidden; v.pooler = pooler; v.t_row = tv.e[0].t_row; v.slot = tv.e[0].slot; v.tk = max_tk;
   auto deliver = [&]() -> hipError_t {
-    return sf_launch_patchify(pixels, pk, ws.xn_hi, ws.xn_lo, n, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr,
+    return sf_launch_patchify(pixels, call.pk, ws.xn_hi, ws.xn_lo, n, e->cfg.num_channels, c->H, c->W, e->cfg.patch_size, s, &e->pixel_norm, nullptr,
                               c->dparams, &v, e->Kp, c->dtable, &tv);
   };
-  // The first call of a shape runs eagerly, so that every lazy per-kernel set-up has happened before its capture is opened
-  // (the lockstep entry's `warmed`, per shape: another row count selects other GEMM kernels).
-  if (!use_graph || !c->ragged_seen[key]) {
+  auto run = [&](hipStream_t on) -> int { return run_position_free(e, c, call, kcls, true, pooler != nullptr, on); };
+  if (call.graph_ok && c->warmed.count(key)) {
+    hipGraphExec_t exec = nullptr;
+    if ((rc = stream_graph(c, key, workspace, pos_dev, run, &exec))) return rc;
     HIP_TRY(deliver());
-    rc = run(s);
-    if (rc != SF_OK) return rc;
-    if (use_graph) c->ragged_seen[key] = true;
-    for (int i = 0; i < n; ++i) c->lens[streams[i]] += 1;
-    return SF_OK;
+    HIP_TRY(hipGraphLaunch(exec, s));
+  } else {      // graphs off, or the first call of this key
+    HIP_TRY(deliver());
+    if ((rc = run(s))) return rc;
+    if (call.graph_ok) c->warmed.insert(key);
   }
-  sf_cache::GraphEntry& g = c->graphs[key];
-  if (g.exec && (g.ws != workspace || g.pos != pos_dev)) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-  if (!g.exec) {
-    hipGraph_t graph = nullptr;
-    if (!c->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
-    HIP_TRY(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
-    rc = run(c->cap_stream);
-    hipError_t ce = hipStreamEndCapture(c->cap_stream, &graph);
-    if (rc != SF_OK || ce != hipSuccess || !graph) {
-      if (graph) (void)hipGraphDestroy(graph);
-      c->graphs.erase(key);
-      if (rc != SF_OK) return rc;
-      return set_err(SF_ERR_HIP, "stream capture failed: %s", hipGetErrorString(ce));
-    }
-    hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) {
-      c->graphs.erase(key);
-      return set_err(SF_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-    }
-    g.ws = workspace; g.pos = pos_dev; g.pooler = pooler != nullptr; g.pixel_kind = pk;
-  }
-  HIP_TRY(deliver());
-  HIP_TRY(hipGraphLaunch(g.exec, s));
   for (int i = 0; i < n; ++i) c->lens[streams[i]] += 1;
   return SF_OK;
 }

@@ -375,13 +375,6 @@ __global__ __launch_bounds__(256) void sf_copy2_kernel(const float* __restrict__
   if (i < na4) reinterpret_cast<f32x4_t*>(a_dst)[i] = reinterpret_cast<const f32x4_t*>(a_src)[i];
   else if (i - na4 < nb4) reinterpret_cast<f32x4_t*>(b_dst)[i - na4] = reinterpret_cast<const f32x4_t*>(b_src)[i - na4];
 }
-__global__ void sf_stream_params_kernel(SfStreamParams* dst, SfStreamParams v) {
-  if (threadIdx.x == 0) *dst = v;
-}
-hipError_t sf_launch_stream_params(SfStreamParams* dst, const SfStreamParams& v, hipStream_t s) {
-  hipLaunchKernelGGL(sf_stream_params_kernel, dim3(1), dim3(64), 0, s, dst, v);
-  return hipGetLastError();
-}
 
 hipError_t sf_launch_copy2(const float* a_src, float* a_dst, size_t na, const float* b_src, float* b_dst, size_t nb, hipStream_t s,
                            const SfStreamParams* sp) {

@@ -871,61 +871,16 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             lhs = torch.empty(B, T, N, D, dtype=torch.float32, device=dev)
             pool = torch.empty(B, T, D, dtype=torch.float32, device=dev)
             hs = torch.empty(L + 1, B, T, N, D, dtype=torch.float32, device=dev) if output_hidden_states else None
-            nbytes = nat.C.c_size_t()
+            # spatial probabilities per layer, of the new frames when streaming (timesformer_encoder.py:494, 557, 720-754); the
+            # reference materialises these anyway (modeling:703-705), here only on request
+            att = torch.empty(L, B * T, c.num_attention_heads, N, N, dtype=torch.float32, device=dev) if output_attentions else None
             if streaming:
-                cache = past_key_values
-                if cache is None:
-                    cache = StreamCache(self, B, max(c.num_frames, T), H, W)
-                elif not isinstance(cache, StreamCache):
-                    raise TypeError("past_key_values must be the StreamCache a previous call returned (or model.new_cache())")
-                ch = cache._require()
-                if cache._model() is not self:
-                    raise ValueError("past_key_values belongs to another model")
-                # a sliding-window cache saturates get_seq_length() at its capacity while frames_seen keeps counting: an HF-style
-                # caller that derives cache_position from get_seq_length() is as right as one that counts frames
-                if stream_ids is not None:
-                    if cache_position is not None:
-                        # one start position per named stream ([B] or [B, T]); checked for the ids the library will accept
-                        cp = torch.as_tensor(cache_position)
-                        cp = (cp[:, 0] if cp.dim() == 2 else cp.reshape(-1)).tolist()
-                        if len(cp) != B:
-                            raise ValueError(f"cache_position must give one start position per named stream ({B}), got {len(cp)}")
-                        seen = cache.frames_seen_per_stream
-                        for sid, pos0 in zip(stream_ids, cp):
-                            if 0 <= sid < cache.batch and int(pos0) not in (seen[sid], min(seen[sid], cache.max_frames)):
-                                raise ValueError(f"cache_position {int(pos0)} does not continue stream {sid} ({seen[sid]} frames seen)")
-                    if (cache.H, cache.W) != (H, W):
-                        raise ValueError("past_key_values was created for a different resolution")
-                    nat.check(nat.lib.sf_stream_workspace_bytes(self._handle, ch, T, nat.C.byref(nbytes)))
-                    ws = self._workspace(("s", cache.batch, T, H, W, skey), nbytes.value)
-                    ids = (nat.C.c_int * max(B, 1))(*stream_ids)
-                    nat.check(nat.lib.sf_forward_stream_slots(self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T, ids, B,
-                                                              lhs.data_ptr(), pool.data_ptr(), nat.ptr(pos), ws.data_ptr(),
-                                                              ws.numel(), stream))
-                    return self._stream_output(cast(lhs), cast(pool), None, None, cache, True, return_dict)
-                if cache_position is not None and int(cache_position[0]) not in (cache.frames_seen, cache.get_seq_length()):
-                    raise ValueError("cache_position must continue the cache (vqa_enc:1340-1349)")
-                if (cache.batch, cache.H, cache.W) != (B, H, W):
-                    raise ValueError("past_key_values was created for a different batch size / resolution")
-                nat.check(nat.lib.sf_stream_workspace_bytes(self._handle, ch, T, nat.C.byref(nbytes)))
-                ws = self._workspace(("s", B, T, H, W, skey), nbytes.value)
-                att = None
-                if output_attentions:            # spatial probabilities of the new frames (timesformer_encoder.py:494, 557, 720-754)
-                    att = torch.empty(L, B * T, c.num_attention_heads, N, N, dtype=torch.float32, device=dev)
-                    nat.check(nat.lib.sf_forward_stream_attentions(self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T,
-                                                                   lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(),
-                                                                   nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
-                else:
-                    nat.check(nat.lib.sf_forward_stream(self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T,
-                                                        lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), nat.ptr(pos), ws.data_ptr(),
-                                                        ws.numel(), stream))
+                cache = self._forward_stream(x, pos, past_key_values, cache_position, stream_ids, lhs, pool, hs, att, stream, skey)
             else:
+                nbytes = nat.C.c_size_t()
                 nat.check(nat.lib.sf_workspace_bytes(self._handle, B, T, H, W, nat.C.byref(nbytes)))
                 ws = self._workspace(("f", B, T, H, W, skey), nbytes.value)
-                att = None
-                if output_attentions:
-                    # the reference materialises these anyway (modeling:703-705); here only on request
-                    att = torch.empty(L, B * T, c.num_attention_heads, N, N, dtype=torch.float32, device=dev)
+                if att is not None:
                     nat.check(nat.lib.sf_forward_attentions(self._handle, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W,
                                                             lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(),
                                                             nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
@@ -937,13 +892,56 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             # the reference hands back patch-major (B, N*T, D) tensors (modeling:1352): permuted views
             hidden = tuple(cast(hs[i]).permute(0, 2, 1, 3).reshape(B, N * T, D) for i in range(L + 1))
         lhs, pool = cast(lhs), cast(pool)
+        attentions = tuple(att[i] for i in range(L)) if att is not None else None
         if streaming:
-            attentions = tuple(att[i] for i in range(L)) if att is not None else None
             return self._stream_output(lhs, pool, hidden, attentions, cache, use_cache or past_key_values is not None, return_dict)
-        attentions = tuple(att[i] for i in range(L)) if att is not None else None    # spatial probabilities per layer
         if not return_dict:
             return (lhs,) + ((hidden,) if hidden is not None else ()) + ((attentions,) if attentions is not None else ())
         return BaseModelOutputWithPooling(lhs, pool, hidden_states=hidden, attentions=attentions)
+
+    def _forward_stream(self, x, pos, cache, cache_position, stream_ids, lhs, pool, hs, att, stream, skey):
+        """One streaming call into the caller's output tensors: every stream of ``cache`` in lockstep, or the streams that
+        ``stream_ids`` names.  Returns the cache (a new one when the caller passed none)."""
+        B, T, _, H, W = x.shape
+        ragged = stream_ids is not None
+        if cache is None:
+            cache = StreamCache(self, B, max(self.config.num_frames, T), H, W)
+        elif not isinstance(cache, StreamCache):
+            raise TypeError("past_key_values must be the StreamCache a previous call returned (or model.new_cache())")
+        ch = cache._require()
+        if cache._model() is not self:
+            raise ValueError("past_key_values belongs to another model")
+        # a sliding-window cache saturates get_seq_length() at its capacity while frames_seen keeps counting: an HF-style
+        # caller that derives cache_position from get_seq_length() is as right as one that counts frames (ADVICE r3)
+        if ragged and cache_position is not None:
+            # one start position per named stream ([B] or [B, T]); checked for the ids the library will accept
+            cp = torch.as_tensor(cache_position)
+            cp = (cp[:, 0] if cp.dim() == 2 else cp.reshape(-1)).tolist()
+            if len(cp) != B:
+                raise ValueError(f"cache_position must give one start position per named stream ({B}), got {len(cp)}")
+            seen = cache.frames_seen_per_stream
+            for sid, pos0 in zip(stream_ids, cp):
+                if 0 <= sid < cache.batch and int(pos0) not in (seen[sid], min(seen[sid], cache.max_frames)):
+                    raise ValueError(f"cache_position {int(pos0)} does not continue stream {sid} ({seen[sid]} frames seen)")
+        elif cache_position is not None and int(cache_position[0]) not in (cache.frames_seen, cache.get_seq_length()):
+            raise ValueError("cache_position must continue the cache (vqa_enc:1340-1349)")
+        if ragged and (cache.H, cache.W) != (H, W):
+            raise ValueError("past_key_values was created for a different resolution")
+        if not ragged and (cache.batch, cache.H, cache.W) != (B, H, W):
+            raise ValueError("past_key_values was created for a different batch size / resolution")
+        nbytes = nat.C.c_size_t()
+        nat.check(nat.lib.sf_stream_workspace_bytes(self._handle, ch, T, nat.C.byref(nbytes)))
+        ws = self._workspace(("s", cache.batch, T, H, W, skey), nbytes.value)      # (a lockstep call has B == cache.batch)
+        frames = (self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T)
+        tail = (nat.ptr(pos), ws.data_ptr(), ws.numel(), stream)
+        if ragged:
+            ids = (nat.C.c_int * max(B, 1))(*stream_ids)
+            nat.check(nat.lib.sf_forward_stream_slots(*frames, ids, B, lhs.data_ptr(), pool.data_ptr(), *tail))
+        elif att is not None:
+            nat.check(nat.lib.sf_forward_stream_attentions(*frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(), *tail))
+        else:
+            nat.check(nat.lib.sf_forward_stream(*frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), *tail))
+        return cache
 
     @staticmethod
     def _stream_output(lhs, pool, hidden, attentions, cache, keep_cache, return_dict):
