@@ -187,6 +187,41 @@ int sf_forward_stream_slots(sf_encoder* enc, sf_cache* cache, const void* pixels
                             const int* streams, int n_streams, float* last_hidden_dev, float* pooler_dev,
                             const float* pos_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- parking a stream: its cached K/V out of the slab and back into any slab ------------------------
+ * (HF's DynamicCache is plain tensors a caller may copy or offload; this is the way out of, and back into, library-owned memory.)
+ * A stream that pauses, yields its slab, moves to another cache or process, or branches is exported to a caller-owned DEVICE blob and
+ * imported later: into the same slab, another one, or a slab of another cache of the same weights, compute mode, resolution,
+ * max_frames and policy (any batch size).  Importing one blob into two slabs forks the stream.
+ * The blob holds the K and V columns of the frames the stream HOLDS (min(frames seen, max_frames)), all layers, in the cache's own
+ * element type: [layers][frames_held * patches][2 * hidden_size], frames in RING-SLOT order.  Import puts every frame back into the
+ * slot it came from and restores the frame count, so the stream's next position (time-embedding row, slot, keys seen) is the one
+ * the source would have had and its continuation is bit-identical.  One kernel launch each way, on the caller's stream.        */
+#define SF_STREAM_BLOB_KV1 0x31564b53u          /* "SKV1": K|V rows in slot order, uncompressed */
+typedef struct {
+  uint32_t format;                              /* SF_STREAM_BLOB_KV1                                              */
+  int32_t compute;                              /* sf_compute of the packing: decides elem_bytes                   */
+  int32_t frames_seen, frames_held;             /* the stream's count; min(frames_seen, max_frames) of them cached */
+  int32_t max_frames, policy;                   /* of the cache (sf_cache_create, sf_cache_set_policy)             */
+  int32_t H, W;                                 /* resolution of the cache                                         */
+  int32_t layers, hidden_size, patches;         /* packed geometry: L, D, N                                        */
+  int32_t elem_bytes;                           /* 2 (bf16) or 4 (fp32)                                            */
+  uint64_t packing;                             /* fingerprint of the configuration and weights that computed the K/V;
+                                                   equal for equal weights, in any process                        */
+  uint64_t blob_bytes;                          /* layers * frames_held * patches * 2 * hidden_size * elem_bytes   */
+} sf_cache_stream_meta;
+/* bytes of that stream's blob as it stands (0 for a stream that holds nothing) */
+int sf_cache_stream_blob_bytes(const sf_cache* cache, int stream, size_t* out);
+/* blob_dev: 16-byte aligned device buffer of exactly `bytes` = sf_cache_stream_blob_bytes; meta_out: HOST, filled in.  The stream
+ * itself is left as it is (release or reset it separately).                                                                    */
+int sf_cache_export_stream(sf_encoder* enc, sf_cache* cache, int stream, void* blob_dev, size_t bytes,
+                           sf_cache_stream_meta* meta_out, sf_stream s);
+/* Everything is checked before anything is launched or changed; a refusal names the field and leaves the slab untouched:
+ * SF_ERR_INVALID for a stream id out of range, another format, compute mode, resolution, max_frames, policy or geometry, an
+ * inconsistent frame count or a wrong byte count; SF_ERR_STATE for a blob computed by other weights (`packing`), or a cache of an
+ * earlier packing of the encoder.  Restoring into a cache of another max_frames is not supported.                              */
+int sf_cache_import_stream(sf_encoder* enc, sf_cache* cache, int stream, const void* blob_dev, size_t bytes,
+                           const sf_cache_stream_meta* meta, sf_stream s);
+
 /* ---- single operators (each is one kernel of the path; used by the parity tests) ----------- */
 /* nn.LayerNorm(D, eps) rows (modeling:860-865,878-880,1251): x fp32 [rows,D] -> y fp32 [rows,D] */
 int sf_op_layernorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, float* y_dev,

@@ -13,6 +13,7 @@ from .modeling import (  # noqa: F401
     BaseModelOutputWithPast,
     BaseModelOutputWithPooling,
     StreamCache,
+    StreamSnapshot,
     TimesformerMultiTaskingModelSigLIP,
     TimesformerVisionTower,
 )

@@ -30,6 +30,16 @@ class SfConfig(C.Structure):
         "add_lora_spatial")] + [("layer_norm_eps", C.c_float)]
 
 
+SF_STREAM_BLOB_KV1 = 0x31564B53
+
+
+class SfCacheStreamMeta(C.Structure):
+    """sf_cache_stream_meta: what a parked stream's blob is and where it may go back."""
+    _fields_ = [("format", C.c_uint32)] + [(n, C.c_int32) for n in (
+        "compute", "frames_seen", "frames_held", "max_frames", "policy", "H", "W", "layers", "hidden_size", "patches",
+        "elem_bytes")] + [("packing", C.c_uint64), ("blob_bytes", C.c_uint64)]
+
+
 class NativeError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"streamformer_hip error {code}: {msg}")
@@ -62,6 +72,9 @@ SIGNATURES = {
     "sf_cache_bytes": (_SZ, [_P]),
     "sf_cache_set_policy": (_I, [_P, _I]),
     "sf_cache_destroy": (None, [_P]),
+    "sf_cache_stream_blob_bytes": (_I, [_P, _I, C.POINTER(_SZ)]),
+    "sf_cache_export_stream": (_I, [_P, _P, _I, _P, _SZ, C.POINTER(SfCacheStreamMeta), _P]),
+    "sf_cache_import_stream": (_I, [_P, _P, _I, _P, _SZ, C.POINTER(SfCacheStreamMeta), _P]),
     "sf_stream_workspace_bytes": (_I, [_P, _P, _I, C.POINTER(_SZ)]),
     "sf_forward_stream": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_forward_stream_slots": (_I, [_P, _P, _P, _I, _I, C.POINTER(_I), _I, _P, _P, _P, _P, _SZ, _P]),

@@ -375,6 +375,18 @@ hipError_t sf_launch_split(const float* x, bf16_t* hi, bf16_t* lo, size_t n, hip
 // two fp32 copies in one launch (b may be null): the streaming path's hand-over of graph-owned outputs to the caller's tensors
 hipError_t sf_launch_copy2(const float* a_src, float* a_dst, size_t na, const float* b_src, float* b_dst, size_t nb, hipStream_t s,
                            const SfStreamParams* sp = nullptr);        // sp != nullptr: a_dst = sp->lhs, b_dst = sp->pooler (device reads)
+// Parking a stream (sf_cache_park.hip): the k | v columns of the first nvec / vpr rows of one slab, of `layers` layers, to or from a
+// contiguous blob [layer][row][vpr x 16 bytes].  All byte counts are multiples of 16.
+#define SF_PARK_MAX_LAYERS 64                  // layer pointers travel as a kernel argument; deeper models take several launches
+struct SfParkArgs {
+  char* layer[SF_PARK_MAX_LAYERS];             // the layers' caches [B, cap, N, 3D]
+  char* blob;
+  size_t slab_off, kv_off, row_bytes;          // the stream's slab inside a layer; the k column inside a row; 3D elements
+  size_t layer_blob_bytes;                     // nvec * 16
+  uint32_t nvec, vpr;                          // 16-byte vectors per layer; per row (2D elements)
+  int layer0;                                  // blob layer of layer[0]
+};
+hipError_t sf_launch_cache_park(const SfParkArgs& a, int layers, bool do_export, hipStream_t s);
 // fp32 rows -> bf16 copy + LayerNorm partial statistics {sum x, sum x^2, 0, 0} per row (stats [rows][4])
 hipError_t sf_launch_rowstats_cast(const float* x, bf16_t* xb, float* stats, int rows, int D, hipStream_t s, bf16_t* xlo = nullptr,
                                    bf16_t* xlo2 = nullptr, int wide = 0);      // wide (or xlo): stats rows of 8 floats

@@ -97,6 +97,7 @@ struct sf_encoder {
   float* head_bv = nullptr;   // [D]
   size_t weight_bytes = 0;
   uint64_t generation = 0;    // process-unique id of this handle's current weight packing (bumped by every finalize)
+  uint64_t fingerprint = 0;   // content hash of what that packing was made from (weights_fingerprint): travels with a parked stream
   SfPixelNorm pixel_norm = {{1.0f / 127.5f, 1.0f / 127.5f, 1.0f / 127.5f, 1.0f / 127.5f}, {-1.f, -1.f, -1.f, -1.f}};
   // sf_forward_profile: HIP events around the launches of four kernel classes INSIDE a real forward (0: N = 768 residual projection
   // at K = D, 1: the same at K = I, 2: spatial attention, 3: temporal attention)
@@ -413,6 +414,39 @@ static void merge_lora_into(std::vector<float>& w, const std::vector<float>& a, 
     }
 }
 
+// What a parked stream's K/V were computed with (sf_cache_stream_meta::packing): the configuration, the packing options and every
+// staged weight, hashed in key order — the same number for the same weights in any process, unlike `generation`.  The compute mode
+// stays out: it is a field of its own.  Four multiply-xor lanes over 64-bit words (one pass over the fp32 master copy).
+static uint64_t weights_fingerprint(const sf_encoder* e, int merge_lora, int fuse_temporal_proj) {
+  const uint64_t kMul = 0x9e3779b97f4a7c15ull;
+  auto mix = [&](uint64_t h, uint64_t v) { h = (h ^ v) * kMul; return h ^ (h >> 29); };
+  uint64_t h = 0x53464b56ull;
+  uint32_t cw[sizeof(sf_config) / 4];
+  memcpy(cw, &e->cfg, sizeof(cw));
+  for (uint32_t w : cw) h = mix(h, w);
+  h = mix(h, (uint64_t)(merge_lora != 0) * 2 + (fuse_temporal_proj != 0));
+  for (const auto& kv : e->host) {
+    for (char ch : kv.first) h = mix(h, (uint8_t)ch);
+    const std::vector<float>& d = kv.second.data;
+    h = mix(h, d.size());
+    uint64_t lane[4] = {h, h ^ 1, h ^ 2, h ^ 3};
+    const size_t words = d.size() / 2, quads = words / 4;
+    const char* p = reinterpret_cast<const char*>(d.data());
+    for (size_t q = 0; q < quads; ++q) {
+      uint64_t w[4];
+      memcpy(w, p + q * 32, 32);
+      for (int k = 0; k < 4; ++k) lane[k] = (lane[k] ^ w[k]) * kMul;
+    }
+    for (size_t i = quads * 8; i < d.size(); ++i) {
+      uint32_t u;
+      memcpy(&u, &d[i], 4);
+      lane[i & 3] = mix(lane[i & 3], u);
+    }
+    for (int k = 0; k < 4; ++k) h = mix(h, lane[k]);
+  }
+  return h ? h : 1;      // 0 is "no packing"
+}
+
 extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, int fuse_temporal_proj) {
   if (!e) return set_err(SF_ERR_INVALID, "null handle");
   if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
@@ -569,6 +603,7 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
 #undef TRY
   e->finalized = true;
   e->generation = next_generation();   // caches created against an earlier packing are refused from here on
+  e->fingerprint = weights_fingerprint(e, merge_lora, fuse_temporal_proj);
   return SF_OK;
 }
 
@@ -1444,6 +1479,91 @@ static int check_cache_owner(const sf_encoder* e, const sf_cache* c) {
   // size) or the device: the generation stamp tells a cache of an earlier packing from a current one
   if (c->enc_generation != e->generation)
     return set_err(SF_ERR_STATE, "cache was created for an earlier weight packing of this encoder (sf_finalize_weights ran since): create a new cache");
+  return SF_OK;
+}
+
+// ---- parking a stream (kernels: sf_cache_park.hip) -------------------------------------------------------------------------------
+static size_t cache_elem_bytes(const sf_encoder* e) { return e->compute == SF_COMPUTE_BF16X3 ? 4 : 2; }
+// bytes of the k | v columns of `held` frames over all layers
+static size_t stream_blob_bytes(const sf_cache* c, int held) {
+  return (size_t)c->enc->L * held * c->N * 2 * c->enc->D * cache_elem_bytes(c->enc);
+}
+static int check_stream_id(const sf_cache* c, int stream) {
+  if (stream < 0 || stream >= c->B) return set_err(SF_ERR_INVALID, "stream %d outside this cache's %d streams (ids are 0 .. %d)", stream, c->B, c->B - 1);
+  return SF_OK;
+}
+extern "C" int sf_cache_stream_blob_bytes(const sf_cache* c, int stream, size_t* out) {
+  if (!c || !out) return set_err(SF_ERR_INVALID, "null argument");
+  if (int rc = check_stream_id(c, stream)) return rc;
+  const int seen = c->lens[stream];
+  *out = stream_blob_bytes(c, seen < c->cap ? seen : c->cap);
+  return SF_OK;
+}
+// one launch for up to SF_PARK_MAX_LAYERS layers (every model the library accepts today), further launches beyond
+static int park_stream(const sf_encoder* e, const sf_cache* c, int stream, int held, void* blob, bool do_export, hipStream_t s) {
+  const size_t esz = cache_elem_bytes(e), row = (size_t)3 * e->D * esz;
+  SfParkArgs a;
+  memset(&a, 0, sizeof(a));
+  a.blob = (char*)blob; a.row_bytes = row; a.kv_off = (size_t)e->D * esz; a.slab_off = (size_t)stream * c->cap * c->N * row;
+  a.vpr = (uint32_t)(2 * e->D * esz / 16);
+  const size_t nvec = (size_t)held * c->N * a.vpr;
+  if (nvec > 0x7fffffffu) return set_err(SF_ERR_CAPACITY, "a stream of %zu bytes per layer is beyond one export launch", nvec * 16);
+  a.nvec = (uint32_t)nvec; a.layer_blob_bytes = nvec * 16;
+  for (int l0 = 0; l0 < e->L; l0 += SF_PARK_MAX_LAYERS) {
+    const int n = e->L - l0 < SF_PARK_MAX_LAYERS ? e->L - l0 : SF_PARK_MAX_LAYERS;
+    for (int l = 0; l < n; ++l) a.layer[l] = (char*)c->qkv[l0 + l];
+    a.layer0 = l0;
+    HIP_TRY(sf_launch_cache_park(a, n, do_export, s));
+  }
+  return SF_OK;
+}
+extern "C" int sf_cache_export_stream(sf_encoder* e, sf_cache* c, int stream, void* blob, size_t bytes, sf_cache_stream_meta* meta,
+                                      sf_stream s) {
+  int rc = check_cache_owner(e, c);
+  if (rc) return rc;
+  if (!meta) return set_err(SF_ERR_INVALID, "null meta_out");
+  if ((rc = check_stream_id(c, stream))) return rc;
+  const int seen = c->lens[stream], held = seen < c->cap ? seen : c->cap;
+  const size_t need = stream_blob_bytes(c, held);
+  if (bytes != need) return set_err(SF_ERR_INVALID, "blob of %zu bytes; stream %d holds %d frames = %zu bytes (sf_cache_stream_blob_bytes)", bytes, stream, held, need);
+  if (need && (!blob || ((size_t)blob & 15))) return set_err(SF_ERR_INVALID, "the blob must be a 16-byte aligned device buffer");
+  if (need && (rc = park_stream(e, c, stream, held, blob, true, (hipStream_t)s))) return rc;
+  memset(meta, 0, sizeof(*meta));
+  meta->format = SF_STREAM_BLOB_KV1; meta->compute = e->compute; meta->frames_seen = seen; meta->frames_held = held;
+  meta->max_frames = c->cap; meta->policy = c->policy; meta->H = c->H; meta->W = c->W;
+  meta->layers = e->L; meta->hidden_size = e->D; meta->patches = c->N; meta->elem_bytes = (int32_t)cache_elem_bytes(e);
+  meta->packing = e->fingerprint; meta->blob_bytes = need;
+  return SF_OK;
+}
+extern "C" int sf_cache_import_stream(sf_encoder* e, sf_cache* c, int stream, const void* blob, size_t bytes,
+                                      const sf_cache_stream_meta* m, sf_stream s) {
+  int rc = check_cache_owner(e, c);
+  if (rc) return rc;
+  if (!m) return set_err(SF_ERR_INVALID, "null meta");
+  if ((rc = check_stream_id(c, stream))) return rc;
+  if (m->format != SF_STREAM_BLOB_KV1) return set_err(SF_ERR_INVALID, "format: blob tag 0x%08x is not SF_STREAM_BLOB_KV1", m->format);
+  if (m->compute != e->compute)
+    return set_err(SF_ERR_INVALID, "compute mode: the stream was parked in mode %d, this encoder is packed for mode %d", m->compute, e->compute);
+  if (m->H != c->H || m->W != c->W) return set_err(SF_ERR_INVALID, "resolution: the stream was parked at %dx%d, this cache is %dx%d", m->H, m->W, c->H, c->W);
+  if (m->max_frames != c->cap)
+    return set_err(SF_ERR_INVALID, "max_frames: the stream was parked from a cache of %d frames, this one holds %d (restoring into another "
+                   "capacity is not supported)", m->max_frames, c->cap);
+  if (m->policy != c->policy) return set_err(SF_ERR_INVALID, "policy: the stream was parked under policy %d, this cache has policy %d", m->policy, c->policy);
+  if (m->layers != e->L || m->hidden_size != e->D || m->patches != c->N || m->elem_bytes != (int32_t)cache_elem_bytes(e))
+    return set_err(SF_ERR_INVALID, "geometry: blob of %d layers x %d patches x width %d x %d bytes, cache of %d x %d x %d x %zu", m->layers, m->patches,
+                   m->hidden_size, m->elem_bytes, e->L, c->N, e->D, cache_elem_bytes(e));
+  if (m->frames_seen < 0 || m->frames_held != (m->frames_seen < c->cap ? m->frames_seen : c->cap) || (c->policy != 1 && m->frames_seen > c->cap))
+    return set_err(SF_ERR_INVALID, "frames: %d seen / %d held do not describe a stream of a %d-frame cache", m->frames_seen, m->frames_held, c->cap);
+  if (m->packing != e->fingerprint)
+    return set_err(SF_ERR_STATE, "packing: the stream was parked by other weights (fingerprint %016llx, this encoder %016llx): its keys and values "
+                   "mean nothing here", (unsigned long long)m->packing, (unsigned long long)e->fingerprint);
+  const size_t need = stream_blob_bytes(c, m->frames_held);
+  if (bytes != need || m->blob_bytes != need)
+    return set_err(SF_ERR_INVALID, "byte count: blob of %zu bytes (meta says %llu), %d frames are %zu", bytes, (unsigned long long)m->blob_bytes,
+                   m->frames_held, need);
+  if (need && (!blob || ((size_t)blob & 15))) return set_err(SF_ERR_INVALID, "the blob must be a 16-byte aligned device buffer");
+  if (need && (rc = park_stream(e, c, stream, m->frames_held, const_cast<void*>(blob), false, (hipStream_t)s))) return rc;
+  c->lens[stream] = m->frames_seen;      // the next frame's time row, slot and key count follow from it (stream_position)
   return SF_OK;
 }
 

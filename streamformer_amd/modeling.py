@@ -77,6 +77,95 @@ def BaseModelOutputWithPast(last_hidden_state, past_key_values=None, hidden_stat
                        hidden_states=hidden_states, attentions=attentions, pooler_output=pooler_output)
 
 
+def _stale_message(what: str, remedy: str) -> str:
+    return (f"this {what} belongs to weights / a compute mode / a device the model has since left (load_state_dict, "
+            f"set_compute_dtype or .to() re-packed it): {remedy}")
+
+
+_SNAPSHOT_FIELDS = tuple(n for n, _ in nat.SfCacheStreamMeta._fields_)
+
+
+class StreamSnapshot:
+    """One parked stream of a ``StreamCache``: the K/V rows of the frames it holds (``blob``, a flat uint8 tensor on the GPU or the
+    host) and ``meta``, the plain-int mirror of ``sf_cache_stream_meta`` that says what the blob is and where it may go back.
+
+    Plain data: it pickles (``torch.save(snapshot)``), and ``state_dict()`` / ``from_state_dict()`` give the form that
+    ``torch.load(..., weights_only=True)`` accepts.  ``StreamCache.restore()`` takes it back, in this process or another."""
+
+    def __init__(self, blob: torch.Tensor, meta: Dict[str, int], _origin=None):
+        self.blob, self.meta = blob, dict(meta)
+        self._origin = _origin      # (weakref of the model, its pack epoch) while in the process that took it; never pickled
+        self._validate()
+
+    def _validate(self) -> None:
+        m, b = self.meta, self.blob
+        missing = [k for k in _SNAPSHOT_FIELDS if k not in m]
+        if missing or len(m) != len(_SNAPSHOT_FIELDS):
+            raise ValueError(f"snapshot meta must hold exactly {_SNAPSHOT_FIELDS}; missing {missing}, "
+                             f"unknown {sorted(set(m) - set(_SNAPSHOT_FIELDS))}")
+        for k in _SNAPSHOT_FIELDS:
+            if not isinstance(m[k], int) or isinstance(m[k], bool) or m[k] < 0:
+                raise ValueError(f"snapshot meta field {k!r} must be a non-negative int, got {m[k]!r}")
+        if m["format"] != nat.SF_STREAM_BLOB_KV1:
+            raise ValueError(f"snapshot meta field 'format' is 0x{m['format']:08x}, not the blob format this version reads "
+                             f"(0x{nat.SF_STREAM_BLOB_KV1:08x})")
+        if m["elem_bytes"] != (4 if m["compute"] == nat.SF_COMPUTE_BF16X3 else 2) or m["compute"] not in (0, 1):
+            raise ValueError(f"snapshot meta fields 'compute' = {m['compute']} and 'elem_bytes' = {m['elem_bytes']} disagree")
+        if m["max_frames"] < 1 or m["frames_held"] != min(m["frames_seen"], m["max_frames"]):
+            raise ValueError(f"snapshot meta field 'frames_held' = {m['frames_held']} is not min(frames_seen = {m['frames_seen']}, "
+                             f"max_frames = {m['max_frames']})")
+        want = m["layers"] * m["frames_held"] * m["patches"] * 2 * m["hidden_size"] * m["elem_bytes"]
+        if m["blob_bytes"] != want:
+            raise ValueError(f"snapshot meta field 'blob_bytes' = {m['blob_bytes']}, but its geometry makes {want}")
+        if not isinstance(b, torch.Tensor) or b.dtype != torch.uint8 or b.dim() != 1 or not b.is_contiguous():
+            raise ValueError("snapshot blob must be a contiguous 1-D uint8 tensor")
+        if b.numel() != want:
+            raise ValueError(f"snapshot blob holds {b.numel()} bytes, its meta describes {want} (truncated?)")
+
+    @property
+    def nbytes(self) -> int:
+        return self.blob.numel()
+
+    @property
+    def frames_seen(self) -> int:
+        return self.meta["frames_seen"]
+
+    @property
+    def device(self) -> torch.device:
+        return self.blob.device
+
+    def to(self, device) -> "StreamSnapshot":
+        """The same snapshot with its blob on ``device``; a blob that leaves the GPU lands in pinned host memory."""
+        device = torch.device(device)
+        if device.type == self.blob.device.type and (device.index is None or device.index == self.blob.device.index):
+            return self
+        if device.type == "cpu" and self.blob.is_cuda:
+            blob = torch.empty(self.blob.numel(), dtype=torch.uint8, pin_memory=True)
+            blob.copy_(self.blob)
+        else:
+            blob = self.blob.to(device)
+        return StreamSnapshot(blob, self.meta, self._origin)
+
+    def state_dict(self) -> Dict[str, Any]:
+        return {"blob": self.blob, "meta": dict(self.meta)}
+
+    @classmethod
+    def from_state_dict(cls, sd: Dict[str, Any]) -> "StreamSnapshot":
+        return cls(sd["blob"], sd["meta"])
+
+    def __getstate__(self):
+        return self.state_dict()
+
+    def __setstate__(self, d):
+        self.blob, self.meta, self._origin = d["blob"], dict(d["meta"]), None
+        self._validate()
+
+    def __repr__(self) -> str:
+        m = self.meta
+        return (f"StreamSnapshot(frames_seen={m['frames_seen']}, frames_held={m['frames_held']}, max_frames={m['max_frames']}, "
+                f"nbytes={self.nbytes}, device={self.blob.device})")
+
+
 class StreamCache:
     """Temporal KV-cache of ``batch`` streams: the ``past_key_values`` object of the streaming forward.
 
@@ -108,8 +197,7 @@ class StreamCache:
 
     def _require(self):
         if not self._h:
-            raise RuntimeError("this past_key_values belongs to weights / a compute mode / a device the model has since "
-                               "left (load_state_dict, set_compute_dtype or .to() re-packed it): start a new cache")
+            raise RuntimeError(_stale_message("past_key_values", "start a new cache"))
         return self._h
 
     def get_seq_length(self, layer_idx: int = 0, stream: Optional[int] = None) -> int:
@@ -152,6 +240,56 @@ class StreamCache:
     @property
     def nbytes(self) -> int:
         return nat.lib.sf_cache_bytes(self._require())
+
+    def snapshot(self, stream: int, device: Any = None) -> StreamSnapshot:
+        """Park ``stream``: its cached K/V (the frames it holds, all layers) packed into one blob by one kernel launch.  The stream
+        itself stays as it is — ``release()`` it to hand the slab on.  ``device="cpu"``: the blob is then moved to pinned host
+        memory; by default it stays on the GPU."""
+        h = self._require()
+        model = self._model()
+        stream = self._check_stream(stream)
+        nbytes = nat.C.c_size_t()
+        nat.check(nat.lib.sf_cache_stream_blob_bytes(h, stream, nat.C.byref(nbytes)))
+        meta = nat.SfCacheStreamMeta()
+        dev = model.device
+        with torch.cuda.device(dev):
+            blob = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+            nat.check(nat.lib.sf_cache_export_stream(model._handle, h, stream, blob.data_ptr(), nbytes.value, nat.C.byref(meta),
+                                                     nat.current_stream_handle(dev)))
+        snap = StreamSnapshot(blob, {k: int(getattr(meta, k)) for k in _SNAPSHOT_FIELDS}, (weakref.ref(model), model._pack_epoch))
+        return snap if device is None else snap.to(device)
+
+    def restore(self, snapshot: StreamSnapshot, stream: Optional[int] = None) -> int:
+        """Resume a parked stream in slab ``stream`` of this cache (a slab the caller holds), or in a slab ``acquire()``d here when
+        ``stream`` is None; returns the slab index.  Every frame goes back to the ring slot it came from and the frame count is
+        restored, so the continuation — the ordinary ``forward(..., past_key_values=cache, stream_ids=[...])`` — is bit-identical
+        to the uninterrupted stream.  Any slab of any cache of the same weights, compute mode, resolution, ``max_frames`` and
+        policy will do (any ``batch_size``); restoring one snapshot into two slabs forks the stream.  A refusal leaves the slab
+        as it was, and an auto-acquired slab goes back to the free list."""
+        if not isinstance(snapshot, StreamSnapshot):
+            raise TypeError("restore() takes the StreamSnapshot that StreamCache.snapshot() returned")
+        model = self._model()
+        if model is not None and self._h:
+            model._sync()               # a pending re-pack happens now: it invalidates this cache and ages the model's snapshots
+        h = self._require()
+        snapshot._validate()
+        origin = snapshot._origin
+        if origin is not None and origin[0]() is model and origin[1] != model._pack_epoch:
+            raise RuntimeError(_stale_message("snapshot", "stream its frames again"))
+        own = stream is None
+        sid = self.acquire() if own else self._check_stream(stream)
+        try:
+            dev = model.device
+            with torch.cuda.device(dev):
+                blob = snapshot.blob.to(dev, non_blocking=True)
+                meta = nat.SfCacheStreamMeta(**snapshot.meta)
+                nat.check(nat.lib.sf_cache_import_stream(model._handle, h, sid, blob.data_ptr(), blob.numel(), nat.C.byref(meta),
+                                                         nat.current_stream_handle(dev)))
+        except Exception:
+            if own:
+                _slab_release(self._free, sid)
+            raise
+        return sid
 
     def _invalidate(self) -> None:
         h, self._h = self._h, None
@@ -442,6 +580,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         self._handle_device: Optional[torch.device] = None
         self._packed_token = None           # (device, version sum, ...) the native weights were packed from
         self._force_repack = True
+        self._pack_epoch = 0                # counts re-packs: a StreamSnapshot of this model remembers the one it was taken in
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._pos_cache: Dict[tuple, torch.Tensor] = {}
         self._caches: "weakref.WeakSet[StreamCache]" = weakref.WeakSet()
@@ -750,6 +889,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             raise RuntimeError("the StreamFormer HIP encoder runs on an AMD GPU only: call .to('cuda') first "
                                "(there is no CPU fallback)")
         self._release_native()           # live StreamCaches of the old packing are invalidated with it
+        self._pack_epoch = getattr(self, "_pack_epoch", 0) + 1      # ... and so are the snapshots taken from them
         cfg = self._sf_config()
         h = nat.C.c_void_p()
         nat.check(nat.lib.sf_create(nat.C.byref(cfg), dev.index or 0, nat.C.byref(h)))
