@@ -424,6 +424,58 @@ int sf_op_layernorm_bwd(const float* x_dev, const float* dy_dev, const float* ga
                         float* dx_dev, float* d_gamma_dev, float* d_beta_dev, int rows, int D, float eps,
                         sf_stream stream);
 
+/* ---- SigLIP text tower: captions and class prompts from token ids ----------------------------------
+ * Replaces the frozen `self.text_encoder = SiglipTextModel.from_pretrained(...)` of the multitask wrapper (modeling:1365-1375) as the
+ * task heads call it: `self.text_encoder(ids)[1]` / `self.text_encoder(**tokenizer_output)[1]` (modeling:1680, 1756, 1997, 2104, 2217,
+ * 2315, 2385).  Inference only.  Pre-LN layers as in SigLIP: LN1 -> packed qkv -> attention -> out_proj + residual -> LN2 -> fc1 + act ->
+ * fc2 + residual, then final_layer_norm; the Linears run on the encoder's GEMM kernels in the `compute` mode of sf_text_finalize,
+ * residual stream, LayerNorm, softmax and the pooled head in fp32 in both.  Kernels: csrc/sf_text.hip.                           */
+typedef struct sf_text sf_text;
+typedef struct {
+  int32_t vocab, positions;        /* vocab_size, max_position_embeddings (<= 128: SF_ERR_CAPACITY)            */
+  int32_t hidden, layers, heads;   /* width rules of sf_create: hidden % 64 == 0, head_dim a multiple of 8 in 8..128 */
+  int32_t intermediate;            /* any positive size (zero-padded to a multiple of 64 at upload)              */
+  int32_t projection;              /* projection_size: rows of `head`                                            */
+  int32_t act;                     /* 0 = "gelu" (erf); 1 = "gelu_pytorch_tanh" (SigLIP); 2 = "relu"             */
+  float eps;                       /* layer_norm_eps                                                             */
+} sf_text_config;
+int sf_text_create(const sf_text_config* cfg, int device, sf_text** out);
+void sf_text_destroy(sf_text* text);
+/* `key`: a key of HF's SiglipTextModel state dict, with or without a leading "text_model." (embeddings.token_embedding.weight,
+ * embeddings.position_embedding.weight, encoder.layers.<i>.{layer_norm1,layer_norm2,self_attn.{q,k,v,out}_proj,mlp.fc1,mlp.fc2}.{weight,bias},
+ * final_layer_norm.*, head.*).  dtype SF_F32 / SF_F64 / SF_BF16; the host buffer is borrowed for the call.  q_proj, k_proj and v_proj
+ * are packed into one [3 hidden, hidden] Linear by sf_text_finalize.  Other keys: SF_ERR_UNKNOWN_KEY.                              */
+int sf_text_load_tensor(sf_text* text, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int sf_text_finalize(sf_text* text, int compute);
+int sf_text_missing_weights(sf_text* text);       /* count; names via sf_last_error() */
+int sf_text_workspace_bytes(sf_text* text, int B, int L, size_t* out);
+/* ids_dev int32 [B, L]; an id outside [0, vocab) is clamped by the kernel (memory safety only: check ids on the host).
+ * mask_dev uint8 [B, L] or NULL: the tokenizer's attention_mask, 0 = padding.  A masked key gets zero weight for every query of its
+ * caption (HF's additive -inf); query rows of padded positions are still computed.  Every caption needs at least one valid key: the
+ * mask lives on the device, so that check belongs to the caller (the Python layer raises); the kernel writes zeros for such a caption
+ * instead of dividing by a zero sum.
+ * last_hidden_dev fp32 [B, L, hidden] or NULL (final_layer_norm of every row); pooled_dev fp32 [B, projection] = head(final_layer_norm(
+ * row L - 1)) whatever the mask says, as SiglipTextModel pools.  workspace: 256-byte aligned, sf_text_workspace_bytes(B, L).
+ * Refused before anything is launched: L > positions and activations past 2^31 - 1 elements (SF_ERR_CAPACITY), bad shapes (SF_ERR_INVALID). */
+int sf_text_forward(sf_text* text, const int32_t* ids_dev, const uint8_t* mask_dev, int B, int L, float* last_hidden_dev,
+                    float* pooled_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+/* Class-prompt tables (modeling:2207-2223): the same forward on B = labels * group captions, prompts of one label consecutive; every
+ * pooled row is L2-normalised, each `group` consecutive rows are averaged and the mean is normalised again: table_dev fp32
+ * [B / group, projection], unit-norm rows.                                                                                        */
+int sf_text_forward_groups(sf_text* text, const int32_t* ids_dev, const uint8_t* mask_dev, int B, int L, int group, float* table_dev,
+                           void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+/* single operators of the tower (parity tests).
+ * attention: ctx[b, l, h] = softmax(head_dim^-0.5 q k^T + key_mask) v, non-causal; qkv_dev fp32 [B * L, 3 * heads * head_dim] (q | k | v
+ * columns), mask_dev uint8 [B, L] or NULL, ctx_dev fp32 [B * L, heads * head_dim]; L in 1..128, head_dim a multiple of 8 in 8..128;
+ * fp32 arithmetic, bit-reproducible.
+ * pool: x_dev fp32 [B * L, D] -> row L - 1 of every caption -> LayerNorm(gamma, beta, eps) (both NULL: rows used as they are) ->
+ * w_dev [P, D] + bias_dev [P] (or NULL).  group == 0: out_dev [B, P].  group >= 1: out_dev [B / group, P] = normalised means of the
+ * normalised rows, scratch_dev fp32 [B, P] required.                                                                              */
+int sf_op_text_attention(const float* qkv_dev, const uint8_t* mask_dev, float* ctx_dev, int B, int L, int heads, int head_dim,
+                         sf_stream stream);
+int sf_op_text_pool(const float* x_dev, int B, int L, int D, const float* gamma_dev, const float* beta_dev, float eps,
+                    const float* w_dev, const float* bias_dev, int P, int group, float* out_dev, float* scratch_dev, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

@@ -30,6 +30,12 @@ class SfConfig(C.Structure):
         "add_lora_spatial")] + [("layer_norm_eps", C.c_float)]
 
 
+class SfTextConfig(C.Structure):
+    """sf_text_config: HF SiglipTextConfig as plain ints (act: 0 erf GELU, 1 tanh GELU, 2 ReLU)."""
+    _fields_ = [(n, C.c_int32) for n in ("vocab", "positions", "hidden", "layers", "heads", "intermediate", "projection", "act")] + [
+        ("eps", C.c_float)]
+
+
 SF_STREAM_BLOB_KV1 = 0x31564B53
 
 
@@ -117,6 +123,16 @@ SIGNATURES = {
     "sf_op_attention_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_attention_bwd_hd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_layernorm_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    "sf_text_create": (_I, [C.POINTER(SfTextConfig), _I, C.POINTER(_P)]),
+    "sf_text_destroy": (None, [_P]),
+    "sf_text_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
+    "sf_text_finalize": (_I, [_P, _I]),
+    "sf_text_missing_weights": (_I, [_P]),
+    "sf_text_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(_SZ)]),
+    "sf_text_forward": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "sf_text_forward_groups": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
+    "sf_op_text_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_op_text_pool": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _P, _I, _I, _P, _P, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),

@@ -15,8 +15,10 @@ referring segmentation (``TimesformerVideoContrastiveCrossEntropySegmentationHea
 
 Encoder forward / backward run in ``libstreamformer_hip.so`` behind one autograd node (``autograd.py``); the loss heads
 are the HIP loss kernels (``sf_loss.hip``, ``sf_mask_loss.hip`` + ``sf_dense_head.hip``, ``sf_text_heads.hip``) behind a second one.
-What is NOT here: the SigLIP *text tower* and tokenizer (``:1365-1373``; hub weights, outside the path) — captions / class prompts
-enter as feature tensors (``task_input["text_features"]``, ``set_label_embeddings``) — and two dispatches of the reference, which
+The SigLIP text tower (``:1365-1373``) is optional: given ``text_encoder`` (``text.SiglipTextModel``, the native tower) and
+``text_tokenizer`` (the caller's tokenizer object), the caption heads take ``task_input["caption"]`` and the label-table heads build
+their prompt-ensemble tables from ``prompt_templates``; without them captions / class prompts enter as feature tensors
+(``task_input["text_features"]``, ``set_label_embeddings``), as before.  What is NOT here: two dispatches of the reference, which
 raise ``NotImplementedError``: ``SSV2`` (the ``Kinetics`` head under a second name) and the naive localization head
 (``THUMOS14`` / ``ActivityNet`` / ``FineAction`` / ``HACS``, ``:2081-2185``: window bookkeeping over pre-extracted features, not in
 the shipped recipe).  With those two exceptions every task entry of the shipped recipe (``scripts/dataset_metadata/all.yaml``) builds.
@@ -69,12 +71,48 @@ class _TaskHead(nn.Module):
         self.logit_scale = nn.Parameter(torch.tensor(math.log(10.0)))
         self.logit_bias = nn.Parameter(torch.tensor(-2.0))
 
+    # the wrapper's frozen text tower and the caller's tokenizer (modeling:2207-2208, 2302-2303): plain attributes, NOT child modules —
+    # the tower's parameters are listed once, under the wrapper, and a head's state_dict stays what it was
+    _text_encoder = None
+    _text_tokenizer = None
+
     def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
-        """modeling:2199-2205 / :2296-2301: every head deep-copies the wrapper's scale / bias pair."""
+        """modeling:2199-2205 / :2296-2301: every head deep-copies the wrapper's scale / bias pair and keeps the text tower."""
         if logit_scale is not None:
             self.logit_scale = copy.deepcopy(logit_scale)
         if logit_bias is not None:
             self.logit_bias = copy.deepcopy(logit_bias)
+        object.__setattr__(self, "_text_encoder", text_encoder)
+        object.__setattr__(self, "_text_tokenizer", text_tokenizer)
+
+    def _caption_features(self, task_specific_input: dict, device) -> torch.Tensor:
+        """``task_input["text_features"]`` [B, D] as given, or — with a text tower — ``task_input["caption"]`` (list of str) tokenised to
+        64 tokens and encoded (modeling:2307-2316, 2378-2386, 1989-1998)."""
+        if "text_features" in task_specific_input:
+            return task_specific_input["text_features"].to(device)
+        if "caption" not in task_specific_input:
+            raise KeyError("task_input needs 'text_features' [B, D] or 'caption' (list of str)")
+        if self._text_encoder is None or self._text_tokenizer is None:
+            raise RuntimeError("task_input['caption'] needs the wrapper's text_encoder and text_tokenizer "
+                               "(StreamformerForMultiTaskingSigLIP(..., text_encoder=, text_tokenizer=) + prepare_for_multi_tasks()); "
+                               "without them pass task_input['text_features']")
+        from .text import encode_captions
+        return encode_captions(self._text_encoder, self._text_tokenizer, list(task_specific_input["caption"])).to(device)
+
+    def _label_table(self, label2id: dict) -> Optional[torch.Tensor]:
+        """The prompt-ensemble table of one label set (modeling:2207-2223), or None without a tower / templates."""
+        templates = getattr(self, "prompt_templates", None)
+        if self._text_encoder is None or self._text_tokenizer is None or not templates or not label2id:
+            return None
+        from .text import encode_label_prompts
+        return encode_label_prompts(self._text_encoder, self._text_tokenizer, list(label2id.keys()), templates)
+
+    def _build_dataset_tables(self) -> None:
+        for name, l2i in self.label2id.items():
+            if name not in self.dataset_label_embeddings and isinstance(l2i, dict):
+                table = self._label_table(l2i)
+                if table is not None:
+                    self.dataset_label_embeddings[name] = table.detach()
 
 
 class TimesformerVideoRetrievalHead(_TaskHead):
@@ -89,7 +127,7 @@ class TimesformerVideoRetrievalHead(_TaskHead):
 
     def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
         pooler = task_head_input.pooler_output
-        text = task_specific_input["text_features"].to(pooler.device)
+        text = local_text = self._caption_features(task_specific_input, pooler.device)
         if not self.training:
             img = pooler[:, -1, :]
             return img / img.norm(p=2, dim=-1, keepdim=True), text / text.norm(p=2, dim=-1, keepdim=True)
@@ -109,7 +147,7 @@ class TimesformerVideoRetrievalHead(_TaskHead):
         with torch.no_grad():             # "logits for debugging" (:2346-2350): scale only, as in the reference
             img = pooler[:, -1, :]
             img = img / img.norm(p=2, dim=-1, keepdim=True)
-            t = task_specific_input["text_features"].to(pooler.device)
+            t = local_text
             logits = img @ (t / t.norm(p=2, dim=-1, keepdim=True)).t() * self.logit_scale.exp()
         return loss, logits
 
@@ -118,14 +156,20 @@ class TimesformerUniversalLocalizationHead(_TaskHead):
     """modeling:2186-2282.  ``label2id``: ``{dataset_name: {label: id}}``; the prompt-ensemble class embeddings of
     ``prepare_multi_task`` (:2207-2223, text tower) are supplied through :meth:`set_label_embeddings` ([L, D], unit norm)."""
 
-    def __init__(self, config: Optional[StreamformerConfig] = None, label2id: Optional[dict] = None):
+    def __init__(self, config: Optional[StreamformerConfig] = None, label2id: Optional[dict] = None, prompt_templates=None):
         super().__init__()
         self.config = config
         self.label2id = label2id or {}
+        self.prompt_templates = list(prompt_templates) if prompt_templates else None
         self.dataset_label_embeddings: Dict[str, torch.Tensor] = {}
 
     def set_label_embeddings(self, dataset_name: str, embeddings: torch.Tensor) -> None:
         self.dataset_label_embeddings[dataset_name] = embeddings.detach()
+
+    def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
+        """With a text tower and ``prompt_templates``: every dataset's table that :meth:`set_label_embeddings` has not supplied."""
+        super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
+        self._build_dataset_tables()
 
     def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
         pooler = task_head_input.pooler_output                     # [B, T, D]
@@ -160,14 +204,23 @@ class TimesformerVideoClassificationHead(_TaskHead):
     head here; the reference computes ``(loss, logits)`` in either mode (:1725-1726).  The prompt-ensemble class embeddings of ``prepare_multi_task`` (:1676-1684,
     text tower) are supplied through :meth:`set_label_embeddings` ([L, D], unit norm)."""
 
-    def __init__(self, config: Optional[StreamformerConfig] = None, label2id: Optional[dict] = None):
+    def __init__(self, config: Optional[StreamformerConfig] = None, label2id: Optional[dict] = None, prompt_templates=None):
         super().__init__()
         self.config = config
         self.label2id = label2id or {}
+        self.prompt_templates = list(prompt_templates) if prompt_templates else None
         self.label_embeddings: Optional[torch.Tensor] = None
 
     def set_label_embeddings(self, embeddings: torch.Tensor) -> None:
         self.label_embeddings = embeddings.detach()
+
+    def prepare_multi_task(self, text_encoder=None, text_tokenizer=None, logit_scale=None, logit_bias=None, vision_model=None):
+        """With a text tower and ``prompt_templates``: the class table, unless :meth:`set_label_embeddings` has supplied it."""
+        super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
+        if self.label_embeddings is None:
+            table = self._label_table(self.label2id)
+            if table is not None:
+                self.label_embeddings = table.detach()
 
     def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
         if self.label_embeddings is None:
@@ -201,7 +254,7 @@ class TimesformerTemporalGroundingHead(_TaskHead):
 
     def forward(self, task_head_input, task_specific_input: Optional[dict] = None):
         pooler = task_head_input.pooler_output                     # [B, T, D]
-        text = task_specific_input["text_features"].to(pooler.device).detach()      # frozen text tower (:1372-1373)
+        text = self._caption_features(task_specific_input, pooler.device).detach()      # frozen text tower (:1372-1373)
         if not self.training:
             with torch.no_grad():
                 return GroundingHead(self.logit_scale, self.logit_bias).logits(pooler, text)
@@ -271,10 +324,12 @@ class _DenseProjectionHead(_TaskHead):
     the child ``head`` and the head's own copies of its value projection, out_proj, layernorm and mlp, applied to every patch token
     by ``DenseHeadProjection``."""
 
-    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None):
+    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None,
+                 prompt_templates=None):
         super().__init__()
         self.config = config
         self.label2id = label2id or {}
+        self.prompt_templates = list(prompt_templates) if prompt_templates else None
         if head is not None:
             self.head = head
         if config.hidden_act != "gelu":
@@ -326,8 +381,9 @@ class TimesformerUniversalVideoInstanceSegmentationHead(_DenseProjectionHead):
     ``label2id``: ``{dataset_name: {label: id}}``; the class embeddings of ``prepare_multi_task`` (:1748-1762, text tower) come
     through :meth:`set_label_embeddings`."""
 
-    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None):
-        super().__init__(config, label2id, head)
+    def __init__(self, config: StreamformerConfig, label2id: Optional[dict] = None, head: Optional[nn.Module] = None,
+                 prompt_templates=None):
+        super().__init__(config, label2id, head, prompt_templates)
         self._build_projection()
         self.dataset_label_embeddings: Dict[str, torch.Tensor] = {}
         self.class_rng: Optional[random.Random] = None      # None: the module-level `random`, as the reference
@@ -336,6 +392,7 @@ class TimesformerUniversalVideoInstanceSegmentationHead(_DenseProjectionHead):
         super().prepare_multi_task(text_encoder, text_tokenizer, logit_scale, logit_bias, vision_model)
         if vision_model is not None:
             self._copy_projection(vision_model)
+        self._build_dataset_tables()            # modeling:1748-1762, when a text tower and prompt_templates are given
 
     def set_label_embeddings(self, dataset_name: str, embeddings: torch.Tensor) -> None:
         self.dataset_label_embeddings[dataset_name] = embeddings.detach()
@@ -406,7 +463,7 @@ class TimesformerVideoContrastiveCrossEntropySegmentationHead(_DenseProjectionHe
             raise RuntimeError("prepare_multi_task(vision_model=...) first: it creates this head's dense projection (modeling:1940-1955)")
         lhs = task_head_input.last_hidden_state                    # [B, T, N, D]
         B, T, N, D = lhs.shape
-        text = task_specific_input["text_features"].to(lhs.device).detach().float()      # frozen text tower (:1372-1373)
+        text = self._caption_features(task_specific_input, lhs.device).detach().float()      # frozen text tower (:1372-1373)
         if tuple(text.shape) != (B, D):
             raise ValueError(f"text_features must be [{B}, {D}] (one caption per clip), got {tuple(text.shape)}")
         if not self.training:
@@ -434,11 +491,22 @@ class TimesformerVideoContrastiveCrossEntropySegmentationHead(_DenseProjectionHe
 
 
 class StreamformerForMultiTaskingSigLIP(nn.Module):
-    """modeling:1356-1536 without the text tower: ``timesformer`` + per-task heads, one task per call."""
+    """modeling:1356-1536: ``timesformer`` + per-task heads, one task per call.  ``text_encoder`` (``text.SiglipTextModel``, frozen;
+    registered as the child ``text_encoder`` like the reference's, :1365-1375) and ``text_tokenizer`` (the caller's tokenizer) are
+    optional and go together; ``multi_task_config[task]["prompt_templates"]`` (format strings with one ``{}``) lets the label-table
+    heads build their class tables from them."""
 
-    def __init__(self, config: StreamformerConfig, multi_task_config: Optional[dict] = None, compute_dtype="fp32"):
+    def __init__(self, config: StreamformerConfig, multi_task_config: Optional[dict] = None, compute_dtype="fp32",
+                 text_encoder=None, text_tokenizer=None):
         super().__init__()
         self.config = config
+        if (text_encoder is None) != (text_tokenizer is None):
+            raise ValueError("text_encoder and text_tokenizer go together: the heads tokenise captions before they encode them")
+        if text_encoder is not None:
+            self.text_encoder = text_encoder
+            for p in self.text_encoder.parameters():             # modeling:1374-1375
+                p.requires_grad = False
+        self.text_tokenizer = text_tokenizer
         self.timesformer = TimesformerMultiTaskingModelSigLIP(config, compute_dtype=compute_dtype)
         self.logit_scale = nn.Parameter(torch.log(torch.tensor(10.0)))
         self.logit_bias = nn.Parameter(torch.tensor(-2.0))
@@ -446,14 +514,17 @@ class StreamformerForMultiTaskingSigLIP(nn.Module):
         self.task_types = list(multi_task_config.keys()) if multi_task_config else []
         for task_type in self.task_types:
             if task_type in LOCALIZATION_TASKS:
-                self.task_heads[task_type] = TimesformerUniversalLocalizationHead(config, (multi_task_config[task_type] or {}).get("label2id"))
+                self.task_heads[task_type] = TimesformerUniversalLocalizationHead(config, (multi_task_config[task_type] or {}).get("label2id"),
+                                                                                  (multi_task_config[task_type] or {}).get("prompt_templates"))
             elif task_type in RETRIEVAL_TASKS:
                 self.task_heads[task_type] = TimesformerVideoRetrievalHead(config)
             elif task_type in CLASSIFICATION_TASKS:
-                self.task_heads[task_type] = TimesformerVideoClassificationHead(config, (multi_task_config[task_type] or {}).get("label2id"))
+                self.task_heads[task_type] = TimesformerVideoClassificationHead(config, (multi_task_config[task_type] or {}).get("label2id"),
+                                                                                (multi_task_config[task_type] or {}).get("prompt_templates"))
             elif task_type in VIS_TASKS:
                 self.task_heads[task_type] = TimesformerUniversalVideoInstanceSegmentationHead(
-                    config, (multi_task_config[task_type] or {}).get("label2id"), self.timesformer.head)
+                    config, (multi_task_config[task_type] or {}).get("label2id"), self.timesformer.head,
+                    (multi_task_config[task_type] or {}).get("prompt_templates"))
             elif task_type in GROUNDING_TASKS:
                 self.task_heads[task_type] = TimesformerTemporalGroundingHead(config)
             elif task_type in REFER_VOS_TASKS:
@@ -474,7 +545,7 @@ class StreamformerForMultiTaskingSigLIP(nn.Module):
 
     def prepare_for_multi_tasks(self):
         for head in self.task_heads.values():
-            head.prepare_multi_task(None, None, self.logit_scale, self.logit_bias, self.timesformer)
+            head.prepare_multi_task(getattr(self, "text_encoder", None), self.text_tokenizer, self.logit_scale, self.logit_bias, self.timesformer)
 
     def add_lora_spatial(self):
         """modeling:1448-1459: rank-32 factors on every spatial qkv / output.dense; `_add_lora` freezes the base qkv / dense
