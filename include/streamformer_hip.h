@@ -476,6 +476,55 @@ int sf_op_text_attention(const float* qkv_dev, const uint8_t* mask_dev, float* c
 int sf_op_text_pool(const float* x_dev, int B, int L, int D, const float* gamma_dev, const float* beta_dev, float eps,
                     const float* w_dev, const float* bias_dev, int P, int group, float* out_dev, float* scratch_dev, sf_stream stream);
 
+/* ---- Video-LLM connector: projector, spatial pooling and newline tokens ---------------------------
+ * The tail between the vision tower's features and the language model's input embeddings in the reference's VideoQA model
+ * (llava_arch: mm_projector :213, get_2dPool :171-190, the newline placement :261-288 and :351-390): feats [F, P * P, in_dim] ->
+ * rows [tokens, out_dim].  Inference only.  The Linears run on the encoder's GEMM kernels in the `compute` mode of
+ * sf_connector_finalize (weights rounded / split once, there); the average and bilinear pools are applied in FRONT of the last
+ * Linear, with which they commute (their taps sum to 1), so that GEMM runs on P'^2 rows per frame; max keeps the reference's order.
+ * Kernel: csrc/sf_connector.hip.                                                                                                  */
+typedef struct sf_connector sf_connector;
+typedef struct {
+  int32_t in_dim, out_dim;     /* mm_hidden_size, LLM hidden_size; both % 64 == 0, else SF_ERR_INVALID  */
+  int32_t depth;               /* Linears in the projector: 0 = identity (in_dim == out_dim), 1 = "linear", n = "mlp{n}x_gelu" (erf GELU between) */
+  int32_t pool_mode;           /* 0 none, 1 average, 2 max, 3 bilinear                                   */
+  int32_t pool_stride;         /* >= 1; 1 forces pool_mode none                                           */
+  int32_t newline;             /* 0 no_token, 1 one_token (one row after the last frame), 2 frame, 3 grid */
+} sf_connector_config;
+int sf_connector_create(const sf_connector_config* cfg, int device, sf_connector** out);
+void sf_connector_destroy(sf_connector* conn);
+/* `key`, with or without a leading "model.": mm_projector.{0,2,4,...}.{weight,bias} (the nn.Sequential indices of the reference
+ * builder, depth >= 2), mm_projector.{weight,bias} (depth 1), image_newline [out_dim] (required only when newline != 0).  dtype
+ * SF_F32 / SF_F64 / SF_BF16; the host buffer is borrowed for the call.  Other keys: SF_ERR_UNKNOWN_KEY; a wrong shape: SF_ERR_INVALID. */
+int sf_connector_load_tensor(sf_connector* conn, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+/* Uploads the weights to the handle's device.  Makes that device current (hipSetDevice) and leaves it current on return.          */
+int sf_connector_finalize(sf_connector* conn, int compute);
+int sf_connector_missing_weights(sf_connector* conn);       /* count; names via sf_last_error() */
+/* Rows of the output for F frames of P x P patches.  P' = ceil(P / stride) (bilinear) or floor(P / stride) (average, max);
+ * no_token F P'^2, one_token F P'^2 + 1, frame F (P'^2 + 1), grid F P' (P' + 1).                                                   */
+int sf_connector_num_tokens(sf_connector* conn, int F, int P, int64_t* out);
+int sf_connector_workspace_bytes(sf_connector* conn, int F, int P, size_t* out);      /* after sf_connector_finalize */
+/* feats_dev fp32 [F, P * P, in_dim]; out_dev [sf_connector_num_tokens, out_dim] in out_dtype (SF_F32, or SF_BF16 rounded to nearest
+ * even).  Row of frame f, cell (oy, ox): grid f P' (P' + 1) + oy (P' + 1) + ox with a newline row after every grid row; frame
+ * f (P'^2 + 1) + oy P' + ox with a newline row after every frame; no_token / one_token f P'^2 + oy P' + ox, one_token adds one newline
+ * row at F P'^2.  workspace: 256-byte aligned, sf_connector_workspace_bytes(F, P).  Refused before anything is launched: F < 1, P < 1
+ * or P' < 1 and a misaligned buffer (SF_ERR_INVALID), an activation past 2^31 - 1 elements (SF_ERR_CAPACITY), a short workspace
+ * (SF_ERR_WORKSPACE), a handle that is not finalized (SF_ERR_STATE).  The call sets no device: the handle's device must be current
+ * in the calling thread, and `stream` and every buffer must belong to it.                                                         */
+int sf_connector_forward(sf_connector* conn, const float* feats_dev, int F, int P, void* out_dev, int out_dtype, void* workspace_dev,
+                         size_t workspace_bytes, sf_stream stream);
+/* The pool-and-layout kernel alone (parity tests), in one of its two input forms.
+ * fp32 form: in_f32_dev [F, P * P, C] -> out_dev [rows, C] in out_dtype (SF_F32 / SF_BF16); in_hi_dev, in_lo_dev, out_hi_dev and
+ * out_lo_dev NULL.  Plane form: in_hi_dev (+ in_lo_dev or NULL) bf16 planes of the same tensor, summed in fp32 -> out_hi_dev
+ * (+ out_lo_dev or NULL), hi = bf16(y), lo = bf16(y - hi); in_f32_dev and out_dev NULL.  Taps as PyTorch's F.avg_pool2d /
+ * F.max_pool2d (floor(P / stride) cells per side) and F.interpolate(mode="bilinear", align_corners=False) (ceil(P / stride)); rows and
+ * newline rows (newline_dev fp32 [C], may be NULL for newline 0) as sf_connector_forward places them.  C % 8 == 0, every buffer
+ * 16-byte aligned; one fixed summation order per element, bit-reproducible.  max takes a tap when it is greater or a NaN, as
+ * F.max_pool2d does: a NaN in a window is the window's result, and of two zeros the first in row-major order stays.              */
+int sf_op_connector_pool(const float* in_f32_dev, const uint16_t* in_hi_dev, const uint16_t* in_lo_dev, int F, int P, int C,
+                         int pool_mode, int pool_stride, int newline, const float* newline_dev, void* out_dev, int out_dtype,
+                         uint16_t* out_hi_dev, uint16_t* out_lo_dev, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

@@ -36,6 +36,12 @@ class SfTextConfig(C.Structure):
         ("eps", C.c_float)]
 
 
+class SfConnectorConfig(C.Structure):
+    """sf_connector_config: the LLaVA connector fields as plain ints (pool_mode 0 none, 1 average, 2 max, 3 bilinear; newline 0 no_token,
+    1 one_token, 2 frame, 3 grid)."""
+    _fields_ = [(n, C.c_int32) for n in ("in_dim", "out_dim", "depth", "pool_mode", "pool_stride", "newline")]
+
+
 SF_STREAM_BLOB_KV1 = 0x31564B53
 
 
@@ -133,6 +139,15 @@ SIGNATURES = {
     "sf_text_forward_groups": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _SZ, _P]),
     "sf_op_text_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "sf_op_text_pool": (_I, [_P, _I, _I, _I, _P, _P, _F, _P, _P, _I, _I, _P, _P, _P]),
+    "sf_connector_create": (_I, [C.POINTER(SfConnectorConfig), _I, C.POINTER(_P)]),
+    "sf_connector_destroy": (None, [_P]),
+    "sf_connector_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
+    "sf_connector_finalize": (_I, [_P, _I]),
+    "sf_connector_missing_weights": (_I, [_P]),
+    "sf_connector_num_tokens": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
+    "sf_connector_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(_SZ)]),
+    "sf_connector_forward": (_I, [_P, _P, _I, _I, _P, _I, _P, _SZ, _P]),
+    "sf_op_connector_pool": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),

@@ -1154,6 +1154,7 @@ class TimesformerVisionTower(nn.Module):
             self.context_length = int(getattr(cfg, "context_length", 16) if context_length is None else context_length)
             self.past_key_values: Optional[StreamCache] = None
             self.hidden_states: Optional[torch.Tensor] = None
+            self.new_frame_features: Optional[torch.Tensor] = None      # (B, T_new, N, D) of the last call alone (read-only: the window is not re-sliced)
         self._spare: Optional[StreamCache] = None
 
     def _adopt(self, model: TimesformerMultiTaskingModelSigLIP) -> None:
@@ -1177,6 +1178,7 @@ class TimesformerVisionTower(nn.Module):
         if not self.streaming_mode:
             return
         self.hidden_states = None
+        self.new_frame_features = None
         if self.past_key_values is not None and self.past_key_values.valid:
             self._spare = self.past_key_values
         self.past_key_values = None
@@ -1203,6 +1205,7 @@ class TimesformerVisionTower(nn.Module):
             outputs = self.vision_tower(x, use_cache=True, past_key_values=cache, cache_position=None)
             self.past_key_values = outputs.past_key_values
             lhs = outputs.last_hidden_state
+            self.new_frame_features = lhs
             self.hidden_states = lhs if self.hidden_states is None else torch.cat([self.hidden_states, lhs], dim=1)
             self.hidden_states = self.hidden_states[:, -self.context_length:]       # bounded: nothing older is ever returned
             return self.hidden_states.to(images.dtype if images.dtype.is_floating_point else lhs.dtype)
