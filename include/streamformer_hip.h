@@ -525,6 +525,63 @@ int sf_op_connector_pool(const float* in_f32_dev, const uint16_t* in_hi_dev, con
                          int pool_mode, int pool_stride, int newline, const float* newline_dev, void* out_dev, int out_dtype,
                          uint16_t* out_hi_dev, uint16_t* out_lo_dev, sf_stream stream);
 
+/* ---- online action detection: the streaming LSTR detector -------------------------------------
+ * The reference's downstream/OAD LSTRStream.stream_inference path (inference only, INPUT.MODALITY 'visual'): feature head, a
+ * long-memory window of L samples compressed by enc_modules (stage 0 through the decomposition k = W_k x, k_pos = W_k pe[i] + b_k,
+ * likewise v, over a per-stream ring of projected rows), a causal work-memory decoder and the classifier.  Keys of
+ * sf_oad_load_tensor are the reference's state-dict names ("feature_head_long.visual_linear.0.weight", "enc_queries.0.weight",
+ * "enc_modules.0.layers.0.multihead_attn.in_proj_weight", "dec_modules.layers.1.linear1.weight", "classifier.bias",
+ * "pos_encoding.pe" with at least L + W rows).  Weights are rounded / split once at sf_oad_finalize, which also computes what does
+ * not depend on the input: stage 0's query self-attention + norm1, their q projection, and k_pos / v_pos.
+ * Kernels: csrc/sf_oad.hip.                                                                                                       */
+typedef struct sf_oad sf_oad;
+typedef struct sf_oad_state sf_oad_state;
+#define SF_OAD_MAX_ENC_MODULES 8
+#define SF_OAD_MAX_CALL_STREAMS 64
+typedef struct {
+  int32_t d_in, d_model, heads, ffn;            /* d_model == d_in when linear_enabled == 0; d_in, d_model, ffn multiples of 64 */
+  int32_t long_samples, work_samples, classes; /* L, W, DATA.NUM_CLASSES                                                      */
+  int32_t act;                                  /* 0 erf GELU, 2 ReLU                                                          */
+  int32_t linear_enabled;                       /* MODEL.FEATURE_HEAD.LINEAR_ENABLED                                           */
+  int32_t enc_modules;                          /* 1..SF_OAD_MAX_ENC_MODULES entries of ENC_MODULE [queries | -1, layers, norm]  */
+  int32_t enc_queries[SF_OAD_MAX_ENC_MODULES], enc_layers[SF_OAD_MAX_ENC_MODULES], enc_norm[SF_OAD_MAX_ENC_MODULES];
+  int32_t dec_layers, dec_norm;                 /* DEC_MODULE [-1, layers, norm]                                               */
+  float eps;                                    /* nn.LayerNorm's 1e-5                                                         */
+} sf_oad_config;
+int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out);
+void sf_oad_destroy(sf_oad* det);
+int sf_oad_load_tensor(sf_oad* det, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+int sf_oad_finalize(sf_oad* det, int compute);             /* makes the handle's device current; launches and synchronises */
+int sf_oad_missing_weights(sf_oad* det);                   /* count; names via sf_last_error() */
+int sf_oad_workspace_bytes(sf_oad* det, int streams, size_t* out);      /* after sf_oad_finalize; streams of one call */
+/* Device-resident state of `streams` independent streams: the ring of projected long-memory rows [L, 2 d_model] (k | v, fp32) and
+ * the cached output of compression stage 0 [Q0, d_model] per stream.  Ring head and fill count are host integers.                 */
+int sf_oad_state_create(sf_oad* det, int streams, sf_oad_state** out);
+void sf_oad_state_destroy(sf_oad_state* st);
+int sf_oad_state_reset(sf_oad_state* st, int stream);      /* stream < 0: all of them */
+int sf_oad_state_fill(sf_oad_state* st, int stream);       /* long samples held: 0 (empty) or L; negative: error */
+/* dst's stream dst_stream becomes a copy of src's stream src_stream (same detector), enqueued on `stream`                         */
+int sf_oad_state_copy(sf_oad_state* dst, int dst_stream, sf_oad_state* src, int src_stream, sf_stream stream);
+/* One step of n <= SF_OAD_MAX_CALL_STREAMS distinct streams (stream_ids: HOST array).  work_dev fp32 [n, W, d_in]; long_rows: HOST
+ * array, per stream 0 (reuse the cached compressed memory), 1 (one new sample, the oldest drops out) or L (the whole window, oldest
+ * first: only on an empty stream, and an empty stream takes nothing else); long_dev fp32 [sum long_rows, d_in] in call order;
+ * mask_dev fp32 [n, L] additive key mask by window position (0 = oldest), -inf allowed, read for streams with long_rows > 0 (NULL:
+ * none; a row of only -inf is the caller's error and yields zeros).  out_dev fp32 [n, W, classes]: scores, or their softmax when
+ * probs != 0.  No allocation and no host synchronisation; every kernel has one fixed summation order.                             */
+int sf_oad_step(sf_oad* det, sf_oad_state* st, const int32_t* stream_ids, int n, const float* work_dev, const float* long_dev,
+                const int32_t* long_rows, const float* mask_dev, float* out_dev, int probs, void* workspace_dev, size_t workspace_bytes,
+                sf_stream stream);
+/* The attention kernel alone (parity tests): ctx[s, i, h, :] = softmax_j(scale q . (k_j + k_pos_j) + mask[s, j] (+ causal)) (v_j + v_pos_j),
+ * fp32.  q_dev [q_streams, Tq, heads * head_dim] with q_streams = 1 (shared by every stream) or streams; k_dev, v_dev
+ * [streams, Tk, heads * head_dim]; key j of stream s is row (ring_start[s] + j) mod Tk (ring_start: HOST array or NULL = 0);
+ * k_pos_dev / v_pos_dev [Tk, heads * head_dim] by key position j, or NULL; mask_dev [streams, Tk] additive or NULL; causal: key j
+ * visible to query i iff j <= i + Tk - Tq.  A key whose mask is -inf contributes exactly zero whatever its rows hold; a query without
+ * a visible key gets zeros.  head_dim a multiple of 8 in 8..256, Tq, Tk >= 1, streams <= SF_OAD_MAX_CALL_STREAMS, buffers 16-byte
+ * aligned.  ctx_dev [streams, Tq, heads * head_dim].                                                                              */
+int sf_op_oad_attention(const float* q_dev, int q_streams, const float* k_dev, const float* v_dev, const int32_t* ring_start,
+                        const float* k_pos_dev, const float* v_pos_dev, const float* mask_dev, float* ctx_dev, int streams, int Tq, int Tk,
+                        int heads, int head_dim, int causal, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

@@ -42,6 +42,15 @@ class SfConnectorConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("in_dim", "out_dim", "depth", "pool_mode", "pool_stride", "newline")]
 
 
+class SfOadConfig(C.Structure):
+    """sf_oad_config: the LSTR stream detector's fields as plain ints (act 0 erf GELU, 2 ReLU; enc_queries -1 = encoder layers)."""
+    _fields_ = [(n, C.c_int32) for n in ("d_in", "d_model", "heads", "ffn", "long_samples", "work_samples", "classes", "act",
+                                         "linear_enabled", "enc_modules")] + [
+        (n, C.c_int32 * 8) for n in ("enc_queries", "enc_layers", "enc_norm")] + [
+        ("dec_layers", C.c_int32), ("dec_norm", C.c_int32), ("eps", C.c_float)]
+
+
+SF_OAD_MAX_CALL_STREAMS = 64
 SF_STREAM_BLOB_KV1 = 0x31564B53
 
 
@@ -148,6 +157,19 @@ SIGNATURES = {
     "sf_connector_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(_SZ)]),
     "sf_connector_forward": (_I, [_P, _P, _I, _I, _P, _I, _P, _SZ, _P]),
     "sf_op_connector_pool": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P]),
+    "sf_oad_create": (_I, [C.POINTER(SfOadConfig), _I, C.POINTER(_P)]),
+    "sf_oad_destroy": (None, [_P]),
+    "sf_oad_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
+    "sf_oad_finalize": (_I, [_P, _I]),
+    "sf_oad_missing_weights": (_I, [_P]),
+    "sf_oad_workspace_bytes": (_I, [_P, _I, C.POINTER(_SZ)]),
+    "sf_oad_state_create": (_I, [_P, _I, C.POINTER(_P)]),
+    "sf_oad_state_destroy": (None, [_P]),
+    "sf_oad_state_reset": (_I, [_P, _I]),
+    "sf_oad_state_fill": (_I, [_P, _I]),
+    "sf_oad_state_copy": (_I, [_P, _I, _P, _I, _P]),
+    "sf_oad_step": (_I, [_P, _P, C.POINTER(C.c_int32), _I, _P, _P, C.POINTER(C.c_int32), _P, _P, _I, _P, _SZ, _P]),
+    "sf_op_oad_attention": (_I, [_P, _I, _P, _P, C.POINTER(C.c_int32), _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
