@@ -209,5 +209,29 @@ def ptr(t) -> int:
     return 0 if t is None else t.data_ptr()
 
 
+def weights_token(device, tensors):
+    """What a packed handle was made from: the device and every tensor's address and in-place version counter."""
+    return (device, tuple((t.data_ptr(), t._version) for t in tensors))
+
+
+def load_tensors(handle, load_fn, items, dtype_of=None) -> None:
+    """Stage ``(key, tensor)`` pairs through a ``*_load_tensor`` entry point from contiguous host copies.  ``dtype_of`` maps a torch
+    dtype that the entry point takes as it is to its SF_* code (None: convert); without it everything goes as fp32."""
+    for k, p in items:
+        t = p.detach().to("cpu").contiguous()
+        code = dtype_of(t.dtype) if dtype_of is not None else None
+        if code is None:
+            t, code = t.float(), SF_F32
+        shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
+        check(load_fn(handle, k.encode(), t.data_ptr(), code, shape, t.dim()))
+
+
+def grow_workspace(current, nbytes: int, device):
+    """The grow-only byte buffer of a module: ``current`` when it is large enough and on ``device``, else a new one."""
+    if current is None or current.numel() < nbytes or current.device != device:
+        current = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return current
+
+
 def current_stream_handle(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream

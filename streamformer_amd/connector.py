@@ -164,7 +164,7 @@ class VideoTokenConnector(nn.Module):
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("the connector runs on the MI355X: move the module with .to('cuda') (there is no CPU fallback)")
-        token = (dev, tuple((p.data_ptr(), p._version) for _, p in params))
+        token = nat.weights_token(dev, [p for _, p in params])
         if token != self._packed_token:
             self._release()
             self._packed_token = token
@@ -172,12 +172,7 @@ class VideoTokenConnector(nn.Module):
         if h is None:
             h = self._create(key, dev.index or 0)
             self._handles[key] = h
-            for k, p in params:
-                if k == "image_newline" and key[2] == 0:
-                    continue
-                t = p.detach().to("cpu", torch.float32).contiguous()
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                nat.check(nat.lib.sf_connector_load_tensor(h, k.encode(), t.data_ptr(), nat.SF_F32, shape, t.dim()))
+            nat.load_tensors(h, nat.lib.sf_connector_load_tensor, [(k, p) for k, p in params if not (k == "image_newline" and key[2] == 0)])
             with torch.cuda.device(dev):
                 nat.check(nat.lib.sf_connector_finalize(h, self._compute))
         return h
@@ -185,8 +180,7 @@ class VideoTokenConnector(nn.Module):
     def _workspace(self, h, F: int, P: int) -> torch.Tensor:
         n = C.c_size_t()
         nat.check(nat.lib.sf_connector_workspace_bytes(h, F, P, C.byref(n)))
-        if self._ws is None or self._ws.numel() < n.value or self._ws.device != self.device:
-            self._ws = torch.empty(max(n.value, 256), dtype=torch.uint8, device=self.device)
+        self._ws = nat.grow_workspace(self._ws, n.value, self.device)
         return self._ws
 
     def _run(self, key: Tuple[int, int, int], feats: torch.Tensor, P: int, out_dtype: torch.dtype) -> torch.Tensor:

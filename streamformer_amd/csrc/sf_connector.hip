@@ -21,13 +21,7 @@
 // Schedule (sf_connector_forward): average and bilinear are linear maps over patch positions whose weights sum to 1, so they commute
 // with the last Linear, pool(x W^T + b) = pool(x) W^T + b: the pool runs in role (a) in FRONT of the last GEMM, which then sees P'^2
 // rows per frame instead of P^2, and role (b) only places rows.  max does not commute and keeps the reference's order.
-#include "sf_common.h"
-#include "sf_internal.h"
-
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include "sf_handle.h"
 
 typedef __attribute__((ext_vector_type(4))) float cf4_t;
 
@@ -197,48 +191,16 @@ static hipError_t conn_launch_pool(const SfConnPool& q, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct ConnLinear { bf16_t* w_hi = nullptr; bf16_t* w_lo = nullptr; float* bias = nullptr; int N = 0, K = 0; };
-struct ConnHost { std::vector<float> data; };
-
-inline uint16_t c_f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline float c_bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-struct ConnCarver {
-  char* base;
-  size_t off = 0;
-  explicit ConnCarver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-}  // namespace
-
 struct sf_connector {
   sf_connector_config cfg;
   int device = 0;
   int pool = CONN_POOL_NONE;                  // cfg.pool_mode with stride 1 folded to none
-  std::map<std::string, ConnHost> host;       // staged fp32 copies until finalize
-  std::map<std::string, std::vector<int64_t>> expected;      // every key load_tensor accepts
-  std::vector<std::string> required;
+  SfWeightStore weights;                      // image_newline is accepted by every layout and required by those that place it
   bool finalized = false;
   int compute = SF_COMPUTE_BF16;
-  std::vector<void*> allocs;
-  std::vector<ConnLinear> lin;
-  float* newline = nullptr;                   // [out_dim] or null
+  SfDeviceAllocs dev;
+  std::vector<SfDevLinear> lin;
+  const float* newline = nullptr;             // [out_dim] or null
 };
 
 static std::string conn_linear_key(const sf_connector* c, int i) {
@@ -259,22 +221,26 @@ extern "C" int sf_connector_create(const sf_connector_config* cfg, int device, s
   h->cfg = c;
   h->device = device;
   h->pool = c.pool_stride == 1 ? CONN_POOL_NONE : c.pool_mode;
+  SfWeightStore& w = h->weights;
+  w.noun = "connector";
+  w.prefix = "model.";
+  w.dtype_msg = "sf_connector_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
+  w.all_required = false;
   for (int i = 0; i < c.depth; ++i) {
     const std::string p = conn_linear_key(h, i);
-    h->expected[p + "weight"] = {c.out_dim, i ? c.out_dim : c.in_dim};
-    h->expected[p + "bias"] = {c.out_dim};
-    h->required.push_back(p + "weight");
-    h->required.push_back(p + "bias");
+    w.expected[p + "weight"] = {c.out_dim, i ? c.out_dim : c.in_dim};
+    w.expected[p + "bias"] = {c.out_dim};
+    w.required.push_back(p + "weight");
+    w.required.push_back(p + "bias");
   }
-  h->expected["image_newline"] = {c.out_dim};
-  if (c.newline != CONN_NL_NONE) h->required.push_back("image_newline");
+  w.expected["image_newline"] = {c.out_dim};
+  if (c.newline != CONN_NL_NONE) w.required.push_back("image_newline");
   *out = h;
   return SF_OK;
 }
 
 static void conn_free_device(sf_connector* c) {
-  for (void* p : c->allocs) (void)hipFree(p);
-  c->allocs.clear();
+  c->dev.free_all();
   c->lin.clear();
   c->newline = nullptr;
 }
@@ -287,80 +253,37 @@ extern "C" void sf_connector_destroy(sf_connector* c) {
 
 extern "C" int sf_connector_load_tensor(sf_connector* c, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
   if (!c || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_connector_load_tensor: null argument");
-  std::string k(key);
-  if (k.rfind("model.", 0) == 0) k = k.substr(6);
-  auto it = c->expected.find(k);
-  if (it == c->expected.end()) return sf_set_err(SF_ERR_UNKNOWN_KEY, "'%s' is not a weight of this connector", key);
-  size_t n = 1;
-  bool same = (int)it->second.size() == ndim;
-  for (int i = 0; i < ndim; ++i) { n *= (size_t)shape[i]; same = same && it->second[i] == shape[i]; }
-  if (!same) return sf_set_err(SF_ERR_INVALID, "'%s': shape mismatch", key);
-  ConnHost h;
-  h.data.resize(n);
-  switch (dtype) {
-    case SF_F32: memcpy(h.data.data(), host_ptr, n * 4); break;
-    case SF_F64: for (size_t i = 0; i < n; ++i) h.data[i] = (float)((const double*)host_ptr)[i]; break;
-    case SF_BF16: for (size_t i = 0; i < n; ++i) h.data[i] = c_bf2f(((const uint16_t*)host_ptr)[i]); break;
-    default: return sf_set_err(SF_ERR_INVALID, "sf_connector_load_tensor: dtype %d unsupported (fp32, fp64, bf16)", dtype);
-  }
-  c->host[k] = std::move(h);
+  std::string err;
+  const int rc = c->weights.load(key, host_ptr, dtype, shape, ndim, &err);
+  if (rc) return sf_set_err(rc, "%s", err.c_str());
   c->finalized = false;
   return SF_OK;
 }
 
 extern "C" int sf_connector_missing_weights(sf_connector* c) {
   if (!c) return sf_set_err(SF_ERR_INVALID, "null handle");
-  int missing = 0;
-  std::string names;
-  for (const std::string& k : c->required)
-    if (!c->host.count(k)) {
-      ++missing;
-      if (names.size() < 800) names += k + " ";
-    }
-  if (missing) sf_set_err(SF_ERR_STATE, "missing %d weights: %s", missing, names.c_str());
+  std::string err;
+  const int missing = c->weights.missing(&err);
+  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
   return missing;
-}
-
-template <typename T>
-static int conn_upload(sf_connector* c, const std::vector<T>& h, T** out) {
-  void* p = nullptr;
-  const size_t bytes = h.size() * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-  c->allocs.push_back(p);
-  if (bytes) HIP_TRY(hipMemcpy(p, h.data(), bytes, hipMemcpyHostToDevice));
-  *out = (T*)p;
-  return SF_OK;
 }
 
 // the weights rounded (bf16 mode) or split into hi + lo planes (bf16x3) ONCE, here: no per-call conversion of 3584^2 fp32 values.
 // Makes the handle's device current and leaves it so, as the encoder's and the text tower's finalize do (stated in the header).
 extern "C" int sf_connector_finalize(sf_connector* c, int compute) {
   if (!c) return sf_set_err(SF_ERR_INVALID, "null handle");
-  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return sf_set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
+  SF_TRY(sf_check_compute_mode(compute));
   if (sf_connector_missing_weights(c)) return SF_ERR_STATE;
   HIP_TRY(hipSetDevice(c->device));
   conn_free_device(c);
   c->compute = compute;
-  const bool split = compute == SF_COMPUTE_BF16X3;
-  int rc;
-  c->lin.assign(c->cfg.depth, ConnLinear());
+  c->lin.assign(c->cfg.depth, SfDevLinear());
   for (int i = 0; i < c->cfg.depth; ++i) {
     const std::string p = conn_linear_key(c, i);
-    const std::vector<float>& w = c->host[p + "weight"].data;
-    std::vector<uint16_t> hi(w.size()), lo;
-    if (split) lo.resize(w.size());
-    for (size_t j = 0; j < w.size(); ++j) {
-      hi[j] = c_f2bf(w[j]);
-      if (split) lo[j] = c_f2bf(w[j] - c_bf2f(hi[j]));
-    }
-    ConnLinear& l = c->lin[i];
-    if ((rc = conn_upload<uint16_t>(c, hi, &l.w_hi))) return rc;
-    if (split && (rc = conn_upload<uint16_t>(c, lo, &l.w_lo))) return rc;
-    if ((rc = conn_upload<float>(c, c->host[p + "bias"].data, &l.bias))) return rc;
-    l.N = c->cfg.out_dim;
-    l.K = i ? c->cfg.out_dim : c->cfg.in_dim;
+    SF_TRY(sf_upload_linear(c->dev, c->weights.data(p + "weight"), &c->weights.data(p + "bias"), c->cfg.out_dim, i ? c->cfg.out_dim : c->cfg.in_dim,
+                            c->cfg.out_dim, compute == SF_COMPUTE_BF16X3, &c->lin[i]));
   }
-  if (c->cfg.newline != CONN_NL_NONE && (rc = conn_upload<float>(c, c->host["image_newline"].data, &c->newline))) return rc;
+  if (c->cfg.newline != CONN_NL_NONE) SF_TRY(c->dev.upload(c->weights.data("image_newline"), &c->newline));
   c->finalized = true;
   return SF_OK;
 }
@@ -401,7 +324,7 @@ struct ConnWorkspace {
 static ConnWorkspace conn_carve(const sf_connector* c, const ConnPlan& pl, void* base) {
   ConnWorkspace w;
   memset(&w, 0, sizeof(w));
-  ConnCarver cv(base);
+  SfCarver cv(base);
   const size_t M = (size_t)pl.M, Mp = (size_t)pl.Mp, Din = c->cfg.in_dim, Dout = c->cfg.out_dim;
   const bool split = c->compute == SF_COMPUTE_BF16X3;
   const int depth = c->cfg.depth;
@@ -474,23 +397,14 @@ extern "C" int sf_connector_forward(sf_connector* c, const float* feats_dev, int
   HIP_TRY(sf_launch_split(feats_dev, ws.x_hi, ws.x_lo, (size_t)pl.M * cfg.in_dim, s));
   const bf16_t* a_hi = ws.x_hi;
   const bf16_t* a_lo = ws.x_lo;
-  auto linear = [&](const ConnLinear& l, int M, int epi) {
-    SfGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr;
-    g.w_hi = l.w_hi; g.w_lo = split ? l.w_lo : nullptr;
-    g.bias = l.bias;
-    g.M = M; g.N = l.N; g.K = l.K; g.ldc = l.N;
-    g.epi = epi; g.act = 0; g.alpha = 1.f;      // act 0: erf GELU (nn.GELU() of the reference builder)
-    return g;
-  };
+  auto linear = [&](const SfDevLinear& l, int M, int epi) { return sf_linear_args(l, a_hi, a_lo, M, epi, 0, split); };      // act 0: erf GELU (nn.GELU() of the reference builder)
   for (int i = 0; i + 1 < depth; ++i) {
     SfGemmArgs g = linear(c->lin[i], (int)pl.M, SF_EPI_ACT_BF16);
     g.out_hi = ws.act_hi[i & 1]; g.out_lo = split ? ws.act_lo[i & 1] : nullptr;
     HIP_TRY(sf_launch_gemm(g, split, s));
     a_hi = ws.act_hi[i & 1]; a_lo = ws.act_lo[i & 1];
   }
-  const ConnLinear& last = c->lin[depth - 1];
+  const SfDevLinear& last = c->lin[depth - 1];
   if (pl.pool_first) {                   // role (a): P^2 -> P'^2 rows per frame in front of the last Linear
     SfConnPool q;
     memset(&q, 0, sizeof(q));

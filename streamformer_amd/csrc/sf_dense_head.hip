@@ -83,16 +83,6 @@ extern "C" size_t sf_dense_head_workspace_bytes(int M, int D, int I) {
   return dh_carve(nullptr, (size_t)M, (size_t)D, (size_t)I).bytes;
 }
 
-static SfGemmArgs dh_gemm(const bf16_t* a, const bf16_t* w, const float* bias, int M, int N, int K, int epi, float* out_f32, bf16_t* out_bf,
-                          const float* resid) {
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a_hi = a; g.w_hi = w; g.bias = bias;
-  g.M = M; g.N = N; g.K = K; g.epi = epi; g.alpha = 1.f; g.resid = resid;
-  g.out_f32 = out_f32; g.out_hi = epi == SF_EPI_RESID_F32 ? nullptr : out_bf; g.ldc = N;
-  return g;
-}
-
 extern "C" int sf_dense_head_forward(const float* x, int M, int D, int I, float eps, const float* const* params, float* out, void* workspace,
                                      size_t workspace_bytes, sf_stream stream) {
   int rc = dh_check("sf_dense_head_forward", M, D, I);
@@ -117,11 +107,11 @@ extern "C" int sf_dense_head_forward(const float* x, int M, int D, int I, float 
     b1 = w.b1;
   }
   HIP_TRY(sf_launch_split(x, w.xb, nullptr, (size_t)M * D, s));
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.xb, w.wv, params[DH_WV_B], M, D, D, SF_EPI_BF16, nullptr, w.a, nullptr), false, s));
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.a, w.vp, params[DH_VP_B], M, D, D, SF_EPI_F32, w.y, nullptr, nullptr), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.xb, w.wv, params[DH_WV_B], M, D, D, SF_EPI_BF16, nullptr, w.a, nullptr), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.a, w.vp, params[DH_VP_B], M, D, D, SF_EPI_F32, w.y, nullptr, nullptr), false, s));
   HIP_TRY(sf_launch_layernorm(w.y, params[DH_LN_G], params[DH_LN_B], nullptr, w.ln, nullptr, M, D, eps, s));
   {   // pre = ln fc1^T + b1, act = gelu(pre): one launch where the 256^2 kernel takes the shape
-    SfGemmArgs g = dh_gemm(w.ln, w.fc1, b1, M, Ip, D, SF_EPI_BF16, nullptr, w.pre, nullptr);
+    SfGemmArgs g = sf_train_gemm_args(w.ln, w.fc1, b1, M, Ip, D, SF_EPI_BF16, nullptr, w.pre, nullptr);
     g.aux_mode = 1; g.aux = w.act;
     if (sf_gemm256_aux_supported(g)) {
       HIP_TRY(sf_launch_gemm(g, false, s));
@@ -131,7 +121,7 @@ extern "C" int sf_dense_head_forward(const float* x, int M, int D, int I, float 
       HIP_TRY(sf_launch_gelu_fwd(w.pre, w.act, (size_t)M * Ip, s));
     }
   }
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.act, w.fc2, params[DH_FC2_B], M, D, Ip, SF_EPI_RESID_F32, out, nullptr, w.y), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.act, w.fc2, params[DH_FC2_B], M, D, Ip, SF_EPI_RESID_F32, out, nullptr, w.y), false, s));
   return SF_OK;
 }
 
@@ -161,7 +151,7 @@ extern "C" int sf_dense_head_backward(const float* d_out, int M, int D, int I, f
   // out = y + fc2(act)
   HIP_TRY(sf_launch_split(d_out, w.g_bf, nullptr, (size_t)M * D, s));
   {   // d_pre = (g fc2) * gelu'(pre)
-    SfGemmArgs g = dh_gemm(w.g_bf, w.fc2T, nullptr, M, Ip, D, SF_EPI_BF16, nullptr, w.d_wide, nullptr);
+    SfGemmArgs g = sf_train_gemm_args(w.g_bf, w.fc2T, nullptr, M, Ip, D, SF_EPI_BF16, nullptr, w.d_wide, nullptr);
     g.aux_mode = 2; g.aux = w.pre;
     if (sf_gemm256_aux_supported(g)) {
       HIP_TRY(sf_launch_gemm(g, false, s));
@@ -172,13 +162,13 @@ extern "C" int sf_dense_head_backward(const float* d_out, int M, int D, int I, f
     }
   }
   HIP_TRY(dh_wgrad(w, w.g_bf, D, w.act, Ip, M, D, I, grads[DH_FC2_W], grads[DH_FC2_B], s));
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.d_wide, w.fc1T, nullptr, M, D, Ip, SF_EPI_F32, w.d_ln, nullptr, nullptr), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.d_wide, w.fc1T, nullptr, M, D, Ip, SF_EPI_F32, w.d_ln, nullptr, nullptr), false, s));
   HIP_TRY(dh_wgrad(w, w.d_wide, Ip, w.ln, D, M, I, D, grads[DH_FC1_W], grads[DH_FC1_B], s));
   // d_y = d_out + dLayerNorm(y; d_ln), also as the bf16 operand of the next two products
   HIP_TRY(sf_launch_ln_bwd(w.y, w.d_ln, 0, params[DH_LN_G], d_out, w.d_y, w.g_bf, grads[DH_LN_G], grads[DH_LN_B], w.ln_partial, M, D, eps, s));
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.g_bf, w.vpT, nullptr, M, D, D, SF_EPI_BF16, nullptr, w.d_a, nullptr), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.g_bf, w.vpT, nullptr, M, D, D, SF_EPI_BF16, nullptr, w.d_a, nullptr), false, s));
   HIP_TRY(dh_wgrad(w, w.g_bf, D, w.a, D, M, D, D, grads[DH_VP_W], grads[DH_VP_B], s));
-  HIP_TRY(sf_launch_gemm(dh_gemm(w.d_a, w.wvT, nullptr, M, D, D, SF_EPI_F32, d_x, nullptr, nullptr), false, s));
+  HIP_TRY(sf_launch_gemm(sf_train_gemm_args(w.d_a, w.wvT, nullptr, M, D, D, SF_EPI_F32, d_x, nullptr, nullptr), false, s));
   HIP_TRY(dh_wgrad(w, w.d_a, D, w.xb, D, M, D, D, grads[DH_WV_W], grads[DH_WV_B], s));
   return SF_OK;
 }

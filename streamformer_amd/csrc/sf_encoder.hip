@@ -1,8 +1,7 @@
 // C-ABI implementation: handle, weight packing, and the launch schedule of the encoder forward
 // (reference TimesformerMultiTaskingModelSigLIP.forward, modeling:1299-1354; layer body :934-1004;
 // streaming copy vqa_enc:1316-1392).  See include/streamformer_hip.h for the contract.
-#include "sf_internal.h"
-#include "sf_common.h"
+#include "sf_handle.h"
 #include "sf_switches.h"
 #include "sf_pool_head.h"
 
@@ -34,36 +33,13 @@ int sf_set_err(int code, const char* fmt, ...) {
 #define set_err sf_set_err
 
 // ------------------------------------------------------------------------------------------------
-// host-side helpers
+// handle (weight staging, uploads and the common GEMM arguments: sf_weights.h, sf_handle.h)
 // ------------------------------------------------------------------------------------------------
-static inline uint16_t h_f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-static inline float h_bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-struct HostTensor {
-  std::vector<int64_t> shape;
-  std::vector<float> data;
-  size_t numel() const { return data.size(); }
+struct DevLinear : SfDevLinear {
+  const float* ln_s = nullptr;    // LN-folded variants only: s_n = sum_k bf16(W'[n,k])
+  const bf16_t* w_frag = nullptr; // t_qkv_f, bf16 mode: w_hi in MFMA-fragment order for sf_stream_fused.hip (SfStreamQkvArgs::w_frag)
 };
-
-struct DevLinear {          // y = x W^T + b ; W [N,K]
-  bf16_t* w_hi = nullptr;
-  bf16_t* w_lo = nullptr;
-  float* bias = nullptr;
-  float* ln_s = nullptr;    // LN-folded variants only: s_n = sum_k bf16(W'[n,k])
-  bf16_t* w_frag = nullptr; // t_qkv_f, bf16 mode: w_hi in MFMA-fragment order for sf_stream_fused.hip (SfStreamQkvArgs::w_frag)
-  int N = 0, K = 0;
-};
-struct DevLN { float* g = nullptr; float* b = nullptr; };
+using DevLN = SfDevLN;
 struct DevLayer {
   DevLN ln_t, ln_b, ln_a;
   DevLinear t_qkv, t_out, t_dense, t_fused, s_qkv, s_out, up, down;
@@ -76,12 +52,11 @@ struct sf_encoder {
   sf_config cfg;
   int device = 0;
   int N = 0, D = 0, I = 0, L = 0, Kp = 0, hd = 64;      // I, Kp: padded to multiples of 64 (see sf_create)
-  std::map<std::string, HostTensor> host;   // staged fp32 copies until finalize
-  std::map<std::string, std::vector<int64_t>> expected;
+  SfWeightStore weights;
   bool finalized = false;
   int compute = SF_COMPUTE_BF16;
   bool fused_temporal = false;
-  std::vector<void*> allocs;
+  SfDeviceAllocs dev;       // dev.uploaded: the bytes of the packed weights
   // device weights
   DevLinear patch;
   float* pos = nullptr;       // [N,D]
@@ -95,7 +70,6 @@ struct sf_encoder {
   float* head_u = nullptr;    // [16, D] fp32
   float* head_wv = nullptr;   // [D, D]
   float* head_bv = nullptr;   // [D]
-  size_t weight_bytes = 0;
   uint64_t generation = 0;    // process-unique id of this handle's current weight packing (bumped by every finalize)
   uint64_t fingerprint = 0;   // content hash of what that packing was made from (weights_fingerprint): travels with a parked stream
   SfPixelNorm pixel_norm = {{1.0f / 127.5f, 1.0f / 127.5f, 1.0f / 127.5f, 1.0f / 127.5f}, {-1.f, -1.f, -1.f, -1.f}};
@@ -170,7 +144,10 @@ static void build_expected(sf_encoder* e) {
   const sf_config& c = e->cfg;
   const int64_t D = c.hidden_size, I = c.intermediate_size, P = c.patch_size, C = c.num_channels;
   const int64_t N = e->N, T = c.num_frames;
-  auto& x = e->expected;
+  e->weights.prefix = "timesformer.";      // wrapper checkpoints (base_model_prefix, modeling:1073)
+  e->weights.accept_f16 = true;
+  e->weights.exact_shape = false;          // checkpoints carry e.g. the gating scalar as [] or [1], the tables with or without a leading 1
+  auto& x = e->weights.expected;
   x["embeddings.position_embeddings"] = {1, N, D};
   x["embeddings.time_embeddings"] = {1, T, D};
   x["embeddings.patch_embeddings.projection.weight"] = {D, C, P, P};
@@ -254,14 +231,9 @@ static uint64_t next_generation() {
   return ++g;
 }
 
-static void free_device(sf_encoder* e) {
-  for (void* p : e->allocs) (void)hipFree(p);
-  e->allocs.clear();
-}
-
 extern "C" void sf_destroy(sf_encoder* e) {
   if (!e) return;
-  free_device(e);
+  e->dev.free_all();
   delete e;
 }
 
@@ -271,39 +243,9 @@ extern "C" void sf_destroy(sf_encoder* e) {
 extern "C" int sf_load_tensor(sf_encoder* e, const char* key, const void* host_ptr, int dtype,
                               const int64_t* shape, int ndim) {
   if (!e || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return set_err(SF_ERR_INVALID, "sf_load_tensor: null argument");
-  std::string k(key);
-  if (k.rfind("timesformer.", 0) == 0) k = k.substr(12);   // wrapper checkpoints (base_model_prefix, modeling:1073)
-  auto it = e->expected.find(k);
-  if (it == e->expected.end()) return set_err(SF_ERR_UNKNOWN_KEY, "'%s' is not a weight of this model", key);
-  size_t n = 1, ne = 1;
-  for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
-  for (int64_t d : it->second) ne *= (size_t)d;
-  bool same = n == ne;
-  if (same && (int)it->second.size() == ndim)
-    for (int i = 0; i < ndim; ++i) same = same && it->second[i] == shape[i];
-  if (!same) return set_err(SF_ERR_INVALID, "'%s': shape mismatch (%zu elements given, %zu expected)", key, n, ne);
-  HostTensor t;
-  t.shape.assign(shape, shape + ndim);
-  t.data.resize(n);
-  switch (dtype) {
-    case SF_F32: memcpy(t.data.data(), host_ptr, n * 4); break;
-    case SF_F64: for (size_t i = 0; i < n; ++i) t.data[i] = (float)((const double*)host_ptr)[i]; break;
-    case SF_BF16: for (size_t i = 0; i < n; ++i) t.data[i] = h_bf2f(((const uint16_t*)host_ptr)[i]); break;
-    case SF_F16: {
-      const uint16_t* p = (const uint16_t*)host_ptr;
-      for (size_t i = 0; i < n; ++i) {
-        const uint32_t s = (p[i] >> 15) & 1, ex = (p[i] >> 10) & 31, m = p[i] & 1023;
-        float v;
-        if (ex == 0) v = ldexpf((float)m, -24);
-        else if (ex == 31) v = m ? NAN : INFINITY;
-        else v = ldexpf((float)(m | 1024), (int)ex - 25);
-        t.data[i] = s ? -v : v;
-      }
-      break;
-    }
-    default: return set_err(SF_ERR_INVALID, "unknown dtype %d", dtype);
-  }
-  e->host[k] = std::move(t);
+  std::string err;
+  const int rc = e->weights.load(key, host_ptr, dtype, shape, ndim, &err);
+  if (rc) return set_err(rc, "%s", err.c_str());
   e->finalized = false;
   return SF_OK;
 }
@@ -321,45 +263,16 @@ extern "C" int sf_set_pixel_normalization(sf_encoder* e, const float* mean, cons
 
 extern "C" int sf_missing_weights(sf_encoder* e) {
   if (!e) return set_err(SF_ERR_INVALID, "null handle");
-  int missing = 0;
-  std::string names;
-  for (auto& kv : e->expected)
-    if (!e->host.count(kv.first)) {
-      ++missing;
-      if (names.size() < 800) names += kv.first + " ";
-    }
-  if (missing) set_err(SF_ERR_STATE, "missing %d weights: %s", missing, names.c_str());
+  std::string err;
+  const int missing = e->weights.missing(&err);
+  if (missing) set_err(SF_ERR_STATE, "%s", err.c_str());
   return missing;
 }
 
-template <typename T>
-static int dev_upload(sf_encoder* e, const std::vector<T>& h, T** out) {
-  void* p = nullptr;
-  const size_t bytes = h.size() * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-  e->allocs.push_back(p);
-  if (bytes) HIP_TRY(hipMemcpy(p, h.data(), bytes, hipMemcpyHostToDevice));
-  e->weight_bytes += bytes;
-  *out = (T*)p;
-  return SF_OK;
-}
-
-static int upload_linear(sf_encoder* e, const std::vector<float>& w, const std::vector<float>* bias, int N,
-                         int K, DevLinear* out, bool force_split = false) {
-  std::vector<uint16_t> hi(w.size()), lo;
-  const bool split = force_split || e->compute == SF_COMPUTE_BF16X3;     // force_split: the pooling head's small Linears keep the lo plane in bf16 mode too
-  if (split) lo.resize(w.size());
-  for (size_t i = 0; i < w.size(); ++i) {
-    hi[i] = h_f2bf(w[i]);
-    if (split) lo[i] = h_f2bf(w[i] - h_bf2f(hi[i]));
-  }
-  int rc = dev_upload<uint16_t>(e, hi, &out->w_hi);
-  if (rc) return rc;
-  if (split && (rc = dev_upload<uint16_t>(e, lo, &out->w_lo))) return rc;
-  if (bias && (rc = dev_upload<float>(e, *bias, &out->bias))) return rc;
-  out->N = N;
-  out->K = K;
-  return SF_OK;
+// force_split: the pooling head's small Linears keep the lo plane in bf16 mode too
+static int upload_linear(sf_encoder* e, const std::vector<float>& w, const std::vector<float>* bias, int N, int K, DevLinear* out,
+                         bool force_split = false) {
+  return sf_upload_linear(e->dev, w, bias, N, K, N, force_split || e->compute == SF_COMPUTE_BF16X3, out);
 }
 
 // LayerNorm(gamma, beta) followed by Linear(W, b)  ==  rstd * (x W'^T - mean * s) + b'
@@ -375,8 +288,8 @@ static int upload_folded_linear(sf_encoder* e, const std::vector<float>& w, cons
       const float wv = w[(size_t)n * K + k];
       const float wg = (float)((double)wv * (double)gamma[k]);
       wf[(size_t)n * K + k] = wg;
-      const float hi = h_bf2f(h_f2bf(wg));
-      ss += (double)hi + (split ? (double)h_bf2f(h_f2bf(wg - hi)) : 0.0);
+      const float hi = sf_host_bf2f(sf_host_f2bf(wg));
+      ss += (double)hi + (split ? (double)sf_host_bf2f(sf_host_f2bf(wg - hi)) : 0.0);
       bb += (double)wv * (double)beta[k];
     }
     bf[n] = (float)bb;
@@ -391,16 +304,15 @@ static int upload_folded_linear(sf_encoder* e, const std::vector<float>& w, cons
     std::vector<uint16_t> fr((size_t)N * K);
     for (int n = 0; n < N; ++n)
       for (int k = 0; k < K; ++k)
-        fr[((((size_t)(n / 16) * NK + k / 32) * 64) + ((k % 32) / 8) * 16 + n % 16) * 8 + k % 8] = h_f2bf(wf[(size_t)n * K + k]);
-    if ((rc = dev_upload<uint16_t>(e, fr, &out->w_frag))) return rc;
+        fr[((((size_t)(n / 16) * NK + k / 32) * 64) + ((k % 32) / 8) * 16 + n % 16) * 8 + k % 8] = sf_host_f2bf(wf[(size_t)n * K + k]);
+    if ((rc = e->dev.upload(fr, &out->w_frag))) return rc;
   }
-  return dev_upload<float>(e, sn, &out->ln_s);
+  return e->dev.upload(sn, &out->ln_s);
 }
 
 static int upload_ln(sf_encoder* e, const std::string& p, DevLN* out) {
-  int rc = dev_upload<float>(e, e->host[p + ".weight"].data, &out->g);
-  if (rc) return rc;
-  return dev_upload<float>(e, e->host[p + ".bias"].data, &out->b);
+  SF_TRY(e->dev.upload(e->weights.data(p + ".weight"), &out->g));
+  return e->dev.upload(e->weights.data(p + ".bias"), &out->b);
 }
 
 // W += B A  (lora_b [out, r] x lora_a [r, in]); accumulate in double
@@ -425,7 +337,7 @@ static uint64_t weights_fingerprint(const sf_encoder* e, int merge_lora, int fus
   memcpy(cw, &e->cfg, sizeof(cw));
   for (uint32_t w : cw) h = mix(h, w);
   h = mix(h, (uint64_t)(merge_lora != 0) * 2 + (fuse_temporal_proj != 0));
-  for (const auto& kv : e->host) {
+  for (const auto& kv : e->weights.host) {
     for (char ch : kv.first) h = mix(h, (uint8_t)ch);
     const std::vector<float>& d = kv.second.data;
     h = mix(h, d.size());
@@ -449,18 +361,17 @@ static uint64_t weights_fingerprint(const sf_encoder* e, int merge_lora, int fus
 
 extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, int fuse_temporal_proj) {
   if (!e) return set_err(SF_ERR_INVALID, "null handle");
-  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
+  SF_TRY(sf_check_compute_mode(compute));
   if (sf_missing_weights(e)) return SF_ERR_STATE;
   if (e->cfg.add_lora_spatial && !merge_lora)
     return set_err(SF_ERR_INVALID, "un-merged LoRA execution is a training-time path; the inference forward needs merge_lora=1");
   HIP_TRY(hipSetDevice(e->device));
-  free_device(e);
-  e->weight_bytes = 0;
+  e->dev.free_all();
   e->compute = compute;
   e->fused_temporal = fuse_temporal_proj != 0;
   const int D = e->D, I = e->I, Ir = e->cfg.intermediate_size;
-  auto H = [&](const std::string& k) -> std::vector<float>& { return e->host[k].data; };
-  auto Hopt = [&](const std::string& k) -> std::vector<float>* { return e->host.count(k) ? &e->host[k].data : nullptr; };
+  auto H = [&](const std::string& k) -> std::vector<float>& { return e->weights.data(k); };
+  auto Hopt = [&](const std::string& k) -> std::vector<float>* { return e->weights.host.count(k) ? &e->weights.data(k) : nullptr; };
   // zero padding of a [rows, cols] matrix to [rows_p, cols_p] (intermediate_size -> I, C*P*P -> Kp); a no-op copy when nothing changes
   auto pad2 = [](const std::vector<float>& w, int rows, int cols, int rows_p, int cols_p) {
     if (rows == rows_p && cols == cols_p) return w;
@@ -473,25 +384,23 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
     if (b) std::copy(b->begin(), b->begin() + n, o.begin());
     return o;
   };
-  int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
   {
     const int Kr = e->cfg.num_channels * e->cfg.patch_size * e->cfg.patch_size;
     const std::vector<float> wp = pad2(H("embeddings.patch_embeddings.projection.weight"), D, Kr, D, e->Kp);
-    TRY(upload_linear(e, wp, Hopt("embeddings.patch_embeddings.projection.bias"), D, e->Kp, &e->patch));
+    SF_TRY(upload_linear(e, wp, Hopt("embeddings.patch_embeddings.projection.bias"), D, e->Kp, &e->patch));
   }
-  TRY(dev_upload<float>(e, H("embeddings.position_embeddings"), &e->pos));
-  TRY(dev_upload<float>(e, H("embeddings.time_embeddings"), &e->time_tab));
+  SF_TRY(e->dev.upload(H("embeddings.position_embeddings"), &e->pos));
+  SF_TRY(e->dev.upload(H("embeddings.time_embeddings"), &e->time_tab));
   e->layers.assign(e->L, DevLayer());
   for (int i = 0; i < e->L; ++i) {
     const std::string p = "encoder.layer." + std::to_string(i) + ".";
     DevLayer& l = e->layers[i];
     l.gate_tanh = std::tanh(H(p + "temporal_attention_gating")[0]);
-    TRY(upload_ln(e, p + "temporal_layernorm", &l.ln_t));
-    TRY(upload_ln(e, p + "layernorm_before", &l.ln_b));
-    TRY(upload_ln(e, p + "layernorm_after", &l.ln_a));
-    TRY(upload_linear(e, H(p + "temporal_attention.attention.qkv.weight"), Hopt(p + "temporal_attention.attention.qkv.bias"), 3 * D, D, &l.t_qkv));
-    TRY(upload_folded_linear(e, H(p + "temporal_attention.attention.qkv.weight"), Hopt(p + "temporal_attention.attention.qkv.bias"),
+    SF_TRY(upload_ln(e, p + "temporal_layernorm", &l.ln_t));
+    SF_TRY(upload_ln(e, p + "layernorm_before", &l.ln_b));
+    SF_TRY(upload_ln(e, p + "layernorm_after", &l.ln_a));
+    SF_TRY(upload_linear(e, H(p + "temporal_attention.attention.qkv.weight"), Hopt(p + "temporal_attention.attention.qkv.bias"), 3 * D, D, &l.t_qkv));
+    SF_TRY(upload_folded_linear(e, H(p + "temporal_attention.attention.qkv.weight"), Hopt(p + "temporal_attention.attention.qkv.bias"),
                              H(p + "temporal_layernorm.weight"), H(p + "temporal_layernorm.bias"), 3 * D, D, &l.t_qkv_f,
                              SF_LAB_SWITCH("SF_STREAM_QKV_FUSE") && e->compute == SF_COMPUTE_BF16 && D % 128 == 0 && D <= 768));
 #ifdef SF_LAB      // lab library only: the permuted copy for sf_gemm_qkv.hip's fused tile (profiles/r04_qkv_fused_ab.txt)
@@ -506,7 +415,7 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
         std::copy(w0.begin() + (size_t)src * D, w0.begin() + (size_t)(src + 1) * D, wp.begin() + (size_t)r * D);
         if (b0) bp[r] = (*b0)[src];
       }
-      TRY(upload_folded_linear(e, wp, b0 ? &bp : nullptr, H(p + "temporal_layernorm.weight"), H(p + "temporal_layernorm.bias"), 3 * D, D, &l.t_qkv_fp));
+      SF_TRY(upload_folded_linear(e, wp, b0 ? &bp : nullptr, H(p + "temporal_layernorm.weight"), H(p + "temporal_layernorm.bias"), 3 * D, D, &l.t_qkv_fp));
     }
 #endif
     if (e->fused_temporal) {
@@ -529,10 +438,10 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
         for (int j = 0; j < D; ++j) wf[(size_t)o * D + j] = (float)row[j];
         bf[o] = (float)bb;
       }
-      TRY(upload_linear(e, wf, &bf, D, D, &l.t_fused));
+      SF_TRY(upload_linear(e, wf, &bf, D, D, &l.t_fused));
     } else {
-      TRY(upload_linear(e, H(p + "temporal_attention.output.dense.weight"), Hopt(p + "temporal_attention.output.dense.bias"), D, D, &l.t_out));
-      TRY(upload_linear(e, H(p + "temporal_dense.weight"), Hopt(p + "temporal_dense.bias"), D, D, &l.t_dense));
+      SF_TRY(upload_linear(e, H(p + "temporal_attention.output.dense.weight"), Hopt(p + "temporal_attention.output.dense.bias"), D, D, &l.t_out));
+      SF_TRY(upload_linear(e, H(p + "temporal_dense.weight"), Hopt(p + "temporal_dense.bias"), D, D, &l.t_dense));
     }
     std::vector<float> wq = H(p + "attention.attention.qkv.weight");
     std::vector<float> wo = H(p + "attention.output.dense.weight");
@@ -540,21 +449,21 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
       merge_lora_into(wq, H(p + "attention.attention.qkv_lora_a.weight"), H(p + "attention.attention.qkv_lora_b.weight"), 3 * D, D, kLoraRank);
       merge_lora_into(wo, H(p + "attention.output.dense_lora_a.weight"), H(p + "attention.output.dense_lora_b.weight"), D, D, kLoraRank);
     }
-    TRY(upload_linear(e, wq, Hopt(p + "attention.attention.qkv.bias"), 3 * D, D, &l.s_qkv));
-    TRY(upload_folded_linear(e, wq, Hopt(p + "attention.attention.qkv.bias"), H(p + "layernorm_before.weight"),
+    SF_TRY(upload_linear(e, wq, Hopt(p + "attention.attention.qkv.bias"), 3 * D, D, &l.s_qkv));
+    SF_TRY(upload_folded_linear(e, wq, Hopt(p + "attention.attention.qkv.bias"), H(p + "layernorm_before.weight"),
                              H(p + "layernorm_before.bias"), 3 * D, D, &l.s_qkv_f));
     {
       const std::vector<float> wu = pad2(H(p + "intermediate.dense.weight"), Ir, D, I, D);
       const std::vector<float> bu = pad1(Hopt(p + "intermediate.dense.bias"), Ir, I);
       const std::vector<float> wd = pad2(H(p + "output.dense.weight"), D, Ir, D, I);
-      TRY(upload_folded_linear(e, wu, &bu, H(p + "layernorm_after.weight"), H(p + "layernorm_after.bias"), I, D, &l.up_f));
-      TRY(upload_linear(e, wo, Hopt(p + "attention.output.dense.bias"), D, D, &l.s_out));
-      TRY(upload_linear(e, wu, &bu, I, D, &l.up));
-      TRY(upload_linear(e, wd, Hopt(p + "output.dense.bias"), D, I, &l.down));
+      SF_TRY(upload_folded_linear(e, wu, &bu, H(p + "layernorm_after.weight"), H(p + "layernorm_after.bias"), I, D, &l.up_f));
+      SF_TRY(upload_linear(e, wo, Hopt(p + "attention.output.dense.bias"), D, D, &l.s_out));
+      SF_TRY(upload_linear(e, wu, &bu, I, D, &l.up));
+      SF_TRY(upload_linear(e, wd, Hopt(p + "output.dense.bias"), D, I, &l.down));
     }
   }
-  TRY(upload_ln(e, "post_layernorm", &e->post_ln));
-  TRY(upload_ln(e, "head.layernorm", &e->head_ln));
+  SF_TRY(upload_ln(e, "post_layernorm", &e->post_ln));
+  SF_TRY(upload_ln(e, "head.layernorm", &e->head_ln));
   {
     // nn.MultiheadAttention packed in_proj rows are [q; k; v] (modeling:1135-1137).  The query is
     // the learned probe only, identical for every frame: project and scale it once, in double.
@@ -581,26 +490,25 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
         for (int j = 0; j < hd; ++j) acc += (double)w[((size_t)D + h * hd + j) * D + d] * q[h * hd + j];
         const float v = (float)acc;
         uf[(size_t)h * D + d] = v;
-        uh[(size_t)h * D + d] = h_f2bf(v);
-        ul[(size_t)h * D + d] = h_f2bf(v - h_bf2f(uh[(size_t)h * D + d]));
+        uh[(size_t)h * D + d] = sf_host_f2bf(v);
+        ul[(size_t)h * D + d] = sf_host_f2bf(v - sf_host_bf2f(uh[(size_t)h * D + d]));
       }
-    TRY(dev_upload<uint16_t>(e, uh, &e->head_u_hi));
-    TRY(dev_upload<uint16_t>(e, ul, &e->head_u_lo));
-    TRY(dev_upload<float>(e, uf, &e->head_u));          // fp32 copy for the generic-width kernel (sf_launch_pool_generic)
+    SF_TRY(e->dev.upload(uh, &e->head_u_hi));
+    SF_TRY(e->dev.upload(ul, &e->head_u_lo));
+    SF_TRY(e->dev.upload(uf, &e->head_u));          // fp32 copy for the generic-width kernel (sf_launch_pool_generic)
     std::vector<float> wv(w.begin() + (size_t)2 * D * D, w.end());
     std::vector<float> bv(b.begin() + 2 * D, b.end());
-    TRY(dev_upload<float>(e, wv, &e->head_wv));
-    TRY(dev_upload<float>(e, bv, &e->head_bv));
+    SF_TRY(e->dev.upload(wv, &e->head_wv));
+    SF_TRY(e->dev.upload(bv, &e->head_bv));
   }
-  TRY(upload_linear(e, H("head.attention.out_proj.weight"), Hopt("head.attention.out_proj.bias"), D, D, &e->head_out, true));
+  SF_TRY(upload_linear(e, H("head.attention.out_proj.weight"), Hopt("head.attention.out_proj.bias"), D, D, &e->head_out, true));
   {
     const std::vector<float> w1 = pad2(H("head.mlp.fc1.weight"), Ir, D, I, D);
     const std::vector<float> b1 = pad1(Hopt("head.mlp.fc1.bias"), Ir, I);
     const std::vector<float> w2 = pad2(H("head.mlp.fc2.weight"), D, Ir, D, I);
-    TRY(upload_linear(e, w1, &b1, I, D, &e->head_fc1, true));
-    TRY(upload_linear(e, w2, Hopt("head.mlp.fc2.bias"), D, I, &e->head_fc2, true));
+    SF_TRY(upload_linear(e, w1, &b1, I, D, &e->head_fc1, true));
+    SF_TRY(upload_linear(e, w2, Hopt("head.mlp.fc2.bias"), D, I, &e->head_fc2, true));
   }
-#undef TRY
   e->finalized = true;
   e->generation = next_generation();   // caches created against an earlier packing are refused from here on
   e->fingerprint = weights_fingerprint(e, merge_lora, fuse_temporal_proj);
@@ -610,19 +518,6 @@ extern "C" int sf_finalize_weights(sf_encoder* e, int compute, int merge_lora, i
 // ------------------------------------------------------------------------------------------------
 // workspace carving
 // ------------------------------------------------------------------------------------------------
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 struct Workspace {
   float* resid; float* te_rows; float* ln_stats;
   float* embed_tab; bf16_t* patch_buf;  // pos + time table [T*N, D]; patch matrix [M, Kp] when the embedding GEMM runs on the
@@ -643,7 +538,7 @@ struct Workspace {
 
 static Workspace carve(const sf_encoder* e, void* base, int B, int T, int N, bool need_tqkv) {
   Workspace w;
-  Carver c(base);
+  SfCarver c(base);
   const size_t M = (size_t)B * T * N, F = (size_t)B * T;
   const size_t D = e->D, I = e->I;
   const bool acc = e->compute == SF_COMPUTE_BF16X3;
@@ -698,13 +593,7 @@ static Workspace carve(const sf_encoder* e, void* base, int B, int T, int N, boo
 // The fields every Linear of the forward shares; a call site then sets what is special about it (outputs, residual, LayerNorm
 // fold, row remap) by field name and launches with the same `split`.
 static SfGemmArgs linear_args(const sf_encoder* e, const DevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, bool split) {
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr;
-  g.w_hi = lin.w_hi; g.w_lo = split ? lin.w_lo : nullptr;
-  g.bias = lin.bias;
-  g.M = M; g.N = lin.N; g.K = lin.K; g.ldc = lin.N;
-  g.epi = epi; g.act = e->cfg.hidden_act; g.alpha = 1.f;
+  SfGemmArgs g = sf_linear_args(lin, a_hi, a_lo, M, epi, e->cfg.hidden_act, split);
   g.ln_eps = e->cfg.layer_norm_eps; g.ln_stats_wide = 1;
   return g;
 }
@@ -1875,7 +1764,7 @@ extern "C" int sf_op_linear(const float* x, const float* w, const float* b, cons
   if (workspace_bytes < sf_op_linear_workspace_bytes(M, N, K)) return set_err(SF_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const bool split = compute == SF_COMPUTE_BF16X3;
-  Carver c(workspace);
+  SfCarver c(workspace);
   bf16_t* xh = c.take<bf16_t>((size_t)M * K); bf16_t* xl = c.take<bf16_t>((size_t)M * K);
   bf16_t* wh = c.take<bf16_t>((size_t)N * K); bf16_t* wl = c.take<bf16_t>((size_t)N * K);
   bf16_t* oh = c.take<bf16_t>((size_t)M * N); bf16_t* ol = c.take<bf16_t>((size_t)M * N);
@@ -1911,7 +1800,7 @@ extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, 
   const bool acc = compute == SF_COMPUTE_BF16X3;
   const int D = heads * head_dim;
   const size_t rows = (size_t)groups * L;
-  Carver c(workspace);
+  SfCarver c(workspace);
   bf16_t* ch = c.take<bf16_t>(rows * D);
   bf16_t* cl = c.take<bf16_t>(rows * D);
   bf16_t* qb = c.take<bf16_t>(rows * 3 * D);
@@ -1993,7 +1882,7 @@ extern "C" int sf_bench_gemm(sf_encoder* e, int M, int which, int iters, void* w
   if (plain) which = which == 4 ? 3 : 1;
   const DevLinear* lin = which == 0 ? &l.up : which == 1 ? &l.down : which == 2 ? &l.s_qkv : &l.s_out;
   const bool acc = e->compute == SF_COMPUTE_BF16X3;
-  Carver c(workspace);
+  SfCarver c(workspace);
   bf16_t* ah = c.take<bf16_t>((size_t)M * lin->K);
   bf16_t* al = c.take<bf16_t>((size_t)M * lin->K);
   bf16_t* oh = c.take<bf16_t>((size_t)M * lin->N);
@@ -2040,7 +1929,7 @@ extern "C" int sf_bench_attention(sf_encoder* e, int B, int T, int which, int it
   const bool acc = e->compute == SF_COMPUTE_BF16X3;
   const int D = e->D, N = e->N, heads = e->cfg.num_attention_heads;
   const size_t M = (size_t)B * T * N, esz = acc ? 4 : 2;
-  Carver c(workspace);
+  SfCarver c(workspace);
   char* qkv = c.take<char>(M * 3 * D * esz);
   bf16_t* ch = c.take<bf16_t>(M * D);
   bf16_t* cl = c.take<bf16_t>(M * D);

@@ -1,0 +1,90 @@
+// Device side of a native model's handle, shared by sf_encoder, sf_text, sf_connector and sf_oad: the device allocations a finalize
+// owns, a Linear's bf16 planes and their upload, and the GEMM arguments every Linear starts from.  The host half is sf_weights.h.
+#pragma once
+#include "sf_common.h"
+#include "sf_internal.h"
+#include "sf_weights.h"
+
+#include <algorithm>
+#include <type_traits>
+
+#define SF_TRY(x)             \
+  do {                        \
+    const int rc_ = (x);      \
+    if (rc_) return rc_;      \
+  } while (0)
+
+static inline int sf_check_compute_mode(int compute) {
+  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return sf_set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
+  return SF_OK;
+}
+
+struct SfDevLinear {          // y = x W^T + b ; W [N, K] as bf16 planes (w_lo: the accurate mode's second plane, else null)
+  const bf16_t* w_hi = nullptr;
+  const bf16_t* w_lo = nullptr;
+  const float* bias = nullptr;
+  int N = 0, K = 0;
+};
+struct SfDevLN { const float* g = nullptr; const float* b = nullptr; };
+
+// what a finalize put on the device; freed together by the next finalize and by destroy
+struct SfDeviceAllocs {
+  std::vector<void*> ptrs;
+  size_t uploaded = 0;        // bytes copied by upload() since the last free_all()
+
+  int alloc(size_t bytes, void** out) {
+    HIP_TRY(hipMalloc(out, bytes));
+    ptrs.push_back(*out);
+    return SF_OK;
+  }
+  template <typename T, typename P>      // P: T or const T
+  int upload(const std::vector<T>& h, P** out) {
+    static_assert(std::is_same<typename std::remove_const<P>::type, T>::value, "upload: pointer type");
+    void* p = nullptr;
+    const size_t bytes = h.size() * sizeof(T);
+    SF_TRY(alloc(bytes ? bytes : 16, &p));
+    if (bytes) HIP_TRY(hipMemcpy(p, h.data(), bytes, hipMemcpyHostToDevice));
+    uploaded += bytes;
+    *out = (P*)p;
+    return SF_OK;
+  }
+  void free_all() {
+    for (void* p : ptrs) (void)hipFree(p);
+    ptrs.clear();
+    uploaded = 0;
+  }
+};
+
+// [N, K] weight (+ bias) -> bf16 hi (+ lo) planes on the device, uploaded in the order hi, lo, bias.  Np >= N zero-pads rows and bias
+// (out->N = Np); without want_lo, out->w_lo is null.  The rounding happens ONCE, here: no per-call conversion of the weights.
+static inline int sf_upload_linear(SfDeviceAllocs& dev, const std::vector<float>& w, const std::vector<float>* bias, int N, int K, int Np,
+                                   bool want_lo, SfDevLinear* out) {
+  const size_t np = (size_t)Np * K;
+  std::vector<uint16_t> hi(np, 0), lo(want_lo ? np : 0, 0);
+  sf_split_planes(w.data(), (size_t)N * K, want_lo, hi.data(), lo.data());
+  SF_TRY(dev.upload(hi, &out->w_hi));
+  out->w_lo = nullptr;
+  if (want_lo) SF_TRY(dev.upload(lo, &out->w_lo));
+  if (bias && Np == N) SF_TRY(dev.upload(*bias, &out->bias));
+  else if (bias) {
+    std::vector<float> b((size_t)Np, 0.f);
+    std::copy(bias->begin(), bias->end(), b.begin());
+    SF_TRY(dev.upload(b, &out->bias));
+  }
+  out->N = Np;
+  out->K = K;
+  return SF_OK;
+}
+
+// The fields every Linear's GEMM shares; a call site then sets what is special about it (outputs, residual, LayerNorm fold, row
+// remap) by field name and launches with the same `split`.
+static inline SfGemmArgs sf_linear_args(const SfDevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, int act, bool split) {
+  SfGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr;
+  g.w_hi = lin.w_hi; g.w_lo = split ? lin.w_lo : nullptr;
+  g.bias = lin.bias;
+  g.M = M; g.N = lin.N; g.K = lin.K; g.ldc = lin.N;
+  g.epi = epi; g.act = act; g.alpha = 1.f;
+  return g;
+}

@@ -27,14 +27,7 @@
 // never changes while it ages, only its positional addend does.  The state keeps W_k x | W_v x per stream in a ring; a step projects
 // only the new sample.  What does not depend on the input is computed once in sf_oad_finalize: the stage-0 queries' self-attention +
 // norm1 (tgt0), their q projection (q0), and k_pos | v_pos.
-#include "sf_common.h"
-#include "sf_internal.h"
-
-#include <cmath>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include "sf_handle.h"
 
 typedef __attribute__((ext_vector_type(4))) float of4_t;
 
@@ -332,47 +325,19 @@ static hipError_t oad_launch_rows(const float* src, float* dst, bf16_t* hi, bf16
 // handle
 // ------------------------------------------------------------------------------------------------
 namespace {
-struct OadLinear { const bf16_t* w_hi = nullptr; const bf16_t* w_lo = nullptr; const float* bias = nullptr; int N = 0, K = 0; };
-struct OadLN { float* g = nullptr; float* b = nullptr; };
 struct OadLayer {
   bool decoder = false;
-  OadLinear self_in, self_out, cross_q, cross_kv, cross_out, lin1, lin2;
-  OadLN n1, n2, n3;
+  SfDevLinear self_in, self_out, cross_q, cross_kv, cross_out, lin1, lin2;
+  SfDevLN n1, n2, n3;
 };
 struct OadModule {
   int queries = -1;                    // -1: encoder layers
   std::vector<OadLayer> layers;
   bool norm = false;
-  OadLN fn;
-  float* qw = nullptr;                 // enc_queries.j.weight [queries, d]
+  SfDevLN fn;
+  const float* qw = nullptr;           // enc_queries.j.weight [queries, d]
 };
-struct OadHost { std::vector<float> data; };
 struct OadAct { float* f = nullptr; bf16_t* hi = nullptr; bf16_t* lo = nullptr; };      // an activation [rows, d]: fp32 + the GEMM operand planes
-
-inline uint16_t o_f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline float o_bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-struct OadCarver {
-  char* base;
-  size_t off = 0;
-  explicit OadCarver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
 struct OadWorkspace {
   OadAct a[3];                         // rotating activations [R, d]
   bf16_t *in_hi, *in_lo;               // split inputs [R, d_in]
@@ -387,16 +352,15 @@ struct sf_oad {
   sf_oad_config cfg;
   int device = 0;
   int d = 0, hd = 0, Cp = 0, Q0 = 0, maxT = 0;      // Cp: classes padded to 16 columns; maxT: longest sequence of any stage
-  std::map<std::string, OadHost> host;
-  std::map<std::string, std::vector<int64_t>> expected;
+  SfWeightStore weights;
   bool finalized = false;
   int compute = SF_COMPUTE_BF16;
-  std::vector<void*> allocs;
-  OadLinear fh_long, fh_work, cls;
-  OadLN fh_long_ln, fh_work_ln;
+  SfDeviceAllocs dev;
+  SfDevLinear fh_long, fh_work, cls;
+  SfDevLN fh_long_ln, fh_work_ln;
   std::vector<OadModule> enc;
   OadModule dec;
-  float* pe = nullptr;                 // [L + W, d]
+  const float* pe = nullptr;           // [L + W, d]
   float* pos_kv = nullptr;             // [L, 2d]: k_pos | v_pos of stage 0
   OadAct tgt0;                         // [Q0, d] stage-0 queries after self-attention + norm1
   float* q0 = nullptr;                 // [Q0, d] their q projection
@@ -412,7 +376,7 @@ struct sf_oad_state {
 
 static void oad_expect_layer(sf_oad* h, const std::string& p, bool decoder) {
   const int64_t d = h->d, F = h->cfg.ffn;
-  auto& e = h->expected;
+  auto& e = h->weights.expected;
   for (const char* a : {"self_attn.", "multihead_attn."}) {
     if (!decoder && a[0] == 'm') continue;
     e[p + a + "in_proj_weight"] = {3 * d, d}; e[p + a + "in_proj_bias"] = {3 * d};
@@ -454,7 +418,9 @@ extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out)
   h->Q0 = c.enc_queries[0];
   h->maxT = c.long_samples > c.work_samples ? c.long_samples : c.work_samples;
   const int64_t d = h->d;
-  auto& e = h->expected;
+  h->weights.noun = "detector";
+  h->weights.dtype_msg = "sf_oad_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
+  auto& e = h->weights.expected;
   if (c.linear_enabled)
     for (const char* fh : {"feature_head_long.", "feature_head_work."}) {
       const std::string p = std::string(fh) + "visual_linear.";
@@ -479,8 +445,7 @@ extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out)
 }
 
 static void oad_free_device(sf_oad* h) {
-  for (void* p : h->allocs) (void)hipFree(p);
-  h->allocs.clear();
+  h->dev.free_all();
   h->enc.clear();
   h->dec = OadModule();
 }
@@ -493,79 +458,31 @@ extern "C" void sf_oad_destroy(sf_oad* h) {
 
 extern "C" int sf_oad_load_tensor(sf_oad* h, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
   if (!h || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_oad_load_tensor: null argument");
-  const std::string k(key);
-  auto it = h->expected.find(k);
-  if (it == h->expected.end()) return sf_set_err(SF_ERR_UNKNOWN_KEY, "'%s' is not a weight of this detector", key);
-  size_t n = 1;
-  if (k == "pos_encoding.pe") {      // the reference's buffer [max_len, 1, d]: the first L + W rows are kept
-    const bool ok = (ndim == 2 || (ndim == 3 && shape[1] == 1)) && shape[ndim - 1] == h->d && shape[0] >= it->second[0];
-    if (!ok) return sf_set_err(SF_ERR_INVALID, "'%s': [rows >= %lld, d_model] or [rows, 1, d_model] expected", key, (long long)it->second[0]);
-    n = (size_t)it->second[0] * h->d;
+  std::string err;
+  int rc;
+  if (!strcmp(key, "pos_encoding.pe")) {      // the reference's buffer [max_len, 1, d]: the first L + W rows are kept
+    const int64_t rows = h->weights.expected.at(key)[0];
+    const bool ok = (ndim == 2 || (ndim == 3 && shape[1] == 1)) && shape[ndim - 1] == h->d && shape[0] >= rows;
+    if (!ok) return sf_set_err(SF_ERR_INVALID, "'%s': [rows >= %lld, d_model] or [rows, 1, d_model] expected", key, (long long)rows);
+    rc = h->weights.stage(key, host_ptr, dtype, (size_t)rows * h->d, shape, ndim, &err);
   } else {
-    bool same = (int)it->second.size() == ndim;
-    for (int i = 0; i < ndim; ++i) { n *= (size_t)shape[i]; same = same && it->second[i] == shape[i]; }
-    if (!same) return sf_set_err(SF_ERR_INVALID, "'%s': shape mismatch", key);
+    rc = h->weights.load(key, host_ptr, dtype, shape, ndim, &err);
   }
-  OadHost t;
-  t.data.resize(n);
-  switch (dtype) {
-    case SF_F32: memcpy(t.data.data(), host_ptr, n * 4); break;
-    case SF_F64: for (size_t i = 0; i < n; ++i) t.data[i] = (float)((const double*)host_ptr)[i]; break;
-    case SF_BF16: for (size_t i = 0; i < n; ++i) t.data[i] = o_bf2f(((const uint16_t*)host_ptr)[i]); break;
-    default: return sf_set_err(SF_ERR_INVALID, "sf_oad_load_tensor: dtype %d unsupported (fp32, fp64, bf16)", dtype);
-  }
-  h->host[k] = std::move(t);
+  if (rc) return sf_set_err(rc, "%s", err.c_str());
   h->finalized = false;
   return SF_OK;
 }
 
 extern "C" int sf_oad_missing_weights(sf_oad* h) {
   if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  int missing = 0;
-  std::string names;
-  for (auto& kv : h->expected)
-    if (!h->host.count(kv.first)) {
-      ++missing;
-      if (names.size() < 800) names += kv.first + " ";
-    }
-  if (missing) sf_set_err(SF_ERR_STATE, "missing %d weights: %s", missing, names.c_str());
+  std::string err;
+  const int missing = h->weights.missing(&err);
+  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
   return missing;
 }
 
-template <typename T>
-static int oad_upload(sf_oad* h, const std::vector<T>& v, T** out) {
-  void* p = nullptr;
-  const size_t bytes = v.size() * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-  h->allocs.push_back(p);
-  if (bytes) HIP_TRY(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
-  *out = (T*)p;
-  return SF_OK;
-}
-
-// [N, K] weight (+ bias) -> bf16 hi (+ lo) planes; rows zero-padded to Np
-static int oad_upload_linear(sf_oad* h, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int Np, OadLinear* out) {
-  const bool split = h->compute == SF_COMPUTE_BF16X3;
-  std::vector<uint16_t> hi((size_t)Np * K, 0), lo;
-  if (split) lo.assign((size_t)Np * K, 0);
-  for (size_t i = 0; i < (size_t)N * K; ++i) {
-    hi[i] = o_f2bf(w[i]);
-    if (split) lo[i] = o_f2bf(w[i] - o_bf2f(hi[i]));
-  }
-  std::vector<float> b((size_t)Np, 0.f);
-  std::copy(bias.begin(), bias.end(), b.begin());
-  uint16_t *dh = nullptr, *dl = nullptr;
-  float* db = nullptr;
-  int rc = oad_upload<uint16_t>(h, hi, &dh);
-  if (rc) return rc;
-  if (split && (rc = oad_upload<uint16_t>(h, lo, &dl))) return rc;
-  if ((rc = oad_upload<float>(h, b, &db))) return rc;
-  out->w_hi = dh; out->w_lo = dl; out->bias = db; out->N = Np; out->K = K;
-  return SF_OK;
-}
-
-static OadLinear oad_rows_of(const OadLinear& l, int row0, int rows, bool with_bias) {
-  OadLinear v = l;
+static SfDevLinear oad_rows_of(const SfDevLinear& l, int row0, int rows, bool with_bias) {
+  SfDevLinear v = l;
   v.w_hi = l.w_hi + (size_t)row0 * l.K;
   v.w_lo = l.w_lo ? l.w_lo + (size_t)row0 * l.K : nullptr;
   v.bias = with_bias ? l.bias + row0 : nullptr;
@@ -573,38 +490,40 @@ static OadLinear oad_rows_of(const OadLinear& l, int row0, int rows, bool with_b
   return v;
 }
 
-static int oad_upload_ln(sf_oad* h, const std::string& p, OadLN* ln) {
-  int rc = oad_upload<float>(h, h->host[p + "weight"].data, &ln->g);
-  return rc ? rc : oad_upload<float>(h, h->host[p + "bias"].data, &ln->b);
+static int oad_upload_ln(sf_oad* h, const std::string& p, SfDevLN* ln) {
+  SF_TRY(h->dev.upload(h->weights.data(p + "weight"), &ln->g));
+  return h->dev.upload(h->weights.data(p + "bias"), &ln->b);
+}
+
+// [N, K] weight + bias -> the planes of the handle's compute mode; rows zero-padded to Np
+static int oad_upload_linear(sf_oad* h, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int Np, SfDevLinear* out) {
+  return sf_upload_linear(h->dev, w, &bias, N, K, Np, h->compute == SF_COMPUTE_BF16X3, out);
 }
 
 static int oad_upload_layer(sf_oad* h, const std::string& p, bool decoder, bool stage0, OadLayer* l) {
   const int d = h->d, F = h->cfg.ffn;
-  auto H = [&](const std::string& k) -> std::vector<float>& { return h->host[p + k].data; };
-  int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
+  auto H = [&](const std::string& k) -> std::vector<float>& { return h->weights.data(p + k); };
   l->decoder = decoder;
-  TRY(oad_upload_linear(h, H("self_attn.in_proj_weight"), H("self_attn.in_proj_bias"), 3 * d, d, 3 * d, &l->self_in));
-  TRY(oad_upload_linear(h, H("self_attn.out_proj.weight"), H("self_attn.out_proj.bias"), d, d, d, &l->self_out));
+  SF_TRY(oad_upload_linear(h, H("self_attn.in_proj_weight"), H("self_attn.in_proj_bias"), 3 * d, d, 3 * d, &l->self_in));
+  SF_TRY(oad_upload_linear(h, H("self_attn.out_proj.weight"), H("self_attn.out_proj.bias"), d, d, d, &l->self_out));
   if (decoder) {
-    OadLinear in;
-    TRY(oad_upload_linear(h, H("multihead_attn.in_proj_weight"), H("multihead_attn.in_proj_bias"), 3 * d, d, 3 * d, &in));
+    SfDevLinear in;
+    SF_TRY(oad_upload_linear(h, H("multihead_attn.in_proj_weight"), H("multihead_attn.in_proj_bias"), 3 * d, d, 3 * d, &in));
     l->cross_q = oad_rows_of(in, 0, d, true);
     l->cross_kv = oad_rows_of(in, d, 2 * d, !stage0);      // stage 0: the bias belongs to k_pos | v_pos
-    TRY(oad_upload_linear(h, H("multihead_attn.out_proj.weight"), H("multihead_attn.out_proj.bias"), d, d, d, &l->cross_out));
+    SF_TRY(oad_upload_linear(h, H("multihead_attn.out_proj.weight"), H("multihead_attn.out_proj.bias"), d, d, d, &l->cross_out));
   }
-  TRY(oad_upload_linear(h, H("linear1.weight"), H("linear1.bias"), F, d, F, &l->lin1));
-  TRY(oad_upload_linear(h, H("linear2.weight"), H("linear2.bias"), d, F, d, &l->lin2));
-  TRY(oad_upload_ln(h, p + "norm1.", &l->n1));
-  TRY(oad_upload_ln(h, p + "norm2.", &l->n2));
-  if (decoder) TRY(oad_upload_ln(h, p + "norm3.", &l->n3));
-#undef TRY
+  SF_TRY(oad_upload_linear(h, H("linear1.weight"), H("linear1.bias"), F, d, F, &l->lin1));
+  SF_TRY(oad_upload_linear(h, H("linear2.weight"), H("linear2.bias"), d, F, d, &l->lin2));
+  SF_TRY(oad_upload_ln(h, p + "norm1.", &l->n1));
+  SF_TRY(oad_upload_ln(h, p + "norm2.", &l->n2));
+  if (decoder) SF_TRY(oad_upload_ln(h, p + "norm3.", &l->n3));
   return SF_OK;
 }
 
 static OadWorkspace oad_carve(const sf_oad* h, void* base, int n) {
   OadWorkspace w;
-  OadCarver c(base);
+  SfCarver c(base);
   const size_t R = (size_t)n * h->maxT, d = h->d, F = h->cfg.ffn;
   for (int i = 0; i < 3; ++i) { w.a[i].f = c.take<float>(R * d); w.a[i].hi = c.take<bf16_t>(R * d); w.a[i].lo = c.take<bf16_t>(R * d); }
   w.in_hi = c.take<bf16_t>(R * h->cfg.d_in); w.in_lo = c.take<bf16_t>(R * h->cfg.d_in);
@@ -626,20 +545,14 @@ struct OadRun {
   hipStream_t s;
   bool acc;
 
-  int gemm(const OadLinear& l, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, float* out_f32, bf16_t* out_hi, bf16_t* out_lo) {
-    SfGemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.a_hi = a_hi; g.a_lo = acc ? a_lo : nullptr;
-    g.w_hi = l.w_hi; g.w_lo = acc ? l.w_lo : nullptr;
-    g.bias = l.bias;
-    g.M = M; g.N = l.N; g.K = l.K; g.ldc = l.N;
-    g.epi = epi; g.act = h->cfg.act; g.alpha = 1.f;
+  int gemm(const SfDevLinear& l, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, float* out_f32, bf16_t* out_hi, bf16_t* out_lo) {
+    SfGemmArgs g = sf_linear_args(l, a_hi, a_lo, M, epi, h->cfg.act, acc);
     g.out_f32 = out_f32; g.out_hi = out_hi; g.out_lo = acc ? out_lo : nullptr;
     HIP_TRY(sf_launch_gemm(g, acc, s));
     return SF_OK;
   }
   // y = LN(x + r[row % r_mod]) -> fp32 + planes (y.f may be r)
-  int add_ln(const float* x, const float* r, int r_mod, const OadLN& ln, const OadAct& y, int rows) {
+  int add_ln(const float* x, const float* r, int r_mod, const SfDevLN& ln, const OadAct& y, int rows) {
     SfOadRow p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.r = r; p.r_mod = r_mod; p.gamma = ln.g; p.beta = ln.b; p.eps = h->cfg.eps;
@@ -682,14 +595,14 @@ struct OadRun {
     return add_ln(ws.tmp, x.f, 0, l.n2, x, M);
   }
   // x = LN(x + linear2(act(linear1(x))))
-  int ffn_block(const OadLayer& l, const OadLN& ln, const OadAct& x, int M) {
+  int ffn_block(const OadLayer& l, const SfDevLN& ln, const OadAct& x, int M) {
     int rc;
     if ((rc = gemm(l.lin1, x.hi, x.lo, M, SF_EPI_ACT_BF16, nullptr, ws.mid_hi, ws.mid_lo))) return rc;
     if ((rc = gemm(l.lin2, ws.mid_hi, ws.mid_lo, M, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
     return add_ln(ws.tmp, x.f, 0, ln, x, M);
   }
   // the module's final norm, out of place on the encoder's LayerNorm kernel
-  int final_norm(const OadLN& ln, const OadAct& x, const OadAct& y, int M) {
+  int final_norm(const SfDevLN& ln, const OadAct& x, const OadAct& y, int M) {
     HIP_TRY(sf_launch_layernorm(x.f, ln.g, ln.b, y.f, y.hi, acc ? y.lo : nullptr, M, h->d, h->cfg.eps, s));
     return SF_OK;
   }
@@ -699,21 +612,19 @@ struct OadRun {
 // Makes the handle's device current and leaves it so, as the other handles' finalize do.
 extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
   if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return sf_set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
+  SF_TRY(sf_check_compute_mode(compute));
   if (sf_oad_missing_weights(h)) return SF_ERR_STATE;
   HIP_TRY(hipSetDevice(h->device));
   oad_free_device(h);
   h->compute = compute;
   const sf_oad_config& c = h->cfg;
   const int d = h->d, L = c.long_samples, Q0 = h->Q0;
-  auto H = [&](const std::string& k) -> std::vector<float>& { return h->host[k].data; };
-  int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
+  auto H = [&](const std::string& k) -> std::vector<float>& { return h->weights.data(k); };
   if (c.linear_enabled) {
-    TRY(oad_upload_linear(h, H("feature_head_long.visual_linear.0.weight"), H("feature_head_long.visual_linear.0.bias"), d, c.d_in, d, &h->fh_long));
-    TRY(oad_upload_linear(h, H("feature_head_work.visual_linear.0.weight"), H("feature_head_work.visual_linear.0.bias"), d, c.d_in, d, &h->fh_work));
-    TRY(oad_upload_ln(h, "feature_head_long.visual_linear.1.", &h->fh_long_ln));
-    TRY(oad_upload_ln(h, "feature_head_work.visual_linear.1.", &h->fh_work_ln));
+    SF_TRY(oad_upload_linear(h, H("feature_head_long.visual_linear.0.weight"), H("feature_head_long.visual_linear.0.bias"), d, c.d_in, d, &h->fh_long));
+    SF_TRY(oad_upload_linear(h, H("feature_head_work.visual_linear.0.weight"), H("feature_head_work.visual_linear.0.bias"), d, c.d_in, d, &h->fh_work));
+    SF_TRY(oad_upload_ln(h, "feature_head_long.visual_linear.1.", &h->fh_long_ln));
+    SF_TRY(oad_upload_ln(h, "feature_head_work.visual_linear.1.", &h->fh_work_ln));
   }
   h->enc.assign(c.enc_modules, OadModule());
   for (int j = 0; j < c.enc_modules; ++j) {
@@ -721,35 +632,34 @@ extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
     const std::string p = "enc_modules." + std::to_string(j) + ".";
     m.queries = c.enc_queries[j];
     m.norm = c.enc_norm[j] != 0;
-    if (m.queries > 0) TRY(oad_upload<float>(h, H("enc_queries." + std::to_string(j) + ".weight"), &m.qw));
+    if (m.queries > 0) SF_TRY(h->dev.upload(H("enc_queries." + std::to_string(j) + ".weight"), &m.qw));
     m.layers.assign(c.enc_layers[j], OadLayer());
-    for (int l = 0; l < c.enc_layers[j]; ++l) TRY(oad_upload_layer(h, p + "layers." + std::to_string(l) + ".", m.queries > 0, j == 0, &m.layers[l]));
-    if (m.norm) TRY(oad_upload_ln(h, p + "norm.", &m.fn));
+    for (int l = 0; l < c.enc_layers[j]; ++l) SF_TRY(oad_upload_layer(h, p + "layers." + std::to_string(l) + ".", m.queries > 0, j == 0, &m.layers[l]));
+    if (m.norm) SF_TRY(oad_upload_ln(h, p + "norm.", &m.fn));
   }
   h->dec.norm = c.dec_norm != 0;
   h->dec.layers.assign(c.dec_layers, OadLayer());
-  for (int l = 0; l < c.dec_layers; ++l) TRY(oad_upload_layer(h, "dec_modules.layers." + std::to_string(l) + ".", true, false, &h->dec.layers[l]));
-  if (h->dec.norm) TRY(oad_upload_ln(h, "dec_modules.norm.", &h->dec.fn));
-  TRY(oad_upload_linear(h, H("classifier.weight"), H("classifier.bias"), c.classes, d, h->Cp, &h->cls));
-  TRY(oad_upload<float>(h, H("pos_encoding.pe"), &h->pe));
+  for (int l = 0; l < c.dec_layers; ++l) SF_TRY(oad_upload_layer(h, "dec_modules.layers." + std::to_string(l) + ".", true, false, &h->dec.layers[l]));
+  if (h->dec.norm) SF_TRY(oad_upload_ln(h, "dec_modules.norm.", &h->dec.fn));
+  SF_TRY(oad_upload_linear(h, H("classifier.weight"), H("classifier.bias"), c.classes, d, h->Cp, &h->cls));
+  SF_TRY(h->dev.upload(H("pos_encoding.pe"), &h->pe));
   // ---- what does not depend on the input: k_pos | v_pos = W_kv pe[:L] + b_kv; tgt0 = norm1(queries + self_attn(queries)); q0 = W_q tgt0 + b_q ----
   {
-    auto dev = [&](size_t bytes, void** p) -> int { HIP_TRY(hipMalloc(p, bytes)); h->allocs.push_back(*p); return SF_OK; };
-    TRY(dev((size_t)L * 2 * d * 4, (void**)&h->pos_kv));
-    TRY(dev((size_t)Q0 * d * 4, (void**)&h->tgt0.f));
-    TRY(dev((size_t)Q0 * d * 2, (void**)&h->tgt0.hi));
-    TRY(dev((size_t)Q0 * d * 2, (void**)&h->tgt0.lo));
-    TRY(dev((size_t)Q0 * d * 4, (void**)&h->q0));
+    SF_TRY(h->dev.alloc((size_t)L * 2 * d * 4, (void**)&h->pos_kv));
+    SF_TRY(h->dev.alloc((size_t)Q0 * d * 4, (void**)&h->tgt0.f));
+    SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.hi));
+    SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.lo));
+    SF_TRY(h->dev.alloc((size_t)Q0 * d * 4, (void**)&h->q0));
     void* wsp = nullptr;
     const size_t bytes = oad_carve(h, nullptr, 1).bytes;
     HIP_TRY(hipMalloc(&wsp, bytes));
     OadRun r{h, oad_carve(h, wsp, 1), (hipStream_t)0, compute == SF_COMPUTE_BF16X3};
     const OadLayer& l0 = h->enc[0].layers[0];
-    rc = SF_OK;
+    int rc = SF_OK;
     do {
       hipError_t e;
       if ((e = sf_launch_split(h->pe, r.ws.a[0].hi, r.ws.a[0].lo, (size_t)L * d, r.s)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
-      OadLinear kvb = l0.cross_kv;
+      SfDevLinear kvb = l0.cross_kv;
       kvb.bias = l0.cross_q.bias + d;      // the k | v rows of in_proj_bias
       if ((rc = r.gemm(kvb, r.ws.a[0].hi, r.ws.a[0].lo, L, SF_EPI_F32, h->pos_kv, nullptr, nullptr))) break;
       SfOadRows t;
@@ -764,7 +674,6 @@ extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
     if (rc) return rc;
     HIP_TRY(es);
   }
-#undef TRY
   h->finalized = true;
   return SF_OK;
 }
@@ -869,7 +778,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
   hipStream_t s = r.s;
   int rc;
   OadAct x = ws.a[0], mem = ws.a[1], spare = ws.a[2];
-  auto row_head = [&](const float* in, const OadLN* ln, const float* pe, int pe_mod, const OadAct& y, bool want_f32, int rows) {
+  auto row_head = [&](const float* in, const SfDevLN* ln, const float* pe, int pe_mod, const OadAct& y, bool want_f32, int rows) {
     SfOadRow p;
     memset(&p, 0, sizeof(p));
     p.x = in; p.eps = c.eps; p.rows = rows; p.D = d;

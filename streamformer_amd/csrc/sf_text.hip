@@ -26,14 +26,7 @@
 //
 // Unmasked calls run the same attention kernel (key_mask = null): sf_launch_spatial_attention rounds q / k / v to bf16 in the bf16 mode at
 // head_dim 64, which is not this kernel's fp32 contract, so routing there would make the result depend on whether a mask was passed.
-#include "sf_common.h"
-#include "sf_internal.h"
-
-#include <cmath>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include "sf_handle.h"
 
 typedef __attribute__((ext_vector_type(4))) float tf4_t;
 
@@ -311,51 +304,20 @@ static hipError_t text_launch_pool(const float* x, int B, int L, int D, const fl
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
-namespace {
-struct TextLinear { bf16_t* w_hi = nullptr; bf16_t* w_lo = nullptr; float* bias = nullptr; int N = 0, K = 0; };
-struct TextLN { float* g = nullptr; float* b = nullptr; };
-struct TextLayer { TextLN ln1, ln2; TextLinear qkv, out, fc1, fc2; };
-struct TextHost { std::vector<int64_t> shape; std::vector<float> data; };
-
-inline uint16_t t_f2bf(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline float t_bf2f(uint16_t b) {
-  uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-struct TextCarver {
-  char* base;
-  size_t off = 0;
-  explicit TextCarver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-}  // namespace
+struct TextLayer { SfDevLN ln1, ln2; SfDevLinear qkv, out, fc1, fc2; };
 
 struct sf_text {
   sf_text_config cfg;
   int device = 0;
   int D = 0, I = 0, hd = 0;                   // I: intermediate_size padded to a multiple of 64 (zero weights, act(0) = 0)
-  std::map<std::string, TextHost> host;       // staged fp32 copies until finalize; q / k / v arrive separately and are packed there
-  std::map<std::string, std::vector<int64_t>> expected;
+  SfWeightStore weights;                      // q / k / v arrive separately and are packed at finalize
   bool finalized = false;
   int compute = SF_COMPUTE_BF16;
-  std::vector<void*> allocs;
-  float* tok = nullptr; float* pos = nullptr;
+  SfDeviceAllocs dev;
+  const float* tok = nullptr; const float* pos = nullptr;
   std::vector<TextLayer> layers;
-  TextLN final_ln;
-  float* head_w = nullptr; float* head_b = nullptr;      // fp32 [P, D], [P]
+  SfDevLN final_ln;
+  const float* head_w = nullptr; const float* head_b = nullptr;      // fp32 [P, D], [P]
 };
 
 struct TextWorkspace {
@@ -366,7 +328,7 @@ struct TextWorkspace {
 
 static TextWorkspace text_carve(const sf_text* t, void* base, int B, int L) {
   TextWorkspace w;
-  TextCarver c(base);
+  SfCarver c(base);
   const size_t M = (size_t)B * L, D = t->D, I = t->I;
   w.resid = c.take<float>(M * D);
   w.qkv = c.take<float>(M * 3 * D);
@@ -381,7 +343,10 @@ static TextWorkspace text_carve(const sf_text* t, void* base, int B, int L) {
 static void text_expected(sf_text* t) {
   const sf_text_config& c = t->cfg;
   const int64_t D = c.hidden, I = c.intermediate;
-  auto& e = t->expected;
+  t->weights.noun = "text model";
+  t->weights.prefix = "text_model.";
+  t->weights.dtype_msg = "sf_text_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
+  auto& e = t->weights.expected;
   e["embeddings.token_embedding.weight"] = {c.vocab, D};
   e["embeddings.position_embedding.weight"] = {c.positions, D};
   for (int i = 0; i < c.layers; ++i) {
@@ -426,101 +391,48 @@ extern "C" int sf_text_create(const sf_text_config* cfg, int device, sf_text** o
   return SF_OK;
 }
 
-static void text_free_device(sf_text* t) {
-  for (void* p : t->allocs) (void)hipFree(p);
-  t->allocs.clear();
-}
-
 extern "C" void sf_text_destroy(sf_text* t) {
   if (!t) return;
-  text_free_device(t);
+  t->dev.free_all();
   delete t;
 }
 
 extern "C" int sf_text_load_tensor(sf_text* t, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
   if (!t || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_text_load_tensor: null argument");
-  std::string k(key);
-  if (k.rfind("text_model.", 0) == 0) k = k.substr(11);
-  auto it = t->expected.find(k);
-  if (it == t->expected.end()) return sf_set_err(SF_ERR_UNKNOWN_KEY, "'%s' is not a weight of this text model", key);
-  size_t n = 1;
-  bool same = (int)it->second.size() == ndim;
-  for (int i = 0; i < ndim; ++i) { n *= (size_t)shape[i]; same = same && it->second[i] == shape[i]; }
-  if (!same) return sf_set_err(SF_ERR_INVALID, "'%s': shape mismatch", key);
-  TextHost h;
-  h.shape.assign(shape, shape + ndim);
-  h.data.resize(n);
-  switch (dtype) {
-    case SF_F32: memcpy(h.data.data(), host_ptr, n * 4); break;
-    case SF_F64: for (size_t i = 0; i < n; ++i) h.data[i] = (float)((const double*)host_ptr)[i]; break;
-    case SF_BF16: for (size_t i = 0; i < n; ++i) h.data[i] = t_bf2f(((const uint16_t*)host_ptr)[i]); break;
-    default: return sf_set_err(SF_ERR_INVALID, "sf_text_load_tensor: dtype %d unsupported (fp32, fp64, bf16)", dtype);
-  }
-  t->host[k] = std::move(h);
+  std::string err;
+  const int rc = t->weights.load(key, host_ptr, dtype, shape, ndim, &err);
+  if (rc) return sf_set_err(rc, "%s", err.c_str());
   t->finalized = false;
   return SF_OK;
 }
 
 extern "C" int sf_text_missing_weights(sf_text* t) {
   if (!t) return sf_set_err(SF_ERR_INVALID, "null handle");
-  int missing = 0;
-  std::string names;
-  for (auto& kv : t->expected)
-    if (!t->host.count(kv.first)) {
-      ++missing;
-      if (names.size() < 800) names += kv.first + " ";
-    }
-  if (missing) sf_set_err(SF_ERR_STATE, "missing %d weights: %s", missing, names.c_str());
+  std::string err;
+  const int missing = t->weights.missing(&err);
+  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
   return missing;
-}
-
-template <typename T>
-static int text_upload(sf_text* t, const std::vector<T>& h, T** out) {
-  void* p = nullptr;
-  const size_t bytes = h.size() * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-  t->allocs.push_back(p);
-  if (bytes) HIP_TRY(hipMemcpy(p, h.data(), bytes, hipMemcpyHostToDevice));
-  *out = (T*)p;
-  return SF_OK;
-}
-
-static int text_upload_linear(sf_text* t, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, TextLinear* out) {
-  std::vector<uint16_t> hi(w.size()), lo;
-  const bool split = t->compute == SF_COMPUTE_BF16X3;
-  if (split) lo.resize(w.size());
-  for (size_t i = 0; i < w.size(); ++i) {
-    hi[i] = t_f2bf(w[i]);
-    if (split) lo[i] = t_f2bf(w[i] - t_bf2f(hi[i]));
-  }
-  int rc = text_upload<uint16_t>(t, hi, &out->w_hi);
-  if (rc) return rc;
-  if (split && (rc = text_upload<uint16_t>(t, lo, &out->w_lo))) return rc;
-  if ((rc = text_upload<float>(t, bias, &out->bias))) return rc;
-  out->N = N;
-  out->K = K;
-  return SF_OK;
 }
 
 extern "C" int sf_text_finalize(sf_text* t, int compute) {
   if (!t) return sf_set_err(SF_ERR_INVALID, "null handle");
-  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return sf_set_err(SF_ERR_INVALID, "unknown compute mode %d", compute);
+  SF_TRY(sf_check_compute_mode(compute));
   if (sf_text_missing_weights(t)) return SF_ERR_STATE;
   HIP_TRY(hipSetDevice(t->device));
-  text_free_device(t);
+  t->dev.free_all();
   t->compute = compute;
   const int D = t->D, I = t->I, Ir = t->cfg.intermediate;
-  auto H = [&](const std::string& k) -> std::vector<float>& { return t->host[k].data; };
-  int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
-  TRY(text_upload<float>(t, H("embeddings.token_embedding.weight"), &t->tok));
-  TRY(text_upload<float>(t, H("embeddings.position_embedding.weight"), &t->pos));
+  const bool split = compute == SF_COMPUTE_BF16X3;
+  SfDeviceAllocs& dev = t->dev;
+  auto H = [&](const std::string& k) -> std::vector<float>& { return t->weights.data(k); };
+  SF_TRY(dev.upload(H("embeddings.token_embedding.weight"), &t->tok));
+  SF_TRY(dev.upload(H("embeddings.position_embedding.weight"), &t->pos));
   t->layers.assign(t->cfg.layers, TextLayer());
   for (int i = 0; i < t->cfg.layers; ++i) {
     const std::string p = "encoder.layers." + std::to_string(i) + ".";
     TextLayer& l = t->layers[i];
-    TRY(text_upload<float>(t, H(p + "layer_norm1.weight"), &l.ln1.g)); TRY(text_upload<float>(t, H(p + "layer_norm1.bias"), &l.ln1.b));
-    TRY(text_upload<float>(t, H(p + "layer_norm2.weight"), &l.ln2.g)); TRY(text_upload<float>(t, H(p + "layer_norm2.bias"), &l.ln2.b));
+    SF_TRY(dev.upload(H(p + "layer_norm1.weight"), &l.ln1.g)); SF_TRY(dev.upload(H(p + "layer_norm1.bias"), &l.ln1.b));
+    SF_TRY(dev.upload(H(p + "layer_norm2.weight"), &l.ln2.g)); SF_TRY(dev.upload(H(p + "layer_norm2.bias"), &l.ln2.b));
     {   // q_proj | k_proj | v_proj -> one [3D, D] Linear
       std::vector<float> w, b;
       w.reserve((size_t)3 * D * D); b.reserve((size_t)3 * D);
@@ -530,9 +442,9 @@ extern "C" int sf_text_finalize(sf_text* t, int compute) {
         w.insert(w.end(), wa.begin(), wa.end());
         b.insert(b.end(), ba.begin(), ba.end());
       }
-      TRY(text_upload_linear(t, w, b, 3 * D, D, &l.qkv));
+      SF_TRY(sf_upload_linear(dev, w, &b, 3 * D, D, 3 * D, split, &l.qkv));
     }
-    TRY(text_upload_linear(t, H(p + "self_attn.out_proj.weight"), H(p + "self_attn.out_proj.bias"), D, D, &l.out));
+    SF_TRY(sf_upload_linear(dev, H(p + "self_attn.out_proj.weight"), &H(p + "self_attn.out_proj.bias"), D, D, D, split, &l.out));
     {   // intermediate_size zero-padded to I: rows of fc1 (and their bias), columns of fc2
       std::vector<float> w1((size_t)I * D, 0.f), b1((size_t)I, 0.f), w2((size_t)D * I, 0.f);
       const std::vector<float>& a1 = H(p + "mlp.fc1.weight");
@@ -541,15 +453,14 @@ extern "C" int sf_text_finalize(sf_text* t, int compute) {
       std::copy(a1.begin(), a1.end(), w1.begin());
       std::copy(c1.begin(), c1.end(), b1.begin());
       for (int r = 0; r < D; ++r) std::copy(a2.begin() + (size_t)r * Ir, a2.begin() + (size_t)(r + 1) * Ir, w2.begin() + (size_t)r * I);
-      TRY(text_upload_linear(t, w1, b1, I, D, &l.fc1));
-      TRY(text_upload_linear(t, w2, H(p + "mlp.fc2.bias"), D, I, &l.fc2));
+      SF_TRY(sf_upload_linear(dev, w1, &b1, I, D, I, split, &l.fc1));
+      SF_TRY(sf_upload_linear(dev, w2, &H(p + "mlp.fc2.bias"), D, I, D, split, &l.fc2));
     }
   }
-  TRY(text_upload<float>(t, H("final_layer_norm.weight"), &t->final_ln.g));
-  TRY(text_upload<float>(t, H("final_layer_norm.bias"), &t->final_ln.b));
-  TRY(text_upload<float>(t, H("head.weight"), &t->head_w));
-  TRY(text_upload<float>(t, H("head.bias"), &t->head_b));
-#undef TRY
+  SF_TRY(dev.upload(H("final_layer_norm.weight"), &t->final_ln.g));
+  SF_TRY(dev.upload(H("final_layer_norm.bias"), &t->final_ln.b));
+  SF_TRY(dev.upload(H("head.weight"), &t->head_w));
+  SF_TRY(dev.upload(H("head.bias"), &t->head_b));
   t->finalized = true;
   return SF_OK;
 }
@@ -572,17 +483,6 @@ extern "C" int sf_text_workspace_bytes(sf_text* t, int B, int L, size_t* out) {
   return SF_OK;
 }
 
-static SfGemmArgs text_linear_args(const sf_text* t, const TextLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, bool split) {
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a_hi = a_hi; g.a_lo = split ? a_lo : nullptr;
-  g.w_hi = lin.w_hi; g.w_lo = split ? lin.w_lo : nullptr;
-  g.bias = lin.bias;
-  g.M = M; g.N = lin.N; g.K = lin.K; g.ldc = lin.N;
-  g.epi = epi; g.act = t->cfg.act; g.alpha = 1.f;
-  return g;
-}
-
 // group == 0: pooled_out [B, P]; group > 0: the normalised means of `group` consecutive captions, [B / group, P]
 static int text_forward(sf_text* t, const int32_t* ids, const uint8_t* mask, int B, int L, int group, float* last_hidden, float* pooled_out,
                         void* workspace, size_t workspace_bytes, hipStream_t s) {
@@ -600,7 +500,7 @@ static int text_forward(sf_text* t, const int32_t* ids, const uint8_t* mask, int
   for (const TextLayer& l : t->layers) {
     HIP_TRY(sf_launch_layernorm(ws.resid, l.ln1.g, l.ln1.b, nullptr, ws.xn_hi, acc ? ws.xn_lo : nullptr, M, D, c.eps, s));
     {
-      SfGemmArgs g = text_linear_args(t, l.qkv, ws.xn_hi, ws.xn_lo, M, SF_EPI_F32, acc);
+      SfGemmArgs g = sf_linear_args(l.qkv, ws.xn_hi, ws.xn_lo, M, SF_EPI_F32, c.act, acc);
       g.out_f32 = ws.qkv;
       HIP_TRY(sf_launch_gemm(g, acc, s));
     }
@@ -612,18 +512,18 @@ static int text_forward(sf_text* t, const int32_t* ids, const uint8_t* mask, int
       HIP_TRY(text_launch_attention(a, s));
     }
     {
-      SfGemmArgs g = text_linear_args(t, l.out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_RESID_F32, acc);
+      SfGemmArgs g = sf_linear_args(l.out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_RESID_F32, c.act, acc);
       g.resid = ws.resid; g.out_f32 = ws.resid;
       HIP_TRY(sf_launch_gemm(g, acc, s));
     }
     HIP_TRY(sf_launch_layernorm(ws.resid, l.ln2.g, l.ln2.b, nullptr, ws.xn_hi, acc ? ws.xn_lo : nullptr, M, D, c.eps, s));
     {
-      SfGemmArgs g = text_linear_args(t, l.fc1, ws.xn_hi, ws.xn_lo, M, SF_EPI_ACT_BF16, acc);
+      SfGemmArgs g = sf_linear_args(l.fc1, ws.xn_hi, ws.xn_lo, M, SF_EPI_ACT_BF16, c.act, acc);
       g.out_hi = ws.mid_hi; g.out_lo = acc ? ws.mid_lo : nullptr;
       HIP_TRY(sf_launch_gemm(g, acc, s));
     }
     {
-      SfGemmArgs g = text_linear_args(t, l.fc2, ws.mid_hi, ws.mid_lo, M, SF_EPI_RESID_F32, acc);
+      SfGemmArgs g = sf_linear_args(l.fc2, ws.mid_hi, ws.mid_lo, M, SF_EPI_RESID_F32, c.act, acc);
       g.resid = ws.resid; g.out_f32 = ws.resid;
       HIP_TRY(sf_launch_gemm(g, acc, s));
     }

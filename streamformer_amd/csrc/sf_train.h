@@ -4,6 +4,20 @@
 // optim_factory.py:59-104 configure it.
 #pragma once
 #include "sf_common.h"
+#include <string.h>
+
+// ------------------------------------------------------------------------------------------------
+// GEMM arguments of the training arithmetic: bf16 operands (one plane), fp32 accumulation
+// ------------------------------------------------------------------------------------------------
+static inline SfGemmArgs sf_train_gemm_args(const bf16_t* a, const bf16_t* w, const float* bias, int M, int N, int K, int epi, float* out_f32,
+                                            bf16_t* out_bf, const float* resid) {
+  SfGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.a_hi = a; g.w_hi = w; g.bias = bias;
+  g.M = M; g.N = N; g.K = K; g.epi = epi; g.alpha = 1.f; g.resid = resid;
+  g.out_f32 = out_f32; g.out_hi = epi == SF_EPI_RESID_F32 ? nullptr : out_bf; g.ldc = N;
+  return g;
+}
 
 // ------------------------------------------------------------------------------------------------
 // weight-gradient GEMM ("TN"):  C[N1,N2] (+)= sum_m dY[m,N1] * X[m,N2]

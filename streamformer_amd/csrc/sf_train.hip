@@ -8,6 +8,7 @@
 #include "sf_switches.h"
 #include "sf_train.h"
 #include "sf_pool_head.h"
+#include "sf_weights.h"
 
 #include <cmath>
 #include <cstdio>
@@ -317,7 +318,7 @@ static int upload_segments(sf_trainer* t) {
   return rc ? rc : upload(&t->seg_train, train, "segment table");
 }
 
-// The bf16 / fp32 working arenas, carved like the workspace (TCarver): null bases count, real bases assign.  Weights round to 128 elements, vectors to 64 floats.
+// The bf16 / fp32 working arenas, carved like the workspace (SfCarver): null bases count, real bases assign.  Weights round to 128 elements, vectors to 64 floats.
 struct ArenaCarver {
   bf16_t* b; float* f;
   size_t nb = 0, nf = 0;
@@ -502,19 +503,6 @@ extern "C" int sf_trainer_sync_weights(sf_trainer* t, const float* params_dev, s
 // ------------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------------
-struct TCarver {
-  char* base;
-  size_t off = 0;
-  explicit TCarver(void* b) : base((char*)b) {}
-  template <typename T>
-  T* take(size_t n) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += n * sizeof(T);
-    return p;
-  }
-};
-
 struct TSavedLayer {
   float *h1, *h2;
   bf16_t *ln_t, *tqkv, *ctx_t, *t_out, *ln_b, *sqkv, *ctx_s, *ln_a, *pre, *act;
@@ -548,7 +536,7 @@ static size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 static TWs tcarve(const sf_trainer* t, void* base, int B, int T) {
   TWs w;
-  TCarver c(base);
+  SfCarver c(base);
   const size_t D = t->D, I = t->Ip, N = t->N;     // activations carry the padded intermediate width
   const size_t M = (size_t)B * T * N, F = (size_t)B * T;
   w.patches = c.take<bf16_t>(M * t->Kpp);
@@ -648,18 +636,9 @@ extern "C" int sf_trainer_workspace_bytes(const sf_trainer* t, int B, int T, siz
 // ------------------------------------------------------------------------------------------------
 // GEMM helpers
 // ------------------------------------------------------------------------------------------------
-static SfGemmArgs tgemm_args(const bf16_t* a, const bf16_t* w, const float* bias, int M, int N, int K, int epi, float* out_f32,
-                            bf16_t* out_bf, const float* resid) {
-  SfGemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.a_hi = a; g.w_hi = w; g.bias = bias;
-  g.M = M; g.N = N; g.K = K; g.epi = epi; g.alpha = 1.f; g.resid = resid;
-  g.out_f32 = out_f32; g.out_hi = epi == SF_EPI_RESID_F32 ? nullptr : out_bf; g.ldc = N;
-  return g;
-}
 static hipError_t tgemm(const bf16_t* a, const bf16_t* w, const float* bias, int M, int N, int K, int epi, hipStream_t s,
                         float* out_f32, bf16_t* out_bf, const float* resid = nullptr) {
-  return sf_launch_gemm(tgemm_args(a, w, bias, M, N, K, epi, out_f32, out_bf, resid), false, s);
+  return sf_launch_gemm(sf_train_gemm_args(a, w, bias, M, N, K, epi, out_f32, out_bf, resid), false, s);
 }
 // y = x W^T + b
 static hipError_t lin_fwd(const sf_trainer* t, const TLin& l, const bf16_t* x, int M, int epi, hipStream_t s, float* out_f32,
@@ -672,7 +651,7 @@ static hipError_t lin_dgrad(const TLin& l, const bf16_t* dy, int M, hipStream_t 
 }
 // pre = x W^T + b and act = gelu(pre): one launch where the 256^2 kernel takes the shape, else GEMM + GELU pass
 static hipError_t lin_fwd_gelu(const sf_trainer* t, const TLin& l, const bf16_t* x, int M, hipStream_t s, bf16_t* pre, bf16_t* act) {
-  SfGemmArgs g = tgemm_args(x, l.w, lin_bias(t, l), M, l.Nw, l.Kw, SF_EPI_BF16, nullptr, pre, nullptr);
+  SfGemmArgs g = sf_train_gemm_args(x, l.w, lin_bias(t, l), M, l.Nw, l.Kw, SF_EPI_BF16, nullptr, pre, nullptr);
   g.aux_mode = 1; g.aux = act;
   if (sf_gemm256_aux_supported(g)) return sf_launch_gemm(g, false, s);
   g.aux_mode = 0; g.aux = nullptr;
@@ -681,7 +660,7 @@ static hipError_t lin_fwd_gelu(const sf_trainer* t, const TLin& l, const bf16_t*
 }
 // d_pre = (dy W) * gelu'(pre): same
 static hipError_t lin_dgrad_dgelu(const TLin& l, const bf16_t* dy, int M, hipStream_t s, bf16_t* d_pre, bf16_t* pre) {
-  SfGemmArgs g = tgemm_args(dy, l.wT, nullptr, M, l.Kw, l.Nw, SF_EPI_BF16, nullptr, d_pre, nullptr);
+  SfGemmArgs g = sf_train_gemm_args(dy, l.wT, nullptr, M, l.Kw, l.Nw, SF_EPI_BF16, nullptr, d_pre, nullptr);
   g.aux_mode = 2; g.aux = pre;                // read only in this mode (the field is the forward's output pointer)
   if (sf_gemm256_aux_supported(g)) return sf_launch_gemm(g, false, s);
   g.aux_mode = 0; g.aux = nullptr;

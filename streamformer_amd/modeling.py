@@ -894,12 +894,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         h = nat.C.c_void_p()
         nat.check(nat.lib.sf_create(nat.C.byref(cfg), dev.index or 0, nat.C.byref(h)))
         self._handle = h
-        for k, p in self._named.items():
-            t = p.detach().to("cpu").contiguous()
-            if t.dtype not in _TORCH2SF or t.dtype == torch.uint8:
-                t = t.float()
-            shape = (nat.C.c_int64 * max(t.dim(), 1))(*t.shape)
-            nat.check(nat.lib.sf_load_tensor(h, k.encode(), t.data_ptr(), _TORCH2SF[t.dtype], shape, t.dim()))
+        nat.load_tensors(h, nat.lib.sf_load_tensor, self._named.items(), lambda d: None if d == torch.uint8 else _TORCH2SF.get(d))
         with torch.cuda.device(dev):
             nat.check(nat.lib.sf_finalize_weights(h, self._compute, 1, int(self._fuse)))
         ip = self.image_processor           # uint8 frames: rescale + normalize fused into the patch kernel

@@ -296,18 +296,13 @@ class OnlineActionDetector(nn.Module):
             raise RuntimeError("the detector runs on the MI355X: move the module with .to('cuda') (there is no CPU fallback)")
         if self._tensors is None:
             self._tensors = list(self.parameters()) + list(self.buffers())
-        token = (dev, tuple((t.data_ptr(), t._version) for t in self._tensors))
+        token = nat.weights_token(dev, self._tensors)
         if token != self._packed_token:
             self._release()
             tensors = list(self.state_dict().items())
             h = self._create(dev.index or 0)
             L, W = self.long_memory_num_samples, self.work_memory_num_samples
-            for k, t in tensors:
-                if k == "pos_encoding.pe":
-                    t = t[:L + W, 0]
-                t = t.detach().to("cpu", torch.float32).contiguous()
-                shape = (C.c_int64 * t.dim())(*t.shape)
-                nat.check(nat.lib.sf_oad_load_tensor(h, k.encode(), t.data_ptr(), nat.SF_F32, shape, t.dim()))
+            nat.load_tensors(h, nat.lib.sf_oad_load_tensor, [(k, t[:L + W, 0] if k == "pos_encoding.pe" else t) for k, t in tensors])
             with torch.cuda.device(dev):
                 nat.check(nat.lib.sf_oad_finalize(h, self._compute))
             self._handle, self._packed_token = h, token
@@ -348,8 +343,7 @@ class OnlineActionDetector(nn.Module):
     def _workspace(self, h, n: int) -> torch.Tensor:
         size = C.c_size_t()
         nat.check(nat.lib.sf_oad_workspace_bytes(h, n, C.byref(size)))
-        if self._ws is None or self._ws.numel() < size.value or self._ws.device != self.device:
-            self._ws = torch.empty(max(size.value, 256), dtype=torch.uint8, device=self.device)
+        self._ws = nat.grow_workspace(self._ws, size.value, self.device)
         return self._ws
 
     @torch.no_grad()

@@ -233,17 +233,14 @@ class SiglipTextModel(nn.Module):
         dev = self.device
         if dev.type != "cuda":
             raise RuntimeError("the text tower runs on the MI355X: move the model with .to('cuda') (there is no CPU fallback)")
-        token = (dev, tuple((p.data_ptr(), p._version) for _, p in params))
+        token = nat.weights_token(dev, [p for _, p in params])
         if self._handle is not None and token == self._packed_token:
             return
         self._release()
         h = C.c_void_p()
         nat.check(nat.lib.sf_text_create(C.byref(self._native_config()), dev.index or 0, C.byref(h)))
         self._handle = h
-        for k, p in params:
-            t = p.detach().to("cpu", torch.float32).contiguous()
-            shape = (C.c_int64 * t.dim())(*t.shape)
-            nat.check(nat.lib.sf_text_load_tensor(h, k.encode(), t.data_ptr(), nat.SF_F32, shape, t.dim()))
+        nat.load_tensors(h, nat.lib.sf_text_load_tensor, params)
         with torch.cuda.device(dev):
             nat.check(nat.lib.sf_text_finalize(h, self._compute))
         self._packed_token = token
