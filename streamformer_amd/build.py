@@ -57,7 +57,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, variant:
     os.makedirs(objdir, exist_ok=True)
     if lab and not os.path.isdir(LAB_DIR):
         raise RuntimeError("the lab kernels (tools/lab/) are not present in this checkout")
-    headers = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "sf_train.h"), os.path.join(CSRC, "sf_internal.h"), os.path.join(CSRC, "sf_pool_head.h"), os.path.join(CSRC, "sf_switches.h"),
+    headers = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "sf_launch.h"), os.path.join(CSRC, "sf_train.h"), os.path.join(CSRC, "sf_internal.h"), os.path.join(CSRC, "sf_pool_head.h"), os.path.join(CSRC, "sf_switches.h"),
                os.path.join(CSRC, "sf_weights.h"), os.path.join(CSRC, "sf_handle.h"),
                os.path.join(os.path.dirname(HERE), "include", "streamformer_hip.h")]
 

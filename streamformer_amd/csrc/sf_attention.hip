@@ -847,14 +847,9 @@ hipError_t sf_launch_spatial_attention(const SfAttnArgs& a, bool accurate, hipSt
   if (nkp > 32 * 7) {                               // more than 224 tokens per frame: streaming-key kernel
     const int qblocks = (a.N + 127) / 128;
     const size_t lds = (size_t)(SL_KC * 128 + HD * 2 * SL_KC + SP_WAVES * 2048) * (accurate ? 2 : 1);
-    static SfPerDeviceOnce attr_l;
-    if (attr_l.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_large_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-    }
     const dim3 grid(a.frames * a.heads * qblocks), block(SP_WAVES * 64);
-    if (accurate) hipLaunchKernelGGL((sf_spatial_attn_large_kernel<true>), grid, block, lds, s, a, qblocks);
-    else hipLaunchKernelGGL((sf_spatial_attn_large_kernel<false>), grid, block, lds, s, a, qblocks);
-    return hipGetLastError();
+    if (accurate) return sf_launch_big_lds(sf_spatial_attn_large_kernel<true>, grid, block, lds, s, a, qblocks);
+    return sf_launch(sf_spatial_attn_large_kernel<false>, grid, block, lds, s, a, qblocks);
   }
   const int vp = (2 * nkp + 255) & ~255;          // V^T row pitch: whole groups of 16 chunks (vswz is 4-bit)
   const size_t lds = (size_t)(nkp * 128 + HD * vp + SP_WAVES * 2048) * (accurate ? 2 : 1);
@@ -870,72 +865,35 @@ hipError_t sf_launch_spatial_attention(const SfAttnArgs& a, bool accurate, hipSt
     if (qsplit < 1) qsplit = 1;
   }
   const dim3 grid(a.frames * a.heads * qsplit), block(SP_WAVES * 64);
-  static SfPerDeviceOnce attr;
-  if (attr.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_kernel<false, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_kernel<true, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   const bool dma_off = sf_sw(SW_DISABLE_SPATIAL_DMA) != nullptr;
-  static SfPerDeviceOnce attr2;
-  if (attr2.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_dma_kernel<14, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_dma_kernel<14, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   if (!accurate && !a.probs && !dma_off && (a.row_pitch_kv % 8) == 0) {
 #ifdef SF_LAB
     // many (frame, head) problems: the persistent double-buffered kernel (>= 4 problems per CU, so that the pipeline has something to overlap)
     const bool pers_off = sf_sw(SW_SPATIAL_PERS) == nullptr;
-    static int cus = 0;
-    if (!cus) {
-      int dev = 0;
-      hipDeviceProp_t prop;
-      cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 256;
-    }
+    int cus = sf_device_cus();
+    if (cus <= 0) cus = 256;
     if (!pers_off && qsplit == 1 && fh >= 4 * cus && a.N >= 64) {
       const size_t lds3 = (size_t)nkp * 512 + SPP_WAVES * 2048;
-      static SfPerDeviceOnce attr3;
-      if (attr3.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_pers_kernel<14>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((sf_spatial_attn_pers_kernel<14>), dim3(cus), dim3(SPP_WAVES * 64), lds3, s, a, fh);
-      return hipGetLastError();
+      return sf_launch_big_lds(sf_spatial_attn_pers_kernel<14>, dim3(cus), dim3(SPP_WAVES * 64), lds3, s, a, fh);
     }
 #endif
     const size_t lds2 = (size_t)nkp * 256 + SP_WAVES * 2048;
-    if (a.drop.on) {
-      static SfPerDeviceOnce attr4;
-      if (attr4.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_dma_kernel<14, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((sf_spatial_attn_dma_kernel<14, false, true>), grid, block, lds2, s, a, qsplit);
-      return hipGetLastError();
-    }
+    if (a.drop.on) return sf_launch_big_lds(sf_spatial_attn_dma_kernel<14, false, true>, grid, block, lds2, s, a, qsplit);
     const bool ntc_off = sf_sw(SW_DISABLE_SPATIAL_NTC) != nullptr;      // A/B switch
-    if (!ntc_off && ((a.N + 15) >> 4) == 13) {       // 193 .. 208 tokens per frame (224^2 inputs): the tile count as a compile-time constant
-      static SfPerDeviceOnce attr5;
-      if (attr5.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_dma_kernel<14, false, false, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((sf_spatial_attn_dma_kernel<14, false, false, 13>), grid, block, lds2, s, a, qsplit);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((sf_spatial_attn_dma_kernel<14, false>), grid, block, lds2, s, a, qsplit);
-    return hipGetLastError();
+    if (!ntc_off && ((a.N + 15) >> 4) == 13)         // 193 .. 208 tokens per frame (224^2 inputs): the tile count as a compile-time constant
+      return sf_launch_big_lds(sf_spatial_attn_dma_kernel<14, false, false, 13>, grid, block, lds2, s, a, qsplit);
+    return sf_launch_big_lds(sf_spatial_attn_dma_kernel<14, false>, grid, block, lds2, s, a, qsplit);
   }
   if (accurate && !a.in_is_f32) {       // hi + lo bf16 planes (sf_spatial_planes_ok): the DMA kernel with three products
     if (a.probs || a.lo_plane_off <= 0 || (a.row_pitch_kv % 8) || (a.lo_plane_off % 8)) return hipErrorInvalidValue;
     const size_t lds2 = (size_t)nkp * 512 + SP_WAVES * 4096;
     const bool ntc_acc_off = sf_sw(SW_DISABLE_SPATIAL_NTC) != nullptr;      // A/B switch (shared with the bf16 instance)
-    if (!ntc_acc_off && ((a.N + 15) >> 4) == 13) {       // compile-time tile count: 129.9 -> 118.2 us per launch, bit-identical (profiles/r04_spatial_ntc_acc_ab.txt)
-      static SfPerDeviceOnce attr6;
-      if (attr6.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_dma_kernel<14, true, false, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      hipLaunchKernelGGL((sf_spatial_attn_dma_kernel<14, true, false, 13>), grid, block, lds2, s, a, qsplit);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((sf_spatial_attn_dma_kernel<14, true>), grid, block, lds2, s, a, qsplit);
-    return hipGetLastError();
+    if (!ntc_acc_off && ((a.N + 15) >> 4) == 13)         // compile-time tile count: 129.9 -> 118.2 us per launch, bit-identical (profiles/r04_spatial_ntc_acc_ab.txt)
+      return sf_launch_big_lds(sf_spatial_attn_dma_kernel<14, true, false, 13>, grid, block, lds2, s, a, qsplit);
+    return sf_launch_big_lds(sf_spatial_attn_dma_kernel<14, true>, grid, block, lds2, s, a, qsplit);
   }
-  if (accurate) hipLaunchKernelGGL((sf_spatial_attn_kernel<true, 7>), grid, block, lds, s, a, vp, qsplit);
-  else hipLaunchKernelGGL((sf_spatial_attn_kernel<false, 7>), grid, block, lds, s, a, vp, qsplit);
-  return hipGetLastError();
+  if (accurate) return sf_launch_big_lds(sf_spatial_attn_kernel<true, 7>, grid, block, lds, s, a, vp, qsplit);
+  return sf_launch_big_lds(sf_spatial_attn_kernel<false, 7>, grid, block, lds, s, a, vp, qsplit);
 }
 
 // ================================================================================================
@@ -1538,31 +1496,25 @@ hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipS
     const int ntasks = a.B * a.N * a.heads;
     const dim3 grid((ntasks + 3) / 4), block(256);
     const int kp = (a.Tk + 63) >> 6;
-#define SF_TD(F, KPV) hipLaunchKernelGGL((sf_temporal_decode_kernel<F, KPV>), grid, block, 0, s, a, ntasks)
+#define SF_TD(F, KPV) return sf_launch(sf_temporal_decode_kernel<F, KPV>, grid, block, 0, s, a, ntasks)
     if (accurate) { if (kp <= 1) SF_TD(true, 1); else if (kp <= 2) SF_TD(true, 2); else SF_TD(true, 4); }
     else if (kp <= 2 && (a.row_pitch_kv % 8) == 0 && (a.row_pitch_q % 8) == 0 && !sf_sw(SW_TEMPORAL_DECODE_LANE_KEY)) {
       // bf16 rows, <= 128 keys: whole cache lines per load instruction
-      if (kp <= 1) hipLaunchKernelGGL(sf_temporal_decode_lines_kernel<1>, grid, block, 0, s, a, ntasks);
-      else hipLaunchKernelGGL(sf_temporal_decode_lines_kernel<2>, grid, block, 0, s, a, ntasks);
+      if (kp <= 1) return sf_launch(sf_temporal_decode_lines_kernel<1>, grid, block, 0, s, a, ntasks);
+      return sf_launch(sf_temporal_decode_lines_kernel<2>, grid, block, 0, s, a, ntasks);
     }
     else { if (kp <= 1) SF_TD(false, 1); else if (kp <= 2) SF_TD(false, 2); else SF_TD(false, 4); }
 #undef SF_TD
-    return hipGetLastError();
   }
   const bool tdma_off = sf_sw(SW_DISABLE_TEMPORAL_DMA) != nullptr;
   if (!accurate && !tdma_off && a.Tq <= 16 && a.Tk <= 32 && (a.row_pitch_kv % 8) == 0) {     // every full 16-frame clip
     const int ntasks = a.B * a.N * a.heads;
-    hipLaunchKernelGGL(sf_temporal_attn_dma_kernel<false>, dim3((ntasks + 3) / 4), dim3(256), 4 * 10240, s, a, ntasks);
-    return hipGetLastError();
+    return sf_launch(sf_temporal_attn_dma_kernel<false>, dim3((ntasks + 3) / 4), dim3(256), 4 * 10240, s, a, ntasks);
   }
   if (accurate && !a.in_is_f32) {        // hi + lo planes (sf_temporal_planes_ok)
     if (a.Tq > 16 || a.Tk > 32 || a.lo_plane_off <= 0 || (a.row_pitch_kv % 8) || (a.lo_plane_off % 8)) return hipErrorInvalidValue;
     const int ntasks = a.B * a.N * a.heads;
-    static SfPerDeviceOnce attr_t;
-    if (attr_t.first())
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_temporal_attn_dma_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 20480);
-    hipLaunchKernelGGL(sf_temporal_attn_dma_kernel<true>, dim3((ntasks + 3) / 4), dim3(256), 4 * 20480, s, a, ntasks);
-    return hipGetLastError();
+    return sf_launch_big_lds(sf_temporal_attn_dma_kernel<true>, dim3((ntasks + 3) / 4), dim3(256), 4 * 20480, s, a, ntasks);
   }
   const int tkp = (a.Tk + 31) & ~31;
   if (tkp > 32 * 8) return hipErrorInvalidValue;   // <= 256 cached frames per stream
@@ -1573,15 +1525,7 @@ hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipS
   const size_t lds = patch * waves;
   const int ntasks = a.B * a.N * a.heads;
   const dim3 grid((ntasks + waves - 1) / waves), block(waves * 64);
-#define SF_TL(ACCV, NT)                                                                              \
-  do {                                                                                               \
-    static SfPerDeviceOnce attr;                                                                        \
-    if (attr.first()) {                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_temporal_attn_kernel<ACCV, NT>),   \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);              \
-    }                                                                                                \
-    hipLaunchKernelGGL((sf_temporal_attn_kernel<ACCV, NT>), grid, block, lds, s, a, vp, ntasks);     \
-  } while (0)
+#define SF_TL(ACCV, NT) return sf_launch_big_lds(sf_temporal_attn_kernel<ACCV, NT>, grid, block, lds, s, a, vp, ntasks)
   const int nt2 = tkp >> 5;
   if (accurate) {
     if (nt2 <= 1) SF_TL(true, 1); else if (nt2 <= 2) SF_TL(true, 2); else if (nt2 <= 4) SF_TL(true, 4); else SF_TL(true, 8);
@@ -1589,5 +1533,4 @@ hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipS
     if (nt2 <= 1) SF_TL(false, 1); else if (nt2 <= 2) SF_TL(false, 2); else if (nt2 <= 4) SF_TL(false, 4); else SF_TL(false, 8);
   }
 #undef SF_TL
-  return hipGetLastError();
 }

@@ -564,22 +564,16 @@ hipError_t sf_launch_spatial_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s
   if (a.L <= 0 || a.L > SB_ROWS || a.nseq <= 0 || a.D != a.heads * 64) return hipErrorInvalidValue;
   if ((a.ld_qkv % 8) || (a.ld_o % 8)) return hipErrorInvalidValue;
   const size_t lds = 4 * SB_IMG + 2 * SB_ROWS * 4 + SB_WAVES * SB_PATCH;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_spatial_attn_bwd_kernel<false, 13>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
   static const int lab = SF_LAB_SWITCH("SF_ATTN_BWD_LAB");      // timing lab: phases off, results invalid (lab builds only)
   const bool ntc_off = sf_sw(SW_DISABLE_SPATIAL_NTC) != nullptr;      // A/B switch (same one as the forward kernel)
   SfAttnBwdArgs b = a;
   b.lab = lab;
   const int nt = (a.L + 15) >> 4;
-  if (b.drop.on) hipLaunchKernelGGL(sf_spatial_attn_bwd_kernel<true>, dim3(a.nseq * a.heads), dim3(SB_THREADS), lds, s, b);
-  else if (nt == 13 && !a.causal && !ntc_off)      // 224^2 frames: 196 patches = 13 tiles, block loops unrolled
-    hipLaunchKernelGGL((sf_spatial_attn_bwd_kernel<false, 13>), dim3(a.nseq * a.heads), dim3(SB_THREADS), lds, s, b);
-  else hipLaunchKernelGGL(sf_spatial_attn_bwd_kernel<false>, dim3(a.nseq * a.heads), dim3(SB_THREADS), lds, s, b);
-  return hipGetLastError();
+  const dim3 grid(a.nseq * a.heads), block(SB_THREADS);
+  if (b.drop.on) return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<true>, grid, block, lds, s, b);
+  if (nt == 13 && !a.causal && !ntc_off)      // 224^2 frames: 196 patches = 13 tiles, block loops unrolled
+    return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<false, 13>, grid, block, lds, s, b);
+  return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<false>, grid, block, lds, s, b);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -672,25 +666,17 @@ hipError_t sf_launch_temporal_attention_bwd(const SfAttnBwdArgs& a, hipStream_t 
 #endif
   const char* own_sw = sf_sw(SW_TBWD_OWN_CU);
   const bool share = own_sw == nullptr || own_sw[0] == '0';      // default: share the CU (exact LDS sizes); the trainer sets 1 when world > 1
-  const size_t whole_cu = (size_t)160 * 1024;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_temporal_attn_bwd_kernel<16, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole_cu);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_temporal_attn_bwd_kernel<32, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)whole_cu);
-  }
+  const size_t whole_cu = SF_LDS_CAP;
   if (a.L <= 16) {
     if (share) {
       size_t lds = 4 * (size_t)(5 * 16 * 128 + 2 * 16 * 4);
       if (lab == 3) lds = 64 * 1024;      // lab: an allocation that cannot share a CU with the 102 KB probe kernel
-      hipLaunchKernelGGL((sf_temporal_attn_bwd_kernel<16, 4>), dim3((nprob + 3) / 4), dim3(256), lds, s, a, nprob, lab);
-    } else {
-      hipLaunchKernelGGL((sf_temporal_attn_bwd_kernel<16, 12>), dim3((nprob + 11) / 12), dim3(768), whole_cu, s, a, nprob, lab);
+      return sf_launch(sf_temporal_attn_bwd_kernel<16, 4>, dim3((nprob + 3) / 4), dim3(256), lds, s, a, nprob, lab);
     }
-  } else {
-    // 32-row images: 4 waves take 83 KB, a second workgroup of this kernel never fitted beside them; the whole-CU request keeps others out too
-    const size_t lds = share ? 4 * (size_t)(5 * 32 * 128 + 2 * 32 * 4) : whole_cu;
-    hipLaunchKernelGGL((sf_temporal_attn_bwd_kernel<32, 4>), dim3((nprob + 3) / 4), dim3(256), lds, s, a, nprob, lab);
+    return sf_launch_big_lds(sf_temporal_attn_bwd_kernel<16, 12>, dim3((nprob + 11) / 12), dim3(768), whole_cu, s, a, nprob, lab);
   }
-  return hipGetLastError();
+  // 32-row images: 4 waves take 83 KB, a second workgroup of this kernel never fitted beside them; the whole-CU request keeps others out too
+  const size_t lds = share ? 4 * (size_t)(5 * 32 * 128 + 2 * 32 * 4) : whole_cu;
+  return sf_launch_big_lds(sf_temporal_attn_bwd_kernel<32, 4>, dim3((nprob + 3) / 4), dim3(256), lds, s, a, nprob, lab);
 }
 

@@ -232,20 +232,15 @@ static hipError_t ga_launch(const SfGenAttn& p, hipStream_t s) {
   const int total = p.nseq * p.a.heads * p.qtiles;
   const dim3 grid((total + 3) / 4), block(256);
   const size_t lds = (size_t)4 * 2 * 16 * (p.hd + 4) * sizeof(float);      // <= 67.6 KB at head_dim 128
-  static SfPerDeviceOnce attr_set[3];
-  if (attr_set[KIND].first()) {
-#define GA_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_attention_generic_kernel<KIND, 2 * E>), hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024);
-    GA_ATTR(13) GA_ATTR(14) GA_ATTR(15) GA_ATTR(16)
-#undef GA_ATTR
-  }
   switch (p.hd / 8) {
-#define GA_CASE(E) case E: hipLaunchKernelGGL((sf_attention_generic_kernel<KIND, 2 * E>), grid, block, lds, s, p); break;
+#define GA_CASE(E) case E: return sf_launch(sf_attention_generic_kernel<KIND, 2 * E>, grid, block, lds, s, p);
+#define GA_BIG(E) case E: return sf_launch_big_lds(sf_attention_generic_kernel<KIND, 2 * E>, grid, block, lds, s, p);      // head_dim > 96: past 64 KB
     GA_CASE(1) GA_CASE(2) GA_CASE(3) GA_CASE(4) GA_CASE(5) GA_CASE(6) GA_CASE(7) GA_CASE(8)
-    GA_CASE(9) GA_CASE(10) GA_CASE(11) GA_CASE(12) GA_CASE(13) GA_CASE(14) GA_CASE(15) GA_CASE(16)
+    GA_CASE(9) GA_CASE(10) GA_CASE(11) GA_CASE(12) GA_BIG(13) GA_BIG(14) GA_BIG(15) GA_BIG(16)
+#undef GA_BIG
 #undef GA_CASE
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 hipError_t sf_launch_attention_generic(const SfAttnArgs& a, int head_dim, bool temporal, hipStream_t s) {

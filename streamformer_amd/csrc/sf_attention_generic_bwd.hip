@@ -183,10 +183,5 @@ hipError_t sf_launch_attention_generic_bwd(const SfAttnBwdArgs& a, bool temporal
   if (a.L > (temporal ? 32 : 224) || (temporal && a.seq_rows <= 0) || a.drop.on) return hipErrorInvalidValue;
   if ((a.ld_qkv % 2) || (a.ld_o % 2)) return hipErrorInvalidValue;
   const size_t lds = gb_lds(a.L, hd);       // <= 129.8 KB at L = 224, head_dim 128
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_attention_generic_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-  hipLaunchKernelGGL(sf_attention_generic_bwd_kernel, dim3(a.nseq * a.heads), dim3(64 * GB_WAVES), lds, s, a, temporal ? 1 : 0);
-  return hipGetLastError();
+  return sf_launch_big_lds(sf_attention_generic_bwd_kernel, dim3(a.nseq * a.heads), dim3(64 * GB_WAVES), lds, s, a, temporal ? 1 : 0);
 }

@@ -44,7 +44,6 @@ hipError_t sf_launch_cache_park(const SfParkArgs& a, int layers, bool do_export,
   // ~2048 workgroups over the layers (8 per CU), 1024 vectors = 16 KiB per workgroup and sweep
   unsigned per_layer = (2048 + layers - 1) / layers, need = (a.nvec + 1023u) / 1024u;
   const dim3 grid(need < per_layer ? need : per_layer, layers);
-  if (do_export) hipLaunchKernelGGL(sf_cache_park_kernel<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(sf_cache_park_kernel<false>, grid, dim3(256), 0, s, a);
-  return hipGetLastError();
+  if (do_export) return sf_launch(sf_cache_park_kernel<true>, grid, dim3(256), 0, s, a);
+  return sf_launch(sf_cache_park_kernel<false>, grid, dim3(256), 0, s, a);
 }

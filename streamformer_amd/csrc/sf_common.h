@@ -104,18 +104,7 @@ SF_DEVICE void sf_lnf_finish(float s1, float s2, int K, float eps, float& mean, 
   rstd = __builtin_amdgcn_rsqf(fmaxf(s2 * inv_k - mean * mean, 0.f) + eps);
 }
 
-// hipFuncSetAttribute (the > 64 KB dynamic-LDS opt-in) is a per-DEVICE setting: run the set-up once for every device a
-// process launches on, not once per process.
-struct SfPerDeviceOnce {
-  bool done[64] = {};
-  bool first() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return true;
-    if (done[d]) return false;
-    done[d] = true;
-    return true;
-  }
-};
+#include "sf_launch.h"   // sf_launch / sf_launch_big_lds / sf_device_cus: how every kernel below is put on a stream
 
 SF_DEVICE float wave_sum(float v) {
 #pragma unroll

@@ -181,11 +181,10 @@ static hipError_t conn_launch_pool(const SfConnPool& q, hipStream_t s) {
   unsigned grid = (p.total + block - 1) / block;
   if (grid > 2048u) grid = 2048u;
   const bool planes = p.in_hi != nullptr;
-  if (planes && p.out_hi) hipLaunchKernelGGL((sf_connector_pool_kernel<true, 2>), dim3(grid), dim3(block), 0, s, p);
-  else if (!planes && p.out_f32) hipLaunchKernelGGL((sf_connector_pool_kernel<false, 0>), dim3(grid), dim3(block), 0, s, p);
-  else if (!planes && p.out_bf16) hipLaunchKernelGGL((sf_connector_pool_kernel<false, 1>), dim3(grid), dim3(block), 0, s, p);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  if (planes && p.out_hi) return sf_launch(sf_connector_pool_kernel<true, 2>, dim3(grid), dim3(block), 0, s, p);
+  if (!planes && p.out_f32) return sf_launch(sf_connector_pool_kernel<false, 0>, dim3(grid), dim3(block), 0, s, p);
+  if (!planes && p.out_bf16) return sf_launch(sf_connector_pool_kernel<false, 1>, dim3(grid), dim3(block), 0, s, p);
+  return hipErrorInvalidValue;
 }
 
 // ------------------------------------------------------------------------------------------------

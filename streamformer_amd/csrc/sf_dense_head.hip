@@ -95,11 +95,10 @@ extern "C" int sf_dense_head_forward(const float* x, int M, int D, int I, float 
   hipStream_t s = (hipStream_t)stream;
   const int Ip = (I + 63) / 64 * 64;
   // fp32 parameters -> bf16 working copies (every call: the parameters train)
-  hipLaunchKernelGGL(sf_dh_prep_kernel, dim3(D / 32, D / 32), dim3(256), 0, s, params[DH_WV_W], D, D, D, D, w.wv, w.wvT);
-  hipLaunchKernelGGL(sf_dh_prep_kernel, dim3(D / 32, D / 32), dim3(256), 0, s, params[DH_VP_W], D, D, D, D, w.vp, w.vpT);
-  hipLaunchKernelGGL(sf_dh_prep_kernel, dim3(D / 32, Ip / 32), dim3(256), 0, s, params[DH_FC1_W], I, D, Ip, D, w.fc1, w.fc1T);
-  hipLaunchKernelGGL(sf_dh_prep_kernel, dim3(Ip / 32, D / 32), dim3(256), 0, s, params[DH_FC2_W], D, I, D, Ip, w.fc2, w.fc2T);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(sf_launch(sf_dh_prep_kernel, dim3(D / 32, D / 32), dim3(256), 0, s, params[DH_WV_W], D, D, D, D, w.wv, w.wvT));
+  HIP_TRY(sf_launch(sf_dh_prep_kernel, dim3(D / 32, D / 32), dim3(256), 0, s, params[DH_VP_W], D, D, D, D, w.vp, w.vpT));
+  HIP_TRY(sf_launch(sf_dh_prep_kernel, dim3(D / 32, Ip / 32), dim3(256), 0, s, params[DH_FC1_W], I, D, Ip, D, w.fc1, w.fc1T));
+  HIP_TRY(sf_launch(sf_dh_prep_kernel, dim3(Ip / 32, D / 32), dim3(256), 0, s, params[DH_FC2_W], D, I, D, Ip, w.fc2, w.fc2T));
   const float* b1 = params[DH_FC1_B];
   if (Ip != I) {
     HIP_TRY(hipMemsetAsync(w.b1, 0, (size_t)Ip * 4, s));

@@ -126,9 +126,11 @@ struct sf_cache {
     const float* pos = nullptr;
   };
   std::map<GraphKey, GraphEntry> graphs;
-  // Keys that have run eagerly once, so that every lazy per-kernel set-up (hipFuncSetAttribute, device queries) has happened
-  // before a capture is opened.  The lockstep entry warms once per cache, under kLockstepWarm; the ragged entry once per key
-  // (another row count selects other GEMM kernels).
+  // Keys that have run eagerly once, so that the lazy per-kernel set-up (sf_launch_big_lds: the dynamic-LDS attribute; device queries) of
+  // the instances that pass ran has happened before a capture is opened.  The lockstep entry warms once per cache, under kLockstepWarm;
+  // the ragged entry once per key (another row count selects other GEMM kernels).  The set-up is per kernel instance: one the warm pass
+  // did not run (a temporal or pooling instance of a longer cache, and the same holds for the GEMM families) gets its attribute at its
+  // first launch, which may be inside a hipStreamCaptureModeThreadLocal capture; setting the attribute is not a stream operation.
   std::set<GraphKey> warmed;
   hipStream_t cap_stream = nullptr;   // captures are recorded on a private stream (the caller's may be the null stream, which
                                       // cannot capture) and replayed on the caller's
@@ -1777,8 +1779,7 @@ extern "C" int sf_op_linear(const float* x, const float* w, const float* b, cons
   if (gelu) {
     g.epi = SF_EPI_ACT_BF16; g.out_hi = oh; g.out_lo = split ? ol : nullptr;
     HIP_TRY(sf_launch_gemm(g, split, s));
-    hipLaunchKernelGGL(sf_combine_kernel, dim3(1024), dim3(256), 0, s, oh, split ? ol : nullptr, y, (size_t)M * N);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, oh, split ? ol : nullptr, y, (size_t)M * N));
   } else {
     g.epi = resid ? SF_EPI_RESID_F32 : SF_EPI_F32; g.out_f32 = y;
     HIP_TRY(sf_launch_gemm(g, split, s));
@@ -1831,8 +1832,7 @@ extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, 
     a.N = L; a.frames = groups;
     HIP_TRY(sf_launch_spatial_attention(a, acc, s));
   }
-  hipLaunchKernelGGL(sf_combine_kernel, dim3(1024), dim3(256), 0, s, ch, acc ? cl : nullptr, ctx, rows * D);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, ch, acc ? cl : nullptr, ctx, rows * D));
   return SF_OK;
 }
 
@@ -1993,8 +1993,9 @@ extern "C" int sf_bench_launch_floor(int device, int launches, int iters, sf_str
   hipGraphExec_t exec = nullptr;
   hipError_t err = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
   if (err == hipSuccess) {
-    for (int i = 0; i < launches; ++i) hipLaunchKernelGGL(sf_null_kernel, dim3(256), dim3(256), 0, cap, (int*)nullptr);
-    err = hipStreamEndCapture(cap, &graph);
+    for (int i = 0; i < launches && err == hipSuccess; ++i) err = sf_launch(sf_null_kernel, dim3(256), dim3(256), 0, cap, (int*)nullptr);
+    const hipError_t end = hipStreamEndCapture(cap, &graph);
+    if (err == hipSuccess) err = end;
   }
   if (err == hipSuccess) err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
   float ms = 0.f;

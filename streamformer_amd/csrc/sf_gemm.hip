@@ -205,10 +205,7 @@ __global__ __launch_bounds__(NTHREADS) void sf_gemm_kernel(SfGemmArgs p) {
 
 template <bool SPLIT>
 static hipError_t launch_epi(const SfGemmArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-#define SF_CASE(E)                                                                       \
-  case E:                                                                                \
-    hipLaunchKernelGGL((sf_gemm_kernel<SPLIT, E>), grid, dim3(NTHREADS), lds, s, a);     \
-    break;
+#define SF_CASE(E) case E: return sf_launch_big_lds(sf_gemm_kernel<SPLIT, E>, grid, dim3(NTHREADS), lds, s, a);
   switch (a.epi) {
     SF_CASE(SF_EPI_F32)
     SF_CASE(SF_EPI_BF16)
@@ -219,7 +216,6 @@ static hipError_t launch_epi(const SfGemmArgs& a, dim3 grid, size_t lds, hipStre
       return hipErrorInvalidValue;
   }
 #undef SF_CASE
-  return hipGetLastError();
 }
 
 int sf_wall_clock_ticks(int ns) {
@@ -282,15 +278,5 @@ hipError_t sf_launch_gemm128(const SfGemmArgs& a, bool split, hipStream_t s) {
   if (split && (!a.a_lo || !a.w_lo)) return hipErrorInvalidValue;
   const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   const size_t lds = 2 * (size_t)BM * 64 * 2 * 2;   // 64 KB: two stages of 32 KB in both modes
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    // > 48 KB of dynamic LDS needs the opt-in attribute once per kernel
-#define SF_ATTR(S, E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_kernel<S, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SF_ATTR(false, SF_EPI_F32) SF_ATTR(false, SF_EPI_BF16) SF_ATTR(false, SF_EPI_ACT_BF16)
-    SF_ATTR(false, SF_EPI_RESID_F32) SF_ATTR(false, SF_EPI_EMBED_F32)
-    SF_ATTR(true, SF_EPI_F32) SF_ATTR(true, SF_EPI_BF16) SF_ATTR(true, SF_EPI_ACT_BF16)
-    SF_ATTR(true, SF_EPI_RESID_F32) SF_ATTR(true, SF_EPI_EMBED_F32)
-#undef SF_ATTR
-  }
   return split ? launch_epi<true>(a, dim3(tiles), lds, s) : launch_epi<false>(a, dim3(tiles), lds, s);
 }

@@ -588,16 +588,9 @@ bool sf_gemm256_aux_supported(const SfGemmArgs& a) {
 }
 
 static int g256_grid() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (const char* e = sf_sw(SW_ASSUME_CUS)) cus = atoi(e);      // experiment: kernels sized for a CU-masked stream
-    if (cus < 8) cus = 256;
-    cus &= ~7;      // the XCD-aware walk wants a multiple of 8
-  }
-  return cus;
+  int cus = sf_device_cus();
+  if (cus < 8) cus = 256;
+  return cus & ~7;      // the XCD-aware walk wants a multiple of 8
 }
 
 template <int BM, bool SPLIT_ONLY = false>
@@ -606,21 +599,6 @@ static hipError_t launch_bm(const SfGemmArgs& a_in, hipStream_t s) {
   if (SF_LAB_SWITCH("SF_G256_LAB_NOSTORE")) a.act = 99;      // lab builds only: main loops without stores (results are discarded)
   const int tiles = ((a.M + BM - 1) / BM) * (a.N / 256);
   const size_t lds = 8 * PIECE_BYTES;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    if constexpr (!SPLIT_ONLY) {
-#define SF_ATTR(E, L) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm256_kernel<E, L, BM>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      SF_ATTR(SF_EPI_F32, false) SF_ATTR(SF_EPI_BF16, false) SF_ATTR(SF_EPI_ACT_BF16, false) SF_ATTR(SF_EPI_RESID_F32, false)
-      SF_ATTR(SF_EPI_BF16, true) SF_ATTR(SF_EPI_ACT_BF16, true) SF_ATTR(G256_EPI_BF16_AUX, false)
-#undef SF_ATTR
-    }
-#define SF_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm256_kernel<E, false, BM, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SF_ATTR(SF_EPI_F32) SF_ATTR(SF_EPI_BF16) SF_ATTR(SF_EPI_ACT_BF16) SF_ATTR(SF_EPI_RESID_F32)
-#undef SF_ATTR
-#define SF_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm256_kernel<E, true, BM, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SF_ATTR(SF_EPI_BF16) SF_ATTR(SF_EPI_ACT_BF16)
-#undef SF_ATTR
-  }
   const dim3 grid(g256_grid()), block(G_THREADS);
   // stagger as wall_clock64() ticks (sf_wall_clock_ticks), only when the launch runs
   // several rounds of tiles per CU; SF_G256_STAGGER_NS overrides (0 disables) for A/B measurements
@@ -651,46 +629,43 @@ static hipError_t launch_bm(const SfGemmArgs& a_in, hipStream_t s) {
     if (cg < 0 || cg > 15 || (cg != 15 && cg >= a.N / 256)) cg = 0;      // 15 = row-major with per-stagger-group runs
     sgroups = (sgroups & 255) | (cg << 8) | (sf_sw(SW_G256_STORE_WT) ? 1 << 12 : 0) | (sf_sw(SW_G256_STORE_NT) ? 1 << 13 : 0);
   }
-#define SF_LAUNCH256(E, L, SP) hipLaunchKernelGGL((sf_gemm256_kernel<E, L, BM, SP>), grid, block, lds, s, a, tiles, stagger, sgroups)
+#define SF_LAUNCH256(E, L, SP) return sf_launch_big_lds(sf_gemm256_kernel<E, L, BM, SP>, grid, block, lds, s, a, tiles, stagger, sgroups)
   if (a.a_lo && a.w_lo) {      // fp32-accurate mode: hi + lo planes of both operands, three products per fragment pair
     if (a.aux_mode) return hipErrorInvalidValue;
     if (a.ln_stats) {          // LayerNorm folded into this Linear (wide statistics of the accurate mode)
       if (!a.ln_stats_wide || !a.ln_s) return hipErrorInvalidValue;
       if (a.epi == SF_EPI_BF16) SF_LAUNCH256(SF_EPI_BF16, true, true);
-      else if (a.epi == SF_EPI_ACT_BF16) SF_LAUNCH256(SF_EPI_ACT_BF16, true, true);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
+      if (a.epi == SF_EPI_ACT_BF16) SF_LAUNCH256(SF_EPI_ACT_BF16, true, true);
+      return hipErrorInvalidValue;
     }
     switch (a.epi) {
-#define SF_CASE(E) case E: SF_LAUNCH256(E, false, true); break;
+#define SF_CASE(E) case E: SF_LAUNCH256(E, false, true);
       SF_CASE(SF_EPI_F32) SF_CASE(SF_EPI_BF16) SF_CASE(SF_EPI_ACT_BF16) SF_CASE(SF_EPI_RESID_F32)
 #undef SF_CASE
       default: return hipErrorInvalidValue;
     }
-    return hipGetLastError();
   }
   if constexpr (SPLIT_ONLY) return hipErrorInvalidValue;
   else {
   const bool lnf = a.ln_stats != nullptr;
   if (lnf && (!a.ln_s || (a.epi != SF_EPI_BF16 && a.epi != SF_EPI_ACT_BF16))) return hipErrorInvalidValue;
   switch (a.epi) {
-    case SF_EPI_F32: SF_LAUNCH256(SF_EPI_F32, false, false); break;
+    case SF_EPI_F32: SF_LAUNCH256(SF_EPI_F32, false, false);
     case SF_EPI_BF16:
       if (a.aux_mode) {
         if (lnf || !a.aux) return hipErrorInvalidValue;
         SF_LAUNCH256(G256_EPI_BF16_AUX, false, false);
-      } else if (lnf) SF_LAUNCH256(SF_EPI_BF16, true, false);
-      else SF_LAUNCH256(SF_EPI_BF16, false, false);
-      break;
+      }
+      if (lnf) SF_LAUNCH256(SF_EPI_BF16, true, false);
+      SF_LAUNCH256(SF_EPI_BF16, false, false);
     case SF_EPI_ACT_BF16:
       if (lnf) SF_LAUNCH256(SF_EPI_ACT_BF16, true, false);
-      else SF_LAUNCH256(SF_EPI_ACT_BF16, false, false);
-      break;
-    case SF_EPI_RESID_F32: SF_LAUNCH256(SF_EPI_RESID_F32, false, false); break;
+      SF_LAUNCH256(SF_EPI_ACT_BF16, false, false);
+    case SF_EPI_RESID_F32: SF_LAUNCH256(SF_EPI_RESID_F32, false, false);
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
   }
+#undef SF_LAUNCH256
 }
 
 hipError_t sf_launch_gemm256(const SfGemmArgs& a, hipStream_t s) {

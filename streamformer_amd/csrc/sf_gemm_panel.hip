@@ -317,16 +317,9 @@ __global__ __launch_bounds__(P_THREADS) void sf_gemm_panel_kernel(SfGemmArgs p, 
 }
 
 static int panel_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (const char* e = sf_sw(SW_ASSUME_CUS)) cus = atoi(e);      // experiment: kernels sized for a CU-masked stream
-    if (cus < 16) cus = 256;
-    cus &= ~15;
-  }
-  return cus;
+  int cus = sf_device_cus();
+  if (cus < 16) cus = 256;
+  return cus & ~15;
 }
 
 // Tiling plan: P row panels (a multiple of CUs/2, so that the 2P tiles fill whole rounds), rows = ceil(M/P)
@@ -371,12 +364,6 @@ hipError_t sf_launch_gemm_panel(const SfGemmArgs& a_in, hipStream_t s) {
   if (!pl.ok) return hipErrorInvalidValue;
   const int cus = panel_cus();
   const int ntiles = pl.panels * 2;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-#define SF_PATTR(MT) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_panel_kernel<MT>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * P_SLOT_BYTES);
-    SF_PATTR(2) SF_PATTR(4) SF_PATTR(7) SF_PATTR(13)
-#undef SF_PATTR
-  }
   // Phase stagger (see sf_gemm256.hip): three groups 3.5 us apart spread the read-heavy main loops and the
   // residual read + store bursts of the epilogues.  Box-dependent: -3.3 % on the whole forward on one MI355X,
   // neutral on another; never slower in the sweeps (tools/stagger_sweep.py).  SF_PANEL_STAGGER_NS overrides.
@@ -387,10 +374,9 @@ hipError_t sf_launch_gemm_panel(const SfGemmArgs& a_in, hipStream_t s) {
   const dim3 grid(ntiles < cus ? ntiles : cus), block(P_THREADS);
   const size_t lds = 4 * P_SLOT_BYTES;
   switch (pl.mt) {
-    case 2: hipLaunchKernelGGL(sf_gemm_panel_kernel<2>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp); break;
-    case 4: hipLaunchKernelGGL(sf_gemm_panel_kernel<4>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp); break;
-    case 7: hipLaunchKernelGGL(sf_gemm_panel_kernel<7>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp); break;
-    default: hipLaunchKernelGGL(sf_gemm_panel_kernel<13>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp); break;
+    case 2: return sf_launch_big_lds(sf_gemm_panel_kernel<2>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp);
+    case 4: return sf_launch_big_lds(sf_gemm_panel_kernel<4>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp);
+    case 7: return sf_launch_big_lds(sf_gemm_panel_kernel<7>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp);
+    default: return sf_launch_big_lds(sf_gemm_panel_kernel<13>, grid, block, lds, s, a, pl.rows, ntiles, stagger, pad_clamp);
   }
-  return hipGetLastError();
 }

@@ -680,66 +680,38 @@ static bool mid_ok(const SfGemmArgs& a, bool split) {
 static hipError_t mid_launch(const SfGemmArgs& a, hipStream_t s) {
   const dim3 grid((a.N + MD_B - 1) / MD_B, (a.M + MD_B - 1) / MD_B);
   const size_t lds = (size_t)MD_STAGES * MD_STAGE;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-#define MD_ATTR(E, L) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_mid_kernel<E, L>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    MD_ATTR(SF_EPI_F32, false) MD_ATTR(SF_EPI_BF16, false) MD_ATTR(SF_EPI_ACT_BF16, false) MD_ATTR(SF_EPI_RESID_F32, false)
-    MD_ATTR(SF_EPI_BF16, true) MD_ATTR(SF_EPI_ACT_BF16, true)
-#undef MD_ATTR
-  }
-#define MD_GO(E, L) hipLaunchKernelGGL((sf_gemm_mid_kernel<E, L>), grid, dim3(SK_THREADS), lds, s, a)
+#define MD_GO(E, L) return sf_launch_big_lds(sf_gemm_mid_kernel<E, L>, grid, dim3(SK_THREADS), lds, s, a)
   if (a.ln_inkernel) {
     if (a.epi == SF_EPI_BF16) MD_GO(SF_EPI_BF16, true);
-    else if (a.epi == SF_EPI_ACT_BF16) MD_GO(SF_EPI_ACT_BF16, true);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    if (a.epi == SF_EPI_ACT_BF16) MD_GO(SF_EPI_ACT_BF16, true);
+    return hipErrorInvalidValue;
   }
   switch (a.epi) {
-    case SF_EPI_F32: MD_GO(SF_EPI_F32, false); break;
-    case SF_EPI_BF16: MD_GO(SF_EPI_BF16, false); break;
-    case SF_EPI_ACT_BF16: MD_GO(SF_EPI_ACT_BF16, false); break;
-    case SF_EPI_RESID_F32: MD_GO(SF_EPI_RESID_F32, false); break;
+    case SF_EPI_F32: MD_GO(SF_EPI_F32, false);
+    case SF_EPI_BF16: MD_GO(SF_EPI_BF16, false);
+    case SF_EPI_ACT_BF16: MD_GO(SF_EPI_ACT_BF16, false);
+    case SF_EPI_RESID_F32: MD_GO(SF_EPI_RESID_F32, false);
     default: return hipErrorInvalidValue;
   }
 #undef MD_GO
-  return hipGetLastError();
 }
 
 template <bool SPLIT, int KG>
 static hipError_t skg_launch(const SfGemmArgs& a, dim3 grid, hipStream_t s) {
   const size_t lds = (size_t)KG * SKG_STAGES * SK_PLANE * (SPLIT ? 2 : 1);
+  const dim3 block(SK_THREADS * KG);
   if (a.ln_inkernel) {       // LayerNorm-folded consumers (bf16 mode): qkv (BF16) and MLP-up (ACT_BF16) epilogues
     if (SPLIT) return hipErrorInvalidValue;
-    static SfPerDeviceOnce attr_ln;
-    if (attr_ln.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kg_kernel<false, SF_EPI_BF16, KG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kg_kernel<false, SF_EPI_ACT_BF16, KG, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    if (a.epi == SF_EPI_BF16) hipLaunchKernelGGL((sf_gemm_skinny_kg_kernel<false, SF_EPI_BF16, KG, true>), grid, dim3(SK_THREADS * KG), lds, s, a);
-    else if (a.epi == SF_EPI_ACT_BF16) hipLaunchKernelGGL((sf_gemm_skinny_kg_kernel<false, SF_EPI_ACT_BF16, KG, true>), grid, dim3(SK_THREADS * KG), lds, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-#define SKG_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kg_kernel<SPLIT, E, KG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    SKG_ATTR(SF_EPI_F32) SKG_ATTR(SF_EPI_BF16) SKG_ATTR(SF_EPI_ACT_BF16) SKG_ATTR(SF_EPI_RESID_F32)
-#undef SKG_ATTR
+    if (a.epi == SF_EPI_BF16) return sf_launch_big_lds(sf_gemm_skinny_kg_kernel<false, SF_EPI_BF16, KG, true>, grid, block, lds, s, a);
+    if (a.epi == SF_EPI_ACT_BF16) return sf_launch_big_lds(sf_gemm_skinny_kg_kernel<false, SF_EPI_ACT_BF16, KG, true>, grid, block, lds, s, a);
+    return hipErrorInvalidValue;
   }
   if constexpr (!SPLIT && KG == 4) {        // the streamed K = 768 residual projections (24 of a frame's 108 launches): three K-tiles per group, unrolled
     const bool pg_off = sf_sw(SW_DISABLE_SKG_UNROLL) != nullptr;      // A/B switch
-    if (!pg_off && a.epi == SF_EPI_RESID_F32 && a.K == 64 * KG * 3) {
-      static SfPerDeviceOnce attr_pg;
-      if (attr_pg.first())
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kg_kernel<false, SF_EPI_RESID_F32, 4, false, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((sf_gemm_skinny_kg_kernel<false, SF_EPI_RESID_F32, 4, false, 3>), grid, dim3(SK_THREADS * KG), lds, s, a);
-      return hipGetLastError();
-    }
+    if (!pg_off && a.epi == SF_EPI_RESID_F32 && a.K == 64 * KG * 3)
+      return sf_launch_big_lds(sf_gemm_skinny_kg_kernel<false, SF_EPI_RESID_F32, 4, false, 3>, grid, block, lds, s, a);
   }
-#define SKG_CASE(E)                                                                                              \
-  case E:                                                                                                        \
-    hipLaunchKernelGGL((sf_gemm_skinny_kg_kernel<SPLIT, E, KG>), grid, dim3(SK_THREADS * KG), lds, s, a);        \
-    break;
+#define SKG_CASE(E) case E: return sf_launch_big_lds(sf_gemm_skinny_kg_kernel<SPLIT, E, KG>, grid, block, lds, s, a);
   switch (a.epi) {
     SKG_CASE(SF_EPI_F32)
     SKG_CASE(SF_EPI_BF16)
@@ -749,7 +721,6 @@ static hipError_t skg_launch(const SfGemmArgs& a, dim3 grid, hipStream_t s) {
       return hipErrorInvalidValue;
   }
 #undef SKG_CASE
-  return hipGetLastError();
 }
 
 int sf_skinny_max_rows() {
@@ -775,16 +746,7 @@ bool sf_gemm_skinny_supported(const SfGemmArgs& a, bool split) {
 
 template <bool SPLIT, int TPS>
 static hipError_t sk_launch_epi(const SfGemmArgs& a, dim3 grid, size_t lds, hipStream_t s) {
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-#define SK_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kernel<SPLIT, E, false, TPS>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * SK_PLANE * 2);
-    SK_ATTR(SF_EPI_F32) SK_ATTR(SF_EPI_BF16) SK_ATTR(SF_EPI_ACT_BF16) SK_ATTR(SF_EPI_RESID_F32) SK_ATTR(SF_EPI_EMBED_F32)
-#undef SK_ATTR
-  }
-#define SK_CASE(E)                                                                                           \
-  case E:                                                                                                    \
-    hipLaunchKernelGGL((sf_gemm_skinny_kernel<SPLIT, E, false, TPS>), grid, dim3(SK_THREADS), lds, s, a);    \
-    break;
+#define SK_CASE(E) case E: return sf_launch_big_lds(sf_gemm_skinny_kernel<SPLIT, E, false, TPS>, grid, dim3(SK_THREADS), lds, s, a);
   switch (a.epi) {
     SK_CASE(SF_EPI_F32)
     SK_CASE(SF_EPI_BF16)
@@ -795,7 +757,6 @@ static hipError_t sk_launch_epi(const SfGemmArgs& a, dim3 grid, size_t lds, hipS
       return hipErrorInvalidValue;
   }
 #undef SK_CASE
-  return hipGetLastError();
 }
 
 hipError_t sf_launch_gemm_skinny(const SfGemmArgs& a_in, bool split, hipStream_t s) {
@@ -811,21 +772,15 @@ hipError_t sf_launch_gemm_skinny(const SfGemmArgs& a_in, bool split, hipStream_t
   if ((int)(grid.x * grid.y) <= 256 && a.K >= 512 && a.epi != SF_EPI_EMBED_F32 && !sf_sw(SW_SKINNY_NO_KG))
     return split ? skg_launch<true, 2>(a, grid, s) : skg_launch<false, 4>(a, grid, s);
   const size_t lds = (size_t)SK_STAGES * SK_PLANE * (split ? 2 : 1);
+  const dim3 block(SK_THREADS);
   if (a.ln_inkernel && split) {      // accurate mode (round 6): statistics of x = hi + lo inside the consumer, fp32 qkv / hi + lo activation outputs
-    static SfPerDeviceOnce attr_lns;
-    if (attr_lns.first()) {
-#define SK_LNSATTR(E, T) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kernel<true, E, true, T>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * SK_PLANE * 2);
-      SK_LNSATTR(SF_EPI_F32, 4) SK_LNSATTR(SF_EPI_F32, 1) SK_LNSATTR(SF_EPI_BF16, 4) SK_LNSATTR(SF_EPI_BF16, 1) SK_LNSATTR(SF_EPI_ACT_BF16, 4) SK_LNSATTR(SF_EPI_ACT_BF16, 1)
-#undef SK_LNSATTR
-    }
     const bool four = ((a.K / SK_BK) % 4) == 0;
-#define SK_LNSGO(E) do { if (four) hipLaunchKernelGGL((sf_gemm_skinny_kernel<true, E, true, 4>), grid, dim3(SK_THREADS), lds, s, a); \
-                         else hipLaunchKernelGGL((sf_gemm_skinny_kernel<true, E, true, 1>), grid, dim3(SK_THREADS), lds, s, a); } while (0)
+#define SK_LNSGO(E) return four ? sf_launch_big_lds(sf_gemm_skinny_kernel<true, E, true, 4>, grid, block, lds, s, a) \
+                                : sf_launch_big_lds(sf_gemm_skinny_kernel<true, E, true, 1>, grid, block, lds, s, a)
     if (a.epi == SF_EPI_F32) SK_LNSGO(SF_EPI_F32);
-    else if (a.epi == SF_EPI_BF16) SK_LNSGO(SF_EPI_BF16);
-    else SK_LNSGO(SF_EPI_ACT_BF16);
+    if (a.epi == SF_EPI_BF16) SK_LNSGO(SF_EPI_BF16);
+    SK_LNSGO(SF_EPI_ACT_BF16);
 #undef SK_LNSGO
-    return hipGetLastError();
   }
   if (a.ln_inkernel && !split && a.M <= 256 && ((a.K / SK_BK) % 4) == 0 && (int)(grid.x * grid.y) > 512) {
     // one streamed frame, more than two 32 x 32 tiles per CU (MLP-up: 672): the narrowest wider tile that gives every workgroup its
@@ -840,49 +795,27 @@ hipError_t sf_launch_gemm_skinny(const SfGemmArgs& a_in, bool split, hipStream_t
     if (nb > 1) {
       const size_t ldw = (size_t)SK_STAGES * (SK_BM + 32 * nb) * SK_BK * 2;
       const dim3 gw(a.N / (32 * nb), grid.y);
-      static SfPerDeviceOnce attr_w;
-      if (attr_w.first()) {
-#define SK_WATTR(E, B) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_wide_kernel<false, E, true, 4, B>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * (SK_BM + 32 * B) * SK_BK * 2);
-        SK_WATTR(SF_EPI_BF16, 2) SK_WATTR(SF_EPI_BF16, 3) SK_WATTR(SF_EPI_ACT_BF16, 2) SK_WATTR(SF_EPI_ACT_BF16, 3)
-#undef SK_WATTR
-      }
-      if (a.epi == SF_EPI_BF16) {
-        if (nb == 2) hipLaunchKernelGGL((sf_gemm_skinny_wide_kernel<false, SF_EPI_BF16, true, 4, 2>), gw, dim3(SK_THREADS), ldw, s, a);
-        else hipLaunchKernelGGL((sf_gemm_skinny_wide_kernel<false, SF_EPI_BF16, true, 4, 3>), gw, dim3(SK_THREADS), ldw, s, a);
-      } else {
-        if (nb == 2) hipLaunchKernelGGL((sf_gemm_skinny_wide_kernel<false, SF_EPI_ACT_BF16, true, 4, 2>), gw, dim3(SK_THREADS), ldw, s, a);
-        else hipLaunchKernelGGL((sf_gemm_skinny_wide_kernel<false, SF_EPI_ACT_BF16, true, 4, 3>), gw, dim3(SK_THREADS), ldw, s, a);
-      }
-      return hipGetLastError();
+#define SK_WGO(E) return nb == 2 ? sf_launch_big_lds(sf_gemm_skinny_wide_kernel<false, E, true, 4, 2>, gw, block, ldw, s, a) \
+                                 : sf_launch_big_lds(sf_gemm_skinny_wide_kernel<false, E, true, 4, 3>, gw, block, ldw, s, a)
+      if (a.epi == SF_EPI_BF16) SK_WGO(SF_EPI_BF16);
+      SK_WGO(SF_EPI_ACT_BF16);
+#undef SK_WGO
     }
   }
   if (a.ln_inkernel) {
-    static SfPerDeviceOnce attr_ln;
-    if (attr_ln.first()) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kernel<false, SF_EPI_BF16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * SK_PLANE * 2);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kernel<false, SF_EPI_ACT_BF16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * SK_PLANE * 2);
-    }
     const int tps_env = sf_sw(SW_SKINNY_TPS) ? atoi(sf_sw(SW_SKINNY_TPS)) : 0;
     const int nkt = a.K / SK_BK;
     int tps = tps_env ? tps_env : 4;
     while (tps > 1 && (nkt % tps)) --tps;
-    static SfPerDeviceOnce attr_ln2;
-    if (attr_ln2.first()) {
-#define SK_LNATTR(E, T) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_skinny_kernel<false, E, true, T>), hipFuncAttributeMaxDynamicSharedMemorySize, SK_STAGES * SK_PLANE * 2);
-      SK_LNATTR(SF_EPI_BF16, 2) SK_LNATTR(SF_EPI_BF16, 3) SK_LNATTR(SF_EPI_BF16, 4)
-      SK_LNATTR(SF_EPI_ACT_BF16, 2) SK_LNATTR(SF_EPI_ACT_BF16, 3) SK_LNATTR(SF_EPI_ACT_BF16, 4)
-#undef SK_LNATTR
-    }
-#define SK_LNGO(E)                                                                                                               \
-    switch (tps) {                                                                                                               \
-      case 4: hipLaunchKernelGGL((sf_gemm_skinny_kernel<false, E, true, 4>), grid, dim3(SK_THREADS), lds, s, a); break;          \
-      case 3: hipLaunchKernelGGL((sf_gemm_skinny_kernel<false, E, true, 3>), grid, dim3(SK_THREADS), lds, s, a); break;          \
-      case 2: hipLaunchKernelGGL((sf_gemm_skinny_kernel<false, E, true, 2>), grid, dim3(SK_THREADS), lds, s, a); break;          \
-      default: hipLaunchKernelGGL((sf_gemm_skinny_kernel<false, E, true>), grid, dim3(SK_THREADS), lds, s, a); break;            \
+#define SK_LNGO(E)                                                                                                  \
+    switch (tps) {                                                                                                  \
+      case 4: return sf_launch_big_lds(sf_gemm_skinny_kernel<false, E, true, 4>, grid, block, lds, s, a);           \
+      case 3: return sf_launch_big_lds(sf_gemm_skinny_kernel<false, E, true, 3>, grid, block, lds, s, a);           \
+      case 2: return sf_launch_big_lds(sf_gemm_skinny_kernel<false, E, true, 2>, grid, block, lds, s, a);           \
+      default: return sf_launch_big_lds(sf_gemm_skinny_kernel<false, E, true>, grid, block, lds, s, a);             \
     }
     if (a.epi == SF_EPI_BF16) { SK_LNGO(SF_EPI_BF16) } else { SK_LNGO(SF_EPI_ACT_BF16) }
 #undef SK_LNGO
-    return hipGetLastError();
   }
   const bool four = ((a.K / SK_BK) % 4) == 0;         // four K-tiles per barrier when the tile count allows
   if (split) return four ? sk_launch_epi<true, 4>(a, grid, lds, s) : sk_launch_epi<true, 1>(a, grid, lds, s);

@@ -320,14 +320,8 @@ __global__ __launch_bounds__(TL_THREADS) void sf_gemm_tile_kernel(SfGemmArgs p, 
 // host side: configuration table and dispatch
 // ------------------------------------------------------------------------------------------------
 static int tile_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus < 8) cus = 256;
-  }
-  return cus;
+  const int cus = sf_device_cus();
+  return cus < 8 ? 256 : cus;
 }
 int sf_tile_min_rows() {
   const int m = sf_sw(SW_TILE_MIN_M) ? atoi(sf_sw(SW_TILE_MIN_M)) : 2560;      // below: skinny / 64 x 64 kernels
@@ -414,17 +408,12 @@ static hipError_t tl_go(const SfGemmArgs& a, hipStream_t s) {
   constexpr int LDS_MAX = (PRODUCER && C::LDS_BYTES + C::PART_BYTES <= 160 * 1024) ? C::LDS_BYTES + C::PART_BYTES : C::LDS_BYTES;
   const int lds = C::LDS_BYTES + (stats ? C::PART_BYTES : 0);
   if (lds > LDS_MAX) return hipErrorInvalidValue;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_tile_kernel<MT, NT, WM, WN, BK, STAGES, EPI, LNF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
   const int tiles_n = a.N / C::BN, tiles_m = (a.M + C::BM - 1) / C::BM;
   const int ntiles = tiles_n * tiles_m;
   const int per_xcd = (ntiles + 7) / 8;
   static const int lab_env = SF_LAB_SWITCH("SF_TILE_LAB");      // lab builds only
-  hipLaunchKernelGGL((sf_gemm_tile_kernel<MT, NT, WM, WN, BK, STAGES, EPI, LNF>), dim3(per_xcd * 8), dim3(TL_THREADS), lds, s,
-                     a, tiles_n, ntiles, per_xcd, lab_env);
-  return hipGetLastError();
+  return sf_launch_big_lds(sf_gemm_tile_kernel<MT, NT, WM, WN, BK, STAGES, EPI, LNF>, dim3(per_xcd * 8), dim3(TL_THREADS), lds, s,
+                           a, tiles_n, ntiles, per_xcd, lab_env);
 }
 
 // producers (narrow tiles): RESID / EMBED / F32;  consumers (wide tiles): BF16 / ACT_BF16 with or without the LayerNorm fold

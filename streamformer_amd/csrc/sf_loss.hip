@@ -247,10 +247,10 @@ size_t sf_loss_partial_bytes(int rows) { return (size_t)(rows > 0 ? rows : 1) * 
 hipError_t sf_launch_retrieval_loss(const float* pooler, const float* text, int B, int T, int D, int Bt,
                                     int pos_offset, const float* logit_scale, const float* logit_bias, float* loss,
                                     float* grad_pooler, float* grad_scalars, float* partial, hipStream_t s) {
-  hipLaunchKernelGGL(sf_retrieval_loss_kernel, dim3(B), dim3(256), 0, s, pooler, text, B, T, D, Bt, pos_offset,
-                     logit_scale, logit_bias, partial, grad_pooler);
-  hipLaunchKernelGGL(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B, loss, grad_scalars);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_retrieval_loss_kernel, dim3(B), dim3(256), 0, s, pooler, text, B, T, D, Bt, pos_offset,
+                                 logit_scale, logit_bias, partial, grad_pooler);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B, loss, grad_scalars);
 }
 
 hipError_t sf_launch_localization_loss(const float* pooler, const float* label_emb, const int* labels,
@@ -258,17 +258,17 @@ hipError_t sf_launch_localization_loss(const float* pooler, const float* label_e
                                        float* loss, float* grad_pooler, float* grad_scalars, float* partial,
                                        hipStream_t s) {
   const size_t lds = (size_t)(2 * L + 8) * sizeof(float);
-  hipLaunchKernelGGL(sf_localization_loss_kernel, dim3(B * T), dim3(256), lds, s, pooler, label_emb, labels, B, T, D, L,
-                     logit_scale, logit_bias, partial, grad_pooler);
-  hipLaunchKernelGGL(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_localization_loss_kernel, dim3(B * T), dim3(256), lds, s, pooler, label_emb, labels, B, T, D, L,
+                                 logit_scale, logit_bias, partial, grad_pooler);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
 }
 
 hipError_t sf_launch_grounding_loss(const float* pooler, const float* text, const float* labels, int B, int T, int D,
                                     const float* logit_scale, const float* logit_bias, float* loss, float* grad_pooler,
                                     float* grad_scalars, float* logits_out, float* partial, hipStream_t s) {
-  hipLaunchKernelGGL(sf_grounding_loss_kernel, dim3(B * T), dim3(256), 0, s, pooler, text, labels, B, T, D, logit_scale,
-                     logit_bias, partial, grad_pooler, logits_out);
-  hipLaunchKernelGGL(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_grounding_loss_kernel, dim3(B * T), dim3(256), 0, s, pooler, text, labels, B, T, D, logit_scale,
+                                 logit_bias, partial, grad_pooler, logits_out);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
 }

@@ -358,10 +358,6 @@ extern "C" int sf_mask_loss(const float* x, int B, int T, int N, int D, const fl
   const size_t clip_stride = (size_t)rows * Lmax;
   const dim3 row_grid((rows + SF_ML_ROWS - 1) / SF_ML_ROWS, 1);
   const size_t sim_lds = (size_t)SF_ML_ROWS * D * sizeof(float);
-  static SfPerDeviceOnce attr_set;      // past the default dynamic-LDS window (gfx950 has 160 KB per workgroup): a per-device setting, made once
-  if (sim_lds > 48 * 1024 && attr_set.first())
-    HIP_TRY(hipFuncSetAttribute((const void*)sf_mask_sim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((size_t)SF_ML_ROWS * SF_ML_MAXD * sizeof(float))));
   for (int c0 = 0; c0 < B; c0 += SF_ML_CLIPS) {
     const int nc = B - c0 < SF_ML_CLIPS ? B - c0 : SF_ML_CLIPS;
     SfMaskClips clips = {};
@@ -370,21 +366,22 @@ extern "C" int sf_mask_loss(const float* x, int B, int T, int N, int D, const fl
       clips.emb[i] = label_emb[c0 + i]; clips.mask[i] = mask[c0 + i]; clips.L[i] = num_labels[c0 + i]; clips.W[i] = mask_width[c0 + i];
       if (clips.W[i] > Wmax) Wmax = clips.W[i];
     }
-    hipLaunchKernelGGL(sf_mask_sim_kernel, dim3(row_grid.x, nc), dim3(256), sim_lds, s, clips, c0, x, rows, D,
-                       clip_stride, sim, inv_norm);
+    if (sim_lds > 48 * 1024)      // wide rows: past the default dynamic-LDS window
+      HIP_TRY(sf_launch_big_lds(sf_mask_sim_kernel, dim3(row_grid.x, nc), dim3(256), sim_lds, s, clips, c0, x, rows, D, clip_stride, sim, inv_norm));
+    else
+      HIP_TRY(sf_launch(sf_mask_sim_kernel, dim3(row_grid.x, nc), dim3(256), sim_lds, s, clips, c0, x, rows, D, clip_stride, sim, inv_norm));
     const size_t lds = ((size_t)SF_ML_MAXP * SF_ML_MAXL + 5 * (size_t)Wmax + 32) * sizeof(float);
-    hipLaunchKernelGGL(sf_mask_pixel_kernel, dim3(P, T, nc), dim3(256), lds, s, clips, c0, sim, dz, partial, logit_scale, logit_bias, T, P, H,
-                       clip_stride, need_grad);
+    HIP_TRY(sf_launch(sf_mask_pixel_kernel, dim3(P, T, nc), dim3(256), lds, s, clips, c0, sim, dz, partial, logit_scale, logit_bias, T, P, H,
+                      clip_stride, need_grad));
   }
-  hipLaunchKernelGGL(sf_mask_finish_kernel, dim3(1), dim3(64), 0, s, partial, B, T, P, logit_scale, clip_scale, loss, grad_scalars);
+  HIP_TRY(sf_launch(sf_mask_finish_kernel, dim3(1), dim3(64), 0, s, partial, B, T, P, logit_scale, clip_scale, loss, grad_scalars));
   if (grad_x)
     for (int c0 = 0; c0 < B; c0 += SF_ML_CLIPS) {
       const int nc = B - c0 < SF_ML_CLIPS ? B - c0 : SF_ML_CLIPS;
       SfMaskClips clips = {};
       for (int i = 0; i < nc; ++i) { clips.emb[i] = label_emb[c0 + i]; clips.L[i] = num_labels[c0 + i]; }
-      hipLaunchKernelGGL(sf_mask_dx_kernel, dim3(row_grid.x, nc), dim3(256), 0, s, clips, c0, x, rows, D, clip_stride, sim, dz, inv_norm, clip_scale,
-                         logit_scale, grad_x);
+      HIP_TRY(sf_launch(sf_mask_dx_kernel, dim3(row_grid.x, nc), dim3(256), 0, s, clips, c0, x, rows, D, clip_stride, sim, dz, inv_norm, clip_scale,
+                        logit_scale, grad_x));
     }
-  HIP_TRY(hipGetLastError());
   return SF_OK;
 }

@@ -293,20 +293,18 @@ static hipError_t oad_launch_attention(const SfOadAttn& p, hipStream_t s) {
   const size_t lds = (size_t)2 * 16 * (p.hd + 4) * sizeof(float);      // 33 KB at head_dim 256
   const dim3 grid((unsigned)blocks), block(64);
   switch ((p.hd + 15) / 16) {
-#define OA_CASE(E) case E: hipLaunchKernelGGL((sf_oad_attention_kernel<E>), grid, block, lds, s, p); break;
+#define OA_CASE(E) case E: return sf_launch(sf_oad_attention_kernel<E>, grid, block, lds, s, p);
     OA_CASE(1) OA_CASE(2) OA_CASE(3) OA_CASE(4) OA_CASE(5) OA_CASE(6) OA_CASE(7) OA_CASE(8)
     OA_CASE(9) OA_CASE(10) OA_CASE(11) OA_CASE(12) OA_CASE(13) OA_CASE(14) OA_CASE(15) OA_CASE(16)
 #undef OA_CASE
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 static hipError_t oad_launch_row(const SfOadRow& p, hipStream_t s) {
   if (p.rows <= 0) return hipSuccess;
   if (p.D < 4 || p.D % 4 || p.D > OAD_MAX_D || !p.x || (p.pe && p.pe_mod < 1) || (!p.gamma) != (!p.beta)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_oad_row_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, s, p);
-  return hipGetLastError();
+  return sf_launch(sf_oad_row_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, s, p);
 }
 
 static hipError_t oad_launch_rows(const float* src, float* dst, bf16_t* hi, bf16_t* lo, int D, const SfOadRows& t, hipStream_t s) {
@@ -317,8 +315,7 @@ static hipError_t oad_launch_rows(const float* src, float* dst, bf16_t* hi, bf16
   if (most <= 0) return hipSuccess;
   unsigned gx = (unsigned)(((size_t)most * (D / 4) + 255) / 256);
   if (gx > 256u) gx = 256u;
-  hipLaunchKernelGGL(sf_oad_rows_kernel, dim3(gx, (unsigned)t.n), dim3(256), 0, s, src, dst, hi, lo, D / 4, t);
-  return hipGetLastError();
+  return sf_launch(sf_oad_rows_kernel, dim3(gx, (unsigned)t.n), dim3(256), 0, s, src, dst, hi, lo, D / 4, t);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -890,8 +887,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
     std::swap(x, spare);
   }
   if ((rc = r.gemm(h->cls, x.hi, x.lo, n * W, SF_EPI_F32, ws.scores, nullptr, nullptr))) return rc;
-  hipLaunchKernelGGL(sf_oad_scores_kernel, dim3((unsigned)((n * W + 3) / 4)), dim3(256), 0, s, ws.scores, out_dev, n * W, h->Cp, c.classes, probs);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(sf_launch(sf_oad_scores_kernel, dim3((unsigned)((n * W + 3) / 4)), dim3(256), 0, s, ws.scores, out_dev, n * W, h->Cp, c.classes, probs));
   return SF_OK;
 }
 

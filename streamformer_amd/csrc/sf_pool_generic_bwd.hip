@@ -23,8 +23,7 @@ __global__ __launch_bounds__(256) void sf_pool_u_gen_kernel(const float* __restr
 }
 hipError_t sf_launch_pool_u_generic(const float* wk, const float* q, float* u, int heads, int hd, int D, hipStream_t s) {
   if (heads < 1 || heads > 16 || hd < 1 || D != heads * hd) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_u_gen_kernel, dim3(16, (D + 255) / 256), dim3(256), 0, s, wk, q, u, heads, hd, D);
-  return hipGetLastError();
+  return sf_launch(sf_pool_u_gen_kernel, dim3(16, (D + 255) / 256), dim3(256), 0, s, wk, q, u, heads, hd, D);
 }
 
 // dz[f][h][d] = sum_j Wv[h*hd + j][d] dctx[f][h*hd + j]           grid (D / 256, F, heads)
@@ -54,9 +53,9 @@ __global__ __launch_bounds__(256) void sf_pool_dwv_gen_kernel(const float* __res
 hipError_t sf_launch_pool_ctx_bwd_generic(const float* dctx, const float* wv, int ldw, const float* z, float* dz, float* dwv, float* dbv, int F,
                                           int heads, int hd, int D, hipStream_t s) {
   if (heads < 1 || heads > 16 || hd < 1 || D != heads * hd || F <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_dz_gen_kernel, dim3((D + 255) / 256, F, heads), dim3(256), 0, s, dctx, wv, ldw, dz, heads, hd, D);
-  if (dwv || dbv) hipLaunchKernelGGL(sf_pool_dwv_gen_kernel, dim3((D + 255) / 256, D), dim3(256), 0, s, dctx, z, dwv, ldw, dbv, F, heads, hd, D);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_pool_dz_gen_kernel, dim3((D + 255) / 256, F, heads), dim3(256), 0, s, dctx, wv, ldw, dz, heads, hd, D);
+  if (e != hipSuccess || !(dwv || dbv)) return e;
+  return sf_launch(sf_pool_dwv_gen_kernel, dim3((D + 255) / 256, D), dim3(256), 0, s, dctx, z, dwv, ldw, dbv, F, heads, hd, D);
 }
 
 // per (frame, head): {max score, sum of exp, Delta = dz_h . z_h}        grid F, a wave per head
@@ -125,9 +124,9 @@ __global__ __launch_bounds__(256) void sf_pool_probe_bwd_gen_kernel(SfPoolGenBwd
 }
 hipError_t sf_launch_pool_probe_bwd_generic(const SfPoolGenBwdArgs& a, hipStream_t s) {
   if (a.heads < 1 || a.heads > 16 || a.F <= 0 || a.N <= 0 || a.D <= 0 || !a.stats) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_bwd_stats_gen_kernel, dim3(a.F), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(sf_pool_probe_bwd_gen_kernel, dim3((a.N + 3) / 4, a.F), dim3(256), 0, s, a);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_pool_bwd_stats_gen_kernel, dim3(a.F), dim3(256), 0, s, a);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_pool_probe_bwd_gen_kernel, dim3((a.N + 3) / 4, a.F), dim3(256), 0, s, a);
 }
 
 // dWk[c][d] += q[c] dU[h][d];  dq[c] = sum_d Wk[c][d] dU[h][d]   (h = c / hd; grid D rows)
@@ -149,6 +148,5 @@ __global__ __launch_bounds__(256) void sf_pool_u_bwd_gen_kernel(const float* __r
 }
 hipError_t sf_launch_pool_u_bwd_generic(const float* du, const float* wk, const float* q, float* dwk, float* dq, int hd, int D, hipStream_t s) {
   if (hd < 1 || D % hd) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_u_bwd_gen_kernel, dim3(D), dim3(256), 0, s, du, wk, q, dwk, dq, hd, D);
-  return hipGetLastError();
+  return sf_launch(sf_pool_u_bwd_gen_kernel, dim3(D), dim3(256), 0, s, du, wk, q, dwk, dq, hd, D);
 }

@@ -68,8 +68,7 @@ __global__ __launch_bounds__(256) void sf_pool_u_kernel(const float* __restrict_
 }
 hipError_t sf_launch_pool_u(const float* wk, const float* q, float* u, bf16_t* u_hi, bf16_t* u_lo, int heads, int D, hipStream_t s) {
   if (heads > 16 || D != heads * 64) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_u_kernel, dim3(16, (D + 255) / 256), dim3(256), 0, s, wk, q, u, u_hi, u_lo, heads, D);
-  return hipGetLastError();
+  return sf_launch(sf_pool_u_kernel, dim3(16, (D + 255) / 256), dim3(256), 0, s, wk, q, u, u_hi, u_lo, heads, D);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -273,22 +272,15 @@ hipError_t sf_launch_pool_probe(const SfPoolArgs& a, hipStream_t s) {
   if (a.S > 1 && !a.ml) return hipErrorInvalidValue;
   const size_t lds = pool_lds(((size_t)PCH * (a.D + 4) + 4 * 64 * 4 + 16 * PCH + 96) * sizeof(float) + (size_t)2 * 16 * (a.D + 8) * sizeof(bf16_t));
   const dim3 grid(a.F * a.S);
-#define SF_POOL_CASE(NH, KI)                                                                                          \
-  {                                                                                                                   \
-    static SfPerDeviceOnce once;                                                                                      \
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_pool_probe_kernel<NH, KI>),         \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);              \
-    hipLaunchKernelGGL((sf_pool_probe_kernel<NH, KI>), grid, dim3(256), lds, s, a);                                   \
-  }
+#define SF_POOL_CASE(NH, KI) return sf_launch_big_lds(sf_pool_probe_kernel<NH, KI>, grid, dim3(256), lds, s, a);
   // D = 64 heads: k-steps per wave = ceil(2 heads / 4)
   if (a.heads <= 2) SF_POOL_CASE(4, 1)
-  else if (a.heads <= 4) SF_POOL_CASE(4, 2)
-  else if (a.heads <= 6) SF_POOL_CASE(8, 3)
-  else if (a.heads <= 8) SF_POOL_CASE(8, 4)
-  else if (a.heads <= 12) SF_POOL_CASE(12, 6)
-  else SF_POOL_CASE(16, 8)
+  if (a.heads <= 4) SF_POOL_CASE(4, 2)
+  if (a.heads <= 6) SF_POOL_CASE(8, 3)
+  if (a.heads <= 8) SF_POOL_CASE(8, 4)
+  if (a.heads <= 12) SF_POOL_CASE(12, 6)
+  SF_POOL_CASE(16, 8)
 #undef SF_POOL_CASE
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -431,21 +423,14 @@ hipError_t sf_launch_pool_ctx(const SfPoolCtxArgs& a, hipStream_t s) {
   if (a.heads > 16 || a.D != a.heads * 64 || a.D > 1024 || a.F <= 0 || a.S < 1 || a.S > 8 || (a.S > 1 && !a.ml)) return hipErrorInvalidValue;
   const size_t lds = pool_lds(((size_t)4 * 64 * 4 + (a.S > 1 ? (size_t)16 * (a.D + 4) + 16 * 8 : 0)) * sizeof(float));
   const dim3 grid((a.F + 15) / 16, a.heads * 4);
-#define SF_CTX_CASE(KI)                                                                                               \
-  {                                                                                                                   \
-    static SfPerDeviceOnce once;                                                                                      \
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_pool_ctx_kernel<KI>),               \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);              \
-    hipLaunchKernelGGL(sf_pool_ctx_kernel<KI>, grid, dim3(256), lds, s, a);                                           \
-  }
+#define SF_CTX_CASE(KI) return sf_launch_big_lds(sf_pool_ctx_kernel<KI>, grid, dim3(256), lds, s, a);
   if (a.heads <= 2) SF_CTX_CASE(1)
-  else if (a.heads <= 4) SF_CTX_CASE(2)
-  else if (a.heads <= 6) SF_CTX_CASE(3)
-  else if (a.heads <= 8) SF_CTX_CASE(4)
-  else if (a.heads <= 12) SF_CTX_CASE(6)
-  else SF_CTX_CASE(8)
+  if (a.heads <= 4) SF_CTX_CASE(2)
+  if (a.heads <= 6) SF_CTX_CASE(3)
+  if (a.heads <= 8) SF_CTX_CASE(4)
+  if (a.heads <= 12) SF_CTX_CASE(6)
+  SF_CTX_CASE(8)
 #undef SF_CTX_CASE
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -534,22 +519,15 @@ hipError_t sf_launch_rowlin(const SfRowLinArgs& a, hipStream_t s) {
   int cpw = (a.N + 1023) / 1024;                      // ~256 workgroups of four columns at a time
   const dim3 grid((a.N + 4 * cpw - 1) / (4 * cpw));
   const size_t lds = (size_t)fr * a.K * sizeof(float);
-#define SF_RL(KI, FR)                                                                                                         \
-  {                                                                                                                           \
-    static SfPerDeviceOnce once;                                                                                              \
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_rowlin_kernel<KI, FR>),                     \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);                       \
-    hipLaunchKernelGGL((sf_rowlin_kernel<KI, FR>), grid, dim3(256), lds, s, a, cpw);                                          \
-  }
-#define SF_RL_F(KI) { if (fr == 1) SF_RL(KI, 1) else if (fr == 2) SF_RL(KI, 2) else SF_RL(KI, 4) }
+#define SF_RL(KI, FR) return sf_launch_big_lds(sf_rowlin_kernel<KI, FR>, grid, dim3(256), lds, s, a, cpw);
+#define SF_RL_F(KI) { if (fr == 1) SF_RL(KI, 1) if (fr == 2) SF_RL(KI, 2) SF_RL(KI, 4) }
   if (ki <= 1) SF_RL_F(1)
-  else if (ki <= 2) SF_RL_F(2)
-  else if (ki <= 4) SF_RL_F(4)
-  else if (ki <= 6) SF_RL_F(6)
-  else SF_RL_F(8)
+  if (ki <= 2) SF_RL_F(2)
+  if (ki <= 4) SF_RL_F(4)
+  if (ki <= 6) SF_RL_F(6)
+  SF_RL_F(8)
 #undef SF_RL_F
 #undef SF_RL
-  return hipGetLastError();
 }
 
 // ================================================================================================
@@ -612,9 +590,9 @@ __global__ __launch_bounds__(256) void sf_pool_dwv_kernel(const float* __restric
 hipError_t sf_launch_pool_ctx_bwd(const float* dctx, const bf16_t* wT, int ldt, int col0, const float* z, float* dz, float* dwv, int ldw,
                                   float* dbv, int F, int heads, int D, hipStream_t s) {
   if (heads > 16 || D != heads * 64 || D > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_pool_dz_kernel, dim3((F + 15) / 16, heads), dim3(256), 0, s, dctx, wT, ldt, col0, dz, F, heads, D);
-  if (dwv || dbv) hipLaunchKernelGGL(sf_pool_dwv_kernel, dim3(heads, 8), dim3(256), 0, s, dctx, z, dwv, ldw, dbv, F, heads, D);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_pool_dz_kernel, dim3((F + 15) / 16, heads), dim3(256), 0, s, dctx, wT, ldt, col0, dz, F, heads, D);
+  if (e != hipSuccess || !(dwv || dbv)) return e;
+  return sf_launch(sf_pool_dwv_kernel, dim3(heads, 8), dim3(256), 0, s, dctx, z, dwv, ldw, dbv, F, heads, D);
 }
 
 // probe attention backward: grid (F, S2), 256 threads; bf16 operands like every backward GEMM.
@@ -778,21 +756,14 @@ hipError_t sf_launch_pool_probe_bwd(const SfPoolBwdArgs& a, hipStream_t s) {
   const size_t lds = lds_for(S2);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   const dim3 grid(a.F, S2);
-#define SF_PB_CASE(KS)                                                                                                 \
-  {                                                                                                                    \
-    static SfPerDeviceOnce once;                                                                                       \
-    if (once.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_pool_probe_bwd_kernel<KS>),          \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);               \
-    hipLaunchKernelGGL(sf_pool_probe_bwd_kernel<KS>, grid, dim3(256), lds, s, a);                                      \
-  }
+#define SF_PB_CASE(KS) return sf_launch_big_lds(sf_pool_probe_bwd_kernel<KS>, grid, dim3(256), lds, s, a);
   const int nks = a.D / 32;
   if (nks <= 4) SF_PB_CASE(4)
-  else if (nks <= 8) SF_PB_CASE(8)
-  else if (nks <= 16) SF_PB_CASE(16)
-  else if (nks <= 24) SF_PB_CASE(24)
-  else SF_PB_CASE(32)
+  if (nks <= 8) SF_PB_CASE(8)
+  if (nks <= 16) SF_PB_CASE(16)
+  if (nks <= 24) SF_PB_CASE(24)
+  SF_PB_CASE(32)
 #undef SF_PB_CASE
-  return hipGetLastError();
 }
 
 // dWk[h*64 + j][d] += q[h*64 + j] dU[h][d];  dq[h*64 + j] = sum_d Wk[h*64 + j][d] dU[h][d]     (grid D rows, 256 threads)
@@ -813,8 +784,7 @@ __global__ __launch_bounds__(256) void sf_pool_u_bwd_kernel(const float* __restr
   if (tid == 0) dq[c] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 hipError_t sf_launch_pool_u_bwd(const float* du, const float* wk, const float* q, float* dwk, float* dq, int D, hipStream_t s) {
-  hipLaunchKernelGGL(sf_pool_u_bwd_kernel, dim3(D), dim3(256), 0, s, du, wk, q, dwk, dq, D);
-  return hipGetLastError();
+  return sf_launch(sf_pool_u_bwd_kernel, dim3(D), dim3(256), 0, s, du, wk, q, dwk, dq, D);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -907,11 +877,8 @@ hipError_t sf_launch_pool_generic(const SfPoolGenArgs& a_in, hipStream_t s) {
   a.scores = a.scratch;                                      // [F][heads][N]
   a.z = a.scratch + (size_t)a.F * a.heads * a.N;             // [F][heads][D]
   const size_t lds = (size_t)a.heads * a.N * sizeof(float);
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_pool_gen_z_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  hipLaunchKernelGGL(sf_pool_gen_scores_kernel, dim3((a.N + 3) / 4, a.F), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(sf_pool_gen_z_kernel, dim3((a.D + 255) / 256, a.F), dim3(256), lds, s, a);
-  hipLaunchKernelGGL(sf_pool_gen_ctx_kernel, dim3((a.D + 63) / 64, a.F), dim3(256), 0, s, a);
-  return hipGetLastError();
+  hipError_t e = sf_launch(sf_pool_gen_scores_kernel, dim3((a.N + 3) / 4, a.F), dim3(256), 0, s, a);
+  if (e == hipSuccess) e = sf_launch_big_lds(sf_pool_gen_z_kernel, dim3((a.D + 255) / 256, a.F), dim3(256), lds, s, a);
+  if (e == hipSuccess) e = sf_launch(sf_pool_gen_ctx_kernel, dim3((a.D + 63) / 64, a.F), dim3(256), 0, s, a);
+  return e;
 }

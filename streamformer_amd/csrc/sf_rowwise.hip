@@ -92,11 +92,10 @@ hipError_t sf_launch_layernorm(const float* x, const float* gamma, const float* 
   if (D % 4 || D > 64 * 4 * 16) return hipErrorInvalidValue;
   const dim3 grid((rows + 3) / 4), block(256);
   const int nv = (D / 4 + 63) / 64;
-  if (nv <= 1) hipLaunchKernelGGL(sf_layernorm_kernel<1>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
-  else if (nv <= 3) hipLaunchKernelGGL(sf_layernorm_kernel<3>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
-  else if (nv <= 8) hipLaunchKernelGGL(sf_layernorm_kernel<8>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
-  else hipLaunchKernelGGL(sf_layernorm_kernel<16>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
-  return hipGetLastError();
+  if (nv <= 1) return sf_launch(sf_layernorm_kernel<1>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
+  if (nv <= 3) return sf_launch(sf_layernorm_kernel<3>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
+  if (nv <= 8) return sf_launch(sf_layernorm_kernel<8>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
+  return sf_launch(sf_layernorm_kernel<16>, grid, block, 0, s, x, gamma, beta, y_f32, y_hi, y_lo, rows, D, eps, xp_hi, xp_lo, xp_lo2, y_f32_ind);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -238,15 +237,13 @@ hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi
     if (!total) return hipSuccess;
     const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     if (tab_write) {
-#define SF_PG_TAB(IN) hipLaunchKernelGGL(sf_patchify_generic_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp_write, spv, tab_write, *tab_value)
+#define SF_PG_TAB(IN) return sf_launch(sf_patchify_generic_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp_write, spv, tab_write, *tab_value)
       if (pixel_kind == 2) SF_PG_TAB(2); else if (pixel_kind == 1) SF_PG_TAB(1); else SF_PG_TAB(0);
 #undef SF_PG_TAB
-      return hipGetLastError();
     }
-    if (pixel_kind == 2) hipLaunchKernelGGL(sf_patchify_generic_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
-    else if (pixel_kind == 1) hipLaunchKernelGGL(sf_patchify_generic_kernel<1>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
-    else hipLaunchKernelGGL(sf_patchify_generic_kernel<0>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
-    return hipGetLastError();
+    if (pixel_kind == 2) return sf_launch(sf_patchify_generic_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
+    if (pixel_kind == 1) return sf_launch(sf_patchify_generic_kernel<1>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
+    return sf_launch(sf_patchify_generic_kernel<0>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, Kpad, norm, sp, sp_write, spv);
   }
   if (pixel_kind == 2 && C > 4) return hipErrorInvalidValue;
   const int gh = H / P, gw = W / P;
@@ -254,18 +251,15 @@ hipError_t sf_launch_patchify(const void* pixels, int pixel_kind, bf16_t* out_hi
   if (!total) return hipSuccess;
   const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   if (tab_write) {
-#define SF_P_TAB(IN) hipLaunchKernelGGL(sf_patchify_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp_write, spv, tab_write, *tab_value)
+#define SF_P_TAB(IN) return sf_launch(sf_patchify_tab_kernel<IN>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp_write, spv, tab_write, *tab_value)
     if (pixel_kind == 2) SF_P_TAB(2); else if (pixel_kind == 1) SF_P_TAB(1); else SF_P_TAB(0);
 #undef SF_P_TAB
-    return hipGetLastError();
   }
   if (pixel_kind == 2)
-    hipLaunchKernelGGL(sf_patchify_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
-  else if (pixel_kind == 1)
-    hipLaunchKernelGGL(sf_patchify_kernel<1>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
-  else
-    hipLaunchKernelGGL(sf_patchify_kernel<0>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
-  return hipGetLastError();
+    return sf_launch(sf_patchify_kernel<2>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
+  if (pixel_kind == 1)
+    return sf_launch(sf_patchify_kernel<1>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
+  return sf_launch(sf_patchify_kernel<0>, dim3(blocks), dim3(256), 0, s, pixels, out_hi, out_lo, F, C, H, W, P, gh, gw, norm, sp, sp_write, spv);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -286,8 +280,7 @@ hipError_t sf_launch_split(const float* x, bf16_t* hi, bf16_t* lo, size_t n, hip
   if (!n) return hipSuccess;
   const size_t n4 = n / 4;
   const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-  hipLaunchKernelGGL(sf_split_kernel, dim3(blocks), dim3(256), 0, s, x, hi, lo, n4);
-  return hipGetLastError();
+  return sf_launch(sf_split_kernel, dim3(blocks), dim3(256), 0, s, x, hi, lo, n4);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -325,8 +318,7 @@ __global__ __launch_bounds__(256) void sf_rowstats_cast_kernel(const float* __re
 hipError_t sf_launch_rowstats_cast(const float* x, bf16_t* xb, float* stats, int rows, int D, hipStream_t s, bf16_t* xlo, bf16_t* xlo2, int wide) {
   if (rows <= 0) return hipSuccess;
   if (D % 4) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_rowstats_cast_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, xb, xlo, xlo2, stats, rows, D, (wide || xlo) ? 1 : 0);
-  return hipGetLastError();
+  return sf_launch(sf_rowstats_cast_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, xb, xlo, xlo2, stats, rows, D, (wide || xlo) ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -341,8 +333,7 @@ __global__ __launch_bounds__(256) void sf_gather_rows_kernel(const float* __rest
 hipError_t sf_launch_gather_rows(const float* table, float* out, const SfRowIndex& idx, int D, hipStream_t s, const int* base_dev,
                                  const SfStreamSlot* tab) {
   if (idx.n <= 0 || idx.n > 256) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_gather_rows_kernel, dim3(idx.n), dim3(256), 0, s, table, out, idx, D, base_dev, tab);
-  return hipGetLastError();
+  return sf_launch(sf_gather_rows_kernel, dim3(idx.n), dim3(256), 0, s, table, out, idx, D, base_dev, tab);
 }
 
 
@@ -363,8 +354,7 @@ hipError_t sf_launch_pos_time_table(const float* pos, const float* time_rows, fl
   if (D % 4) return hipErrorInvalidValue;
   const size_t total = (size_t)T * N * (D / 4);
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(sf_pos_time_table_kernel, dim3(blocks), dim3(256), 0, s, pos, time_rows, out, T, N, D / 4);
-  return hipGetLastError();
+  return sf_launch(sf_pos_time_table_kernel, dim3(blocks), dim3(256), 0, s, pos, time_rows, out, T, N, D / 4);
 }
 
 __global__ __launch_bounds__(256) void sf_copy2_kernel(const float* __restrict__ a_src, float* __restrict__ a_dst, size_t na4,
@@ -382,6 +372,5 @@ hipError_t sf_launch_copy2(const float* a_src, float* a_dst, size_t na, const fl
   if (!b_src || (!b_dst && !sp)) nb = 0;
   const size_t n4 = (na + nb) / 4;
   if (!n4) return hipSuccess;
-  hipLaunchKernelGGL(sf_copy2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a_src, a_dst, na / 4, b_src, b_dst, nb / 4, sp);
-  return hipGetLastError();
+  return sf_launch(sf_copy2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a_src, a_dst, na / 4, b_src, b_dst, nb / 4, sp);
 }

@@ -250,8 +250,7 @@ static hipError_t text_launch_embed(const int* ids, const float* tok, const floa
   const size_t total = (size_t)rows * (D / 4);
   size_t grid = (total + 255) / 256;
   if (grid > 4096) grid = 4096;
-  hipLaunchKernelGGL(sf_text_embed_kernel, dim3((unsigned)grid), dim3(256), 0, s, ids, tok, pos, out, rows, L, D / 4, vocab);
-  return hipGetLastError();
+  return sf_launch(sf_text_embed_kernel, dim3((unsigned)grid), dim3(256), 0, s, ids, tok, pos, out, rows, L, D / 4, vocab);
 }
 
 static hipError_t text_launch_attention(const SfTextAttn& p, hipStream_t s) {
@@ -262,22 +261,14 @@ static hipError_t text_launch_attention(const SfTextAttn& p, hipStream_t s) {
   if ((size_t)p.B * p.heads > 0x7fffffffu) return hipErrorInvalidValue;
   const int Lp = (p.L + 15) & ~15;
   const size_t lds = (size_t)2 * Lp * (hd + 4) * sizeof(float);      // <= 132 KB at L = 128, head_dim 128
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-#define TA_ATTR(E) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_text_attention_kernel<2 * E>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * SF_TEXT_MAX_L * 132 * 4);
-    TA_ATTR(1) TA_ATTR(2) TA_ATTR(3) TA_ATTR(4) TA_ATTR(5) TA_ATTR(6) TA_ATTR(7) TA_ATTR(8)
-    TA_ATTR(9) TA_ATTR(10) TA_ATTR(11) TA_ATTR(12) TA_ATTR(13) TA_ATTR(14) TA_ATTR(15) TA_ATTR(16)
-#undef TA_ATTR
-  }
   const dim3 grid((unsigned)(p.B * p.heads)), block(256);
   switch (hd / 8) {
-#define TA_CASE(E) case E: hipLaunchKernelGGL((sf_text_attention_kernel<2 * E>), grid, block, lds, s, p); break;
+#define TA_CASE(E) case E: return sf_launch_big_lds(sf_text_attention_kernel<2 * E>, grid, block, lds, s, p);
     TA_CASE(1) TA_CASE(2) TA_CASE(3) TA_CASE(4) TA_CASE(5) TA_CASE(6) TA_CASE(7) TA_CASE(8)
     TA_CASE(9) TA_CASE(10) TA_CASE(11) TA_CASE(12) TA_CASE(13) TA_CASE(14) TA_CASE(15) TA_CASE(16)
 #undef TA_CASE
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
 }
 
 // out [B, P] (group == 0), or the normalised group means [B / group, P] with `scratch` [B, P] holding the pooled rows
@@ -288,17 +279,11 @@ static hipError_t text_launch_pool(const float* x, int B, int L, int D, const fl
   if (((uintptr_t)x & 15) || ((uintptr_t)w & 15)) return hipErrorInvalidValue;
   float* pooled = group ? scratch : out;
   const dim3 grid((unsigned)((B + SF_TEXT_POOL_ROWS - 1) / SF_TEXT_POOL_ROWS), (unsigned)((P + SF_TEXT_POOL_COLS - 1) / SF_TEXT_POOL_COLS));
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_text_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              SF_TEXT_POOL_ROWS * SF_TEXT_MAX_D * 4);
-  hipLaunchKernelGGL(sf_text_pool_kernel, grid, dim3(256), (size_t)SF_TEXT_POOL_ROWS * D * sizeof(float), s, x, B, L, D, gamma, beta, eps, w,
-                     bias, P, pooled);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = sf_launch_big_lds(sf_text_pool_kernel, grid, dim3(256), (size_t)SF_TEXT_POOL_ROWS * D * sizeof(float), s, x, B, L, D, gamma,
+                                         beta, eps, w, bias, P, pooled);
   if (e != hipSuccess || !group) return e;
   const int labels = B / group;
-  hipLaunchKernelGGL(sf_text_group_mean_kernel, dim3((unsigned)((labels + 3) / 4)), dim3(256), 0, s, pooled, out, labels, group, P);
-  return hipGetLastError();
+  return sf_launch(sf_text_group_mean_kernel, dim3((unsigned)((labels + 3) / 4)), dim3(256), 0, s, pooled, out, labels, group, P);
 }
 
 // ------------------------------------------------------------------------------------------------

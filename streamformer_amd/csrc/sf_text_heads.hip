@@ -99,13 +99,9 @@ template <int KV>
 static int tl_launch(const float* x, const float* text, int M, int D, int n, int chunk, const float* ls, const float* lb, float* out,
                      hipStream_t s) {
   const size_t lds = (size_t)chunk * KV * 64 * sizeof(float4);
-  static SfPerDeviceOnce attr_set;              // past the default dynamic-LDS window: a per-device setting, made once
-  if (attr_set.first())
-    HIP_TRY(hipFuncSetAttribute((const void*)sf_dense_text_logits_kernel<KV>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_TL_LDS_BYTES));
   int grid = (M + SF_TL_WAVES - 1) / SF_TL_WAVES;
   if (grid > 512) grid = 512;                   // two workgroups per CU; co-resident (16 waves, two rows each in flight) while 2 x lds <= 160 KB
-  hipLaunchKernelGGL(sf_dense_text_logits_kernel<KV>, dim3(grid), dim3(SF_TL_THREADS), lds, s, x, text, M, D, n, chunk, ls, lb, out);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(sf_launch_big_lds(sf_dense_text_logits_kernel<KV>, dim3(grid), dim3(SF_TL_THREADS), lds, s, x, text, M, D, n, chunk, ls, lb, out));
   return SF_OK;
 }
 

@@ -89,8 +89,7 @@ hipError_t sf_launch_rowscale_bf16(const bf16_t* in, bf16_t* out, const float* s
   const size_t n = (size_t)rows * (D / 8);
   if (!n) return hipSuccess;
   if (n * 8 >= ((size_t)1 << 32)) return hipErrorInvalidValue;       // mask indices are 32-bit
-  hipLaunchKernelGGL(sf_rowscale_bf16_kernel, dim3(ew_grid(n)), dim3(256), 0, s, in, out, scales, n, D / 8, mode, T, N, drop);
-  return hipGetLastError();
+  return sf_launch(sf_rowscale_bf16_kernel, dim3(ew_grid(n)), dim3(256), 0, s, in, out, scales, n, D / 8, mode, T, N, drop);
 }
 // out = resid + scale[group(row)] * mask * y        (out may alias resid)
 __global__ __launch_bounds__(256) void sf_resid_rowscale_kernel(float* __restrict__ out, const float* __restrict__ resid, const float* __restrict__ y,
@@ -113,8 +112,7 @@ hipError_t sf_launch_resid_rowscale(float* out, const float* resid, const float*
   const size_t n = (size_t)rows * (D / 4);
   if (!n) return hipSuccess;
   if (n * 4 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_resid_rowscale_kernel, dim3(ew_grid(n)), dim3(256), 0, s, out, resid, y, scales, n, D / 4, mode, T, N, drop);
-  return hipGetLastError();
+  return sf_launch(sf_resid_rowscale_kernel, dim3(ew_grid(n)), dim3(256), 0, s, out, resid, y, scales, n, D / 4, mode, T, N, drop);
 }
 // h = m_time o (m_pos o h + time[t])   (modeling:374, 378; rows (b, t, n))
 __global__ __launch_bounds__(256) void sf_embed_dropout_kernel(float* __restrict__ h, const float* __restrict__ te, size_t nchunks, int D4, int T, int N,
@@ -135,8 +133,7 @@ hipError_t sf_launch_embed_dropout(float* h, const float* time_rows, int M, int 
   const size_t n = (size_t)M * (D / 4);
   if (!n) return hipSuccess;
   if (n * 4 >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_embed_dropout_kernel, dim3(ew_grid(n)), dim3(256), 0, s, h, time_rows, n, D / 4, T, N, pos_drop, time_drop);
-  return hipGetLastError();
+  return sf_launch(sf_embed_dropout_kernel, dim3(ew_grid(n)), dim3(256), 0, s, h, time_rows, n, D / 4, T, N, pos_drop, time_drop);
 }
 __global__ __launch_bounds__(256) void sf_dropout_f32_kernel(float* __restrict__ g, bf16_t* __restrict__ g_bf, size_t nchunks, SfDrop d) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (size_t)gridDim.x * 256) {
@@ -152,21 +149,18 @@ hipError_t sf_launch_dropout_f32(float* g, bf16_t* g_bf, size_t n, SfDrop drop, 
   if (n % 4 || !drop.on) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
   if (n >= ((size_t)1 << 32)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_dropout_f32_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, s, g, g_bf, n / 4, drop);
-  return hipGetLastError();
+  return sf_launch(sf_dropout_f32_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, s, g, g_bf, n / 4, drop);
 }
 
 hipError_t sf_launch_gelu_fwd(const bf16_t* pre, bf16_t* act, size_t n, hipStream_t s) {
   if (n % 8) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(sf_gelu_fwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, s, pre, act, n / 8);
-  return hipGetLastError();
+  return sf_launch(sf_gelu_fwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, s, pre, act, n / 8);
 }
 hipError_t sf_launch_gelu_bwd(bf16_t* d, const bf16_t* pre, size_t n, hipStream_t s) {
   if (n % 8) return hipErrorInvalidValue;
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(sf_gelu_bwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, s, d, pre, n / 8);
-  return hipGetLastError();
+  return sf_launch(sf_gelu_bwd_kernel, dim3(ew_grid(n / 8)), dim3(256), 0, s, d, pre, n / 8);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -332,22 +326,13 @@ hipError_t sf_launch_ln_bwd(const float* x, const void* dy, int dy_is_bf16, cons
   if (blocks > LN_BWD_MAX_BLOCKS) blocks = LN_BWD_MAX_BLOCKS;
   const size_t lds = (size_t)3 * 2 * D * sizeof(float);
   const int nv = (D / 4 + 63) / 64;
-#define SF_LNB(MV)                                                                                                                     \
-  do {                                                                                                                               \
-    if (dy_is_bf16) hipLaunchKernelGGL((sf_ln_bwd_kernel<MV, true>), dim3(blocks), dim3(256), lds, s, x, dy, gamma, g_in, g_out, g_out_bf, partial, rows, D, eps); \
-    else hipLaunchKernelGGL((sf_ln_bwd_kernel<MV, false>), dim3(blocks), dim3(256), lds, s, x, dy, gamma, g_in, g_out, g_out_bf, partial, rows, D, eps);           \
-  } while (0)
-  if (nv <= 1) SF_LNB(1);
-  else if (nv <= 3) SF_LNB(3);
-  else SF_LNB(8);
+#define SF_LNB(MV)                                                                                                                                    \
+  (dy_is_bf16 ? sf_launch(sf_ln_bwd_kernel<MV, true>, dim3(blocks), dim3(256), lds, s, x, dy, gamma, g_in, g_out, g_out_bf, partial, rows, D, eps)    \
+              : sf_launch(sf_ln_bwd_kernel<MV, false>, dim3(blocks), dim3(256), lds, s, x, dy, gamma, g_in, g_out, g_out_bf, partial, rows, D, eps))
+  const hipError_t e = nv <= 1 ? SF_LNB(1) : (nv <= 3 ? SF_LNB(3) : SF_LNB(8));
 #undef SF_LNB
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  if (d_gamma || d_beta) {
-    hipLaunchKernelGGL(sf_ln_bwd_finish_kernel, dim3((D + 63) / 64), dim3(1024), 0, s, partial, blocks, D, d_gamma, d_beta);
-    e = hipGetLastError();
-  }
-  return e;
+  if (e != hipSuccess || !(d_gamma || d_beta)) return e;
+  return sf_launch(sf_ln_bwd_finish_kernel, dim3((D + 63) / 64), dim3(1024), 0, s, partial, blocks, D, d_gamma, d_beta);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -410,9 +395,9 @@ hipError_t sf_launch_colsum_bf16(const bf16_t* x, int rows, int cols, int ld, fl
   int rpc = 256;
   while ((rows + rpc - 1) / rpc > CS_MAX_CHUNKS) rpc *= 2;
   const int nchunks = (rows + rpc - 1) / rpc;
-  hipLaunchKernelGGL(sf_colsum_bf16_kernel, dim3((cols + 255) / 256, nchunks), dim3(256), 0, s, x, rows, cols, ld, rpc, partial);
-  hipLaunchKernelGGL(sf_colsum_finish_kernel, dim3((cols + 63) / 64), dim3(256), 0, s, partial, nchunks, cols, alpha, out, accumulate);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_colsum_bf16_kernel, dim3((cols + 255) / 256, nchunks), dim3(256), 0, s, x, rows, cols, ld, rpc, partial);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_colsum_finish_kernel, dim3((cols + 63) / 64), dim3(256), 0, s, partial, nchunks, cols, alpha, out, accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -434,8 +419,7 @@ hipError_t sf_launch_sum_rows(const float* in, float* out, int n_out, int n_a, l
                               long stride_r, int D, int accumulate, hipStream_t s) {
   if (n_out <= 0) return hipSuccess;
   if (D % 4 || n_a <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_sum_rows_kernel, dim3(n_out), dim3(256), 0, s, in, out, n_a, stride_a, stride_b, R, stride_r, D, accumulate);
-  return hipGetLastError();
+  return sf_launch(sf_sum_rows_kernel, dim3(n_out), dim3(256), 0, s, in, out, n_a, stride_a, stride_b, R, stride_r, D, accumulate);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -545,8 +529,7 @@ __global__ __launch_bounds__(256) void sf_prep_weights_batched_kernel(const floa
 hipError_t sf_launch_prep_weights_batched(const float* base, const SfPrepJob* jobs_dev, int njobs, int total_tiles,
                                           hipStream_t s) {
   if (njobs <= 0 || total_tiles <= 0) return hipSuccess;
-  hipLaunchKernelGGL(sf_prep_weights_batched_kernel, dim3(total_tiles), dim3(256), 0, s, base, jobs_dev, njobs);
-  return hipGetLastError();
+  return sf_launch(sf_prep_weights_batched_kernel, dim3(total_tiles), dim3(256), 0, s, base, jobs_dev, njobs);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -563,8 +546,7 @@ __global__ __launch_bounds__(256) void sf_head_query_kernel(const float* __restr
 }
 hipError_t sf_launch_head_query(const float* probe, const float* wq, const float* bq, float scale, float* q, int D,
                                 hipStream_t s) {
-  hipLaunchKernelGGL(sf_head_query_kernel, dim3((D + 3) / 4), dim3(256), 0, s, probe, wq, bq, scale, q, D);
-  return hipGetLastError();
+  return sf_launch(sf_head_query_kernel, dim3((D + 3) / 4), dim3(256), 0, s, probe, wq, bq, scale, q, D);
 }
 
 __global__ __launch_bounds__(256) void sf_head_query_bwd_kernel(const float* __restrict__ dq, const float* __restrict__ probe,
@@ -585,8 +567,7 @@ __global__ __launch_bounds__(256) void sf_head_query_bwd_kernel(const float* __r
 }
 hipError_t sf_launch_head_query_bwd(const float* dq, const float* probe, const float* wq, float scale, float* d_wq,
                                     float* d_bq, float* d_probe, int D, hipStream_t s) {
-  hipLaunchKernelGGL(sf_head_query_bwd_kernel, dim3((D * D + 255) / 256), dim3(256), 0, s, dq, probe, wq, scale, d_wq, d_bq, d_probe, D);
-  return hipGetLastError();
+  return sf_launch(sf_head_query_bwd_kernel, dim3((D * D + 255) / 256), dim3(256), 0, s, dq, probe, wq, scale, d_wq, d_bq, d_probe, D);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -642,9 +623,9 @@ __global__ __launch_bounds__(64) void sf_gate_grad_finish_kernel(const float* __
 hipError_t sf_launch_gate_grad(const float* G, const float* cs, const float* w, const float* b, const float* gate,
                                float* d_w, float* d_b, float* d_gate, float* partial, int N, int K, hipStream_t s, const float* r1) {
   if (((size_t)N * K) % 4 || (K % 4)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sf_gate_grad_kernel, dim3(GATE_BLOCKS), dim3(256), 0, s, G, cs, w, b, gate, d_w, d_b, partial, N, K, r1);
-  hipLaunchKernelGGL(sf_gate_grad_finish_kernel, dim3(1), dim3(64), 0, s, partial, gate, d_gate);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_gate_grad_kernel, dim3(GATE_BLOCKS), dim3(256), 0, s, G, cs, w, b, gate, d_w, d_b, partial, N, K, r1);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_gate_grad_finish_kernel, dim3(1), dim3(64), 0, s, partial, gate, d_gate);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -714,9 +695,9 @@ hipError_t sf_launch_fuse_temporal(const float* base, const SfFuseJob* jobs_dev,
   if (layers <= 0) return hipSuccess;
   if (D % 64) return hipErrorInvalidValue;
   const int strips = (D / 16) * (D / 64);
-  hipLaunchKernelGGL(sf_fuse_temporal_kernel, dim3((strips + 3) / 4, layers), dim3(256), 0, s, jobs_dev, D);
-  hipLaunchKernelGGL(sf_fuse_temporal_bias_kernel, dim3((D + 3) / 4, layers), dim3(256), 0, s, base, jobs_dev, D);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_fuse_temporal_kernel, dim3((strips + 3) / 4, layers), dim3(256), 0, s, jobs_dev, D);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_fuse_temporal_bias_kernel, dim3((D + 3) / 4, layers), dim3(256), 0, s, base, jobs_dev, D);
 }
 // out[k] += sum_i w[i * ld + k] * v[i]   (w bf16 [rows, ld]): db_o = (tanh(g) W_d)^T colsum(g) of the fused temporal projections
 __global__ __launch_bounds__(1024) void sf_matvec_t_bf16_kernel(const bf16_t* __restrict__ w, int ld, const float* __restrict__ v, float* __restrict__ out,
@@ -738,8 +719,7 @@ __global__ __launch_bounds__(1024) void sf_matvec_t_bf16_kernel(const bf16_t* __
   }
 }
 hipError_t sf_launch_matvec_t_bf16(const bf16_t* w, int ld, const float* v, float* out, int rows, int cols, hipStream_t s) {
-  hipLaunchKernelGGL(sf_matvec_t_bf16_kernel, dim3((cols + 63) / 64), dim3(1024), 0, s, w, ld, v, out, rows, cols);
-  return hipGetLastError();
+  return sf_launch(sf_matvec_t_bf16_kernel, dim3((cols + 63) / 64), dim3(1024), 0, s, w, ld, v, out, rows, cols);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -804,8 +784,7 @@ __global__ __launch_bounds__(256) void sf_adamw_kernel(SfAdamWArgs a) {
 hipError_t sf_launch_adamw(const SfAdamWArgs& a, hipStream_t s) {
   if (a.n % 4 || a.nseg <= 0) return hipErrorInvalidValue;
   if (!a.n) return hipSuccess;
-  hipLaunchKernelGGL(sf_adamw_kernel, dim3(ew_grid(a.n / 4)), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return sf_launch(sf_adamw_kernel, dim3(ew_grid(a.n / 4)), dim3(256), 0, s, a);
 }
 
 // 16-byte loads, four in flight per lane, four independent accumulators (round 4: the 4-byte, one-at-a-time loop of the first version ran
@@ -838,7 +817,7 @@ __global__ __launch_bounds__(64) void sf_sumsq_finish_kernel(const float* __rest
 }
 hipError_t sf_launch_sumsq(const float* g, size_t n, float* out, float* partial, hipStream_t s) {
   const int blocks = 1024;
-  hipLaunchKernelGGL(sf_sumsq_kernel, dim3(blocks), dim3(256), 0, s, g, n, partial);
-  hipLaunchKernelGGL(sf_sumsq_finish_kernel, dim3(1), dim3(64), 0, s, partial, blocks, out);
-  return hipGetLastError();
+  const hipError_t e = sf_launch(sf_sumsq_kernel, dim3(blocks), dim3(256), 0, s, g, n, partial);
+  if (e != hipSuccess) return e;
+  return sf_launch(sf_sumsq_finish_kernel, dim3(1), dim3(64), 0, s, partial, blocks, out);
 }

@@ -409,14 +409,8 @@ __global__ __launch_bounds__(256) void sf_wgrad_reduce_kernel(const float* __res
 }
 
 static int wg_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-    if (cus < 16) cus = 256;
-  }
-  return cus;
+  const int cus = sf_device_cus();
+  return cus < 16 ? 256 : cus;
 }
 
 // ---- grouped 256^2 launches ----------------------------------------------------------------------------------------------
@@ -468,18 +462,13 @@ hipError_t sf_launch_wgrad_group(SfWgradGroup& g, hipStream_t s) {
   nsplit = (kt_total + kt_per - 1) / kt_per;
   const int items = ntiles * nsplit;
   const int per_xcd = (items + 7) / 8;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_wgrad256_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * WB_TILE_BYTES);
-  hipLaunchKernelGGL(sf_wgrad256_kernel, dim3(per_xcd * 8), dim3(WB_THREADS), 4 * WB_TILE_BYTES, s, g, ntiles, nsplit, per_xcd, kt_per, kt_total,
-                     (unsigned)part, (unsigned)bias);
-  hipError_t e = hipGetLastError();
+  const hipError_t e = sf_launch_big_lds(sf_wgrad256_kernel, dim3(per_xcd * 8), dim3(WB_THREADS), 4 * WB_TILE_BYTES, s, g, ntiles, nsplit, per_xcd,
+                                         kt_per, kt_total, (unsigned)part, (unsigned)bias);
   if (e != hipSuccess || nsplit == 1) return e;
   const int main_blocks = (int)(part / 1024);
   const int bias_blocks = (int)((bias + 255) / 256);
-  hipLaunchKernelGGL(sf_wgrad_group_reduce_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, g, nsplit, (unsigned)part, (unsigned)bias,
-                     main_blocks);
-  return hipGetLastError();
+  return sf_launch(sf_wgrad_group_reduce_kernel, dim3(main_blocks + bias_blocks), dim3(256), 0, s, g, nsplit, (unsigned)part, (unsigned)bias,
+                   main_blocks);
 }
 
 struct WgPlan { int tiles1, tiles2, ntiles, kt_total, kt_per, nsplit; };
@@ -518,17 +507,12 @@ hipError_t sf_launch_wgrad(const SfWgradArgs& a, hipStream_t s) {
   }
   const WgPlan pl = wg_plan(a.M, a.N1, a.N2);
   const size_t n12 = (size_t)a.N1 * a.N2;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * WG_TILE_BYTES);
-  hipLaunchKernelGGL(sf_wgrad_kernel, dim3(pl.ntiles * pl.nsplit), dim3(WG_THREADS), 4 * WG_TILE_BYTES, s, a, pl.tiles2, pl.ntiles,
-                     pl.kt_per, pl.kt_total);
-  hipError_t e = hipGetLastError();
+  hipError_t e = sf_launch_big_lds(sf_wgrad_kernel, dim3(pl.ntiles * pl.nsplit), dim3(WG_THREADS), 4 * WG_TILE_BYTES, s, a, pl.tiles2, pl.ntiles,
+                                   pl.kt_per, pl.kt_total);
   if (e != hipSuccess) return e;
   if (a.out) {
-    hipLaunchKernelGGL(sf_wgrad_reduce_kernel, dim3((unsigned)((n12 / 4 + 63) / 64)), dim3(256), 0, s, a.partial, pl.nsplit, n12, a.N2,
-                       a.alpha, a.out, a.ldo, a.accumulate);
-    e = hipGetLastError();
+    e = sf_launch(sf_wgrad_reduce_kernel, dim3((unsigned)((n12 / 4 + 63) / 64)), dim3(256), 0, s, a.partial, pl.nsplit, n12, a.N2,
+                  a.alpha, a.out, a.ldo, a.accumulate);
     if (e != hipSuccess) return e;
   }
   if (a.dbias)      // small-tile path: separate column-sum kernel

@@ -96,3 +96,19 @@ def test_switch_table_is_the_only_reader_of_the_environment():
         assert n == 0 or f.endswith("sf_switches.hip"), f
         total += n
     assert total <= 5
+
+
+def test_launch_header_is_the_only_place_that_sets_up_kernels():
+    """One launch helper (csrc/sf_launch.h): the dynamic-LDS attribute and the CU-count query live there and nowhere else in the product
+    sources, and the per-site once-per-device flags it replaced are gone."""
+    import glob
+    csrc = os.path.join(ROOT, "streamformer_amd", "csrc")
+    files = glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h"))
+    assert len(files) >= 30 and os.path.join(csrc, "sf_launch.h") in files
+    for f in files:
+        src = open(f).read()
+        assert "SfPerDeviceOnce" not in src, f
+        for name in ("hipFuncSetAttribute", "hipGetDeviceProperties"):
+            assert name not in src or f.endswith("sf_launch.h"), (name, f)
+    src = open(os.path.join(csrc, "sf_launch.h")).read()
+    assert "hipFuncSetAttribute(" in src and "hipGetDeviceProperties(" in src

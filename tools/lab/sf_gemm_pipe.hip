@@ -467,10 +467,6 @@ bool sf_gemm_pipe_supported(const SfGemmArgs& a, bool split) {
 hipError_t sf_launch_gemm_pipe(const SfGemmArgs& a, hipStream_t s) {
   int panels = 0, rows = 0;
   if (!pipe_plan(a.M, &panels, &rows)) return hipErrorInvalidValue;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_pipe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PI_LDS_BYTES);
   const int cus = pipe_cus();
-  hipLaunchKernelGGL(sf_gemm_pipe_kernel, dim3(panels < cus ? panels : cus), dim3(PI_THREADS), PI_LDS_BYTES, s, a, rows, panels, pipe_fail_flag());
-  return hipGetLastError();
+  return sf_launch_big_lds(sf_gemm_pipe_kernel, dim3(panels < cus ? panels : cus), dim3(PI_THREADS), PI_LDS_BYTES, s, a, rows, panels, pipe_fail_flag());
 }

@@ -295,14 +295,10 @@ bool sf_gemm_pp_supported(const SfGemmArgs& a, bool split) {
 hipError_t sf_launch_gemm_pp(const SfGemmArgs& a, hipStream_t s) {
   int panels = 0, rows = 0;
   if (!pp_plan(a.M, &panels, &rows)) return hipErrorInvalidValue;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_pp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Q_LDS_BYTES);
   // stagger = about one main loop of a tile running alone on its SIMDs (K-tiles x ~0.33 us), SF_PANEL_PP_STAGGER_NS overrides
   static const int forced_ns = getenv("SF_PANEL_PP_STAGGER_NS") ? atoi(getenv("SF_PANEL_PP_STAGGER_NS")) : -1;
   static const int mode = getenv("SF_PANEL_PP_STAGGER_MODE") ? atoi(getenv("SF_PANEL_PP_STAGGER_MODE")) : 1;
   const int ns = forced_ns >= 0 ? forced_ns : (a.K >> 5) * 330;
   const int stagger = ns > 0 ? sf_wall_clock_ticks(ns) : 0;
-  hipLaunchKernelGGL(sf_gemm_pp_kernel, dim3(panels * 4), dim3(Q_THREADS), Q_LDS_BYTES, s, a, rows, panels, stagger, mode);
-  return hipGetLastError();
+  return sf_launch_big_lds(sf_gemm_pp_kernel, dim3(panels * 4), dim3(Q_THREADS), Q_LDS_BYTES, s, a, rows, panels, stagger, mode);
 }

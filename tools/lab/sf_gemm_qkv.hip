@@ -330,22 +330,16 @@ hipError_t sf_launch_gemm_qkv(const SfQkvArgs& a, bool fused, hipStream_t s) {
     if (cached_cus < 8) cached_cus = 256;
   }
   cus = cached_cus;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first()) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_qkv_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * Q_SLOT_BYTES);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_gemm_qkv_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * Q_SLOT_BYTES);
-  }
   const size_t lds = 4 * Q_SLOT_BYTES;
   if (fused) {
     const int npanels = (a.B * a.NP + 12) / 13;
-    hipLaunchKernelGGL(sf_gemm_qkv_kernel<true>, dim3(cus), dim3(Q_THREADS), lds, s, a, 208, npanels);
+    return sf_launch_big_lds(sf_gemm_qkv_kernel<true>, dim3(cus), dim3(Q_THREADS), lds, s, a, 208, npanels);
   } else {
     // rows per tile: the panel plan of sf_gemm_panel.hip — P a multiple of CUs / 2 ... here simply ceil(M / panels) <= 208 with panels a multiple of 8
     int panels = ((a.M + 207) / 208 + 7) & ~7;
     int rows = (a.M + panels - 1) / panels;
     // prefer exactly 196-row panels when they divide M (one frame per panel at 224^2)
     if (a.M % 196 == 0 && ((a.M / 196) & 7) == 0) { panels = a.M / 196; rows = 196; }
-    hipLaunchKernelGGL(sf_gemm_qkv_kernel<false>, dim3(cus), dim3(Q_THREADS), lds, s, a, rows, panels);
+    return sf_launch_big_lds(sf_gemm_qkv_kernel<false>, dim3(cus), dim3(Q_THREADS), lds, s, a, rows, panels);
   }
-  return hipGetLastError();
 }

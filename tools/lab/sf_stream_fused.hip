@@ -232,10 +232,9 @@ hipError_t sf_launch_stream_qkv_decode(const SfStreamQkvArgs& a, hipStream_t s) 
   const dim3 grid((a.M + SQ_ROWS - 1) / SQ_ROWS, a.heads), block(SQ_THREADS);
   const size_t lds = (size_t)16 * a.K * 2 + 16 * 192 * 2;
   switch (a.K / 32) {
-    case 4: hipLaunchKernelGGL(sf_stream_qkv_decode_kernel<4>, grid, block, lds, s, a); break;
-    case 8: hipLaunchKernelGGL(sf_stream_qkv_decode_kernel<8>, grid, block, lds, s, a); break;
-    case 16: hipLaunchKernelGGL(sf_stream_qkv_decode_kernel<16>, grid, block, lds, s, a); break;
-    default: hipLaunchKernelGGL(sf_stream_qkv_decode_kernel<24>, grid, block, lds, s, a); break;
+    case 4: return sf_launch(sf_stream_qkv_decode_kernel<4>, grid, block, lds, s, a);
+    case 8: return sf_launch(sf_stream_qkv_decode_kernel<8>, grid, block, lds, s, a);
+    case 16: return sf_launch(sf_stream_qkv_decode_kernel<16>, grid, block, lds, s, a);
+    default: return sf_launch(sf_stream_qkv_decode_kernel<24>, grid, block, lds, s, a);
   }
-  return hipGetLastError();
 }

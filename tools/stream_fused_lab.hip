@@ -246,10 +246,6 @@ bool sf_qkv_decode_supported(const SfQkvDecodeArgs& a) {
 
 hipError_t sf_launch_qkv_decode(const SfQkvDecodeArgs& a, hipStream_t s) {
   if (!sf_qkv_decode_supported(a)) return hipErrorInvalidValue;
-  static SfPerDeviceOnce attr_set;
-  if (attr_set.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sf_qkv_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, QD_LDS);
   const int row_tiles = (a.M + QD_ROWS - 1) / QD_ROWS;
-  hipLaunchKernelGGL(sf_qkv_decode_kernel, dim3(row_tiles * a.heads), dim3(QD_THREADS), QD_LDS, s, a);
-  return hipGetLastError();
+  return sf_launch_big_lds(sf_qkv_decode_kernel, dim3(row_tiles * a.heads), dim3(QD_THREADS), QD_LDS, s, a);
 }
