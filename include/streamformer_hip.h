@@ -582,6 +582,36 @@ int sf_op_oad_attention(const float* q_dev, int q_streams, const float* k_dev, c
                         const float* k_pos_dev, const float* v_pos_dev, const float* mask_dev, float* ctx_dev, int streams, int Tq, int Tk,
                         int heads, int head_dim, int causal, sf_stream stream);
 
+/* ---- multi-scale deformable attention (Deformable DETR's MSDeformAttn; the reference's CUDA op under
+ * downstream/OVIS/mask2former/modeling/pixel_decoder/ops/, used by the Mask2Former pixel decoder and the ViT-Adapter) ----------
+ * out[n, q, m, :] = sum over levels l and points p of attention_weights[n, q, m, l, p] * bilinear(value[n, level l, m, :], location),
+ * all fp32.  value_dev [N, S, M, D]; spatial_shapes [L, 2] = (H_l, W_l) and level_start_index [L] are HOST arrays, copied into the
+ * kernel arguments; sampling_locations_dev [N, Lq, M, L, P, 2] normalised (x, y); attention_weights_dev [N, Lq, M, L, P];
+ * out_dev [N, Lq, M * D].  Sampling as the CUDA kernel and grid_sample(bilinear, zeros, align_corners=False): pixel = loc * size - 0.5,
+ * a sample counts iff -1 < h < H and -1 < w < W, each corner bounds-checked on its own.  D a multiple of 8 in 8..128, L and P in 1..8,
+ * N, S, M, Lq >= 1, sum of H_l * W_l == S, every level inside [0, S), value and out 16-byte aligned: anything else, and a null
+ * pointer, is SF_ERR_INVALID before anything is launched.  One owner per output element, one fixed order: bit-reproducible.      */
+int sf_op_msda_forward(const float* value_dev, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                       const float* sampling_locations_dev, const float* attention_weights_dev, float* out_dev, int N, int S, int M,
+                       int D, int Lq, int L, int P, sf_stream stream);
+/* The same with the front of MSDeformAttn.forward (modules/ms_deform_attn.py:102-112) folded in: offsets_dev holds the RAW rows of
+ * the sampling_offsets Linear, [N * Lq] rows of offsets_ld floats of which the first M * L * P * 2 are read; logits_dev the raw rows
+ * of the attention_weights Linear, logits_ld floats each, the first M * L * P read (both may be column ranges of one GEMM output);
+ * reference_points_dev [N, Lq, L, ref_dim].  The softmax over L * P and the sampling location (ref_dim 2: ref + offset / (W_l, H_l);
+ * ref_dim 4: ref_xy + offset / P * ref_wh * 0.5) are computed in the kernel; padding_mask_dev [N, S] uint8 or NULL: a non-zero
+ * entry makes that value row read as zeros.  Neither the locations, nor the softmax, nor a masked copy of value is ever stored.  */
+int sf_op_msda_forward_fused(const float* value_dev, const uint8_t* padding_mask_dev, const int32_t* spatial_shapes,
+                             const int32_t* level_start_index, const float* offsets_dev, int offsets_ld, const float* logits_dev,
+                             int logits_ld, const float* reference_points_dev, int ref_dim, float* out_dev, int N, int S, int M, int D,
+                             int Lq, int L, int P, sf_stream stream);
+/* Backward of sf_op_msda_forward for grad_out_dev [N, Lq, M * D]: grad_value_dev [N, S, M, D] is zeroed by the call and then
+ * accumulated with float atomics, grad_sampling_locations_dev [N, Lq, M, L, P, 2] and grad_attention_weights_dev [N, Lq, M, L, P]
+ * are written once by their one owner.  The latter two are bit-reproducible; grad_value is a sum in arrival order and is not.    */
+int sf_op_msda_backward(const float* value_dev, const int32_t* spatial_shapes, const int32_t* level_start_index,
+                        const float* sampling_locations_dev, const float* attention_weights_dev, const float* grad_out_dev,
+                        float* grad_value_dev, float* grad_sampling_locations_dev, float* grad_attention_weights_dev, int N, int S,
+                        int M, int D, int Lq, int L, int P, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */
