@@ -8,7 +8,9 @@ has already loaded and shares its device context, allocator pointers and streams
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 import os
+import weakref
 
 import torch  # noqa: F401  (must precede the CDLL below: shared HIP runtime)
 
@@ -230,11 +232,126 @@ def load_tensors(handle, load_fn, items, dtype_of=None) -> None:
         check(load_fn(handle, k.encode(), t.data_ptr(), code, shape, t.dim()))
 
 
-def grow_workspace(current, nbytes: int, device):
-    """The grow-only byte buffer of a module: ``current`` when it is large enough and on ``device``, else a new one."""
-    if current is None or current.numel() < nbytes or current.device != device:
-        current = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
-    return current
+_COMPUTE_MODES = {"bf16": SF_COMPUTE_BF16, "bfloat16": SF_COMPUTE_BF16, torch.bfloat16: SF_COMPUTE_BF16,
+                  "bf16x3": SF_COMPUTE_BF16X3, "fp32": SF_COMPUTE_BF16X3, "float32": SF_COMPUTE_BF16X3, torch.float32: SF_COMPUTE_BF16X3}
+
+
+def compute_mode(value) -> int:
+    """The SF_COMPUTE_* code of a module's ``compute_dtype`` argument."""
+    try:
+        return _COMPUTE_MODES[value]
+    except KeyError:
+        raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {value!r}") from None
+
+
+class OwnedHandle(C.c_void_p):
+    """A native handle that is not rebuilt from weights (a probe, a detector state, a stream cache).  It IS the ``c_void_p``: its
+    ``*_create`` fills it through ``C.byref`` and every entry point takes it as it is.  Destroyed once, by ``release()`` or when it is
+    collected; false afterwards; never copied."""
+
+    def __init__(self, destroy, noun: str):
+        super().__init__()
+        self._destroy, self._noun = destroy, noun
+
+    def release(self) -> None:
+        h, self.value = self.value, None
+        if h:
+            self._destroy(h)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    __hash__ = object.__hash__             # (c_void_p is unhashable; PackedHandle.dependents is a WeakSet)
+
+    def __reduce_ex__(self, protocol):
+        raise TypeError(f"a {self._noun} is device memory of one native handle and cannot be copied or pickled: make a new one")
+
+
+def _held(fn):
+    """How an owner keeps a callable.  A bound method weakly: the module owns the PackedHandle, and a strong reference back would leave
+    the native memory to the cycle collector instead of freeing it with the module's last reference.  A library entry point by name
+    (``_strong`` looks it up): ctypes function pointers neither pickle nor deep-copy."""
+    if isinstance(fn, lib._FuncPtr):
+        return fn.__name__
+    return weakref.WeakMethod(fn) if inspect.ismethod(fn) else fn
+
+
+def _strong(fn):
+    return getattr(lib, fn) if isinstance(fn, str) else fn() if isinstance(fn, weakref.WeakMethod) else fn
+
+
+class PackedHandle:
+    """The native state one module builds from its tensors: the packed handle(s), the token of what they were packed from, the
+    workspaces.  ``create(device_index[, key]) -> c_void_p``, ``load_tensor`` (a ``*_load_tensor`` entry point), ``finalize(handle)`` and
+    ``destroy(handle)`` are the family's calls; ``on_release()`` runs before handles are destroyed, while the module lives; ``noun`` (or
+    the whole ``refusal``) words the error for a module that is not on the GPU; ``dtype_of`` is ``load_tensors``'s.  ``dependents`` are
+    OwnedHandles made against a packed handle (stream caches): released before it, whoever releases it.  A copy or a pickle of an owner
+    is an empty owner of the same family, so the callables are bound methods of the module, library entry points or module-level
+    functions; ``destroy`` must not be a method of the module, which may be gone when it is called."""
+
+    def __init__(self, create=None, load_tensor=None, finalize=None, destroy=None, noun: str = "module", on_release=None, dtype_of=None,
+                 refusal: str = None):
+        self._family = tuple(_held(f) for f in (create, load_tensor, finalize, destroy, on_release, dtype_of))
+        self._noun, self._refusal = noun, refusal
+        self.handles: dict = {}             # key -> c_void_p; the one handle of most modules is under None
+        self.token = None
+        self.workspaces: dict = {}          # key -> uint8 tensor; dropped with the handles
+        self.dependents = weakref.WeakSet()
+
+    def get(self, device, token, items, key=None):
+        """The handle of ``key``, packed from ``items`` ((name, tensor) pairs, or a callable that lists them) unless the handles held
+        were made from ``token`` already.  Another token destroys every handle held and drops the workspaces first."""
+        if device.type != "cuda":
+            raise RuntimeError(self._refusal or f"the {self._noun} runs on the MI355X: move the module with .to('cuda') (there is no CPU fallback)")
+        if token != self.token:
+            self.release()
+            self.token = token
+        h = self.handles.get(key)
+        if h is None:
+            create, load_tensor, finalize, destroy, _, dtype_of = map(_strong, self._family)
+            h = create(device.index or 0) if key is None else create(device.index or 0, key)
+            try:
+                load_tensors(h, load_tensor, items() if callable(items) else items, dtype_of)
+                with torch.cuda.device(device):
+                    finalize(h)
+            except BaseException:
+                destroy(h)
+                raise
+            self.handles[key] = h
+        return h
+
+    def workspace(self, nbytes: int, device, key=None) -> torch.Tensor:
+        """The grow-only byte buffer of ``key``: the one held when it is large enough and on ``device``, else a new one."""
+        ws = self.workspaces.get(key)
+        if ws is None or ws.numel() < nbytes or ws.device != device:
+            self.workspaces.pop(key, None)       # before the new one is made: both need not fit at once
+            ws = self.workspaces[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+        return ws
+
+    def release(self) -> None:
+        handles, self.handles, self.token = self.handles, {}, None
+        self.workspaces.clear()
+        if handles:
+            on_release, destroy = _strong(self._family[4]), _strong(self._family[3])
+            if on_release is not None:
+                on_release()
+            for d in list(self.dependents):
+                d.release()
+            for h in handles.values():
+                destroy(h)
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def __reduce_ex__(self, protocol):
+        family = tuple(f() if isinstance(f, weakref.WeakMethod) else f for f in self._family)      # entry points stay names
+        return (PackedHandle, family[:4] + (self._noun,) + family[4:] + (self._refusal,))
 
 
 def current_stream_handle(device) -> int:

@@ -23,8 +23,8 @@ import torch
 from torch import nn
 
 from . import _native as nat
+from .convert import read_state_dict
 
-_COMPUTE = {"bf16": nat.SF_COMPUTE_BF16, "fp32": nat.SF_COMPUTE_BF16X3, "bf16x3": nat.SF_COMPUTE_BF16X3}
 POOL_MODES = {"none": 0, "average": 1, "max": 2, "bilinear": 3}
 NEWLINE_POSITIONS = {"no_token": 0, "one_token": 1, "frame": 2, "grid": 3}
 _OUT_DTYPES = {torch.float32: nat.SF_F32, torch.bfloat16: nat.SF_BF16}
@@ -62,8 +62,7 @@ def pooled_side(patches_per_side: int, mode: str, stride: int) -> int:
 class VideoTokenConnector(nn.Module):
     def __init__(self, config: Any, compute_dtype: Any = "fp32", out_dtype: torch.dtype = torch.float32, device: Any = None):
         super().__init__()
-        if compute_dtype not in _COMPUTE:
-            raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {compute_dtype!r}")
+        self._compute = nat.compute_mode(compute_dtype)
         if out_dtype not in _OUT_DTYPES:
             raise ValueError(f"out_dtype must be torch.float32 or torch.bfloat16, got {out_dtype}")
         if _field(config, "add_faster_video", False):
@@ -97,11 +96,11 @@ class VideoTokenConnector(nn.Module):
                            mm_spatial_pool_stride=self.pool_stride, mm_spatial_pool_mode=self.pool_mode,
                            mm_newline_position=self.newline_position, mm_patch_merge_type=self.patch_merge_type,
                            image_aspect_ratio=self.image_aspect_ratio)
-        self._compute = _COMPUTE[compute_dtype]
         self.out_dtype = out_dtype
-        # the library's width rules, checked here so that a refusal names the field before any weight exists; the handle stays for num_tokens
-        self._probe = self._create(self._video_key(), 0)
-        self._layout_probe = self._create((0, 1, self._video_key()[2]), 0)        # rows of `layout`: the same newline rule, no pool
+        self._probes: Dict[Tuple[int, int, int], nat.OwnedHandle] = {}
+        # the library's width rules, checked here so that a refusal names the field before any weight exists; the handles stay for num_tokens
+        self._probe(self._video_key())
+        self._probe((0, 1, self._video_key()[2]))       # rows of `layout`: the same newline rule, no pool
         if self.depth == 0:
             self.mm_projector = nn.Identity()
         elif self.depth == 1:
@@ -113,9 +112,8 @@ class VideoTokenConnector(nn.Module):
             self.mm_projector = nn.Sequential(*mods)
         if unpad or self.newline != "no_token":          # llava_arch:45-46, :107-109
             self.image_newline = nn.Parameter(torch.randn(self.out_dim) / math.sqrt(self.out_dim))
-        self._handles: Dict[Tuple[int, int, int], Any] = {}
-        self._packed_token = None
-        self._ws: Optional[torch.Tensor] = None         # one workspace, the largest any call has needed since the weights were packed
+        # handles by (pool_mode, stride, newline) layout under one token; one workspace, the largest any call has needed since the pack
+        self._native = nat.PackedHandle(self._create, nat.lib.sf_connector_load_tensor, self._finalize, nat.lib.sf_connector_destroy, "connector")
         self.requires_grad_(False)
         self.eval()
         if device is not None:
@@ -128,10 +126,20 @@ class VideoTokenConnector(nn.Module):
     def _frames_key(self) -> Tuple[int, int, int]:
         return (POOL_MODES[self.pool_mode], self.pool_stride, 0)
 
-    def _create(self, key: Tuple[int, int, int], device_index: int):
-        h = C.c_void_p()
+    def _create(self, device_index: int, key: Tuple[int, int, int], h: Any = None):
+        h = C.c_void_p() if h is None else h
         cfg = nat.SfConnectorConfig(self.in_dim, self.out_dim, self.depth, key[0], key[1], key[2])
         nat.check(nat.lib.sf_connector_create(C.byref(cfg), device_index, C.byref(h)))
+        return h
+
+    def _finalize(self, h) -> None:
+        nat.check(nat.lib.sf_connector_finalize(h, self._compute))
+
+    def _probe(self, key: Tuple[int, int, int]):
+        """A handle without weights that answers ``sf_connector_num_tokens`` for one layout; a copied connector makes its own."""
+        h = self._probes.get(key)
+        if h is None:
+            h = self._probes[key] = self._create(0, key, nat.OwnedHandle(nat.lib.sf_connector_destroy, "connector probe"))
         return h
 
     @property
@@ -140,48 +148,21 @@ class VideoTokenConnector(nn.Module):
             return p.device
         return torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
 
-    def _release(self) -> None:
-        for h in getattr(self, "_handles", {}).values():
-            nat.lib.sf_connector_destroy(h)
-        self._handles = {}
-        self._packed_token = None
-        self._ws = None
-
-    def __del__(self):
-        try:
-            self._release()
-            for name in ("_probe", "_layout_probe"):
-                if getattr(self, name, None) is not None:
-                    nat.lib.sf_connector_destroy(getattr(self, name))
-                    setattr(self, name, None)
-        except Exception:
-            pass
+    def __getstate__(self):
+        return dict(self.__dict__, _probes={})
 
     def _handle(self, key: Tuple[int, int, int]):
         """The native connector of one (pool_mode, stride, newline) layout, (re)packed when a parameter changed (in-place update,
         load_state_dict, .to(device))."""
         params = list(self.named_parameters())
         dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("the connector runs on the MI355X: move the module with .to('cuda') (there is no CPU fallback)")
-        token = nat.weights_token(dev, [p for _, p in params])
-        if token != self._packed_token:
-            self._release()
-            self._packed_token = token
-        h = self._handles.get(key)
-        if h is None:
-            h = self._create(key, dev.index or 0)
-            self._handles[key] = h
-            nat.load_tensors(h, nat.lib.sf_connector_load_tensor, [(k, p) for k, p in params if not (k == "image_newline" and key[2] == 0)])
-            with torch.cuda.device(dev):
-                nat.check(nat.lib.sf_connector_finalize(h, self._compute))
-        return h
+        return self._native.get(dev, nat.weights_token(dev, [p for _, p in params]),
+                                lambda: [(k, p) for k, p in params if not (k == "image_newline" and key[2] == 0)], key)
 
     def _workspace(self, h, F: int, P: int) -> torch.Tensor:
         n = C.c_size_t()
         nat.check(nat.lib.sf_connector_workspace_bytes(h, F, P, C.byref(n)))
-        self._ws = nat.grow_workspace(self._ws, n.value, self.device)
-        return self._ws
+        return self._native.workspace(n.value, self.device)
 
     def _run(self, key: Tuple[int, int, int], feats: torch.Tensor, P: int, out_dtype: torch.dtype) -> torch.Tensor:
         h = self._handle(key)
@@ -227,18 +208,7 @@ class VideoTokenConnector(nn.Module):
         if config is None:
             with open(os.path.join(path, "config.json")) as f:
                 config = json.load(f)
-        sd = None
-        for name in ("mm_projector.bin", "mm_projector.safetensors", "model.safetensors"):
-            p = os.path.join(path, name)
-            if os.path.isfile(p):
-                if name.endswith(".bin"):
-                    sd = torch.load(p, map_location="cpu", weights_only=True)
-                else:
-                    from safetensors.torch import load_file
-                    sd = load_file(p)
-                break
-        if sd is None:
-            raise OSError(f"no mm_projector.bin / mm_projector.safetensors / model.safetensors under {path!r}")
+        sd = read_state_dict(path, ("mm_projector.bin", "mm_projector.safetensors", "model.safetensors"))
         model = cls(config, compute_dtype=compute_dtype, out_dtype=out_dtype)
         missing = model.load_state_dict(sd, strict=False).missing_keys
         if missing:
@@ -253,7 +223,7 @@ class VideoTokenConnector(nn.Module):
     def num_tokens(self, frames: int, patches_per_side: int) -> int:
         """Rows of ``forward`` for a clip of ``frames`` frames of ``patches_per_side``^2 patches (``sf_connector_num_tokens``)."""
         n = C.c_int64()
-        nat.check(nat.lib.sf_connector_num_tokens(self._probe, int(frames), int(patches_per_side), C.byref(n)))
+        nat.check(nat.lib.sf_connector_num_tokens(self._probe(self._video_key()), int(frames), int(patches_per_side), C.byref(n)))
         return int(n.value)
 
     @staticmethod
@@ -295,7 +265,7 @@ class VideoTokenConnector(nn.Module):
         Po = self._side(cells)
         nl = NEWLINE_POSITIONS[self.newline]
         rows = C.c_int64()
-        nat.check(nat.lib.sf_connector_num_tokens(self._layout_probe, F, Po, C.byref(rows)))
+        nat.check(nat.lib.sf_connector_num_tokens(self._probe((0, 1, nl)), F, Po, C.byref(rows)))
         x = frame_tokens.to(device=dev, dtype=torch.float32).contiguous()
         newline = self.image_newline.detach().to(device=dev, dtype=torch.float32).contiguous() if nl else None
         out = torch.empty(rows.value, D, dtype=self.out_dtype, device=dev)

@@ -8,11 +8,13 @@
   zero gate (``:229-240``), so the converted model reproduces per-frame SigLIP until it is trained.
 * ``load_training_checkpoint``: the ``checkpoint-*.pth`` dict the reference trainer writes
   (``utils.py:625-631``: ``{"model", "optimizer", "epoch", "scaler", "args"}``) -> encoder state_dict.
+* ``read_state_dict`` / ``write_state_dict``: the weight file of a checkpoint directory, safetensors or ``torch.save``.
 """
 from __future__ import annotations
 
+import os
 from collections import OrderedDict
-from typing import Dict
+from typing import Dict, Sequence
 
 import torch
 
@@ -71,6 +73,30 @@ def load_training_checkpoint(path: str) -> "OrderedDict[str, torch.Tensor]":
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     sd = ckpt["model"] if isinstance(ckpt, dict) and "model" in ckpt else ckpt
     return normalize_checkpoint_keys(sd)
+
+
+def read_state_dict(directory: str, names: Sequence[str]) -> Dict[str, torch.Tensor]:
+    """The first of ``names`` that exists under ``directory``, on the CPU: ``*.safetensors`` through safetensors, anything else through
+    ``torch.load(weights_only=True)``."""
+    for name in names:
+        path = os.path.join(directory, name)
+        if os.path.isfile(path):
+            if name.endswith(".safetensors"):
+                from safetensors.torch import load_file
+                return load_file(path)
+            return torch.load(path, map_location="cpu", weights_only=True)
+    shown = [n for n in names if n != "model.bin"]      # the legacy name is read, not advertised
+    raise OSError(f"no {' / '.join(shown)} under {directory!r}")
+
+
+def write_state_dict(directory: str, state_dict: Dict[str, torch.Tensor], name: str, safe_serialization: bool) -> None:
+    """``state_dict`` as contiguous CPU tensors in ``directory/name``: safetensors, or ``torch.save`` without ``safe_serialization``."""
+    sd = {k: v.detach().to("cpu").contiguous() for k, v in state_dict.items()}
+    if safe_serialization:
+        from safetensors.torch import save_file
+        save_file(sd, os.path.join(directory, name), metadata={"format": "pt"})
+    else:
+        torch.save(sd, os.path.join(directory, name))
 
 
 def dump_for_c_host(config, state_dict: Dict[str, torch.Tensor], path: str) -> None:

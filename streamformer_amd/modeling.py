@@ -39,9 +39,6 @@ from . import _native as nat
 from .configuration import LORA_RANK, StreamformerConfig
 
 _ACT_CODES = {"gelu": 0, "gelu_new": 1, "gelu_pytorch_tanh": 1, "relu": 2}
-_COMPUTE = {"bf16": nat.SF_COMPUTE_BF16, "bfloat16": nat.SF_COMPUTE_BF16, torch.bfloat16: nat.SF_COMPUTE_BF16,
-            "bf16x3": nat.SF_COMPUTE_BF16X3, "fp32": nat.SF_COMPUTE_BF16X3, "float32": nat.SF_COMPUTE_BF16X3,
-            torch.float32: nat.SF_COMPUTE_BF16X3}
 _TORCH2SF = {torch.uint8: nat.SF_U8, torch.float32: nat.SF_F32, torch.bfloat16: nat.SF_BF16, torch.float16: nat.SF_F16,
              torch.float64: nat.SF_F64}
 
@@ -183,13 +180,13 @@ class StreamCache:
         if policy not in ("stop", "slide"):
             raise ValueError("policy must be 'stop' (raise at capacity, like the reference) or 'slide' (sliding window over the last max_frames frames)")
         self._model = weakref.ref(model)
-        self._h = nat.C.c_void_p()
+        self._h = nat.OwnedHandle(nat.lib.sf_cache_destroy, "StreamCache")
         nat.check(nat.lib.sf_cache_create(model._handle, batch, max_frames, H, W, nat.C.byref(self._h)))
         self.batch, self.max_frames, self.H, self.W, self.policy = batch, max_frames, H, W, policy
         self._free = list(range(batch))      # slabs no session holds, lowest first (acquire / release)
         if policy == "slide":
             nat.check(nat.lib.sf_cache_set_policy(self._h, 1))
-        model._caches.add(self)
+        model._native.dependents.add(self._h)      # invalidated (released) with the packing it was created against
 
     @property
     def valid(self) -> bool:
@@ -290,17 +287,6 @@ class StreamCache:
                 _slab_release(self._free, sid)
             raise
         return sid
-
-    def _invalidate(self) -> None:
-        h, self._h = self._h, None
-        if h:
-            nat.lib.sf_cache_destroy(h)
-
-    def __del__(self):
-        try:
-            self._invalidate()
-        except Exception:
-            pass
 
 
 def _slab_acquire(free: List[int], batch: int) -> int:
@@ -434,6 +420,11 @@ class _Node(nn.Module):
 
     def __iter__(self):
         return (self._modules[str(j)] for j in range(len(self)))
+
+
+def _staged_as(dtype: torch.dtype) -> Optional[int]:
+    """The SF_* code a checkpoint dtype is staged in as it is (None: converted to fp32 first)."""
+    return None if dtype == torch.uint8 else _TORCH2SF.get(dtype)
 
 
 def _to_frame_major(x: torch.Tensor, T: int) -> torch.Tensor:
@@ -570,20 +561,17 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
                 f"attention_type={config.attention_type!r}: only 'divided_space_time' is on the StreamFormer path")
         if config.hidden_act not in _ACT_CODES:
             raise ValueError(f"unsupported hidden_act {config.hidden_act!r}")
-        if compute_dtype not in _COMPUTE:
-            raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {compute_dtype!r}")
+        self._compute = nat.compute_mode(compute_dtype)
         self.config = config
-        self._compute = _COMPUTE[compute_dtype]
         self._fuse = bool(fuse_temporal_proj)
         self._lora = bool(config.add_lora_spatial)
-        self._handle = None
-        self._handle_device: Optional[torch.device] = None
-        self._packed_token = None           # (device, version sum, ...) the native weights were packed from
+        # the packed handle, its token (device, version sum, ...) and one workspace per call shape
+        self._native = nat.PackedHandle(self._create, nat.lib.sf_load_tensor, self._finalize, nat.lib.sf_destroy, "encoder", self._on_release,
+                                        _staged_as, "the StreamFormer HIP encoder runs on an AMD GPU only: call .to('cuda') first "
+                                        "(there is no CPU fallback)")
         self._force_repack = True
         self._pack_epoch = 0                # counts re-packs: a StreamSnapshot of this model remembers the one it was taken in
-        self._ws: Dict[tuple, torch.Tensor] = {}
         self._pos_cache: Dict[tuple, torch.Tensor] = {}
-        self._caches: "weakref.WeakSet[StreamCache]" = weakref.WeakSet()
         self._plist: List[torch.Tensor] = []
         from .processing import TimesformerImageProcessor
         self.image_processor = TimesformerImageProcessor(size=(config.image_size, config.image_size),
@@ -701,19 +689,8 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
                               "and pass its directory") from e
         cfg_over = {k: kwargs.pop(k) for k in list(kwargs) if k in StreamformerConfig().to_dict()}
         cfg = config or StreamformerConfig.from_pretrained(path, **cfg_over)
-        sd = None
-        st = os.path.join(path, "model.safetensors")
-        if os.path.isfile(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        else:
-            for name in ("pytorch_model.bin", "model.bin"):
-                p = os.path.join(path, name)
-                if os.path.isfile(p):
-                    sd = torch.load(p, map_location="cpu", weights_only=True)
-                    break
-        if sd is None:
-            raise OSError(f"no model.safetensors / pytorch_model.bin under {path!r}")
+        from .convert import read_state_dict      # (convert imports this module)
+        sd = read_state_dict(path, ("model.safetensors", "pytorch_model.bin", "model.bin"))
         if isinstance(sd, dict) and "model" in sd and "state_dict" not in sd and not any(k.startswith(("embeddings", "timesformer")) for k in sd):
             sd = sd["model"]     # checkpoint-*.pth layout (utils.py:625-631)
         if any("_lora_" in k for k in sd):
@@ -735,12 +712,8 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         os.makedirs(save_directory, exist_ok=True)
         self.config.add_lora_spatial = self._lora
         self.config.save_pretrained(save_directory)
-        sd = {k: v.detach().to("cpu").contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-            save_file(sd, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
-        else:
-            torch.save(sd, os.path.join(save_directory, "pytorch_model.bin"))
+        from .convert import write_state_dict
+        write_state_dict(save_directory, self.state_dict(), "model.safetensors" if safe_serialization else "pytorch_model.bin", safe_serialization)
 
     # ------------------------------------------------------------------------------ LoRA surface
     def _enable_lora_keys(self) -> None:
@@ -807,16 +780,16 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         out = super()._apply(fn, recurse)
         self._refresh_plist()            # .to() / .cuda() / .half(): new storage -> re-pack, drop device-bound scratch
         self._engine = None
-        self._ws.clear()
+        self._native.workspaces.clear()
         self._pos_cache.clear()
         return out
 
     def set_compute_dtype(self, compute_dtype: Any):
-        c = _COMPUTE[compute_dtype]
+        c = nat.compute_mode(compute_dtype)
         if c != self._compute:
             self._compute = c
             self._force_repack = True
-            self._ws.clear()
+            self._native.workspaces.clear()
         return self
 
     def refresh_weights(self) -> None:
@@ -826,14 +799,9 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
 
     # -------------------------------------------------------------------- copy / pickle (torch.save(model), copy.deepcopy)
     def __getstate__(self):
-        d = dict(self.__dict__)
-        d["_handle"] = None                   # native state is rebuilt from the parameters on first use
-        d["_handle_device"] = None
-        d["_packed_token"] = None
+        d = dict(self.__dict__)               # (_native copies as an empty owner: native state is rebuilt from the parameters on first use)
         d["_force_repack"] = True
-        d["_ws"] = {}
         d["_pos_cache"] = {}
-        d["_caches"] = None
         d["_engine"] = None
         d.pop("_named", None)
         d.pop("_plist", None)
@@ -841,24 +809,10 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
 
     def __setstate__(self, d):
         self.__dict__.update(d)
-        self._caches = weakref.WeakSet()
         for m in self.modules():
             if isinstance(m, _Node):
                 m._bind(self)
         self._refresh_plist()
-
-    def _release_native(self) -> None:
-        for c in list(self._caches):
-            c._invalidate()
-        h, self._handle = self._handle, None
-        if h:
-            nat.lib.sf_destroy(h)
-
-    def __del__(self):
-        try:
-            self._release_native()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------ native sync
     def _sf_config(self) -> nat.SfConfig:
@@ -875,44 +829,41 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         ip = self.image_processor
         return (self._plist[0].device, self._compute, v, tuple(ip.image_mean), tuple(ip.image_std), ip.rescale_factor)
 
-    def _sync(self, trust_versions: bool = False) -> None:
-        """Create the handle on the current device and (re)upload packed weights when stale.
-        ``trust_versions``: skip the scan of the parameters' version counters (~45 us for SigLIP-base) — used for the
-        frames of a running stream, whose valid cache already proves the packing it was started on is still the live one."""
-        if trust_versions and self._handle and not self._force_repack:
-            return
-        tok = self._token()
-        if not self._force_repack and self._handle and tok == self._packed_token:
-            return
-        dev = tok[0]
-        if dev.type != "cuda":
-            raise RuntimeError("the StreamFormer HIP encoder runs on an AMD GPU only: call .to('cuda') first "
-                               "(there is no CPU fallback)")
-        self._release_native()           # live StreamCaches of the old packing are invalidated with it
-        self._pack_epoch = getattr(self, "_pack_epoch", 0) + 1      # ... and so are the snapshots taken from them
-        cfg = self._sf_config()
+    @property
+    def _handle(self):
+        return self._native.handles.get(None)
+
+    def _create(self, device_index: int):
         h = nat.C.c_void_p()
-        nat.check(nat.lib.sf_create(nat.C.byref(cfg), dev.index or 0, nat.C.byref(h)))
-        self._handle = h
-        nat.load_tensors(h, nat.lib.sf_load_tensor, self._named.items(), lambda d: None if d == torch.uint8 else _TORCH2SF.get(d))
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_finalize_weights(h, self._compute, 1, int(self._fuse)))
+        nat.check(nat.lib.sf_create(nat.C.byref(self._sf_config()), device_index, nat.C.byref(h)))
+        return h
+
+    def _finalize(self, h) -> None:
+        nat.check(nat.lib.sf_finalize_weights(h, self._compute, 1, int(self._fuse)))
         ip = self.image_processor           # uint8 frames: rescale + normalize fused into the patch kernel
         nch = len(ip.image_mean)
         mean = (nat.C.c_float * nch)(*ip.image_mean)
         std = (nat.C.c_float * nch)(*ip.image_std)
         nat.check(nat.lib.sf_set_pixel_normalization(h, mean, std, nch, ip.rescale_factor))
-        self._pos_cache.clear()
-        self._packed_token = tok
-        self._force_repack = False
 
-    def _workspace(self, key: tuple, nbytes: int) -> torch.Tensor:
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            self._ws.pop(key, None)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        return ws
+    def _on_release(self) -> None:
+        """A packing goes (its live StreamCaches with it: PackedHandle.dependents).  Only where one was held: before the first handle
+        there is no snapshot to age and no position table to drop."""
+        self._pack_epoch += 1            # the snapshots taken from its caches are stale
+        self._pos_cache.clear()
+
+    def _sync(self, trust_versions: bool = False) -> None:
+        """Create the handle on the current device and (re)upload packed weights when stale.
+        ``trust_versions``: skip the scan of the parameters' version counters (~45 us for SigLIP-base) — used for the
+        frames of a running stream, whose valid cache already proves the packing it was started on is still the live one."""
+        native = self._native
+        if trust_versions and native.handles and not self._force_repack:
+            return
+        tok = self._token()
+        if self._force_repack:
+            native.token = None          # whatever is packed is stale
+        native.get(tok[0], tok, self._named.items)
+        self._force_repack = False
 
     def _pos_table(self, H: int, W: int) -> Optional[torch.Tensor]:
         """Resized position table for non-native inputs (modeling:380-411): a handful of KFLOP of
@@ -1013,14 +964,15 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
                 cache = self._forward_stream(x, pos, past_key_values, cache_position, stream_ids, lhs, pool, hs, att, stream, skey)
             else:
                 nbytes = nat.C.c_size_t()
-                nat.check(nat.lib.sf_workspace_bytes(self._handle, B, T, H, W, nat.C.byref(nbytes)))
-                ws = self._workspace(("f", B, T, H, W, skey), nbytes.value)
+                h = self._native.handles[None]
+                nat.check(nat.lib.sf_workspace_bytes(h, B, T, H, W, nat.C.byref(nbytes)))
+                ws = self._native.workspace(nbytes.value, dev, ("f", B, T, H, W, skey))
                 if att is not None:
-                    nat.check(nat.lib.sf_forward_attentions(self._handle, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W,
+                    nat.check(nat.lib.sf_forward_attentions(h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W,
                                                             lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(),
                                                             nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
                 else:
-                    nat.check(nat.lib.sf_forward(self._handle, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, lhs.data_ptr(),
+                    nat.check(nat.lib.sf_forward(h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, lhs.data_ptr(),
                                                  pool.data_ptr(), nat.ptr(hs), nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
         hidden = None
         if hs is not None:
@@ -1065,9 +1017,10 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         if not ragged and (cache.batch, cache.H, cache.W) != (B, H, W):
             raise ValueError("past_key_values was created for a different batch size / resolution")
         nbytes = nat.C.c_size_t()
-        nat.check(nat.lib.sf_stream_workspace_bytes(self._handle, ch, T, nat.C.byref(nbytes)))
-        ws = self._workspace(("s", cache.batch, T, H, W, skey), nbytes.value)      # (a lockstep call has B == cache.batch)
-        frames = (self._handle, ch, x.data_ptr(), _TORCH2SF[x.dtype], T)
+        h = self._native.handles[None]
+        nat.check(nat.lib.sf_stream_workspace_bytes(h, ch, T, nat.C.byref(nbytes)))
+        ws = self._native.workspace(nbytes.value, x.device, ("s", cache.batch, T, H, W, skey))      # (a lockstep call has B == cache.batch)
+        frames = (h, ch, x.data_ptr(), _TORCH2SF[x.dtype], T)
         tail = (nat.ptr(pos), ws.data_ptr(), ws.numel(), stream)
         if ragged:
             ids = (nat.C.c_int * max(B, 1))(*stream_ids)
@@ -1095,7 +1048,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
         self._sync()
         n = nat.C.c_size_t()
         nat.check(nat.lib.sf_workspace_bytes(self._handle, B, T, H, W, nat.C.byref(n)))
-        return self._workspace(("f", B, T, H, W, int(nat.current_stream_handle(self.device) or 0)), n.value)
+        return self._native.workspace(n.value, self.device, ("f", B, T, H, W, int(nat.current_stream_handle(self.device) or 0)))
 
     def _grid(self, n_tokens: int, T: int) -> Tuple[int, int]:
         """(H, W) of a frame whose patch grid has n_tokens / T cells (square, or the config's aspect)."""

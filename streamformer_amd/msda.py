@@ -17,7 +17,7 @@ import ctypes as C
 import math
 import types
 import weakref
-from typing import Any, Optional, Sequence, Tuple
+from typing import Any, Sequence, Tuple
 
 import torch
 from torch import nn
@@ -28,9 +28,6 @@ from torch.nn.init import constant_, xavier_uniform_
 from . import _native as nat
 
 __all__ = ["ms_deform_attn", "MSDeformAttnFunction", "MSDeformAttn", "as_compiled_op"]
-
-_COMPUTE = {"bf16": nat.SF_COMPUTE_BF16, torch.bfloat16: nat.SF_COMPUTE_BF16, "fp32": nat.SF_COMPUTE_BF16X3, "bf16x3": nat.SF_COMPUTE_BF16X3,
-            torch.float32: nat.SF_COMPUTE_BF16X3}
 
 # device tensor -> its values on the host, read back ONCE per tensor object (and in-place version): a repeated or captured call
 # with the same shapes tensor does not synchronise
@@ -181,19 +178,16 @@ class MSDeformAttn(nn.Module):
         super().__init__()
         if d_model % n_heads != 0:
             raise ValueError("d_model must be divisible by n_heads, but got {} and {}".format(d_model, n_heads))
-        if compute_dtype not in _COMPUTE:
-            raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {compute_dtype!r}")
+        self._compute = nat.compute_mode(compute_dtype)
         self.im2col_step = 128
         self.d_model, self.n_levels, self.n_heads, self.n_points = d_model, n_levels, n_heads, n_points
         self.compute_dtype = compute_dtype
-        self._compute = _COMPUTE[compute_dtype]
         self.sampling_offsets = nn.Linear(d_model, n_heads * n_levels * n_points * 2)
         self.attention_weights = nn.Linear(d_model, n_heads * n_levels * n_points)
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
-        self._workspace: Optional[torch.Tensor] = None
-        self._front: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
-        self._front_token = None
+        self._native = nat.PackedHandle(noun="MSDeformAttn")       # no handle of its own: the GEMMs' workspace
+        self._front, self._front_token = None, None
         self._reset_parameters()
 
     def _reset_parameters(self) -> None:
@@ -218,9 +212,9 @@ class MSDeformAttn(nn.Module):
         N = w.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         nbytes = nat.lib.sf_op_linear_workspace_bytes(M, N, K)
-        self._workspace = nat.grow_workspace(self._workspace, nbytes, x.device)
+        ws = self._native.workspace(nbytes, x.device)
         nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), None, 1.0, 0, y.data_ptr(), M, N, K, self._compute,
-                                       self._workspace.data_ptr(), self._workspace.numel(), nat.current_stream_handle(x.device)))
+                                       ws.data_ptr(), ws.numel(), nat.current_stream_handle(x.device)))
         return y
 
     def _front_weights(self, dev) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -232,6 +226,9 @@ class MSDeformAttn(nn.Module):
                 self._front = (torch.cat([ps[0], ps[2]]).float().contiguous(), torch.cat([ps[1], ps[3]]).float().contiguous())
             self._front_token = token
         return self._front
+
+    def __getstate__(self):
+        return dict(self.__dict__, _front=None, _front_token=None)      # a copy concatenates its own
 
     def _forward_native(self, query, reference_points, input_flatten, lv: _Levels, input_padding_mask):
         N, Lq, Cq = query.shape

@@ -24,8 +24,6 @@ from torch import nn
 
 from . import _native as nat
 
-_COMPUTE = {"bf16": nat.SF_COMPUTE_BF16, torch.bfloat16: nat.SF_COMPUTE_BF16, "fp32": nat.SF_COMPUTE_BF16X3, "bf16x3": nat.SF_COMPUTE_BF16X3,
-            torch.float32: nat.SF_COMPUTE_BF16X3}
 _ACT = {"gelu": 0, "relu": 2}
 _IGNORED_PREFIXES = ("gen_query.", "gen_layer.", "final_query.", "work_fusions.", "fut_fusions.")
 PE_MAX_LEN = 5000
@@ -193,11 +191,10 @@ class DetectorState:
     def __init__(self, detector: "OnlineActionDetector", streams: int):
         self.detector, self.streams = detector, int(streams)
         det_h = detector._handle_ptr()      # packs the weights if they have changed: the token below is the packed one
-        self._token = detector._packed_token
-        h = C.c_void_p()
+        self._token = detector._native.token
+        self._h = nat.OwnedHandle(nat.lib.sf_oad_state_destroy, "DetectorState")
         with torch.cuda.device(detector.device):
-            nat.check(nat.lib.sf_oad_state_create(det_h, self.streams, C.byref(h)))
-        self._h = h
+            nat.check(nat.lib.sf_oad_state_create(det_h, self.streams, C.byref(self._h)))
 
     def fill(self, stream: int) -> int:
         n = nat.lib.sf_oad_state_fill(self._h, int(stream))
@@ -216,24 +213,14 @@ class DetectorState:
                 nat.check(nat.lib.sf_oad_state_copy(other._h, i, self._h, i, nat.current_stream_handle(dev)))
         return other
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) is not None:
-                nat.lib.sf_oad_state_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 class OnlineActionDetector(nn.Module):
     def __init__(self, config: Any, compute_dtype: Any = "fp32", device: Any = None):
         super().__init__()
         if not isinstance(config, OADConfig):
             config = OADConfig.from_reference_dict(config)
-        if compute_dtype not in _COMPUTE:
-            raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {compute_dtype!r}")
+        self._compute = nat.compute_mode(compute_dtype)
         self.config = config
-        self._compute = _COMPUTE[compute_dtype]
         c = config
         d = self.d_model = c.d_model
         self.long_memory_num_samples, self.work_memory_num_samples = c.LONG_MEMORY_NUM_SAMPLES, c.WORK_MEMORY_NUM_SAMPLES
@@ -247,9 +234,7 @@ class OnlineActionDetector(nn.Module):
         self.dec_modules = _Stack(d, c.DIM_FEEDFORWARD, True, c.DEC_MODULE[1], bool(c.DEC_MODULE[2]))
         self.classifier = nn.Linear(d, c.NUM_CLASSES)
         self.ignored_keys: List[str] = []
-        self._handle = None
-        self._packed_token = None
-        self._ws: Optional[torch.Tensor] = None
+        self._native = nat.PackedHandle(self._create, nat.lib.sf_oad_load_tensor, self._finalize, nat.lib.sf_oad_destroy, "detector")
         self._tensors = None                # the parameter / buffer objects, listed once: the per-step token reads their versions only
         self.requires_grad_(False)
         self.eval()
@@ -277,36 +262,20 @@ class OnlineActionDetector(nn.Module):
     def device(self) -> torch.device:
         return self.classifier.weight.device
 
-    def _release(self) -> None:
-        if getattr(self, "_handle", None) is not None:
-            nat.lib.sf_oad_destroy(self._handle)
-        self._handle, self._packed_token, self._ws = None, None, None
+    def _finalize(self, h) -> None:
+        nat.check(nat.lib.sf_oad_finalize(h, self._compute))
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
+    def _items(self):
+        rows = self.long_memory_num_samples + self.work_memory_num_samples
+        return [(k, t[:rows, 0] if k == "pos_encoding.pe" else t) for k, t in self.state_dict().items()]
 
     def _handle_ptr(self):
         """The native detector, (re)packed when a parameter changed (in-place update, load_state_dict, .to(device)).  States made before
         a repack belong to the old weights and are refused."""
         dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("the detector runs on the MI355X: move the module with .to('cuda') (there is no CPU fallback)")
         if self._tensors is None:
             self._tensors = list(self.parameters()) + list(self.buffers())
-        token = nat.weights_token(dev, self._tensors)
-        if token != self._packed_token:
-            self._release()
-            tensors = list(self.state_dict().items())
-            h = self._create(dev.index or 0)
-            L, W = self.long_memory_num_samples, self.work_memory_num_samples
-            nat.load_tensors(h, nat.lib.sf_oad_load_tensor, [(k, t[:L + W, 0] if k == "pos_encoding.pe" else t) for k, t in tensors])
-            with torch.cuda.device(dev):
-                nat.check(nat.lib.sf_oad_finalize(h, self._compute))
-            self._handle, self._packed_token = h, token
-        return self._handle
+        return self._native.get(dev, nat.weights_token(dev, self._tensors), self._items)
 
     # ------------------------------------------------------------------------------------ weights
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
@@ -343,8 +312,7 @@ class OnlineActionDetector(nn.Module):
     def _workspace(self, h, n: int) -> torch.Tensor:
         size = C.c_size_t()
         nat.check(nat.lib.sf_oad_workspace_bytes(h, n, C.byref(size)))
-        self._ws = nat.grow_workspace(self._ws, size.value, self.device)
-        return self._ws
+        return self._native.workspace(size.value, self.device)
 
     @torch.no_grad()
     def step(self, work_features: torch.Tensor, long_features: Any = None, memory_key_padding_mask: Any = None, state: DetectorState = None,
@@ -376,7 +344,7 @@ class OnlineActionDetector(nn.Module):
         if state is None:
             raise ValueError("step needs state=detector.new_state(streams=...)")
         h = self._handle_ptr()
-        if state.detector is not self or state._token != self._packed_token:
+        if state.detector is not self or state._token != self._native.token:
             raise ValueError("this state belongs to another detector (or to weights that have changed since): make a new_state()")
         dev = self.device
         L, W, d_in = self.long_memory_num_samples, self.work_memory_num_samples, self.config.VISUAL_SIZE

@@ -22,9 +22,9 @@ import torch
 from torch import nn
 
 from . import _native as nat
+from .convert import read_state_dict, write_state_dict
 
 _ACT_CODES = {"gelu": 0, "gelu_new": 1, "gelu_pytorch_tanh": 1, "relu": 2}
-_COMPUTE = {"bf16": nat.SF_COMPUTE_BF16, "fp32": nat.SF_COMPUTE_BF16X3, "bf16x3": nat.SF_COMPUTE_BF16X3}
 MAX_CAPTION_TOKENS = 64                   # the reference tokenises every caption and prompt to max_length = 64
 
 
@@ -145,21 +145,15 @@ class SiglipTextModel(nn.Module):
         c = config
         if c.hidden_act not in _ACT_CODES:
             raise ValueError(f"unsupported hidden_act {c.hidden_act!r}")
-        if compute_dtype not in _COMPUTE:
-            raise ValueError(f"compute_dtype must be one of 'bf16' (throughput) or 'fp32'/'bf16x3' (accurate), got {compute_dtype!r}")
+        self._compute = nat.compute_mode(compute_dtype)
         self.config = c
-        self._compute = _COMPUTE[compute_dtype]
-        # the library's width rules, checked here so that a refusal names the field before any weight exists
-        probe = C.c_void_p()
-        nat.check(nat.lib.sf_text_create(C.byref(self._native_config()), 0, C.byref(probe)))
-        nat.lib.sf_text_destroy(probe)
+        nat.lib.sf_text_destroy(self._create(0))      # the library's width rules, checked here so that a refusal names the field before any weight exists
         self.embeddings = _Embeddings(c)
         self.encoder = _Encoder(c)
         self.final_layer_norm = nn.LayerNorm(c.hidden_size, eps=c.layer_norm_eps)
         self.head = nn.Linear(c.hidden_size, c.projection_size)
-        self._handle = None
-        self._packed_token = None
-        self._ws: Dict[tuple, torch.Tensor] = {}
+        self._native = nat.PackedHandle(self._create, nat.lib.sf_text_load_tensor, self._finalize, nat.lib.sf_text_destroy, "text tower",
+                                        refusal="the text tower runs on the MI355X: move the model with .to('cuda') (there is no CPU fallback)")
         self.requires_grad_(False)
         self.eval()
         if device is not None:
@@ -169,6 +163,14 @@ class SiglipTextModel(nn.Module):
         c = self.config
         return nat.SfTextConfig(c.vocab_size, c.max_position_embeddings, c.hidden_size, c.num_hidden_layers, c.num_attention_heads,
                                 c.intermediate_size, c.projection_size, _ACT_CODES[c.hidden_act], c.layer_norm_eps)
+
+    def _create(self, device_index: int):
+        h = C.c_void_p()
+        nat.check(nat.lib.sf_text_create(C.byref(self._native_config()), device_index, C.byref(h)))
+        return h
+
+    def _finalize(self, h) -> None:
+        nat.check(nat.lib.sf_text_finalize(h, self._compute))
 
     # ------------------------------------------------------------------------------------ weights
     @property
@@ -187,16 +189,8 @@ class SiglipTextModel(nn.Module):
             raise OSError(f"{path!r} is not a local directory: download the checkpoint (config.json + model.safetensors or "
                           "pytorch_model.bin) and pass its directory")
         cfg = config or SiglipTextConfig.from_pretrained(path)
-        st = os.path.join(path, "model.safetensors")
-        if os.path.isfile(st):
-            from safetensors.torch import load_file
-            sd = load_file(st)
-        elif os.path.isfile(os.path.join(path, "pytorch_model.bin")):
-            sd = torch.load(os.path.join(path, "pytorch_model.bin"), map_location="cpu", weights_only=True)
-        else:
-            raise OSError(f"no model.safetensors / pytorch_model.bin under {path!r}")
         model = cls(cfg, compute_dtype=compute_dtype)
-        model.load_state_dict(sd, strict=True)
+        model.load_state_dict(read_state_dict(path, ("model.safetensors", "pytorch_model.bin")), strict=True)
         if device is None and torch.cuda.is_available():
             device = "cuda"
         if device is not None:
@@ -207,52 +201,25 @@ class SiglipTextModel(nn.Module):
         os.makedirs(save_directory, exist_ok=True)
         with open(os.path.join(save_directory, "config.json"), "w") as f:
             json.dump(self.config.to_dict(), f, indent=2, sort_keys=True)
-        sd = {k: v.detach().to("cpu").contiguous() for k, v in self.state_dict().items()}
-        if safe_serialization:
-            from safetensors.torch import save_file
-            save_file(sd, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
-        else:
-            torch.save(sd, os.path.join(save_directory, "pytorch_model.bin"))
+        write_state_dict(save_directory, self.state_dict(), "model.safetensors" if safe_serialization else "pytorch_model.bin", safe_serialization)
 
-    def _release(self) -> None:
-        if self._handle is not None:
-            nat.lib.sf_text_destroy(self._handle)
-            self._handle = None
-        self._packed_token = None
-        self._ws = {}
+    @property
+    def _handle(self):
+        return self._native.handles.get(None)
 
-    def __del__(self):
-        try:
-            self._release()
-        except Exception:
-            pass
-
-    def _ensure_packed(self) -> None:
-        """(Re)pack the native weights when the parameters changed (in-place update, load_state_dict, .to(device))."""
+    def _packed(self):
+        """The native tower, (re)packed when the parameters changed (in-place update, load_state_dict, .to(device))."""
         params = list(self.named_parameters())
         dev = self.device
-        if dev.type != "cuda":
-            raise RuntimeError("the text tower runs on the MI355X: move the model with .to('cuda') (there is no CPU fallback)")
-        token = nat.weights_token(dev, [p for _, p in params])
-        if self._handle is not None and token == self._packed_token:
-            return
-        self._release()
-        h = C.c_void_p()
-        nat.check(nat.lib.sf_text_create(C.byref(self._native_config()), dev.index or 0, C.byref(h)))
-        self._handle = h
-        nat.load_tensors(h, nat.lib.sf_text_load_tensor, params)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_text_finalize(h, self._compute))
-        self._packed_token = token
+        return self._native.get(dev, nat.weights_token(dev, [p for _, p in params]), params)
 
-    def _workspace(self, B: int, L: int) -> torch.Tensor:
-        key = (B, L)
-        ws = self._ws.get(key)
+    def _workspace(self, h, B: int, L: int) -> torch.Tensor:
+        ws = self._native.workspaces.get((B, L))
         if ws is None:
             n = C.c_size_t()
-            nat.check(nat.lib.sf_text_workspace_bytes(self._handle, B, L, C.byref(n)))
-            self._ws = {key: torch.empty(n.value, dtype=torch.uint8, device=self.device)}      # one shape at a time: class tables are large
-            ws = self._ws[key]
+            nat.check(nat.lib.sf_text_workspace_bytes(h, B, L, C.byref(n)))
+            self._native.workspaces.clear()      # one shape at a time: class tables are large
+            ws = self._native.workspace(n.value, self.device, (B, L))
         return ws
 
     # ------------------------------------------------------------------------------------ forward
@@ -293,15 +260,15 @@ class SiglipTextModel(nn.Module):
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, return_dict: bool = True, **unused):
         ids, mask = self._check_inputs(input_ids, attention_mask, position_ids)
-        self._ensure_packed()
+        h = self._packed()
         c, dev = self.config, self.device
         B, L = ids.shape
         ids_d, mask_d = self._device_inputs(ids, mask)
         last = torch.empty(B, L, c.hidden_size, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, c.projection_size, dtype=torch.float32, device=dev)
-        ws = self._workspace(B, L)
+        ws = self._workspace(h, B, L)
         with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_text_forward(self._handle, ids_d.data_ptr(), nat.ptr(mask_d), B, L, last.data_ptr(), pooled.data_ptr(),
+            nat.check(nat.lib.sf_text_forward(h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, last.data_ptr(), pooled.data_ptr(),
                                               ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
         last = last.reshape(*input_ids.shape, c.hidden_size)
         out = TextModelOutput(last, pooled)
@@ -315,13 +282,13 @@ class SiglipTextModel(nn.Module):
         B, L = ids.shape
         if group < 1 or B % group:
             raise ValueError(f"{B} prompts are not whole groups of {group}")
-        self._ensure_packed()
+        h = self._packed()
         dev = self.device
         ids_d, mask_d = self._device_inputs(ids, mask)
         table = torch.empty(B // group, self.config.projection_size, dtype=torch.float32, device=dev)
-        ws = self._workspace(B, L)
+        ws = self._workspace(h, B, L)
         with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_text_forward_groups(self._handle, ids_d.data_ptr(), nat.ptr(mask_d), B, L, group, table.data_ptr(),
+            nat.check(nat.lib.sf_text_forward_groups(h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, group, table.data_ptr(),
                                                      ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
         return table
 

@@ -168,10 +168,9 @@ class StreamformerTrainer:
         sc = nat.SfConfig(c.image_size, c.patch_size, c.num_channels, c.num_frames, c.hidden_size, c.num_hidden_layers,
                           c.num_attention_heads, c.intermediate_size, _ACT[c.hidden_act], int(c.qkv_bias),
                           int(c.enable_causal_temporal), int(c.add_lora_spatial), float(c.layer_norm_eps))
-        h = C.c_void_p()
+        self._h = h = nat.OwnedHandle(nat.lib.sf_trainer_destroy, "trainer")
         nat.check(nat.lib.sf_trainer_create(C.byref(sc), self.device.index or 0, int(freeze_spatial), 2 * len(self.task_heads),
                                             C.byref(h)))
-        self._h = h
         # ---- layout -------------------------------------------------------------------------------------
         self.layout: Dict[str, dict] = {}
         name = C.create_string_buffer(256)
@@ -479,12 +478,6 @@ class StreamformerTrainer:
         if not e["trainable"]:
             raise KeyError(f"{key} is frozen")
         return self.grads[e["offset"]: e["offset"] + e["numel"]].view(e["shape"])
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h and nat is not None and getattr(nat, "lib", None) is not None:    # interpreter shutdown: globals may be gone
-            nat.lib.sf_trainer_destroy(h)
-            self._h = None
 
     # ---- guards ------------------------------------------------------------------------------------------
     def nonfinite_steps(self) -> int:

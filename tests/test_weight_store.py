@@ -3,8 +3,12 @@
 The Python wrappers always stage fp32 (the encoder's passes checkpoint dtypes through), so SF_F64 and SF_BF16 are reached only here.
 Weights are drawn seeded and rounded to bf16-representable values: fp32, fp64 and bf16 then hold the SAME numbers, every conversion of
 the weight store is exact, and three fresh handles loaded from the three forms must produce bitwise equal outputs in both compute
-modes: no tolerance.  A handle with one key withheld must refuse to finalize and name the key."""
+modes: no tolerance.  A handle with one key withheld must refuse to finalize and name the key.
+
+The modules that own such handles copy and pickle like any ``nn.Module``: the copy packs a handle of its own from its own weights."""
+import copy
 import ctypes as C
+import io
 
 import pytest
 import torch
@@ -262,3 +266,73 @@ def test_encoder_forms():
     w = {k: t.to(torch.bfloat16).float() for k, t in named.items()}
     _refuses_without(create, nat.lib.sf_load_tensor, lambda h: nat.lib.sf_finalize_weights(h, nat.SF_COMPUTE_BF16, 1, 0), nat.lib.sf_destroy, w,
                      "encoder.layer.1.output.dense.weight")
+
+
+# ------------------------------------------------------------------------------------------------ copies of the owning modules
+def _copies(m):
+    buf = io.BytesIO()
+    torch.save(m, buf)
+    buf.seek(0)
+    return copy.deepcopy(m), torch.load(buf, weights_only=False)
+
+
+def _bits(t):
+    return t.detach().cpu().view(torch.int32)
+
+
+def test_text_tower_copies():
+    dev = _gpu()
+    torch.manual_seed(71)
+    m = sa.SiglipTextModel(sa.SiglipTextConfig(vocab_size=32, hidden_size=64, intermediate_size=64, num_hidden_layers=1, num_attention_heads=2,
+                                               max_position_embeddings=8), device=dev)
+    ids = torch.randint(0, 32, (2, 4), generator=torch.Generator().manual_seed(72)).to(dev)
+    want = [_bits(t) for t in m(ids)]
+    assert m._handle is not None and float(m(ids)[1].abs().max()) > 0
+    for other in _copies(m):
+        assert other._handle is None and other._native is not m._native       # an empty owner: nothing of the original's is shared
+        assert all(torch.equal(a, _bits(b)) for a, b in zip(want, other(ids)))
+        with torch.no_grad():
+            other.embeddings.token_embedding.weight.add_(0.5)
+        assert not any(torch.equal(a, _bits(b)) for a, b in zip(want, other(ids)))
+        assert all(torch.equal(a, _bits(b)) for a, b in zip(want, m(ids)))    # the edit reached the copy alone
+
+
+def test_connector_copies():
+    dev = _gpu()
+    torch.manual_seed(73)
+    F, P = 2, 4
+    m = sa.VideoTokenConnector(dict(mm_projector_type="mlp2x_gelu", mm_hidden_size=64, hidden_size=64, mm_spatial_pool_stride=2), device=dev)
+    feats = frames(74, (F, P * P, 64)).to(dev)
+    want = _bits(m(feats))
+    rows = m.num_tokens(F, P)
+    assert want.shape == (rows, 64) and float(m(feats).abs().max()) > 0
+    for other in _copies(m):
+        assert other._probes == {} and other._native.handles == {}
+        assert other.num_tokens(F, P) == rows                                 # the copy makes probes of its own
+        assert torch.equal(want, _bits(other(feats)))
+        assert torch.equal(_bits(m.layout(m.project_frames(feats))), _bits(other.layout(other.project_frames(feats))))
+        with torch.no_grad():
+            other.mm_projector[2].bias.add_(0.5)
+        assert not torch.equal(want, _bits(other(feats)))
+        assert torch.equal(want, _bits(m(feats)))
+
+
+def test_detector_copies():
+    dev = _gpu()
+    torch.manual_seed(75)
+    d, L, W = 64, 4, 2                                        # the config of test_detector_forms
+    m = sa.OnlineActionDetector(sa.OADConfig(VISUAL_SIZE=d, NUM_CLASSES=3, LINEAR_OUT_FEATURES=d, NUM_HEADS=2, DIM_FEEDFORWARD=64,
+                                             LONG_MEMORY_NUM_SAMPLES=L, WORK_MEMORY_NUM_SAMPLES=W, ENC_MODULE=[[2, 1, True]],
+                                             DEC_MODULE=[-1, 1, True]), device=dev)
+    work, long = frames(76, (1, W, d)).to(dev), frames(77, (L, d)).to(dev)
+    state = m.new_state(1)
+    want = _bits(m.step(work, [long], state=state))
+    assert float(want.float().abs().max()) > 0
+    for other in _copies(m):
+        assert other._native.handles == {} and other._native.token is None
+        assert torch.equal(want, _bits(other.step(work, [long], state=other.new_state(1))))
+        with pytest.raises(ValueError, match="this state belongs to another detector"):
+            other.step(work, None, state=state)
+    with pytest.raises(TypeError, match="a DetectorState is device memory of one native handle and cannot be copied or pickled"):
+        copy.deepcopy(state)
+    assert state.fill(0) == L                                 # refused, not harmed
