@@ -612,6 +612,24 @@ int sf_op_msda_backward(const float* value_dev, const int32_t* spatial_shapes, c
                         float* grad_value_dev, float* grad_sampling_locations_dev, float* grad_attention_weights_dev, int N, int S,
                         int M, int D, int Lq, int L, int P, sf_stream stream);
 
+/* ---- the ViT-Adapter's two streaming kernels (models/modeling_timesformer_siglip_adapter.py; csrc/sf_adapter.hip) -----------------
+ * ConvFFN's depthwise 3x3 + exact-erf GELU (adapter:244-254, 231-232) on the three-level token tensor: x_dev, y_dev fp32
+ * [F, 21 * (H/2 * W/2), C], levels 2H x 2W, H x W, H/2 x W/2 in that order, channels contiguous; w_dev [C, 3, 3], b_dev [C].  ONE shared
+ * 3x3 filter per channel, zero padding 1, applied to each level on its own grid: a tap outside its level's grid contributes zero and is
+ * never read.  H, W even, C a multiple of 4 up to 1024, x, y, b 16-byte aligned, y must not alias x.  Bit-reproducible.             */
+int sf_op_adapter_dwconv_gelu(const float* x_dev, const float* w_dev, const float* b_dev, float* y_dev, int F, int H, int W, int C,
+                              sf_stream stream);
+/* One level of the adapter's tail (adapter:651-673), written NCHW: level 0..3 = res2..res5 of a ViT grid of H x W patches,
+ *   out[f, c, y, x] = scale[c] * (tokens[f, pix, c] + bilinear(vit[f, :, c])(y, x) [+ c1[f, c, y, x]]) + shift[c]
+ * out_dev fp32 [F, D, Ho, Wo] with (Ho, Wo) = (4H, 4W), (2H, 2W), (H, W), (H/2, W/2).  tokens_dev: levels 1..3 fp32 rows of D floats,
+ * pixel-major, frame f at tokens_dev + f * tokens_frame_stride floats (a level's slice of the [F, 21 n, D] tensor); level 0 the
+ * transposed convolution as a GEMM output, [F, 2H * 2W, 4 D] with columns (dy, dx, c)-major, read through the 2 x 2 pixel shuffle.
+ * vit_dev fp32 [F, H * W, D] or NULL (add_vit_feature=False): resampled x4, x2, x1, x0.5 by F.interpolate(mode="bilinear",
+ * align_corners=False)'s rule, edges clamped.  c1_dev fp32 [F, D, 4H, 4W] or NULL, level 0 only.  scale_dev / shift_dev [D]: the eval
+ * BatchNorm folded on the host (and the transposed convolution's bias at level 0).  D a multiple of 4; level 3 needs H and W even.  */
+int sf_op_adapter_fuse(int level, const float* tokens_dev, long long tokens_frame_stride, const float* vit_dev, const float* c1_dev,
+                       const float* scale_dev, const float* shift_dev, float* out_dev, int F, int H, int W, int D, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

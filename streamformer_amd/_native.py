@@ -176,6 +176,8 @@ SIGNATURES = {
     "sf_op_msda_forward_fused": (_I, [_P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _P, _I, _P, _I, _P,
                                       _I, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_msda_backward": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sf_op_adapter_dwconv_gelu": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_op_adapter_fuse": (_I, [_I, _P, C.c_longlong, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),

@@ -1,7 +1,8 @@
 """Multi-scale deformable attention on the MI355X: the operator, its autograd function and the ``MSDeformAttn`` module.
 
 The reference's only native code is this operator (``downstream/OVIS/mask2former/modeling/pixel_decoder/ops``, CUDA); its Mask2Former /
-CTVIS pixel decoder and the ViT-Adapter around the encoder (``models/modeling_timesformer_siglip_adapter.py``) both run on it.  Here it
+CTVIS pixel decoder and the ViT-Adapter around the encoder (``models/modeling_timesformer_siglip_adapter.py``; here ``adapter.py``) both run
+on it.  Here it
 is three HIP entry points (``csrc/sf_msda.hip``): the forward and the backward of the reference op's contract, and a forward with the
 front of ``MSDeformAttn.forward`` folded in (softmax over levels x points, sampling locations from reference points and raw offsets,
 padding mask), which the module's no-grad path uses.
@@ -207,13 +208,13 @@ class MSDeformAttn(nn.Module):
         constant_(self.output_proj.bias.data, 0.)
 
     # ---- no-grad path ------------------------------------------------------------------------------
-    def _linear(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    def _linear(self, x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, resid: torch.Tensor = None) -> torch.Tensor:
         M, K = x.shape
         N = w.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         nbytes = nat.lib.sf_op_linear_workspace_bytes(M, N, K)
         ws = self._native.workspace(nbytes, x.device)
-        nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), None, 1.0, 0, y.data_ptr(), M, N, K, self._compute,
+        nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), nat.ptr(resid), 1.0, 0, y.data_ptr(), M, N, K, self._compute,
                                        ws.data_ptr(), ws.numel(), nat.current_stream_handle(x.device)))
         return y
 
@@ -230,7 +231,8 @@ class MSDeformAttn(nn.Module):
     def __getstate__(self):
         return dict(self.__dict__, _front=None, _front_token=None)      # a copy concatenates its own
 
-    def _forward_native(self, query, reference_points, input_flatten, lv: _Levels, input_padding_mask):
+    def _forward_native(self, query, reference_points, input_flatten, lv: _Levels, input_padding_mask, resid=None):
+        """``resid`` [N, Lq, d_model] fp32 contiguous (the ViT-Adapter's extractors): added to the result by the output GEMM's epilogue."""
         N, Lq, Cq = query.shape
         S = input_flatten.shape[1]
         Mh, L, P, D = self.n_heads, self.n_levels, self.n_points, self.d_model // self.n_heads
@@ -252,7 +254,7 @@ class MSDeformAttn(nn.Module):
             nat.check(nat.lib.sf_op_msda_forward_fused(
                 value.data_ptr(), nat.ptr(pad), lv.c_hw, lv.c_start, front.data_ptr(), front.shape[1], front.data_ptr() + 4 * n_off, front.shape[1],
                 ref.data_ptr(), ref.shape[-1], ctx.data_ptr(), N, S, Mh, D, Lq, L, P, nat.current_stream_handle(dev)))
-            return self._linear(ctx, self.output_proj.weight.detach(), self.output_proj.bias.detach()).view(N, Lq, self.d_model)
+            return self._linear(ctx, self.output_proj.weight.detach(), self.output_proj.bias.detach(), resid).view(N, Lq, self.d_model)
 
     # ---- grad path ---------------------------------------------------------------------------------
     def _forward_autograd(self, query, reference_points, input_flatten, lv: _Levels, input_padding_mask):
