@@ -22,11 +22,9 @@ Sequences are [nseq, L, C] here; to_sequences / from_sequences convert the tempo
 import torch
 import torch.nn.functional as F
 
+from tests.oracle_ops import bf16_round
+
 FAULTS = ("ds_scale", "drop_last_query", "half_last_key")
-
-
-def bf16_round(t):
-    return t.to(torch.bfloat16).to(t.dtype)
 
 
 def to_sequences(x):
@@ -121,7 +119,7 @@ def wgrad(dy, x, dtype=torch.float64):
 
 
 # ---------------------------------------------------------------------------------------------------
-# metrics
+# metrics: the oracles import nothing that loads the library, so these stay beside tests.helpers' (whose guard is 1e-30, on CPU copies)
 # ---------------------------------------------------------------------------------------------------
 def rel_l2(got, want):
     got, want = got.double(), want.double()

@@ -15,13 +15,15 @@ f19_connector.npz`` holds the outputs of the reference's own code, and the tap r
 
 ``forward(..., dtype=torch.float64)`` is the reference of the GPU tests; ``dtype=torch.float32`` with ``bf16_operands="x3"`` / ``True`` are
 the precision floors of the accurate and the bf16 mode (operands of every Linear as hi + lo bf16 planes with the lo * lo product dropped /
-rounded to bf16; fp32 accumulation; everything else fp32), as in ``tests/text_tower_oracle.py``.
+rounded to bf16; fp32 accumulation; everything else fp32), stated once in ``tests/oracle_ops.py``.
 """
 import math
 import os
 
 import numpy as np
 import torch
+
+from tests.oracle_ops import activation, operand_linear
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f19_connector.npz")
 
@@ -82,26 +84,12 @@ def make_features(seed, frames, P, d_in=D_IN):
     return torch.from_numpy(rs.standard_normal((frames, P * P, d_in)).astype(np.float32))
 
 
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
-def _linear(x, w, b, bf16_operands):
-    if bf16_operands == "x3":
-        xh, wh = _bf16(x), _bf16(w)
-        xl, wl = _bf16(x - xh), _bf16(w - wh)
-        return xh @ wh.t() + xh @ wl.t() + xl @ wh.t() + b
-    if bf16_operands:
-        x, w = _bf16(x), _bf16(w)
-    return x @ w.t() + b
-
-
 def project(sd, projector_type, x, bf16_operands=False):
     """x [..., d_in] in the dtype of the computation; sd already in that dtype."""
     for i, p in enumerate(linear_keys(projector_type)):
         if i:
-            x = 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
-        x = _linear(x, sd[p + "weight"], sd[p + "bias"], bf16_operands)
+            x = activation(x, "gelu")
+        x = operand_linear(x, sd[p + "weight"], sd[p + "bias"], bf16_operands)
     return x
 
 

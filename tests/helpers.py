@@ -1,4 +1,4 @@
-"""Shared test helpers: seeded inputs identical to oracle/make_golden.py, small configs."""
+"""Shared test helpers: seeded inputs identical to oracle/make_golden.py, small configs, the precision-floor rule, guard buffers, metrics."""
 import numpy as np
 import torch
 
@@ -22,6 +22,85 @@ def maxabs(a, b):
     a = torch.as_tensor(np.asarray(a)) if not torch.is_tensor(a) else a
     b = torch.as_tensor(np.asarray(b)) if not torch.is_tensor(b) else b
     return float((a.double().cpu() - b.double().cpu()).abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------
+# precision floors: a bound is MARGIN times the error, against fp64, of the same operator sequence in torch at the operand precision of
+# the code under test, and never less than one fp32 rounding of the result
+# ---------------------------------------------------------------------------------------------------
+EPS32 = 2.0 ** -24
+MARGIN = 4.0
+
+
+def fp32_floor(got32, want):
+    """Precision floor of a computation: what its torch restatement ``got32`` loses against fp64, at least one fp32 rounding of ``want``."""
+    return max(maxabs(got32, want), EPS32 * float(want.abs().max()))
+
+
+def check_against_floor(what, got, floor32, want, margin=MARGIN):
+    bound = margin * fp32_floor(floor32, want)
+    err = maxabs(got, want)
+    print(f"  {what}: error {err:.3e}, bound {bound:.3e} ({err / bound:.3f})")
+    assert err <= bound, (what, err, bound)
+
+
+# ---------------------------------------------------------------------------------------------------
+# guard buffers: an out-of-bounds or a missing store of a kernel shows as a NaN in the wrong place
+# ---------------------------------------------------------------------------------------------------
+def guarded(dev, *shape):
+    """A NaN-filled buffer with one guard row behind the tensor: (whole buffer, view)."""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 64,), float("nan"), device=dev)
+    return buf, buf[:n].view(*shape)
+
+
+def read_guarded(buf, view):
+    """The view's CPU copy, after asserting that the guard row is untouched and that every element of the view was written."""
+    host = buf.cpu()
+    assert torch.isnan(host[view.numel():]).all(), "the guard row was written"
+    assert not torch.isnan(host[:view.numel()]).any(), "output elements left unwritten"
+    return host[:view.numel()].view(view.shape)
+
+
+# ---------------------------------------------------------------------------------------------------
+# metrics (fp64, on CPU copies) and small helpers
+# ---------------------------------------------------------------------------------------------------
+def rel_l2(got, want):
+    got, want = got.double().cpu(), want.double().cpu()
+    return float((got - want).norm() / (want.norm() + 1e-30))
+
+
+def cosine(a, b):
+    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
+    return float(a @ b / (a.norm() * b.norm() + 1e-30))
+
+
+def rel_max(got, want):
+    """max-abs error over max |want|."""
+    got, want = got.double().cpu(), want.double().cpu()
+    return float((got - want).abs().max() / (want.abs().max() + 1e-30))
+
+
+def randn(seed, *shape):
+    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def bf16_bits(t):
+    """fp32 -> the bf16 bit patterns (round-to-nearest-even) as int16."""
+    return t.to(torch.bfloat16).view(torch.int16)
+
+
+def from_bf16_bits(t):
+    return t.view(torch.bfloat16).double()
+
+
+def gpu_device(or_skip=False):
+    """cuda:0.  A file marked gpu as a whole asserts that the GPU is there; ``or_skip`` is for a test that may be collected without one."""
+    if or_skip and not torch.cuda.is_available():
+        import pytest
+        pytest.skip("needs a GPU")
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    return torch.device("cuda:0")
 
 
 def load_npz(path):

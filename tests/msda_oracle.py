@@ -8,7 +8,7 @@ at a chosen precision.  Nothing here imports the package under test or the refer
     core_grid_sample(...)               the REFERENCE'S operator sequence (split per level, grid_sample, weighted sum): in fp32 it is the
                                         precision floor of the GPU tests, in fp64 it must agree with core().
     locations(...), module(...)         the front of MSDeformAttn.forward and the whole module; ``bf16_operands="x3"`` / ``True`` round the
-                                        operands of every Linear as the library's two compute modes do (tests/oad_oracle.py).
+                                        operands of every Linear as the library's two compute modes do (tests/oracle_ops.py).
 
 Fixture F21 (tests/golden/f21_msda.npz, written by tools/make_golden_msda.py from the reference's own classes in fp64): per case the
 inputs, the outputs and the autograd gradients; module weights are redrawn from the stored seed by make_weights().
@@ -18,6 +18,8 @@ import os
 import numpy as np
 import torch
 import torch.nn.functional as F
+
+from tests.oracle_ops import operand_linear
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f21_msda.npz")
 
@@ -133,22 +135,6 @@ def core_with_grads(fn, value, shapes, loc, w, grad_out):
 # ------------------------------------------------------------------------------------------------
 # the module
 # ------------------------------------------------------------------------------------------------
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
-def linear(x, w, b, bf16_operands=False):
-    if bf16_operands == "x3":
-        xh, wh = _bf16(x), _bf16(w)
-        xl, wl = _bf16(x - xh), _bf16(w - wh)
-        y = xh @ wh.t() + xh @ wl.t() + xl @ wh.t()
-    elif bf16_operands:
-        y = _bf16(x) @ _bf16(w).t()
-    else:
-        y = x @ w.t()
-    return y + b
-
-
 def weight_shapes(c):
     d, n = c["d_model"], c["heads"] * len(c["shapes"]) * c["P"]
     return {"sampling_offsets.weight": (2 * n, d), "sampling_offsets.bias": (2 * n,), "attention_weights.weight": (n, d), "attention_weights.bias": (n,),
@@ -211,15 +197,15 @@ def module(sd, c, query, flat, ref, mask=None, dtype=torch.float64, bf16_operand
     N, Lq, d = query.shape
     M, shapes, P = c["heads"], c["shapes"], c["P"]
     L = len(shapes)
-    value = linear(flat, sd["value_proj.weight"], sd["value_proj.bias"], bf16_operands)
+    value = operand_linear(flat, sd["value_proj.weight"], sd["value_proj.bias"], bf16_operands)
     if mask is not None:
         value = value.masked_fill(mask[..., None], 0.0)
     value = value.view(N, -1, M, d // M)
-    offsets = linear(query, sd["sampling_offsets.weight"], sd["sampling_offsets.bias"], bf16_operands).view(N, Lq, M, L, P, 2)
-    logits = linear(query, sd["attention_weights.weight"], sd["attention_weights.bias"], bf16_operands).view(N, Lq, M, L * P)
+    offsets = operand_linear(query, sd["sampling_offsets.weight"], sd["sampling_offsets.bias"], bf16_operands).view(N, Lq, M, L, P, 2)
+    logits = operand_linear(query, sd["attention_weights.weight"], sd["attention_weights.bias"], bf16_operands).view(N, Lq, M, L * P)
     w = torch.softmax(logits, -1).view(N, Lq, M, L, P)
     loc = locations(offsets, ref, shapes, P)
-    out = linear(sample(value, shapes, loc, w), sd["output_proj.weight"], sd["output_proj.bias"], bf16_operands)
+    out = operand_linear(sample(value, shapes, loc, w), sd["output_proj.weight"], sd["output_proj.bias"], bf16_operands)
     if parts:
         return out, value, offsets, logits, loc, w
     return out

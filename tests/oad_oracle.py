@@ -12,7 +12,7 @@ a chosen precision, written out explicitly.  Nothing here imports the package un
                    all post-LN; classifier
 
 ``Stream(..., dtype=torch.float64)`` is the reference; ``dtype=torch.float32`` with ``bf16_operands="x3"`` / ``True`` are the precision
-floors of the GPU tests (tests/text_tower_oracle.py: both operands of every Linear as hi + lo bf16 planes, three of four products /
+floors of the GPU tests (tests/oracle_ops.py: both operands of every Linear as hi + lo bf16 planes, three of four products /
 rounded to bf16; everything else in fp32).  ``from_scratch`` evaluates one step from a whole window, without a ring.
 """
 import math
@@ -20,6 +20,8 @@ import os
 
 import numpy as np
 import torch
+
+from tests.oracle_ops import activation, layernorm, operand_linear
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f20_oad.npz")
 LN_EPS = 1e-5
@@ -105,34 +107,8 @@ def make_weights(cfg, seed):
     return sd
 
 
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
-def _linear(x, w, b, bf16_operands):
-    if bf16_operands == "x3":
-        xh, wh = _bf16(x), _bf16(w)
-        xl, wl = _bf16(x - xh), _bf16(w - wh)
-        y = xh @ wh.t() + xh @ wl.t() + xl @ wh.t()
-    elif bf16_operands:
-        y = _bf16(x) @ _bf16(w).t()
-    else:
-        y = x @ w.t()
-    return y if b is None else y + b
-
-
 def _ln(x, g, b):
-    mu = x.mean(dim=-1, keepdim=True)
-    var = ((x - mu) ** 2).mean(dim=-1, keepdim=True)
-    return (x - mu) / torch.sqrt(var + LN_EPS) * g + b
-
-
-def _act(x, name):
-    if name == "gelu":
-        return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
-    if name == "relu":
-        return torch.relu(x)
-    raise ValueError(name)
+    return layernorm(x, g, b, LN_EPS)
 
 
 def attention(q, k, v, heads, mask=None, causal=False):
@@ -167,8 +143,8 @@ class Stream:
         # input independent: the queries' self-attention + norm1, their q projection, the positional addends
         tgt = self.W["enc_queries.0.weight"]
         self.tgt0 = self._self_attn(p, tgt, False)
-        self.q0 = _linear(self.tgt0, w[:d], b[:d], self.bo)
-        self.pos_kv = _linear(self.pe[:self.L], self.w_kv, self.b_kv, self.bo)
+        self.q0 = operand_linear(self.tgt0, w[:d], b[:d], self.bo)
+        self.pos_kv = operand_linear(self.pe[:self.L], self.w_kv, self.b_kv, self.bo)
         self.ring = torch.zeros(self.L, 2 * d, dtype=dtype)      # W_k x | W_v x by SLOT
         self.head = 0                                             # slot of the oldest sample
         self.fill = 0
@@ -180,27 +156,27 @@ class Stream:
         if not self.cfg["linear_enabled"]:
             return x
         p = f"feature_head_{which}.visual_linear."
-        return torch.relu(_ln(_linear(x, self.W[p + "0.weight"], self.W[p + "0.bias"], self.bo), self.W[p + "1.weight"], self.W[p + "1.bias"]))
+        return torch.relu(_ln(operand_linear(x, self.W[p + "0.weight"], self.W[p + "0.bias"], self.bo), self.W[p + "1.weight"], self.W[p + "1.bias"]))
 
     def _self_attn(self, p, x, causal):
         d = self.d
-        qkv = _linear(x, self.W[p + "self_attn.in_proj_weight"], self.W[p + "self_attn.in_proj_bias"], self.bo)
+        qkv = operand_linear(x, self.W[p + "self_attn.in_proj_weight"], self.W[p + "self_attn.in_proj_bias"], self.bo)
         ctx = attention(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], self.heads, causal=causal)
-        y = _linear(ctx, self.W[p + "self_attn.out_proj.weight"], self.W[p + "self_attn.out_proj.bias"], self.bo)
+        y = operand_linear(ctx, self.W[p + "self_attn.out_proj.weight"], self.W[p + "self_attn.out_proj.bias"], self.bo)
         return _ln(x + y, self.W[p + "norm1.weight"], self.W[p + "norm1.bias"])
 
     def _cross_attn(self, p, x, mem):
         d = self.d
         w, b = self.W[p + "multihead_attn.in_proj_weight"], self.W[p + "multihead_attn.in_proj_bias"]
-        q = _linear(x, w[:d], b[:d], self.bo)
-        kv = _linear(mem, w[d:], b[d:], self.bo)
-        y = _linear(attention(q, kv[:, :d], kv[:, d:], self.heads), self.W[p + "multihead_attn.out_proj.weight"],
+        q = operand_linear(x, w[:d], b[:d], self.bo)
+        kv = operand_linear(mem, w[d:], b[d:], self.bo)
+        y = operand_linear(attention(q, kv[:, :d], kv[:, d:], self.heads), self.W[p + "multihead_attn.out_proj.weight"],
                     self.W[p + "multihead_attn.out_proj.bias"], self.bo)
         return _ln(x + y, self.W[p + "norm2.weight"], self.W[p + "norm2.bias"])
 
     def _ffn(self, p, x, norm):
-        h = _act(_linear(x, self.W[p + "linear1.weight"], self.W[p + "linear1.bias"], self.bo), self.cfg["activation"])
-        y = _linear(h, self.W[p + "linear2.weight"], self.W[p + "linear2.bias"], self.bo)
+        h = activation(operand_linear(x, self.W[p + "linear1.weight"], self.W[p + "linear1.bias"], self.bo), self.cfg["activation"])
+        y = operand_linear(h, self.W[p + "linear2.weight"], self.W[p + "linear2.bias"], self.bo)
         return _ln(x + y, self.W[p + norm + ".weight"], self.W[p + norm + ".bias"])
 
     def _module_norm(self, p, x, on):
@@ -212,7 +188,7 @@ class Stream:
         d, p = self.d, "enc_modules.0.layers.0."
         kv = kv_window + self.pos_kv
         ctx = attention(self.q0, kv[:, :d], kv[:, d:], self.heads, mask=mask)
-        y = _linear(ctx, self.W[p + "multihead_attn.out_proj.weight"], self.W[p + "multihead_attn.out_proj.bias"], self.bo)
+        y = operand_linear(ctx, self.W[p + "multihead_attn.out_proj.weight"], self.W[p + "multihead_attn.out_proj.bias"], self.bo)
         x = _ln(self.tgt0 + y, self.W[p + "norm2.weight"], self.W[p + "norm2.bias"])
         x = self._ffn(p, x, "norm3")
         return self._module_norm("enc_modules.0.", x, self.cfg["enc_module"][0][2])
@@ -239,12 +215,12 @@ class Stream:
             p = f"dec_modules.layers.{i}."
             x = self._ffn(p, self._cross_attn(p, self._self_attn(p, x, True), mem), "norm3")
         x = self._module_norm("dec_modules.", x, cfg["dec_module"][2])
-        return _linear(x, self.W["classifier.weight"], self.W["classifier.bias"], self.bo)
+        return operand_linear(x, self.W["classifier.weight"], self.W["classifier.bias"], self.bo)
 
     def step(self, work, long=None, mask=None):
         L = self.L
         if long is not None:
-            rows = _linear(self._feature_head("long", long), self.w_kv, None, self.bo)
+            rows = operand_linear(self._feature_head("long", long), self.w_kv, None, self.bo)
             if rows.shape[0] == L and self.fill == 0:
                 self.ring[:] = rows
                 self.head, self.fill = 0, L
@@ -261,7 +237,7 @@ class Stream:
 
     def from_scratch(self, work, window, mask=None):
         """The same step computed from the whole window of raw long samples [L, d_in] (oldest first), no ring, no cache."""
-        kv = _linear(self._feature_head("long", window), self.w_kv, None, self.bo)
+        kv = operand_linear(self._feature_head("long", window), self.w_kv, None, self.bo)
         return self._tail(self._stage0(kv, mask), work)
 
 

@@ -10,17 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import load_npz, small_cfg
-
-
-def rel_l2(got, want):
-    got, want = got.double().cpu(), want.double().cpu()
-    return float((got - want).norm() / (want.norm() + 1e-30))
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-30))
+from tests.helpers import cosine, load_npz, rel_l2, small_cfg
 
 
 def test_module_is_born_in_eval_mode_and_refuses_cpu_training():

@@ -29,22 +29,15 @@ import pytest
 import torch
 
 from tests import backward_oracle as BO
+from tests.helpers import EPS32, MARGIN, gpu_device
 
 gpu = pytest.mark.gpu
 
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
 ORDERS = 8                # summation orders of the fp32 run that a floor is taken over (_attn_case)
 GUARD_ROWS = 64
 NAN16 = 0x7FC5            # quiet bf16 NaN with a payload, compared as int16
 NAN32 = 0x7FC00A5A        # the same for fp32 buffers, compared as int32
 SLICES = ("dq", "dk", "dv")
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
 
 
 def _gen(*key):
@@ -177,7 +170,7 @@ def _check_guards(ints, inner_ints, pattern, what):
 def _run_attention(key, fn="auto"):
     """d_qkv of the case on the GPU, in sequence form on the CPU (bf16); guard rows checked"""
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = gpu_device(or_skip=True)
     layout, B, N, heads, hd, L, causal, _ = key
     c = _attn_case(key)
     nseq, D = B * N, heads * hd
@@ -200,7 +193,7 @@ def _run_attention(key, fn="auto"):
 
 def _check_attention(family, key):
     layout, B, N, heads, hd, L, causal, _ = key
-    _dev()
+    gpu_device(or_skip=True)
     c, bound = _attn_case(key), {k: MARGIN * v for k, v in _attn_floor(family).items()}
     got = _run_attention(key)
     again = _run_attention(key)
@@ -244,7 +237,7 @@ def test_generic_temporal_attention_bwd(key):
 @gpu
 @pytest.mark.parametrize("key", [(0, 3, 1, 3, 64, 17, 0, 1.5), (1, 2, 5, 1, 64, 31, 1, 1.5)], ids=["spatial-L17", "temporal-L31"])
 def test_head_dim_64_entry_stays_the_tuned_kernel_at_the_new_edges(key):
-    _dev()
+    gpu_device(or_skip=True)
     a = _run_attention(key, fn="sf_op_attention_bwd_hd")
     b = _run_attention(key, fn="sf_op_attention_bwd")
     assert torch.equal(a.view(torch.int16), b.view(torch.int16))
@@ -328,7 +321,7 @@ def _ln_floor(family):
 @gpu
 @pytest.mark.parametrize("key", LN_CASES, ids=lambda k: f"rows{k[0]}-D{k[1]}-{k[2].replace(' ', '_')}-gin{int(k[3])}-dgdb{int(k[4])}")
 def test_layernorm_bwd(key):
-    dev = _dev()
+    dev = gpu_device(or_skip=True)
     import streamformer_amd._native as nat
     rows, D, regime, with_gin, with_dgdb = key
     c, floor = _ln_case(key), _ln_floor(_ln_family(key))
@@ -387,7 +380,7 @@ def _wgrad_floor():
 @gpu
 @pytest.mark.parametrize("key", WGRAD_CASES, ids=lambda k: f"M{k[0]}-{k[1]}x{k[2]}-acc{k[3]}")
 def test_wgrad(key):
-    dev = _dev()
+    dev = gpu_device(or_skip=True)
     import streamformer_amd._native as nat
     M, N1, N2, acc = key
     c, floor = _wgrad_case(key), _wgrad_floor()

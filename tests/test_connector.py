@@ -15,32 +15,16 @@ import torch
 import torch.nn.functional as Fn
 
 from tests import connector_oracle as CO
-from tests.helpers import frames, maxabs, small_cfg
+from tests.helpers import MARGIN, bf16_bits, fp32_floor, frames, from_bf16_bits, gpu_device, maxabs, randn, small_cfg
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
 BF16_ROUND = 2.0 ** -8          # one bf16 rounding of a result, relative (round-to-nearest-even loses at most 2^-9)
 # hi = bf16(y), lo = bf16(y - hi): |y - hi| <= 2^-9 |y| and |(y - hi) - lo| <= 2^-9 |y - hi|, so hi + lo holds y to 2^-18 |y|; 2^-17 leaves
 # room for y's own distance from the fp64 value the bound is written against
 PLANES_ROUND = 2.0 ** -17
 MODES = {"none": 0, "average": 1, "max": 2, "bilinear": 3}
 NEWLINES = {"no_token": 0, "one_token": 1, "frame": 2, "grid": 3}
-
-
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _floor(f32_result, want):
-    """Precision floor of an fp32 computation: what torch's fp32 loses against fp64, and never less than one rounding of the result."""
-    return max(maxabs(f32_result, want), EPS32 * float(want.abs().max()))
-
-
-def _randn(seed, *shape):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -57,15 +41,6 @@ def _torch_pool(x, P, mode, stride):
     elif mode == "bilinear":
         g = Fn.interpolate(g, size=[-(-P // stride)] * 2, mode="bilinear")
     return g.permute(0, 2, 3, 1).reshape(F, -1, Cc)
-
-
-def _bits(t):
-    """fp32 -> the bf16 bit patterns (round-to-nearest-even) as int16."""
-    return t.to(torch.bfloat16).view(torch.int16)
-
-
-def _from_bits(t):
-    return t.view(torch.bfloat16).double()
 
 
 def _pool_call(nat, dev, *, x=None, hi=None, lo=None, F, P, Cc, mode, stride, nl, newline, out_dtype=None, out_lo=True):
@@ -101,19 +76,19 @@ POOL_CASES = [(5, 2, "bilinear"), (5, 2, "average"), (5, 2, "max"), (6, 2, "bili
 @pytest.mark.parametrize("P,stride,mode", POOL_CASES)
 def test_pool_kernel_vs_torch(P, stride, mode):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     worst = 0.0
     for Cc, F in ((64, 1), (64, 3), (200, 1), (200, 3)):
-        x = _randn(1900 + 17 * P + Cc + F, F, P * P, Cc) * 1.5
-        newline = _randn(7, Cc)
+        x = randn(1900 + 17 * P + Cc + F, F, P * P, Cc) * 1.5
+        newline = randn(7, Cc)
         # plane form: the tensor the planes hold (hi + lo, or hi alone) is the input of that form's reference
-        hi, lo = _bits(x), _bits(x - x.to(torch.bfloat16).float())
-        x_planes = {True: (_from_bits(hi) + _from_bits(lo)), False: _from_bits(hi)}
+        hi, lo = bf16_bits(x), bf16_bits(x - x.to(torch.bfloat16).float())
+        x_planes = {True: (from_bf16_bits(hi) + from_bf16_bits(lo)), False: from_bf16_bits(hi)}
         refs = {}
         for tag, xin in (("f32", x.double()), ("hilo", x_planes[True]), ("hi", x_planes[False])):
             want = _torch_pool(xin, P, mode, stride)
             f32 = _torch_pool(xin.float(), P, mode, stride)
-            refs[tag] = (want, f32, _floor(f32, want))
+            refs[tag] = (want, f32, fp32_floor(f32, want))
         for pos, nl in NEWLINES.items():
             is_nl = CO.add_newline(torch.zeros(F, refs["f32"][0].shape[1], 1), torch.ones(1), pos)[:, 0] == 1
             assert int(is_nl.sum()) == {"no_token": 0, "one_token": 1, "frame": F, "grid": F * CO.pooled_side(P, mode, stride)}[pos]
@@ -133,13 +108,13 @@ def test_pool_kernel_vs_torch(P, stride, mode):
                     for b in bufs:
                         assert torch.isnan(b[rows:].view(torch.bfloat16).float()).all(), "the guard row was written"
                         assert not torch.isnan(b[:rows].view(torch.bfloat16).float()).any(), "output elements left unwritten"
-                    got = sum(_from_bits(b) for b in body)
+                    got = sum(from_bf16_bits(b) for b in body)
                     rel = PLANES_ROUND if form == "planes" else BF16_ROUND
-                    exact_hi = _bits(seq32)
+                    exact_hi = bf16_bits(seq32)
                     if mode in ("max", "none"):                      # no arithmetic: the split of torch's own fp32 result, bit for bit
                         assert torch.equal(body[0], exact_hi)
                         if form == "planes":
-                            assert torch.equal(body[1], _bits(seq32 - seq32.to(torch.bfloat16).float()))
+                            assert torch.equal(body[1], bf16_bits(seq32 - seq32.to(torch.bfloat16).float()))
                     assert torch.equal(body[0][is_nl], exact_hi[is_nl])
                 else:
                     out = bufs[0]
@@ -162,8 +137,8 @@ def test_pool_kernel_vs_torch(P, stride, mode):
 
 def test_max_pool_propagates_nan_as_torch_does():
     import streamformer_amd._native as nat
-    dev = _gpu()
-    x = _randn(1990, 2, 25, 64)
+    dev = gpu_device()
+    x = randn(1990, 2, 25, 64)
     x[0, 6, 3] = float("nan")               # patch (1, 1): the last tap of cell (0, 0)'s window ...
     x[1, 0, 9] = float("nan")               # ... and patch (0, 0), the first tap of the same cell in the next frame
     want = _torch_pool(x, 5, "max", 2)
@@ -191,7 +166,7 @@ def _reference(sd, cfg, feats, key):
     """fp64 restatement in the reference's order and the two modes' floors: computed once per key, shared, never changed."""
     if key not in _REFS:
         want = CO.forward(sd, cfg, feats)
-        _REFS[key] = dict(want=want, floor={m: _floor(CO.forward(sd, cfg, feats, dtype=torch.float32, bf16_operands=op), want)
+        _REFS[key] = dict(want=want, floor={m: fp32_floor(CO.forward(sd, cfg, feats, dtype=torch.float32, bf16_operands=op), want)
                                             for m, op in FLOOR_OPERANDS.items()})
     return _REFS[key]
 
@@ -200,13 +175,13 @@ def _connector(cfg, sd, mode, out_dtype=torch.float32):
     import streamformer_amd as sa
     m = sa.VideoTokenConnector(cfg, compute_dtype=mode, out_dtype=out_dtype)
     m.load_state_dict({k: v for k, v in sd.items() if k in m.state_dict()})
-    return m.to(_gpu())
+    return m.to(gpu_device())
 
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", list(CO.CASES))
 def test_connector_vs_fixture_and_fp64(name, mode):
-    dev = _gpu()
+    dev = gpu_device()
     sd, cfg, feats, stored = CO.golden_case(_gold(), name)
     ref = _reference(sd, cfg, feats, name)
     m = _connector(cfg, sd, mode)
@@ -233,7 +208,7 @@ def test_connector_vs_fixture_and_fp64(name, mode):
         img = m(feats.to(dev), modality="image").cpu()
         flat = dict(cfg, mm_patch_merge_type="flat", mm_spatial_pool_stride=1)
         want_img = CO.forward(sd, flat, feats)
-        fl = _floor(CO.forward(sd, flat, feats, dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want_img)
+        fl = fp32_floor(CO.forward(sd, flat, feats, dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want_img)
         assert img.shape == want_img.shape == (CO.FRAMES * 25, CO.D_OUT) and maxabs(img, want_img) <= MARGIN * fl
 
 
@@ -242,7 +217,7 @@ def test_connector_vs_fixture_and_fp64(name, mode):
 # ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_full_width_once(mode):
-    dev = _gpu()
+    dev = gpu_device()
     cfg = CO.make_config("mlp2x_gelu", "bilinear", "grid", d_in=768, d_out=3584)
     if "full.sd" not in _REFS:
         _REFS["full.sd"] = CO.make_weights("mlp2x_gelu", 1931, 768, 3584)
@@ -266,7 +241,7 @@ def test_full_width_once(mode):
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", ["mlp_bil_p5_grid", "mlp_max_p5_none", "lin_avg_p5_none"])
 def test_frames_one_at_a_time(name, mode):
-    dev = _gpu()
+    dev = gpu_device()
     sd, cfg, _, _ = CO.golden_case(_gold(), name)
     feats = CO.make_features(1940, 3, 5)
     ref = _reference(sd, cfg, feats, ("seq", name))
@@ -298,7 +273,7 @@ def test_streaming_video_tokens(mode, newline, monkeypatch):
     import streamformer_amd._native as nat
     from oracle import streamformer_oracle as O
     from streamformer_amd.init_weights import make_state_dict
-    dev = _gpu()
+    dev = gpu_device()
     ecfg = small_cfg(num_frames=8)                      # 48 / 16: a 3 x 3 grid, bilinear stride 2 -> 2 x 2
     esd = make_state_dict(ecfg, seed=19)
     enc = sa.TimesformerMultiTaskingModelSigLIP(ecfg, compute_dtype="fp32")
@@ -325,10 +300,10 @@ def test_streaming_video_tokens(mode, newline, monkeypatch):
             held = min(t + 1, 3)
             assert stream.frames_held == held and got.shape == (conn.num_tokens(held, 3), 192)
             want = CO.forward(sd, cfg, window[0])
-            floor = _floor(CO.forward(sd, cfg, window[0], dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want)
+            floor = fp32_floor(CO.forward(sd, cfg, window[0], dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want)
             native_window = tower.hidden_states[0].cpu()
             want_own = CO.forward(sd, cfg, native_window)
-            floor_own = _floor(CO.forward(sd, cfg, native_window, dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want_own)
+            floor_own = fp32_floor(CO.forward(sd, cfg, native_window, dtype=torch.float32, bf16_operands=FLOOR_OPERANDS[mode]), want_own)
             err_own, err = maxabs(got, want_own), maxabs(got, want)
             print(f"[streaming tokens {mode} {newline} push {t}] on the native tower's window {err_own:.3e}  floor {floor_own:.3e}  ratio "
                   f"{err_own / floor_own:.2f}   on the oracle tower's window {err:.3e}  floor {floor:.3e}  ratio {err / floor:.2f}   "
@@ -347,7 +322,7 @@ def test_streaming_video_tokens(mode, newline, monkeypatch):
 # ------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_output_untouched():
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     sd, cfg, feats, _ = CO.golden_case(_gold(), "mlp_bil_p5_grid")
     m = _connector(cfg, sd, "fp32")
     key = m._video_key()

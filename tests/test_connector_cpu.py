@@ -7,14 +7,7 @@ import pytest
 import torch
 
 from tests import connector_oracle as CO
-from tests.helpers import maxabs
-
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
-
-
-def _floor(f32_result, want):
-    return max(maxabs(f32_result, want), EPS32 * float(want.abs().max()))
+from tests.helpers import MARGIN, fp32_floor, maxabs
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +22,7 @@ def test_oracle_reproduces_the_reference(gold, name):
     redrawn = CO.make_weights(cfg["mm_projector_type"], int(gold[f"w.{cfg['mm_projector_type']}.seed"]))
     assert set(redrawn) == set(sd) and all(torch.equal(redrawn[k], sd[k]) for k in redrawn)
     want = CO.forward(sd, cfg, feats)
-    floor = _floor(CO.forward(sd, cfg, feats, dtype=torch.float32), want)
+    floor = fp32_floor(CO.forward(sd, cfg, feats, dtype=torch.float32), want)
     assert ref.shape == want.shape == (CO.num_tokens(cfg, CO.FRAMES, CO.CASES[name][2]), CO.D_OUT)
     err = maxabs(ref, want)
     print(f"[connector oracle {name}] reference fp32 vs fp64 restatement {err:.3e}  floor {floor:.3e}  ratio {err / floor:.2f}")

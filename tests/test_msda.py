@@ -21,12 +21,10 @@ import torch
 
 from tests import msda_oracle as MO
 from tests.conftest import ROOT
-from tests.helpers import maxabs
+from tests.helpers import EPS32, MARGIN, check_against_floor, fp32_floor, gpu_device, guarded, maxabs, read_guarded
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
 MODES = {"fp32": "x3", "bf16": True}
 N = MO.N_BATCH
 
@@ -41,69 +39,37 @@ SWEEP = [(8, 1, [(6, 5), (3, 3), (1, 2)], 4, 7),
          (32, 3, [(12, 12), (6, 6), (3, 3)], 4, 4)]          # injector-like: S >> Lq
 
 
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _floor(got32, want):
-    return max(maxabs(got32, want), EPS32 * float(want.abs().max()))
-
-
-def _check(what, got, floor32, want):
-    bound = MARGIN * _floor(floor32, want)
-    err = maxabs(got, want)
-    print(f"  {what}: error {err:.3e}, bound {bound:.3e} ({err / bound:.3f})")
-    assert err <= bound, (what, err, bound)
-
-
 def _levels(shapes):
     flat = [v for hw in shapes for v in hw]
     return (C.c_int32 * len(flat))(*flat), (C.c_int32 * len(shapes))(*MO.level_starts(shapes))
 
 
-def _guarded(dev, *shape):
-    """A NaN-filled buffer with one guard row behind the tensor: (whole buffer, view)."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 64,), float("nan"), device=dev)
-    return buf, buf[:n].view(*shape)
-
-
 def _op_forward(value, shapes, loc, w):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     _, S, M, D = value.shape
     Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
     hw, st = _levels(shapes)
     v, l, a = (t.to(dev).contiguous() for t in (value, loc, w))
-    buf, out = _guarded(dev, N, Lq, M * D)
+    buf, out = guarded(dev, N, Lq, M * D)
     nat.check(nat.lib.sf_op_msda_forward(v.data_ptr(), hw, st, l.data_ptr(), a.data_ptr(), out.data_ptr(), N, S, M, D, Lq, L, P,
                                          nat.current_stream_handle(dev)))
     torch.cuda.synchronize()
-    host = buf.cpu()
-    assert torch.isnan(host[out.numel():]).all(), "the guard row was written"
-    assert not torch.isnan(host[:out.numel()]).any(), "output elements left unwritten"
-    return host[:out.numel()].view(N, Lq, M * D)
+    return read_guarded(buf, out)
 
 
 def _op_backward(value, shapes, loc, w, grad_out):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     _, S, M, D = value.shape
     Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
     hw, st = _levels(shapes)
     v, l, a, g = (t.to(dev).contiguous() for t in (value, loc, w, grad_out))
-    bufs, views = zip(*(_guarded(dev, *t.shape) for t in (value, loc, w)))
+    bufs, views = zip(*(guarded(dev, *t.shape) for t in (value, loc, w)))
     nat.check(nat.lib.sf_op_msda_backward(v.data_ptr(), hw, st, l.data_ptr(), a.data_ptr(), g.data_ptr(), views[0].data_ptr(), views[1].data_ptr(),
                                           views[2].data_ptr(), N, S, M, D, Lq, L, P, nat.current_stream_handle(dev)))
     torch.cuda.synchronize()
-    out = []
-    for buf, view in zip(bufs, views):
-        host = buf.cpu()
-        assert torch.isnan(host[view.numel():]).all(), "a guard row was written"
-        assert not torch.isnan(host[:view.numel()]).any(), "gradient elements left unwritten"
-        out.append(host[:view.numel()].view(view.shape))
-    return out
+    return [read_guarded(buf, view) for buf, view in zip(bufs, views)]
 
 
 def _draw(seed, D, M, shapes, P, Lq):
@@ -132,12 +98,12 @@ def test_forward_and_backward_vs_fp64(D, M, shapes, P, Lq):
     want, floor = _both_floors(value, shapes, loc, w, grad_out)
     got = [_op_forward(value, shapes, loc, w)] + _op_backward(value, shapes, loc, w, grad_out)
     for name, g, f, t in zip(("out", "grad_value", "grad_sampling_locations", "grad_attention_weights"), got, floor, want):
-        _check(name, g, f, t)
+        check_against_floor(name, g, f, t)
     # reproducibility: forward and the two owned gradients bit for bit; grad_value (float atomics) only to its floor, checked above
     again = [_op_forward(value, shapes, loc, w)] + _op_backward(value, shapes, loc, w, grad_out)
     for i in (0, 2, 3):
         assert torch.equal(got[i], again[i]), i
-    _check("grad_value, second run", again[1], floor[1], want[1])
+    check_against_floor("grad_value, second run", again[1], floor[1], want[1])
 
 
 def test_f21_operator_cases():
@@ -147,7 +113,7 @@ def test_f21_operator_cases():
         _, floor = _both_floors(value, c["shapes"], loc, w, grad_out)
         got = [_op_forward(value, c["shapes"], loc, w)] + _op_backward(value, c["shapes"], loc, w, grad_out)
         for key, gg, f in zip(("out", "grad_value", "grad_loc", "grad_w"), got, floor):
-            _check(f"{name}.{key}", gg, f, torch.from_numpy(g[f"{name}.{key}"]))
+            check_against_floor(f"{name}.{key}", gg, f, torch.from_numpy(g[f"{name}.{key}"]))
 
 
 def test_samples_on_pixel_centres_and_limits():
@@ -168,7 +134,7 @@ def test_samples_on_pixel_centres_and_limits():
     value = torch.from_numpy(rs.standard_normal((N, MO.pixels(shapes), M, D)).astype(np.float32))
     w = torch.softmax(torch.from_numpy(rs.standard_normal((N, Lq, M, L * P)).astype(np.float32)), -1).view(N, Lq, M, L, P)
     want = MO.core(value.double(), shapes, loc.double(), w.double())
-    _check("out", _op_forward(value, shapes, loc, w), MO.core_grid_sample(value, shapes, loc, w), want)
+    check_against_floor("out", _op_forward(value, shapes, loc, w), MO.core_grid_sample(value, shapes, loc, w), want)
 
 
 def test_scatter_collisions():
@@ -182,7 +148,7 @@ def test_scatter_collisions():
     got = _op_backward(value, shapes, loc, w, grad_out)
     assert int((want[1].abs().sum((2, 3)) > 0).sum()) == 4 * N
     for name, g, f, t in zip(("grad_value", "grad_sampling_locations", "grad_attention_weights"), got, floor[1:], want[1:]):
-        _check(name, g, f, t)
+        check_against_floor(name, g, f, t)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -190,20 +156,18 @@ def test_scatter_collisions():
 # ------------------------------------------------------------------------------------------------
 def _op_fused(value, mask, shapes, offsets, logits, ref):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     _, S, M, D = value.shape
     Lq, L = ref.shape[1], len(shapes)
     P = logits.shape[-1] // (M * L)
     hw, st = _levels(shapes)
     v, o, lg, r = (t.to(dev).contiguous() for t in (value, offsets, logits, ref))
     pad = None if mask is None else mask.to(dev, torch.uint8).contiguous()
-    buf, out = _guarded(dev, N, Lq, M * D)
+    buf, out = guarded(dev, N, Lq, M * D)
     nat.check(nat.lib.sf_op_msda_forward_fused(v.data_ptr(), nat.ptr(pad), hw, st, o.data_ptr(), o.shape[-1], lg.data_ptr(), lg.shape[-1], r.data_ptr(),
                                                r.shape[-1], out.data_ptr(), N, S, M, D, Lq, L, P, nat.current_stream_handle(dev)))
     torch.cuda.synchronize()
-    host = buf.cpu()
-    assert torch.isnan(host[out.numel():]).all() and not torch.isnan(host[:out.numel()]).any()
-    return host[:out.numel()].view(N, Lq, M * D)
+    return read_guarded(buf, out)
 
 
 @pytest.mark.parametrize("big_logits", [False, True])
@@ -237,9 +201,9 @@ def test_fused_entry(ref_dim, masked, big_logits):
     v32, loc32, w32 = sides[torch.float32]
     floor = MO.core_grid_sample(v32, shapes, loc32, w32)
     got = _op_fused(value, mask, shapes, offsets, logits, ref)
-    _check("fused vs fp64", got, floor, want)
+    check_against_floor("fused vs fp64", got, floor, want)
     unfused = _op_forward(v32, shapes, loc32, w32)           # the unfused entry fed torch's masked value, locations and softmax
-    bound = MARGIN * _floor(floor, want)
+    bound = MARGIN * fp32_floor(floor, want)
     assert maxabs(got, unfused) <= bound, (maxabs(got, unfused), bound)
     assert torch.equal(_op_fused(value, mask, shapes, offsets, logits, ref), got)
 
@@ -265,11 +229,11 @@ def _module(name, mode):
     c = MO.MODULE_CASES[name]
     m = sa.MSDeformAttn(c["d_model"], len(c["shapes"]), c["heads"], c["P"], ratio=0.5, compute_dtype=mode)
     m.load_state_dict(MO.make_weights(c))
-    return m.to(_gpu())
+    return m.to(gpu_device())
 
 
 def _run(m, c, query, ref, flat, mask, shapes_as=list):
-    dev = _gpu()
+    dev = gpu_device()
     shapes, starts = c["shapes"], MO.level_starts(c["shapes"])
     if shapes_as is not list:
         shapes, starts = shapes_as(shapes), shapes_as(starts)
@@ -284,17 +248,17 @@ def test_module_vs_f21_and_oracle(name, mode):
     m = _module(name, mode).eval()
     with torch.no_grad():
         got = _run(m, c, query, ref, flat, mask).cpu()
-        on_device = _run(m, c, query, ref, flat, mask, shapes_as=lambda v: torch.tensor(v, device=_gpu())).cpu()
-    _check(f"{name} {mode} vs oracle", got, floors[mode], want)
-    _check(f"{name} {mode} vs F21", got, floors[mode], stored)
+        on_device = _run(m, c, query, ref, flat, mask, shapes_as=lambda v: torch.tensor(v, device=gpu_device())).cpu()
+    check_against_floor(f"{name} {mode} vs oracle", got, floors[mode], want)
+    check_against_floor(f"{name} {mode} vs F21", got, floors[mode], stored)
     assert torch.equal(on_device, got), "shapes given as device tensors change the result"
     # the grad path (plain torch projections + the autograd function) agrees within the mode's floor
     for p in m.parameters():
         p.requires_grad_(True)
     with_grad = _run(m, c, query, ref, flat, mask).detach().cpu()
-    bound = MARGIN * _floor(floors[mode], want)
+    bound = MARGIN * fp32_floor(floors[mode], want)
     assert maxabs(with_grad, got) <= bound, (maxabs(with_grad, got), bound)
-    _check(f"{name} grad path vs oracle", with_grad, floors["fp32"], want)
+    check_against_floor(f"{name} grad path vs oracle", with_grad, floors["fp32"], want)
 
 
 @pytest.mark.parametrize("name", ["tiny", "tiny4"])
@@ -304,7 +268,7 @@ def test_module_parameter_gradients_vs_f21(name):
     c = MO.MODULE_CASES[name]
     _, floor = MO.module_with_grads(sd, c, query, flat, ref, mask, go, dtype=torch.float32, sample=MO.core_grid_sample)
     m = _module(name, "fp32")
-    dev = _gpu()
+    dev = gpu_device()
     q, f = query.to(dev).requires_grad_(True), flat.to(dev).requires_grad_(True)
     out = m(q, ref.to(dev), f, torch.tensor(c["shapes"]), torch.tensor(MO.level_starts(c["shapes"])), None if mask is None else mask.to(dev))
     out.backward(go.to(dev))
@@ -312,7 +276,7 @@ def test_module_parameter_gradients_vs_f21(name):
     got.update(query=q.grad.cpu(), input_flatten=f.grad.cpu())
     assert set(got) == set(floor)
     for k in got:
-        _check(f"{name} d/d {k}", got[k], floor[k], torch.from_numpy(g[f"{name}.grad.{k}"]))
+        check_against_floor(f"{name} d/d {k}", got[k], floor[k], torch.from_numpy(g[f"{name}.grad.{k}"]))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -320,7 +284,7 @@ def test_module_parameter_gradients_vs_f21(name):
 # ------------------------------------------------------------------------------------------------
 def test_non_default_stream_is_honoured():
     import streamformer_amd as sa
-    dev = _gpu()
+    dev = gpu_device()
     D, M, shapes, P, Lq = 32, 3, [(6, 5), (3, 3), (1, 2)], 4, 37
     value, loc, w, _ = _draw(2501, D, M, shapes, P, Lq)
     v, l, a = value.to(dev), loc.to(dev), w.to(dev)
@@ -344,7 +308,7 @@ def test_graph_capture_of_the_fused_forward():
     name, mode = "pix", "fp32"
     (query, flat, ref, mask, _), _, _, _, _ = _module_case(name)
     c = MO.MODULE_CASES[name]
-    dev = _gpu()
+    dev = gpu_device()
     m = _module(name, mode).eval()
     shapes = torch.tensor(c["shapes"], device=dev)
     starts = torch.tensor(MO.level_starts(c["shapes"]), device=dev)
@@ -372,7 +336,7 @@ def test_graph_capture_of_the_fused_forward():
 
 def test_compiled_op_stand_in_runs():
     import streamformer_amd as sa
-    dev = _gpu()
+    dev = gpu_device()
     c = MO.CORE_CASES["c0"]
     value, loc, w, grad_out = (t.to(dev) for t in MO.make_core_inputs(c))
     op = sa.as_compiled_op()

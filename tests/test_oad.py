@@ -15,27 +15,12 @@ import pytest
 import torch
 
 from tests import oad_oracle as OO
-from tests.helpers import frames, maxabs, small_cfg
+from tests.helpers import MARGIN, fp32_floor, frames, gpu_device, maxabs, randn, small_cfg
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
 MODES = {"fp32": "x3", "bf16": True}
 NINF = float("-inf")
-
-
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _floor(got32, want):
-    return max(maxabs(got32, want), EPS32 * float(want.abs().max()))
-
-
-def _randn(seed, *shape):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -78,7 +63,7 @@ def _attention_call(nat, dev, q, k, v, starts, kpos, vpos, mask, heads, hd, caus
 @pytest.mark.parametrize("hd", [8, 32, 72, 256])
 def test_attention_kernel_vs_fp64(hd, Tq, Tk, causal):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     heads = 2
     D = heads * hd
     leads = sorted({0, min(3, Tk - 1), Tk - 1})
@@ -86,13 +71,13 @@ def test_attention_kernel_vs_fp64(hd, Tq, Tk, causal):
     worst = 0.0
     for S, shared in itertools.product((1, 3), (True, False)):
         seed = 2100 + hd + 7 * Tq + 3 * S + int(shared)
-        q = _randn(seed, 1 if shared else S, Tq, D)
-        k, v = _randn(seed + 1, S, Tk, D), _randn(seed + 2, S, Tk, D)
-        kpos, vpos = 0.5 * _randn(seed + 3, Tk, D), 0.5 * _randn(seed + 4, Tk, D)
+        q = randn(seed, 1 if shared else S, Tq, D)
+        k, v = randn(seed + 1, S, Tk, D), randn(seed + 2, S, Tk, D)
+        kpos, vpos = 0.5 * randn(seed + 3, Tk, D), 0.5 * randn(seed + 4, Tk, D)
         for lead, ring in itertools.product(leads, rings):
             mask = None
             if lead:
-                mask = 0.3 * _randn(seed + 5, S, Tk)
+                mask = 0.3 * randn(seed + 5, S, Tk)
                 mask[:, :lead] = NINF
                 mask[S - 1, lead - 1] = 0.0      # streams differ: the last one keeps one more key
             starts = None if ring is None else [(ring + s) % Tk for s in range(S)]
@@ -101,7 +86,7 @@ def test_attention_kernel_vs_fp64(hd, Tq, Tk, causal):
             want = _attention_ref(q.double(), k.double(), v.double(), st, None if kp is None else kp.double(), None if vp is None else vp.double(), mask, heads, causal)
             f32 = _attention_ref(q, k, v, st, kp, vp, mask, heads, causal)
             got = _attention_call(nat, dev, q, k, v, starts, kp, vp, mask, heads, hd, causal)
-            bound = MARGIN * _floor(f32, want)
+            bound = MARGIN * fp32_floor(f32, want)
             err = maxabs(got, want)
             worst = max(worst, err / bound)
             assert err <= bound, (S, shared, lead, ring, err, bound)
@@ -133,7 +118,7 @@ def _detector(c, sd, mode):
     det = sa.OnlineActionDetector(_config(c), compute_dtype=mode)
     res = det.load_state_dict(sd, strict=False)
     assert res.missing_keys == ["pos_encoding.pe"] and not res.unexpected_keys
-    return det.to(_gpu())
+    return det.to(gpu_device())
 
 
 @functools.lru_cache(maxsize=None)
@@ -156,7 +141,7 @@ def _case(name):
 
 
 def _bound(floor32, want):
-    return MARGIN * _floor(floor32, want)
+    return MARGIN * fp32_floor(floor32, want)
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -254,7 +239,7 @@ def test_full_width_case():
     c = OO.FULL
     sd = OO.make_weights(c, 2003)
     L, W = c["long_samples"], c["work_samples"]
-    window, work, new = _randn(1, L, c["d_in"]), _randn(2, 3, W, c["d_in"]), _randn(3, 1, c["d_in"])
+    window, work, new = randn(1, L, c["d_in"]), randn(2, 3, W, c["d_in"]), randn(3, 1, c["d_in"])
     mask = torch.zeros(L)
     mask[:5] = NINF
     plan = [(work[0], window, mask), (work[1], new, mask), (work[2], None, None)]
@@ -296,7 +281,7 @@ def _reference_long_plan(frames_total, L, W, rate):
 def test_streaming_action_detector():
     import streamformer_amd as sa
     from streamformer_amd.init_weights import make_state_dict
-    dev = _gpu()
+    dev = gpu_device()
     cfg = small_cfg()
     tower = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype="fp32")
     tower.load_state_dict(make_state_dict(cfg, seed=4))

@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from tests import spatial_head_oracle as S
-from tests.helpers import load_npz, maxabs, small_cfg
+from tests.helpers import cosine, load_npz, maxabs, rel_l2, small_cfg
 
 T_FRAMES = 4
 FLOOR_FACTOR = 8.0
@@ -36,16 +36,7 @@ def f16(golden_dir):
     return load_npz(os.path.join(golden_dir, "f16_vis_head.npz"))
 
 
-def rel_l2(got, want):
-    got, want = got.double().cpu(), want.double().cpu()
-    return float((got - want).norm() / (want.norm() + 1e-30))
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-30))
-
-
+# local: unlike helpers.rel_max it has no guard in the denominator, so an all-zero reference fails instead of passing
 def relmax(got, want):
     want = want.double().cpu()
     return float((got.double().cpu() - want).abs().max() / want.abs().max())
@@ -207,6 +198,7 @@ def test_wrapper_builds_the_vis_and_classification_heads(f16):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
+# local: this file is not marked gpu as a whole, so a missing GPU skips here where helpers.gpu_device() asserts
 def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")

@@ -20,6 +20,7 @@ from oracle import streamformer_oracle as O
 from streamformer_amd.configuration import StreamformerConfig
 from streamformer_amd.init_weights import make_state_dict
 from tests.helpers import frames, maxabs
+from tests.oracle_ops import bf16_round
 
 pytestmark = pytest.mark.gpu
 
@@ -131,10 +132,6 @@ EMB_CASES = [
 EMB_TOL = {"fp32": 6e-5, "bf16": 6e-6}
 
 
-def _bf16(x):
-    return x.to(torch.bfloat16).double()
-
-
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 @pytest.mark.parametrize("case", EMB_CASES, ids=lambda c: "-".join(str(v) for v in c[:6]))
 def test_embeddings_vs_reference(mode, case):
@@ -162,7 +159,7 @@ def test_embeddings_vs_reference(mode, case):
     w = w.reshape(w.shape[0], -1)
     pat = O.patchify(pix[sel], cfg.patch_size)
     if mode == "bf16":          # the patch kernel rounds each pixel value (after the uint8 FMA) to bf16; the weights are bf16
-        pat, w = _bf16(pat), _bf16(w)
+        pat, w = bf16_round(pat), bf16_round(w)
     want = pat @ w.t() + sd64["embeddings.patch_embeddings.projection.bias"]
     want = want + O.position_embedding(sd, cfg, H, W).double()[None, None]        # bicubic table in fp32, as the model builds it
     want = want + O.time_embedding_rows(sd64, cfg, 0, T, False)[None, :, None, :]

@@ -25,9 +25,9 @@ import torch
 
 from tests import spatial_head_oracle as S
 from tests import text_heads_oracle as X
-from tests.helpers import load_npz, maxabs, small_cfg
-from tests.test_spatial_head import FLOOR_FACTOR, LOSS_TOL, cosine, f16_cfg, fp64_mask_loss, rel_l2, relmax
-from tests.test_train_widths import GRAD_COS, GRAD_REL_L2, SCALAR_REL
+from tests.helpers import cosine, load_npz, maxabs, rel_l2, small_cfg
+from tests.test_spatial_head import FLOOR_FACTOR, LOSS_TOL, f16_cfg, fp64_mask_loss, relmax
+from tests.train_support import GRAD_COS, GRAD_REL_L2, SCALAR_REL, to_dev
 
 T_FRAMES = 4
 GROUNDING_NAMES = ("CharadesSTA", "QVHighlights", "TaCoS", "TVSum", "ActivityNetCaptions", "DiDeMo", "QuerYD", "TaskGrounding")
@@ -230,6 +230,7 @@ def test_refusals_come_with_a_message(f17):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
+# local: as in test_spatial_head.py, a missing GPU skips
 def _gpu():
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
@@ -385,10 +386,6 @@ def _train_setup(lr=1e-3, wd=0.05):
     return cfg, sd, tr, orc, x, ground, retr
 
 
-def _to_dev(ti, dev):
-    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in ti.items()}
-
-
 @pytest.mark.gpu
 def test_grounding_through_the_wrapper_and_the_trainer_vs_oracle_autograd():
     """loss.backward() through StreamformerForMultiTaskingSigLIP fills the encoder's .grad with the oracle's autograd gradients of the
@@ -411,7 +408,7 @@ def test_grounding_through_the_wrapper_and_the_trainer_vs_oracle_autograd():
     assert abs(float(losses["TaskGrounding"]) - float(want_loss)) < 2e-2 * abs(float(want_loss))
     assert outs["TaskGrounding"].shape == (2, 8)
     # update_freq = 2: the first micro-step accumulates half the gradient and leaves the optimizer alone
-    got_loss = tr.micro_step("grounding", x.to(dev), _to_dev(ground, dev), update_freq=2)
+    got_loss = tr.micro_step("grounding", x.to(dev), to_dev(ground, dev), update_freq=2)
     torch.cuda.synchronize()
     assert abs(float(got_loss) - float(losses["TaskGrounding"])) < 1e-3 * abs(float(got_loss)) + 1e-5
     named = dict(model.timesformer.named_parameters())
@@ -456,7 +453,7 @@ def test_three_adamw_steps_alternating_grounding_and_retrieval_track_the_oracle(
         orc.opt.step()
         orc.opt.zero_grad(set_to_none=True)
         want.append(float(want_loss.detach()))
-        got.append(float(tr.micro_step(task, x.to(dev), _to_dev(ti, dev), lr=1e-3, weight_decay=0.05, clip_grad=1.0)))
+        got.append(float(tr.micro_step(task, x.to(dev), to_dev(ti, dev), lr=1e-3, weight_decay=0.05, clip_grad=1.0)))
     rel = [abs(a - b) / abs(b) for a, b in zip(got, want)]
     print("grounding / retrieval / grounding losses (trainer, oracle):", list(zip(got, want)))
     assert max(rel) < 3e-2, list(zip(got, want))

@@ -15,26 +15,9 @@ import pytest
 import torch
 
 from tests import text_tower_oracle as TO
-from tests.helpers import maxabs, small_cfg
+from tests.helpers import EPS32, MARGIN, fp32_floor, gpu_device, maxabs, randn, small_cfg
 
 pytestmark = pytest.mark.gpu
-
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
-
-
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _randn(seed, *shape):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def _floor(f32_result, want):
-    """Precision floor of an fp32 computation: what torch's fp32 loses against fp64, and never less than one rounding of the result."""
-    return max(maxabs(f32_result, want), EPS32 * float(want.abs().max()))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -69,12 +52,12 @@ def _attention(nat, dev, qkv, mask, heads, hd):
 @pytest.mark.parametrize("L", [1, 7, 16, 17, 64, 77, 128])
 def test_text_attention_vs_fp64(L, hd):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     B, heads = 3, 2
-    qkv = _randn(1800 + 131 * L + hd, B, L, 3 * heads * hd) * 1.5          # as tests/test_train_widths.py draws attention inputs
+    qkv = randn(1800 + 131 * L + hd, B, L, 3 * heads * hd) * 1.5          # as tests/test_train_widths.py draws attention inputs
     for name, mask in _masks(B, L).items():
         want = TO.attention(qkv.double(), mask, heads)
-        floor = _floor(TO.attention(qkv, mask, heads), want)
+        floor = fp32_floor(TO.attention(qkv, mask, heads), want)
         got = _attention(nat, dev, qkv, mask, heads, hd)
         assert not torch.isnan(got).any(), f"{name}: output elements left unwritten"
         err = maxabs(got, want)
@@ -87,7 +70,7 @@ def test_text_attention_vs_fp64(L, hd):
             # a masked key has weight exactly 0: changing its k and v rows changes nothing
             other = qkv.clone().reshape(B, L, 3, heads * hd)
             dead = (mask == 0)
-            other[:, :, 1:][dead] = _randn(5, int(dead.sum()), 2, heads * hd) * 3.0
+            other[:, :, 1:][dead] = randn(5, int(dead.sum()), 2, heads * hd) * 3.0
             assert torch.equal(_attention(nat, dev, other.reshape(B, L, -1), mask, heads, hd), got), f"{name}: a masked key leaked"
 
 
@@ -99,12 +82,12 @@ def test_text_attention_vs_fp64(L, hd):
 @pytest.mark.parametrize("G", [0, 1, 3])
 def test_text_pool_vs_fp64(B, L, D, P, G):
     import streamformer_amd._native as nat
-    dev = _gpu()
-    x = _randn(1850 + B, B, L, D) * 1.5
-    gamma, beta = 1.0 + 0.1 * _randn(1, D), 0.1 * _randn(2, D)
-    w, b = _randn(3, P, D) / math.sqrt(D), 0.1 * _randn(4, P)
+    dev = gpu_device()
+    x = randn(1850 + B, B, L, D) * 1.5
+    gamma, beta = 1.0 + 0.1 * randn(1, D), 0.1 * randn(2, D)
+    w, b = randn(3, P, D) / math.sqrt(D), 0.1 * randn(4, P)
     want = TO.pool(x.double(), gamma.double(), beta.double(), 1e-6, w.double(), b.double(), G)
-    floor = _floor(TO.pool(x, gamma, beta, 1e-6, w, b, G), want)
+    floor = fp32_floor(TO.pool(x, gamma, beta, 1e-6, w, b, G), want)
     rows = B // G if G else B
     out = torch.full((rows, P), float("nan"), dtype=torch.float32, device=dev)
     scratch = torch.empty(B, P, dtype=torch.float32, device=dev)
@@ -162,8 +145,8 @@ def _reference(name, case):
         x3 = TO.forward(sd, cfg, ids, mask, dtype=torch.float32, bf16_operands="x3")
         b16 = TO.forward(sd, cfg, ids, mask, dtype=torch.float32, bf16_operands=True)
         _FLOORS[key] = dict(ids=ids, mask=mask, want=want, hf=(hf_last, hf_pooled),
-                            floor={"fp32": tuple(_floor(x3[i], want[i]) for i in range(2)),
-                                   "bf16": tuple(_floor(b16[i], want[i]) for i in range(2))})
+                            floor={"fp32": tuple(fp32_floor(x3[i], want[i]) for i in range(2)),
+                                   "bf16": tuple(fp32_floor(b16[i], want[i]) for i in range(2))})
     return _FLOORS[key]
 
 
@@ -173,7 +156,7 @@ def _tower(name, mode):
         import streamformer_amd as sa
         m = sa.SiglipTextModel(sa.SiglipTextConfig(**TO.CONFIGS[name]), compute_dtype=mode)
         m.load_state_dict(TO.make_weights(TO.CONFIGS[name], TO.SEEDS[name]))
-        _TOWERS[key] = m.to(_gpu())
+        _TOWERS[key] = m.to(gpu_device())
     return _TOWERS[key]
 
 
@@ -181,7 +164,7 @@ def _tower(name, mode):
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 @pytest.mark.parametrize("name", list(TO.CONFIGS))
 def test_whole_tower_vs_fixture_and_fp64(name, mode, case):
-    dev = _gpu()
+    dev = gpu_device()
     ref = _reference(name, case)
     m = _tower(name, mode)
     out = m(ref["ids"].to(dev), attention_mask=None if ref["mask"] is None else ref["mask"].to(dev))
@@ -236,11 +219,11 @@ def _wrapper(tasks):
 
 @pytest.mark.parametrize("task", ["TaskRetrieval", "TaskGrounding"])
 def test_captions_through_the_wrapper_equal_their_text_features(task):
-    dev = _gpu()
+    dev = gpu_device()
     cfg, w = _wrapper({task: {}})
     w.train()
     captions = ["a person opens the door", "two dogs run"]
-    x = _randn(1890, 2, 8, 3, cfg.image_size, cfg.image_size).to(dev)
+    x = randn(1890, 2, 8, 3, cfg.image_size, cfg.image_size).to(dev)
     extra = {"label": torch.tensor([[0, 1, 1, 0, 0, 1, 0, 1], [1, 1, 0, 0, 1, 0, 0, 0]], device=dev).float()} if task == "TaskGrounding" else {}
     tok = stub_tokenizer(captions)
     feats = w.text_encoder(tok["input_ids"].to(dev), attention_mask=tok["attention_mask"].to(dev))[1]
@@ -261,11 +244,11 @@ def test_captions_through_the_wrapper_equal_their_text_features(task):
 
 def test_localization_table_from_templates_equals_encode_label_prompts():
     import streamformer_amd as sa
-    dev = _gpu()
+    dev = gpu_device()
     templates = ["a clip of someone {}.", "footage showing {} outdoors"]
     labels = {"toy": {"running": 0, "high jump": 1, "opening a door": 2}, "given": {"x": 0}}
     cfg, w = _wrapper({"TaskRetrieval": {}})          # a wrapper only for its tower
-    given = torch.nn.functional.normalize(_randn(3, 1, cfg.hidden_size), dim=-1)
+    given = torch.nn.functional.normalize(randn(3, 1, cfg.hidden_size), dim=-1)
     import streamformer_amd.multitask as mt
     head = mt.TimesformerUniversalLocalizationHead(cfg, labels, prompt_templates=templates)
     head.set_label_embeddings("given", given)

@@ -16,35 +16,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import load_npz, small_cfg
+from tests.helpers import cosine, load_npz, rel_l2, rel_max, small_cfg
+from tests.train_support import GRAD_COS, GRAD_REL_L2, OP_TOL, attn_ref, compare_grads, device, to_dev, trainer_and_oracle
 
 pytestmark = pytest.mark.gpu
-
-OP_TOL = 2e-2
-GRAD_REL_L2 = 2.6e-2        # measured worst 1.7e-2 (head.probe, small model), 1.1e-2 on SigLIP-base; + 50 %
-GRAD_COS = 0.9995           # measured lowest 0.99987
-SCALAR_REL = 0.10           # measured worst 6.7e-2 (a temporal gate: one sum over ~1e6 bf16-rounded products)
-
-
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
-
-
-def rel_max(got, want):
-    got, want = got.double().cpu(), want.double().cpu()
-    return float((got - want).abs().max() / (want.abs().max() + 1e-30))
-
-
-def rel_l2(got, want):
-    got, want = got.double().cpu(), want.double().cpu()
-    return float((got - want).norm() / (want.norm() + 1e-30))
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-30))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -53,7 +28,7 @@ def cosine(a, b):
 @pytest.mark.parametrize("M,N1,N2", [(3136, 768, 768), (777, 136, 72), (40, 128, 256), (25088, 768, 3072), (130, 64, 64), (25088, 2304, 768), (2100, 256, 512)])
 def test_wgrad_matches_torch(M, N1, N2):
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = device()
     g = torch.Generator().manual_seed(M + N1)
     dy = torch.randn(M, N1, generator=g).to(dev).bfloat16()
     x = torch.randn(M, N2, generator=g).to(dev).bfloat16()
@@ -73,28 +48,15 @@ def test_wgrad_matches_torch(M, N1, N2):
     assert rel_max(out2, wide[:, :N1].double().t() @ x.double()) < 1e-4
 
 
-def _attn_ref(qkv, d_o, nseq, L, heads, causal):
-    """torch autograd reference on [nseq, L, 3D] fp64 tensors -> (o, d_qkv)."""
-    D = heads * 64
-    t = qkv.double().clone().requires_grad_(True)
-    q, k, v = (t[..., i * D:(i + 1) * D].reshape(nseq, L, heads, 64).transpose(1, 2) for i in range(3))
-    s = q @ k.transpose(-1, -2) * 0.125
-    if causal:
-        s = s.masked_fill(~torch.tril(torch.ones(L, L, dtype=torch.bool)), float("-inf"))
-    o = (s.softmax(-1) @ v).transpose(1, 2).reshape(nseq, L, D)
-    o.backward(d_o.double())
-    return o.detach(), t.grad
-
-
 @pytest.mark.parametrize("nseq,L,heads", [(3, 196, 2), (2, 9, 2), (1, 224, 1), (5, 33, 3), (2, 193, 2), (1, 208, 1), (1, 192, 2), (2, 209, 1)])
 def test_spatial_attention_bwd_matches_autograd(nseq, L, heads):
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = device()
     D = heads * 64
     g = torch.Generator().manual_seed(L)
     qkv = (torch.randn(nseq, L, 3 * D, generator=g) * 1.5).bfloat16()
     d_o = torch.randn(nseq, L, D, generator=g).bfloat16()
-    o_ref, dqkv_ref = _attn_ref(qkv.float(), d_o.float(), nseq, L, heads, False)
+    o_ref, dqkv_ref = attn_ref(qkv.float(), d_o.float(), nseq, L, heads, 64, False)
     o = o_ref.bfloat16()
     dq = torch.full((nseq, L, 3 * D), float("nan")).bfloat16().to(dev)
     qd, od, dod = qkv.to(dev), o.to(dev), d_o.to(dev)
@@ -110,14 +72,14 @@ def test_spatial_attention_bwd_matches_autograd(nseq, L, heads):
 @pytest.mark.parametrize("B,N,L,heads,causal", [(2, 5, 16, 2, 1), (1, 3, 4, 2, 1), (2, 2, 24, 1, 1), (1, 4, 16, 2, 0), (1, 2, 32, 1, 1), (1, 2, 1, 1, 1)])
 def test_temporal_attention_bwd_matches_autograd(B, N, L, heads, causal):
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = device()
     D = heads * 64
     g = torch.Generator().manual_seed(100 + L)
     # token row of (b, t, n) = (b*L + t)*N + n
     qkv = (torch.randn(B, L, N, 3 * D, generator=g) * 1.5).bfloat16()
     d_o = torch.randn(B, L, N, D, generator=g).bfloat16()
     seq = qkv.float().permute(0, 2, 1, 3).reshape(B * N, L, 3 * D)
-    o_ref, dqkv_ref = _attn_ref(seq, d_o.float().permute(0, 2, 1, 3).reshape(B * N, L, D), B * N, L, heads, bool(causal))
+    o_ref, dqkv_ref = attn_ref(seq, d_o.float().permute(0, 2, 1, 3).reshape(B * N, L, D), B * N, L, heads, 64, bool(causal))
     o = o_ref.reshape(B, N, L, D).permute(0, 2, 1, 3).contiguous().bfloat16()
     want = dqkv_ref.reshape(B, N, L, 3 * D).permute(0, 2, 1, 3)
     dq = torch.full((B, L, N, 3 * D), float("nan")).bfloat16().to(dev)
@@ -134,7 +96,7 @@ def test_temporal_attention_bwd_matches_autograd(B, N, L, heads, causal):
 @pytest.mark.parametrize("rows,D", [(1000, 768), (37, 128), (5000, 64)])
 def test_layernorm_bwd_matches_autograd(rows, D):
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = device()
     g = torch.Generator().manual_seed(rows)
     x = torch.randn(rows, D, generator=g) * 2 + 0.3
     dy = torch.randn(rows, D, generator=g)
@@ -157,74 +119,24 @@ def test_layernorm_bwd_matches_autograd(rows, D):
 # ---------------------------------------------------------------------------------------------------
 # whole model: gradients of one micro-step vs the oracle
 # ---------------------------------------------------------------------------------------------------
-def _trainer_and_oracle(cfg, freeze, seed, lora, lr=1e-3, wd=0.05):
-    from oracle import train_oracle as TO
-    from streamformer_amd.init_weights import make_state_dict
-    from streamformer_amd.training import StreamformerTrainer
-    sd = make_state_dict(cfg, seed=seed, lora=lora)
-    tr = StreamformerTrainer(cfg, sd, ["retrieval", "localization"], freeze_spatial=freeze, device=_dev(), lr=lr, weight_decay=wd)
-    orc = TO.OracleTrainer(sd, cfg, ["retrieval", "localization"], freeze_spatial=freeze, lr=lr, weight_decay=wd)
-    return tr, orc
-
-
-def _to_dev(ti, dev):
-    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in ti.items()}
-
-
-def _compare_grads(tr, orc, floor=1e-3, scalar_rel=SCALAR_REL):
-    og = orc.grads()
-    names = set(tr.parameter_names(trainable_only=True))
-    assert names == set(og), sorted(names ^ set(og))[:6]
-    gmax = max(float(v.abs().max()) for v in og.values())
-    report = {}
-    for n, want in og.items():
-        got = tr.grad(n).detach().cpu()
-        if float(want.abs().max()) < floor * gmax * 1e-3:        # gradient that is (numerically) zero: absolute check
-            assert float((got - want).abs().max()) < floor * gmax, n
-            continue
-        report[n] = (rel_l2(got, want), cosine(got, want))
-    scalars = {n: r for n, r in report.items() if og[n].numel() == 1}
-    report = {n: r for n, r in report.items() if og[n].numel() > 1}
-    if os.environ.get("SF_TEST_VERBOSE"):
-        for n in scalars:
-            print(f"[0-dim] {n}: got {float(tr.grad(n)):+.5e} want {float(og[n]):+.5e} rel {scalars[n][0]:.3e}")
-    # 0-dim parameters: one sum over ~1e6 bf16-rounded products with heavy cancellation.  A gate whose gradient happens to cancel to
-    # 1e-4 when its eleven siblings sit at 5e-2 carries the same ABSOLUTE error as they do, so the bound is relative to the
-    # larger of the value and the family's median magnitude (family = last name component: the twelve temporal gates, ...)
-    fam = {}
-    for n in scalars:
-        fam.setdefault(n.rsplit(".", 1)[-1], []).append(abs(float(og[n])))
-    for n, r in scalars.items():
-        w = float(og[n])
-        scale = max(abs(w), float(np.median(fam[n.rsplit(".", 1)[-1]])))
-        assert abs(float(tr.grad(n)) - w) < scalar_rel * scale, (n, r, float(tr.grad(n)), w, scale)
-    worst = max(report.items(), key=lambda kv: kv[1][0])
-    wc = min(report.items(), key=lambda kv: kv[1][1])
-    ws = max(scalars.items(), key=lambda kv: kv[1][0]) if scalars else ("-", (0.0, 1.0))
-    print(f"[grad parity] worst rel-L2 {worst[1][0]:.3e} ({worst[0]}), lowest cosine {wc[1][1]:.6f} ({wc[0]}), worst 0-dim rel {ws[1][0]:.3e} ({ws[0]})")
-    assert worst[1][0] < GRAD_REL_L2, worst
-    assert wc[1][1] > GRAD_COS, wc
-    return report
-
-
 @pytest.mark.parametrize("task_idx", [0, 1])
 @pytest.mark.parametrize("lora,freeze", [(True, True), (False, False), (True, False)])
 def test_small_model_gradients_match_oracle(task_idx, lora, freeze):
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=lora)
-    tr, orc = _trainer_and_oracle(cfg, freeze, seed=8, lora=lora)
+    tr, orc = trainer_and_oracle(cfg, freeze, seed=8, lora=lora)
     task, x, ti, _ = TO.schedule(cfg)[task_idx]
     want_loss = orc.loss(task, x, ti)
     want_loss.backward()
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
     torch.cuda.synchronize()
     assert abs(float(loss) - float(want_loss)) < 2e-2 * abs(float(want_loss))
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 def test_three_head_model_gradients_match_oracle():
@@ -234,19 +146,19 @@ def test_three_head_model_gradients_match_oracle():
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=True, hidden_size=192, num_attention_heads=3, intermediate_size=384)
     for task_idx in (0, 1):
-        tr, orc = _trainer_and_oracle(cfg, True, seed=9, lora=True)
+        tr, orc = trainer_and_oracle(cfg, True, seed=9, lora=True)
         task, x, ti, _ = TO.schedule(cfg)[task_idx]
         want_loss = orc.loss(task, x, ti)
         want_loss.backward()
         dev = tr.device
         _, pooler = tr.forward(x.to(dev))
-        loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+        loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
         tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
         tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
         tr.backward(gp)
         torch.cuda.synchronize()
         assert abs(float(loss) - float(want_loss)) < 2e-2 * abs(float(want_loss))
-        _compare_grads(tr, orc)
+        compare_grads(tr, orc)
 
 
 def test_wide_model_gradients_match_oracle():
@@ -255,31 +167,31 @@ def test_wide_model_gradients_match_oracle():
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=True, hidden_size=1024, num_attention_heads=16, intermediate_size=4096, num_hidden_layers=1, image_size=224,
                     num_frames=4)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=10, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=10, lora=True)
     task, x, ti, _ = TO.schedule(cfg, B=2)[1]
     want_loss = orc.loss(task, x, ti)
     want_loss.backward()
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
     torch.cuda.synchronize()
     assert abs(float(loss) - float(want_loss)) < 2e-2 * abs(float(want_loss))
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 def test_gradients_are_deterministic_and_accumulate():
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=True)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True)
     task, x, ti, _ = TO.schedule(cfg)[1]
     dev = tr.device
 
     def run():
         _, pooler = tr.forward(x.to(dev))
-        _, gp, _ = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+        _, gp, _ = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
         tr.backward(gp)
         torch.cuda.synchronize()
     run()
@@ -302,14 +214,14 @@ def test_f8_three_optimizer_steps_follow_the_reference(golden_dir):
     sd = make_state_dict(cfg, seed=8, lora=True)
     if state_dict_sha256(sd) != str(f8["sha256"]):
         pytest.skip("seeded weights differ from the fixture's (RNG drift on this box)")
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True, lr=float(f8["lr"]), wd=float(f8["wd"]))
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True, lr=float(f8["lr"]), wd=float(f8["wd"]))
     dev = tr.device
     init = tr.state_dict()
     losses = []
     for i, (task, x, ti, uf) in enumerate(TO.schedule(cfg)):
         if i == 0:       # first-step gradients against the reference's
             _, pooler = tr.forward(x.to(dev))
-            _, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+            _, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
             tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
             tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
             tr.backward(gp)
@@ -321,7 +233,7 @@ def test_f8_three_optimizer_steps_follow_the_reference(golden_dir):
                     if float(want.abs().max()) > 1e-6:
                         assert rel_l2(got, want) < GRAD_REL_L2 and cosine(got, want) > GRAD_COS, n
             tr.zero_grad()
-        losses.append(float(tr.micro_step(task, x.to(dev), _to_dev(ti, dev), update_freq=uf)))
+        losses.append(float(tr.micro_step(task, x.to(dev), to_dev(ti, dev), update_freq=uf)))
     want_losses = f8["losses"]
     assert np.allclose(losses, want_losses, rtol=3e-2), (losses, want_losses)
     assert tr.step_count == 3
@@ -352,7 +264,7 @@ def test_base_model_gradients_match_oracle():
     from oracle import train_oracle as TO
     from streamformer_amd.configuration import siglip_base
     cfg = siglip_base(add_lora_spatial=True)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=3, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=3, lora=True)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(1, 4, 3, 224, 224, generator=g)
     lab_emb = torch.randn(20, cfg.hidden_size, generator=g)
@@ -363,20 +275,20 @@ def test_base_model_gradients_match_oracle():
     want.backward()
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, gs = tr.loss_and_grad("localization", pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad("localization", pooler, to_dev(ti, dev))
     tr.grad("task_heads.localization.logit_scale").add_(gs[0])
     tr.grad("task_heads.localization.logit_bias").add_(gs[1])
     tr.backward(gp)
     torch.cuda.synchronize()
     assert abs(float(loss) - float(want)) < 2e-2 * abs(float(want))
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 def _base_grad_case(B, T, task, seed, freeze=True):
     from oracle import train_oracle as TO
     from streamformer_amd.configuration import siglip_base
     cfg = siglip_base(add_lora_spatial=True)
-    tr, orc = _trainer_and_oracle(cfg, freeze, seed=seed, lora=True)
+    tr, orc = trainer_and_oracle(cfg, freeze, seed=seed, lora=True)
     g = torch.Generator().manual_seed(seed + 2)
     x = torch.randn(B, T, 3, 224, 224, generator=g)
     if task == "localization":
@@ -390,13 +302,13 @@ def _base_grad_case(B, T, task, seed, freeze=True):
     want.backward()
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
     torch.cuda.synchronize()
     assert abs(float(loss) - float(want)) < 2e-2 * abs(float(want))
-    return _compare_grads(tr, orc)
+    return compare_grads(tr, orc)
 
 
 def test_base_model_gradients_match_oracle_at_sixteen_frames():
@@ -425,7 +337,7 @@ def test_base_model_gradients_on_the_big_tile_kernels():
     switch is read once per process: the case runs in a child interpreter."""
     import subprocess
     import sys
-    _dev()
+    device()
     env = dict(os.environ, SF_TEST_BIG_TILES_INNER="1", SF_DISABLE_GEMM_TILE="1")
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-s", "-k",
                         "test_base_model_gradients_big_tiles_inner"], env=env, capture_output=True, text=True, timeout=900,
@@ -476,11 +388,11 @@ def test_two_rank_retrieval_step_with_gathered_negatives(reduce_dtype):
     (gloo, both on cuda:0) and compared with the oracle's autograd on the same split."""
     from oracle import train_oracle as TO
     from tests.helpers import run_ranks
-    _dev()
+    device()
     res = run_ranks(_gn_worker, 2, (reduce_dtype,))
     ret = {"loss0": res[0][0], "loss1": res[1][0], "grads": torch.from_numpy(res[0][1])}
     cfg = small_cfg(add_lora_spatial=True)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=8, lora=True)
     task, x, ti, _ = TO.schedule(cfg, B=4)[0]
     total = 0.0
     for rank in range(2):
@@ -505,7 +417,7 @@ def test_retrieval_loss_has_no_batch_limit():
     """B * Bt > 4096 used to fail (32 clips x 8 ranks).  64 local clips against 1024 gathered captions."""
     import streamformer_amd as sa
     from oracle import streamformer_oracle as O
-    dev = _dev()
+    dev = device()
     g = torch.Generator().manual_seed(3)
     B, T, D, Bt, rank = 64, 3, 768, 1024 + 64, 5
     pooler = torch.randn(B, T, D, generator=g)
@@ -548,14 +460,14 @@ def _dp_worker(rank, world):
 def test_two_rank_allreduced_gradients_equal_the_big_batch():
     from oracle import train_oracle as TO
     from tests.helpers import run_ranks
-    _dev()
+    device()
     ret = {"grads": torch.from_numpy(run_ranks(_dp_worker, 2)[0])}
     cfg = small_cfg(add_lora_spatial=True)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True)
     task, x, ti, _ = TO.schedule(cfg, B=4)[1]
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    _, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    _, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
@@ -621,7 +533,7 @@ def test_rccl_world_size_1_step_equals_the_plain_step(reduce_dtype):
     format), the caption all-gather, `all_reduce_mean_` — executed on one GPU at world_size 1 and compared bit for bit with
     the step that issues no collective."""
     from tests.helpers import run_ranks
-    _dev()
+    device()
     r = run_ranks(_nccl_worker, 1, (reduce_dtype,), backend="nccl")[0]
     for task in ("retrieval", "localization"):
         assert r[f"{task}_loss_equal"] and r[f"{task}_grads_equal"] and r[f"{task}_grad_absmax"] > 0, r
@@ -641,7 +553,7 @@ def test_twenty_step_trajectory_tracks_the_oracle():
     from oracle import train_oracle as TO
     from streamformer_amd.training import cosine_scheduler
     cfg = small_cfg(add_lora_spatial=True)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.05)
+    tr, orc = trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.05)
     dev = tr.device
     sched = TO.schedule(cfg, B=4)
     lrs = cosine_scheduler(1e-3, 1e-5, epochs=1, niter_per_ep=20, warmup_epochs=0.25)     # 5 warm-up steps
@@ -658,7 +570,7 @@ def test_twenty_step_trajectory_tracks_the_oracle():
         orc.opt.step()
         orc.opt.zero_grad(set_to_none=True)
         want.append(float(want_loss.detach()))
-        got.append(float(tr.micro_step(task, x.to(dev), _to_dev(ti, dev), lr=lrs[it], weight_decay=wds[it], clip_grad=1.0)))
+        got.append(float(tr.micro_step(task, x.to(dev), to_dev(ti, dev), lr=lrs[it], weight_decay=wds[it], clip_grad=1.0)))
     rel = [abs(a - b) / abs(b) for a, b in zip(got, want)]
     assert max(rel) < 3e-2, list(zip(got, want))
     assert want[16] < want[0] and got[16] < got[0]                      # the run actually trains (same batch as step 0)
@@ -684,12 +596,12 @@ def test_checkpoint_resume_and_reference_optimizer_layout(golden_dir, tmp_path):
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
     cfg = small_cfg(add_lora_spatial=True)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True)
     dev = tr.device
     sched = TO.schedule(cfg, B=4)
     for it in range(3):
         task, x, ti, _ = sched[it % 4]
-        tr.micro_step(task, x.to(dev), _to_dev(ti, dev))
+        tr.micro_step(task, x.to(dev), to_dev(ti, dev))
     path = str(tmp_path / "checkpoint-2.pth")
     tr.save_checkpoint(path, epoch=2, args={"lr": 1e-3})
     ck = torch.load(path, map_location="cpu", weights_only=False)
@@ -745,8 +657,8 @@ def test_checkpoint_resume_and_reference_optimizer_layout(golden_dir, tmp_path):
     assert tr2.load_checkpoint(path) == 2 and tr2.step_count == 3 and tr2.lr == 1e-3 and tr2.weight_decay == 0.05
     assert tr2.head_steps == tr.head_steps == {"retrieval": 1, "localization": 2}
     task, x, ti, _ = sched[3]
-    la = tr.micro_step(task, x.to(dev), _to_dev(ti, dev))
-    lb = tr2.micro_step(task, x.to(dev), _to_dev(ti, dev))
+    la = tr.micro_step(task, x.to(dev), to_dev(ti, dev))
+    lb = tr2.micro_step(task, x.to(dev), to_dev(ti, dev))
     assert float(la) == float(lb)
     assert torch.equal(tr.params, tr2.params) and torch.equal(tr.exp_avg, tr2.exp_avg) and torch.equal(tr.exp_avg_sq, tr2.exp_avg_sq)
 
@@ -762,7 +674,7 @@ def test_drop_path_gradients_match_the_oracle_on_the_same_draw(task_idx):
     from streamformer_amd.training import StreamformerTrainer
     cfg = small_cfg(add_lora_spatial=True, drop_path_rate=0.4, num_hidden_layers=3)
     sd = make_state_dict(cfg, seed=8, lora=True)
-    dev = _dev()
+    dev = device()
     tr = StreamformerTrainer(cfg, sd, ["retrieval", "localization"], freeze_spatial=True, device=dev, drop_path_seed=5)
     orc = TO.OracleTrainer(sd, cfg, ["retrieval", "localization"], freeze_spatial=True)
     task, x, ti, _ = TO.schedule(cfg, B=4)[task_idx]
@@ -771,7 +683,7 @@ def test_drop_path_gradients_match_the_oracle_on_the_same_draw(task_idx):
     assert dp is not None and tuple(dp.shape) == (3, 4 * 9 + 4 * 4 + 4)
     assert float(dp[0].min()) == 1.0 and float(dp[0].max()) == 1.0                 # layer 0: rate 0
     assert {round(v, 4) for v in torch.unique(dp[2]).tolist()} <= {0.0, round(1.0 / 0.6, 4)} and float(dp[2].min()) == 0.0      # layer 2: rate 0.4
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
@@ -779,7 +691,7 @@ def test_drop_path_gradients_match_the_oracle_on_the_same_draw(task_idx):
     want_loss = orc.loss(task, x, ti, drop_path=dp)
     want_loss.backward()
     assert abs(float(loss) - float(want_loss)) < 2e-2 * abs(float(want_loss))
-    _compare_grads(tr, orc, scalar_rel=0.2)       # gate gradients: the same cancelling sum over 40 % fewer live rows (measured 12 %)
+    compare_grads(tr, orc, scalar_rel=0.2)       # gate gradients: the same cancelling sum over 40 % fewer live rows (measured 12 %)
     plain = float(orc.loss(task, x, ti).detach())
     assert abs(plain - float(want_loss)) > 1e-4 * abs(plain)                      # the draw really changes the forward
     _, p2 = tr.forward(x.to(dev))
@@ -787,7 +699,7 @@ def test_drop_path_gradients_match_the_oracle_on_the_same_draw(task_idx):
     tr.drop_path = False
     _, p3 = tr.forward(x.to(dev))
     want = orc.loss(task, x, ti)
-    l3, _, _ = tr.loss_and_grad(task, p3, _to_dev(ti, dev))
+    l3, _, _ = tr.loss_and_grad(task, p3, to_dev(ti, dev))
     assert tr.last_drop_path is None and abs(float(l3) - float(want.detach())) < 2e-2 * abs(float(want.detach()))
 
 
@@ -802,14 +714,14 @@ def test_dropout_gradients_match_the_oracle_on_the_same_masks(task_idx, hid, att
     from streamformer_amd.training import StreamformerTrainer
     cfg = small_cfg(add_lora_spatial=True, hidden_dropout_prob=hid, attention_probs_dropout_prob=att, drop_path_rate=dpr, num_hidden_layers=3)
     sd = make_state_dict(cfg, seed=8, lora=True)
-    dev = _dev()
+    dev = device()
     tr = StreamformerTrainer(cfg, sd, ["retrieval", "localization"], freeze_spatial=True, device=dev, drop_path_seed=7)
     orc = TO.OracleTrainer(sd, cfg, ["retrieval", "localization"], freeze_spatial=True)
     task, x, ti, _ = TO.schedule(cfg, B=4)[task_idx]
     _, pooler = tr.forward(x.to(dev))
     drop = tr.last_dropout
     assert drop is not None and drop[1:] == (hid, att)
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
@@ -817,7 +729,7 @@ def test_dropout_gradients_match_the_oracle_on_the_same_masks(task_idx, hid, att
     want_loss = orc.loss(task, x, ti, drop_path=tr.last_drop_path, dropout=drop)
     want_loss.backward()
     assert abs(float(loss) - float(want_loss)) < 2e-2 * abs(float(want_loss))
-    _compare_grads(tr, orc, scalar_rel=0.2)
+    compare_grads(tr, orc, scalar_rel=0.2)
     plain = float(orc.loss(task, x, ti).detach())
     assert abs(plain - float(want_loss)) > 1e-4 * abs(plain)                      # the masks really change the forward
     tr.forward(x.to(dev))
@@ -825,7 +737,7 @@ def test_dropout_gradients_match_the_oracle_on_the_same_masks(task_idx, hid, att
     tr.dropout = False
     tr.drop_path = False
     _, p3 = tr.forward(x.to(dev))
-    l3, _, _ = tr.loss_and_grad(task, p3, _to_dev(ti, dev))
+    l3, _, _ = tr.loss_and_grad(task, p3, to_dev(ti, dev))
     assert tr.last_dropout is None and abs(float(l3) - plain) < 2e-2 * abs(plain)
 
 
@@ -836,7 +748,7 @@ def test_localization_batch_with_per_clip_dataset_tables():
     against the oracle's per-clip restatement, and the whole micro-step's parameter gradients against its autograd."""
     from oracle import streamformer_oracle as O
     cfg = small_cfg(add_lora_spatial=True)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=8, lora=True)
     dev = tr.device
     g = torch.Generator().manual_seed(77)
     B, T, D = 5, 16, cfg.hidden_size
@@ -869,14 +781,14 @@ def test_localization_batch_with_per_clip_dataset_tables():
     l2 = tr.micro_step("localization", x.to(dev), ti, update_freq=2)       # update_freq 2: gradients stay in the buffer (scaled by 1/2)
     assert abs(float(l2) - float(want2)) < 2e-2 * abs(float(want2))
     tr.grads.mul_(2.0)
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 def test_trainer_rejects_what_it_cannot_do():
     import streamformer_amd._native as nat
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
-    dev = _dev()
+    dev = device()
     cfg = small_cfg(add_lora_spatial=True)
     sd = make_state_dict(cfg, seed=8, lora=True)
     tr = StreamformerTrainer(cfg, sd, ["retrieval"], device=dev)
@@ -910,19 +822,19 @@ def test_nonfinite_step_is_skipped_on_the_device_and_reported():
     moments bit-identical, clears the gradients, raises the sticky flag; check_finite() / checkpoint() then raise."""
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=True)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.05)
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.05)
     dev = tr.device
     task, x, ti, _ = TO.schedule(cfg, B=2)[0]
     other, xo, tio, _ = TO.schedule(cfg, B=2)[1]
     assert other != task
-    tr.micro_step(other, xo.to(dev), _to_dev(tio, dev))        # the other head takes one clean step of its own
-    tr.micro_step(task, x.to(dev), _to_dev(ti, dev))
+    tr.micro_step(other, xo.to(dev), to_dev(tio, dev))        # the other head takes one clean step of its own
+    tr.micro_step(task, x.to(dev), to_dev(ti, dev))
     tr.check_finite()                                          # a finite step raises nothing
     assert tr.nonfinite_steps() == 0
     p0, m0, v0 = tr.params.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone()
     bad = x.clone()
     bad[0, 0, 0, 0, 0] = float("nan")
-    loss = tr.micro_step(task, bad.to(dev), _to_dev(ti, dev))
+    loss = tr.micro_step(task, bad.to(dev), to_dev(ti, dev))
     assert not math.isfinite(float(loss))
     assert torch.equal(tr.params, p0) and torch.equal(tr.exp_avg, m0) and torch.equal(tr.exp_avg_sq, v0)
     assert float(tr.grads.abs().max()) == 0.0                  # cleared although the update was skipped
@@ -942,13 +854,13 @@ def test_nonfinite_step_is_skipped_on_the_device_and_reported():
     assert tr.nonfinite_steps() == 0 and tr._last_loss is None
     # a poisoned FIRST micro-step of an accumulation window is still seen by the step that closes the window
     tr.zero_grad()
-    tr.micro_step(task, bad.to(dev), _to_dev(ti, dev), update_freq=2)
+    tr.micro_step(task, bad.to(dev), to_dev(ti, dev), update_freq=2)
     tr.grads.zero_()                                           # finite gradients, non-finite loss sum
-    tr.micro_step(task, x.to(dev), _to_dev(ti, dev), update_freq=2)
+    tr.micro_step(task, x.to(dev), to_dev(ti, dev), update_freq=2)
     assert tr.nonfinite_steps() == 1
     tr.reset_nonfinite()
     # inf gradients with a finite loss (the GradScaler case): poison the gradient buffer directly
-    tr2, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True)
+    tr2, _ = trainer_and_oracle(cfg, True, seed=8, lora=True)
     tr2.forward(x.to(dev))
     tr2.grads[5] = float("inf")
     q0 = tr2.params.clone()
@@ -966,7 +878,7 @@ def TO_trainer_without_guard(cfg):
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
     return StreamformerTrainer(cfg, make_state_dict(cfg, seed=8, lora=True), ["retrieval", "localization"], freeze_spatial=True,
-                               device=_dev(), nonfinite_guard=False)
+                               device=device(), nonfinite_guard=False)
 
 
 def _task_mismatch_worker(rank, world):
@@ -989,7 +901,7 @@ def test_ranks_that_schedule_different_tasks_are_refused_not_hung():
     """sampler.py:218-337 gives every rank the same task per micro-step; a retrieval rank issues the caption all-gather, a
     localization rank does not, so a mismatch would hang in a collective.  The trainer checks the first micro-step."""
     from tests.helpers import run_ranks
-    _dev()
+    device()
     res = run_ranks(_task_mismatch_worker, 2)
     assert all(r.startswith("refused") for r in res), res
 
@@ -999,10 +911,10 @@ def test_training_reduces_the_loss_on_a_fixed_batch():
     drive both task losses down (the oracle does the same in tests of its own trajectory, fixture F8)."""
     from oracle import train_oracle as TO
     cfg = small_cfg(add_lora_spatial=True)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True, lr=2e-3, wd=0.0)
+    tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True, lr=2e-3, wd=0.0)
     dev = tr.device
     sched = TO.schedule(cfg, B=4)
-    batches = [(sched[0][0], sched[0][1].to(dev), _to_dev(sched[0][2], dev)), (sched[1][0], sched[1][1].to(dev), _to_dev(sched[1][2], dev))]
+    batches = [(sched[0][0], sched[0][1].to(dev), to_dev(sched[0][2], dev)), (sched[1][0], sched[1][1].to(dev), to_dev(sched[1][2], dev))]
     first, last = {}, {}
     for it in range(40):
         task, x, ti = batches[it % 2]
@@ -1023,10 +935,10 @@ def test_grad_norm_and_clipping_follow_torch():
     task, x, ti, _ = TO.schedule(cfg)[0]
     results = []
     for clip in (None, 0.05):
-        tr, _ = _trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.0)
+        tr, _ = trainer_and_oracle(cfg, True, seed=8, lora=True, lr=1e-3, wd=0.0)
         dev = tr.device
         _, pooler = tr.forward(x.to(dev))
-        _, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+        _, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
         tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
         tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
         tr.backward(gp)
@@ -1049,7 +961,7 @@ def test_full_size_training_step_properties():
     from streamformer_amd.configuration import siglip_base
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
-    dev = _dev()
+    dev = device()
     cfg = siglip_base(add_lora_spatial=True)
     sd = make_state_dict(cfg, seed=0, lora=True)
     tr = StreamformerTrainer(cfg, sd, ["localization"], freeze_spatial=True, device=dev)

@@ -1,21 +1,16 @@
 """The training step at head widths other than 64 (SigLIP-so400m: 1152 / 16 heads of 72, I = 4304, 14 x 14 patches): the generic-width
 attention backward (sf_attention_generic_bwd.hip) against torch autograd, whole-model gradients of the trainer and of the public layers
-against oracle/train_oracle.py, the optimizer path, and what the trainer still refuses.  Tolerances are those of test_train_parity.py."""
+against oracle/train_oracle.py, the optimizer path, and what the trainer still refuses.  Tolerances are those of tests/train_support.py."""
 import math
 
-import numpy as np
 import pytest
 import torch
 
 from streamformer_amd.configuration import StreamformerConfig
-from tests.helpers import small_cfg
+from tests.helpers import cosine, rel_l2, small_cfg
+from tests.train_support import GRAD_COS, GRAD_REL_L2, OP_TOL, attn_ref, compare_grads, device, to_dev, trainer_and_oracle
 
 pytestmark = pytest.mark.gpu
-
-OP_TOL = 2e-2
-GRAD_REL_L2 = 2.6e-2
-GRAD_COS = 0.9995
-SCALAR_REL = 0.10
 
 HD72W = dict(image_size=42, patch_size=14, num_frames=8, hidden_size=576, num_hidden_layers=2, num_attention_heads=8, intermediate_size=1072)
 HD32 = dict(image_size=48, patch_size=16, num_frames=8, hidden_size=128, num_hidden_layers=2, num_attention_heads=4, intermediate_size=256)
@@ -23,40 +18,12 @@ SO400M_LAYER = dict(image_size=196, patch_size=14, num_frames=4, hidden_size=115
                     intermediate_size=4304)
 
 
-def _dev():
-    if not torch.cuda.is_available():
-        pytest.skip("needs a GPU")
-    return torch.device("cuda:0")
-
-
-def rel_l2(got, want):
-    got, want = got.double().cpu(), want.double().cpu()
-    return float((got - want).norm() / (want.norm() + 1e-30))
-
-
-def cosine(a, b):
-    a, b = a.double().cpu().flatten(), b.double().cpu().flatten()
-    return float(a @ b / (a.norm() * b.norm() + 1e-30))
-
-
 # ---------------------------------------------------------------------------------------------------
 # the attention backward alone
 # ---------------------------------------------------------------------------------------------------
-def _attn_ref(qkv, d_o, nseq, L, heads, hd, causal):
-    D = heads * hd
-    t = qkv.double().clone().requires_grad_(True)
-    q, k, v = (t[..., i * D:(i + 1) * D].reshape(nseq, L, heads, hd).transpose(1, 2) for i in range(3))
-    s = q @ k.transpose(-1, -2) * hd ** -0.5
-    if causal:
-        s = s.masked_fill(~torch.tril(torch.ones(L, L, dtype=torch.bool)), float("-inf"))
-    o = (s.softmax(-1) @ v).transpose(1, 2).reshape(nseq, L, D)
-    o.backward(d_o.double())
-    return o.detach(), t.grad
-
-
 def _op(layout, qkv, o, d_o, nseq, L, seq_rows, heads, hd, causal, fn="sf_op_attention_bwd_hd"):
     import streamformer_amd._native as nat
-    dev = _dev()
+    dev = device()
     D = heads * hd
     dq = torch.full(tuple(qkv.shape[:-1]) + (3 * D,), float("nan")).bfloat16().to(dev)
     qd, od, dod = qkv.to(dev), o.to(dev), d_o.to(dev)
@@ -83,7 +50,7 @@ def test_generic_spatial_attention_bwd_matches_autograd(hd, L):
     g = torch.Generator().manual_seed(hd * 1000 + L)
     qkv = (torch.randn(nseq, L, 3 * D, generator=g) * 1.5).bfloat16()
     d_o = torch.randn(nseq, L, D, generator=g).bfloat16()
-    o_ref, want = _attn_ref(qkv.float(), d_o.float(), nseq, L, heads, hd, False)
+    o_ref, want = attn_ref(qkv.float(), d_o.float(), nseq, L, heads, hd, False)
     dq = _op(0, qkv, o_ref.bfloat16(), d_o, nseq, L, 1, heads, hd, 0)
     _check(dq, want, D)
 
@@ -98,7 +65,7 @@ def test_generic_temporal_attention_bwd_matches_autograd(hd, L, causal):
     qkv = (torch.randn(B, L, N, 3 * D, generator=g) * 1.5).bfloat16()      # token row of (b, t, n) = (b*L + t)*N + n
     d_o = torch.randn(B, L, N, D, generator=g).bfloat16()
     seq = qkv.float().permute(0, 2, 1, 3).reshape(B * N, L, 3 * D)
-    o_ref, dref = _attn_ref(seq, d_o.float().permute(0, 2, 1, 3).reshape(B * N, L, D), B * N, L, heads, hd, bool(causal))
+    o_ref, dref = attn_ref(seq, d_o.float().permute(0, 2, 1, 3).reshape(B * N, L, D), B * N, L, heads, hd, bool(causal))
     o = o_ref.reshape(B, N, L, D).permute(0, 2, 1, 3).contiguous().bfloat16()
     want = dref.reshape(B, N, L, 3 * D).permute(0, 2, 1, 3)
     dq = _op(1, qkv, o, d_o, B * N, L, N, heads, hd, causal)
@@ -128,50 +95,6 @@ def _cfg(kw, lora=True):
     return StreamformerConfig(enable_causal_temporal=True, add_lora_spatial=lora, **kw)
 
 
-def _trainer_and_oracle(cfg, freeze, seed, lora, lr=1e-3, wd=0.05):
-    from oracle import train_oracle as TO
-    from streamformer_amd.init_weights import make_state_dict
-    from streamformer_amd.training import StreamformerTrainer
-    sd = make_state_dict(cfg, seed=seed, lora=lora)
-    tr = StreamformerTrainer(cfg, sd, ["retrieval", "localization"], freeze_spatial=freeze, device=_dev(), lr=lr, weight_decay=wd)
-    orc = TO.OracleTrainer(sd, cfg, ["retrieval", "localization"], freeze_spatial=freeze, lr=lr, weight_decay=wd)
-    return tr, orc
-
-
-def _to_dev(ti, dev):
-    return {k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in ti.items()}
-
-
-def _compare_grads(tr, orc, floor=1e-3, scalar_rel=SCALAR_REL):
-    """test_train_parity._compare_grads: rel-L2 and cosine per tensor, 0-dim parameters against their family's median magnitude."""
-    og = orc.grads()
-    names = set(tr.parameter_names(trainable_only=True))
-    assert names == set(og), sorted(names ^ set(og))[:6]
-    gmax = max(float(v.abs().max()) for v in og.values())
-    report = {}
-    for n, want in og.items():
-        got = tr.grad(n).detach().cpu()
-        if float(want.abs().max()) < floor * gmax * 1e-3:
-            assert float((got - want).abs().max()) < floor * gmax, n
-            continue
-        report[n] = (rel_l2(got, want), cosine(got, want))
-    scalars = {n: r for n, r in report.items() if og[n].numel() == 1}
-    report = {n: r for n, r in report.items() if og[n].numel() > 1}
-    fam = {}
-    for n in scalars:
-        fam.setdefault(n.rsplit(".", 1)[-1], []).append(abs(float(og[n])))
-    for n, r in scalars.items():
-        w = float(og[n])
-        scale = max(abs(w), float(np.median(fam[n.rsplit(".", 1)[-1]])))
-        assert abs(float(tr.grad(n)) - w) < scalar_rel * scale, (n, r, float(tr.grad(n)), w, scale)
-    worst = max(report.items(), key=lambda kv: kv[1][0])
-    wc = min(report.items(), key=lambda kv: kv[1][1])
-    print(f"[grad parity] worst rel-L2 {worst[1][0]:.3e} ({worst[0]}), lowest cosine {wc[1][1]:.6f} ({wc[0]})")
-    assert worst[1][0] < GRAD_REL_L2, worst
-    assert wc[1][1] > GRAD_COS, wc
-    return report
-
-
 def _one_step(tr, orc, cfg, task_idx, B=2):
     from oracle import train_oracle as TO
     task, x, ti, _ = TO.schedule(cfg, B=B)[task_idx]
@@ -179,7 +102,7 @@ def _one_step(tr, orc, cfg, task_idx, B=2):
     want_loss.backward()
     dev = tr.device
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, gs = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, gs = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.grad(f"task_heads.{task}.logit_scale").add_(gs[0])
     tr.grad(f"task_heads.{task}.logit_bias").add_(gs[1])
     tr.backward(gp)
@@ -193,38 +116,38 @@ def test_hd72w_gradients_match_oracle(task_idx, freeze):
     """576 / 8 heads of 72, I = 1072 and 14 x 14 patches (588-long patch vectors): generic attention and pooling head, padded MLP and
     patch widths; LoRA with the spatial base frozen and trained."""
     cfg = _cfg(HD72W)
-    tr, orc = _trainer_and_oracle(cfg, freeze, seed=15, lora=True)
+    tr, orc = trainer_and_oracle(cfg, freeze, seed=15, lora=True)
     _one_step(tr, orc, cfg, task_idx)
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 @pytest.mark.parametrize("task_idx", [0, 1])
 def test_hd32_gradients_match_oracle(task_idx):
     cfg = _cfg(HD32)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=13, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=13, lora=True)
     _one_step(tr, orc, cfg, task_idx)
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 @pytest.mark.parametrize("task_idx", [0, 1])
 def test_so400m_layer_gradients_match_oracle(task_idx):
     """One so400m-width layer: 1152 / 16 heads of 72, I = 4304, 196 patches of 14 x 14, 4 frames, B = 2."""
     cfg = _cfg(SO400M_LAYER)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=16, lora=True)
+    tr, orc = trainer_and_oracle(cfg, True, seed=16, lora=True)
     _one_step(tr, orc, cfg, task_idx)
-    _compare_grads(tr, orc)
+    compare_grads(tr, orc)
 
 
 def test_hd72w_gradients_are_deterministic_and_state_dict_keeps_reference_shapes():
     from oracle import train_oracle as TO
     cfg = _cfg(HD72W)
-    tr, _ = _trainer_and_oracle(cfg, True, seed=15, lora=True)
+    tr, _ = trainer_and_oracle(cfg, True, seed=15, lora=True)
     task, x, ti, _ = TO.schedule(cfg)[1]
     dev = tr.device
 
     def run():
         _, pooler = tr.forward(x.to(dev))
-        _, gp, _ = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+        _, gp, _ = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
         tr.backward(gp)
         torch.cuda.synchronize()
     run()
@@ -246,7 +169,7 @@ def test_hd72w_three_adamw_steps_track_the_oracle():
     turns bf16 noise on near-zero gradients into full-size steps of random sign)."""
     from oracle import train_oracle as TO
     cfg = _cfg(HD72W)
-    tr, orc = _trainer_and_oracle(cfg, True, seed=15, lora=True, lr=1e-3, wd=0.05)
+    tr, orc = trainer_and_oracle(cfg, True, seed=15, lora=True, lr=1e-3, wd=0.05)
     dev = tr.device
     sched = TO.schedule(cfg, B=2)
     start = {k: v.detach().clone() for k, v in orc.named.items()}
@@ -261,7 +184,7 @@ def test_hd72w_three_adamw_steps_track_the_oracle():
         orc.opt.step()
         orc.opt.zero_grad(set_to_none=True)
         want.append(float(want_loss.detach()))
-        got.append(float(tr.micro_step(task, x.to(dev), _to_dev(ti, dev), lr=1e-3, weight_decay=0.05, clip_grad=1.0)))
+        got.append(float(tr.micro_step(task, x.to(dev), to_dev(ti, dev), lr=1e-3, weight_decay=0.05, clip_grad=1.0)))
     rel = [abs(a - b) / abs(b) for a, b in zip(got, want)]
     assert max(rel) < 3e-2, list(zip(got, want))
     sd = tr.state_dict()
@@ -284,7 +207,7 @@ def test_autograd_module_at_hd72w_matches_oracle():
     """model.train(); loss(out).backward() at head_dim 72 -> .grad of every trainable parameter vs the oracle's autograd."""
     import streamformer_amd as sa
     from oracle import streamformer_oracle as O
-    _dev()
+    device()
     cfg = _cfg(HD72W, lora=False)
     sd = sa.make_state_dict(cfg, seed=15)
     m = sa.TimesformerMultiTaskingModelSigLIP(cfg)
@@ -320,7 +243,7 @@ def test_multitask_wrapper_at_hd72w_gives_the_trainer_gradients():
     .grad with what StreamformerTrainer computes for the same batch."""
     import streamformer_amd as sa
     from oracle import train_oracle as TO
-    dev = _dev()
+    dev = device()
     cfg = _cfg(HD72W)
     sd = sa.make_state_dict(cfg, seed=15, lora=True)
     model = sa.StreamformerForMultiTaskingSigLIP(cfg, {"TaskRetrieval": {}, "TaskLocalization": {"label2id": {"synthetic": {}}}})
@@ -333,9 +256,9 @@ def test_multitask_wrapper_at_hd72w_gives_the_trainer_gradients():
     ls, _ = model(x.to(dev), multi_task_input={"task_name": "TaskRetrieval", "task_input": {"text_features": ti["text"].to(dev)}})
     ls["TaskRetrieval"].backward()
     torch.cuda.synchronize()
-    tr, _ = _trainer_and_oracle(cfg, True, seed=15, lora=True)
+    tr, _ = trainer_and_oracle(cfg, True, seed=15, lora=True)
     _, pooler = tr.forward(x.to(dev))
-    loss, gp, _ = tr.loss_and_grad(task, pooler, _to_dev(ti, dev))
+    loss, gp, _ = tr.loss_and_grad(task, pooler, to_dev(ti, dev))
     tr.backward(gp)
     torch.cuda.synchronize()
     assert abs(float(loss) - float(ls["TaskRetrieval"])) < 1e-3 * abs(float(loss)) + 1e-5
@@ -368,7 +291,7 @@ def test_trainer_refuses_widths_beyond_its_limits(kw, needle):
     import streamformer_amd._native as nat
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
-    dev = _dev()
+    dev = device()
     cfg = small_cfg(add_lora_spatial=True, num_hidden_layers=1, **kw)
     with pytest.raises(nat.NativeError) as ei:
         StreamformerTrainer(cfg, make_state_dict(cfg, seed=1, lora=True), ["retrieval"], device=dev)
@@ -378,7 +301,7 @@ def test_trainer_refuses_widths_beyond_its_limits(kw, needle):
 def test_attention_dropout_at_generic_width_is_refused_at_construction():
     from streamformer_amd.init_weights import make_state_dict
     from streamformer_amd.training import StreamformerTrainer
-    dev = _dev()
+    dev = device()
     cfg = _cfg(HD72W)
     cfg.attention_probs_dropout_prob = 0.1
     with pytest.raises(NotImplementedError, match="head_dim 64"):

@@ -19,48 +19,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests import msda_oracle as MO
 from tests import vit_adapter_oracle as VO
 from tests.conftest import ROOT
-from tests.helpers import maxabs
+from tests.helpers import check_against_floor, gpu_device, guarded, read_guarded
+from tests.oracle_ops import operand_linear
 
 pytestmark = pytest.mark.gpu
 
-MARGIN = 4.0
-EPS32 = 2.0 ** -24
 MODES = {"fp32": "x3", "bf16": True}
 GRIDS = [(2, 2), (4, 6), (14, 14)]
 FRAMES = 2
-
-
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def _floor(got32, want):
-    return max(maxabs(got32, want), EPS32 * float(want.abs().max()))
-
-
-def _check(what, got, floor32, want):
-    bound = MARGIN * _floor(floor32, want)
-    err = maxabs(got, want)
-    print(f"  {what}: error {err:.3e}, bound {bound:.3e} ({err / bound:.3f})")
-    assert err <= bound, (what, err, bound)
-
-
-def _guarded(dev, *shape):
-    """A NaN-filled buffer with a guard row behind the tensor: (whole buffer, view)."""
-    n = int(np.prod(shape))
-    buf = torch.full((n + 64,), float("nan"), device=dev)
-    return buf, buf[:n].view(*shape)
-
-
-def _read_guarded(buf, view):
-    host = buf.cpu()
-    assert torch.isnan(host[view.numel():]).all(), "the guard row was written"
-    assert not torch.isnan(host[:view.numel()]).any(), "output elements left unwritten"
-    return host[:view.numel()].view(view.shape)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -68,13 +36,13 @@ def _read_guarded(buf, view):
 # ------------------------------------------------------------------------------------------------
 def _op_dwconv(x, w, b, H, W):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     Fr, _, C = x.shape
     xd, wd, bd = x.to(dev).contiguous(), w.reshape(C, 3, 3).to(dev).contiguous(), b.to(dev).contiguous()
-    buf, y = _guarded(dev, *x.shape)
+    buf, y = guarded(dev, *x.shape)
     nat.check(nat.lib.sf_op_adapter_dwconv_gelu(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), Fr, H, W, C, nat.current_stream_handle(dev)))
     torch.cuda.synchronize()
-    return _read_guarded(buf, y)
+    return read_guarded(buf, y)
 
 
 def _dwconv_sides(x, w, b, H, W):
@@ -92,7 +60,7 @@ def test_dwconv_gelu_vs_fp64(H, W, C):
     b = torch.from_numpy((0.1 * rs.standard_normal(C)).astype(np.float32))
     want, floor = _dwconv_sides(x, w, b, H, W)
     got = _op_dwconv(x, w, b, H, W)
-    _check(f"dwconv {H}x{W} C={C}", got, floor, want)
+    check_against_floor(f"dwconv {H}x{W} C={C}", got, floor, want)
     assert torch.equal(_op_dwconv(x, w, b, H, W), got), "two runs differ"
     # every level of every frame holds its own large constant: a tap that crosses a level or a frame boundary shows at once
     flat = torch.empty(FRAMES, 21 * n, C)
@@ -100,7 +68,7 @@ def test_dwconv_gelu_vs_fp64(H, W, C):
         for l, (a, e) in enumerate(((0, 16 * n), (16 * n, 20 * n), (20 * n, 21 * n))):
             flat[f, a:e] = 1000.0 * (1 + 3 * f + l) * (-1.0) ** l
     want, floor = _dwconv_sides(flat, w, b, H, W)
-    _check(f"dwconv {H}x{W} C={C}, constant levels", _op_dwconv(flat, w, b, H, W), floor, want)
+    check_against_floor(f"dwconv {H}x{W} C={C}, constant levels", _op_dwconv(flat, w, b, H, W), floor, want)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -111,7 +79,7 @@ SCALE = {0: 4, 1: 2, 2: 1, 3: 0.5}
 
 def _linear_gpu(x, w, mode="fp32"):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     M, K = x.shape
     N = w.shape[0]
     xd, wd = x.to(dev).contiguous(), w.to(dev).contiguous()
@@ -144,7 +112,7 @@ def _fuse_case(level, H, W, D, seed):
                 m = F.conv_transpose2d(VO.tokens_to_map(inp["c2"].to(dt), 2 * H, 2 * W), inp["up_w"].to(dt), inp["up_b"].to(dt), 2)
             else:
                 wl = inp["up_w"].permute(2, 3, 1, 0).reshape(4 * D, D)
-                m = MO.linear(inp["c2"], wl, inp["up_b"].repeat(4), "x3").reshape(FRAMES, 2 * H, 2 * W, 2, 2, D)
+                m = operand_linear(inp["c2"], wl, inp["up_b"].repeat(4), "x3").reshape(FRAMES, 2 * H, 2 * W, 2, 2, D)
                 m = m.permute(0, 5, 1, 3, 2, 4).reshape(FRAMES, D, Ho, Wo)
             m = m + inp["c1"].to(dt)
         else:
@@ -158,7 +126,7 @@ def _fuse_case(level, H, W, D, seed):
 
 def _op_fuse(level, H, W, D, inp, with_vit):
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     scale = SCALE[level]
     Ho, Wo = int(H * scale), int(W * scale)
     bn = inp["bn"]
@@ -175,11 +143,11 @@ def _op_fuse(level, H, W, D, inp, with_vit):
         tok_ptr, stride = tok.data_ptr() + 4 * 3 * D, (Ho * Wo + 5) * D
     vit = inp["vit"].to(dev).contiguous() if with_vit else None
     sc, sh = s64.float().to(dev), t64.float().to(dev)
-    buf, out = _guarded(dev, FRAMES, D, Ho, Wo)
+    buf, out = guarded(dev, FRAMES, D, Ho, Wo)
     nat.check(nat.lib.sf_op_adapter_fuse(level, tok_ptr, stride, nat.ptr(vit), nat.ptr(c1), sc.data_ptr(), sh.data_ptr(), out.data_ptr(), FRAMES, H, W, D,
                                          nat.current_stream_handle(dev)))
     torch.cuda.synchronize()
-    return _read_guarded(buf, out)
+    return read_guarded(buf, out)
 
 
 @pytest.mark.parametrize("D", [64, 96])
@@ -189,7 +157,7 @@ def test_fuse_vs_fp64(level, H, W, D):
     inp, want, floor = _fuse_case(level, H, W, D, 2700 + 1000 * level + 10 * H + W + D)
     for with_vit in (True, False):
         got = _op_fuse(level, H, W, D, inp, with_vit)
-        _check(f"res{level + 2} {H}x{W} D={D} vit={with_vit}", got, floor[with_vit], want[with_vit])
+        check_against_floor(f"res{level + 2} {H}x{W} D={D} vit={with_vit}", got, floor[with_vit], want[with_vit])
         assert torch.equal(_op_fuse(level, H, W, D, inp, with_vit), got), "two runs differ"
 
 
@@ -214,7 +182,7 @@ def _model(name, mode, sd=None):
     c = VO.CASES[name]
     m = sa.TimesformerMultiTaskingModelSigLIPViTAdapter(VO.config(c), compute_dtype=mode, **VO.adapter_kwargs(c))
     m.load_state_dict(VO.make_weights(c) if sd is None else sd, strict=True)
-    return m.to(_gpu()).eval()
+    return m.to(gpu_device()).eval()
 
 
 @pytest.mark.parametrize("mode", list(MODES))
@@ -222,17 +190,17 @@ def _model(name, mode, sd=None):
 def test_module_vs_f22(name, mode):
     g, c = _golden(), VO.CASES[name]
     m = _model(name, mode)
-    pixels = VO.make_pixels(c).to(_gpu())
+    pixels = VO.make_pixels(c).to(gpu_device())
     outs, tokens = m.forward_with_tokens(pixels)
     assert list(outs) == list(VO.OUTPUTS)
     assert all(v.dtype == torch.float32 and not v.requires_grad and v.is_contiguous() for v in outs.values())
     floor_out, floor_c = _floors(name, mode)
     last = len(c["indexes"]) - 1
-    _check(f"{name} {mode} c", tokens.cpu(), floor_c, torch.from_numpy(g[f"{name}.c{last}"]))
+    check_against_floor(f"{name} {mode} c", tokens.cpu(), floor_c, torch.from_numpy(g[f"{name}.c{last}"]))
     for k in VO.OUTPUTS:
         want = torch.from_numpy(g[f"{name}.{k}"])
         assert tuple(outs[k].shape) == tuple(want.shape)
-        _check(f"{name} {mode} {k}", outs[k].cpu(), floor_out[k], want)
+        check_against_floor(f"{name} {mode} {k}", outs[k].cpu(), floor_out[k], want)
     again = m(pixels)
     assert all(torch.equal(again[k], outs[k]) for k in VO.OUTPUTS), "two forwards differ"
 
@@ -242,7 +210,7 @@ def test_checkpoint_dtype_does_not_change_the_result():
     name = "sq"
     c = VO.CASES[name]
     sd = {k: (v.to(torch.bfloat16).float() if v.is_floating_point() else v) for k, v in VO.make_weights(c).items()}
-    pixels = VO.make_pixels(c).to(_gpu())
+    pixels = VO.make_pixels(c).to(gpu_device())
     base = _model(name, "fp32", sd)(pixels)
     for dt in (torch.float64, torch.bfloat16):
         got = _model(name, "fp32", {k: (v.to(dt) if v.is_floating_point() else v) for k, v in sd.items()})(pixels)
@@ -254,7 +222,7 @@ def test_checkpoint_dtype_does_not_change_the_result():
 # ------------------------------------------------------------------------------------------------
 def test_non_default_stream_is_honoured():
     import streamformer_amd._native as nat
-    dev = _gpu()
+    dev = gpu_device()
     H, W, C = 4, 6, 64
     n = (H // 2) * (W // 2)
     rs = np.random.RandomState(2801)

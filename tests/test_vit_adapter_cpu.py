@@ -8,6 +8,7 @@ import torch
 
 from oracle import streamformer_oracle as O
 from tests import vit_adapter_oracle as VO
+from tests.oracle_ops import operand_linear
 
 REL = 1e-10
 
@@ -49,7 +50,7 @@ def test_encoder_layer_restatement_equals_the_encoder_oracle():
     cfg = VO.config(c)
     sd = O.cast_state_dict(VO.make_weights(c), torch.float64)
     h = torch.from_numpy(np.random.RandomState(5).standard_normal((2, 2, 16, c["hidden"])))
-    lin = lambda x, w, b: VO.MO.linear(x, w, b, False)      # noqa: E731
+    lin = lambda x, w, b: operand_linear(x, w, b, False)      # noqa: E731
     for i in range(2):
         want = O.layer_forward(sd, cfg, i, h)
         assert float((VO.encoder_layer(sd, cfg, i, h, lin, lambda t: t) - want).abs().max()) <= 1e-12 * float(want.abs().max())

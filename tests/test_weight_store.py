@@ -15,17 +15,12 @@ import torch
 
 import streamformer_amd as sa
 from streamformer_amd import _native as nat
-from tests.helpers import frames, small_cfg
+from tests.helpers import frames, gpu_device, small_cfg
 
 pytestmark = pytest.mark.gpu
 
 FORMS = {nat.SF_F32: torch.float32, nat.SF_F64: torch.float64, nat.SF_BF16: torch.bfloat16, nat.SF_F16: torch.float16}
 COMPUTES = (nat.SF_COMPUTE_BF16, nat.SF_COMPUTE_BF16X3)
-
-
-def _gpu():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
 
 
 def _weights(seed, shapes):
@@ -81,7 +76,7 @@ def _refuses_without(create, load_fn, finalize, destroy, weights, key, **kw):
 
 # ------------------------------------------------------------------------------------------------ text tower
 def test_text_tower_forms():
-    dev = _gpu()
+    dev = gpu_device()
     V, Pn, D, I, Pr, B, L = 32, 8, 64, 96, 16, 2, 5          # intermediate 96: the zero-padding to 128 is on the path
     shapes = {"embeddings.token_embedding.weight": (V, D), "embeddings.position_embedding.weight": (Pn, D),
               "final_layer_norm.weight": (D,), "final_layer_norm.bias": (D,), "head.weight": (Pr, D), "head.bias": (Pr,)}
@@ -125,7 +120,7 @@ def test_text_tower_forms():
 
 # ------------------------------------------------------------------------------------------------ connector
 def test_connector_forms():
-    dev = _gpu()
+    dev = gpu_device()
     Din, Dout, F, P = 64, 128, 1, 4
     w = _weights(41, {"mm_projector.0.weight": (Dout, Din), "mm_projector.0.bias": (Dout,), "mm_projector.2.weight": (Dout, Dout),
                       "mm_projector.2.bias": (Dout,), "image_newline": (Dout,)})
@@ -172,7 +167,7 @@ def _oad_layer_shapes(p, d, ffn, decoder):
 
 
 def test_detector_forms():
-    dev = _gpu()
+    dev = gpu_device()
     d, heads, ffn, L, W, classes, Q0, pe_rows = 64, 2, 64, 4, 2, 3, 2, 8      # classes 3: the classifier's padding to 16 rows is on the path
     shapes = {}
     for fh in ("feature_head_long.", "feature_head_work."):
@@ -229,7 +224,7 @@ def test_detector_forms():
 
 # ------------------------------------------------------------------------------------------------ encoder
 def test_encoder_forms():
-    dev = _gpu()
+    dev = gpu_device()
     cfg = small_cfg()                                          # the smallest encoder the parity tests build
     m = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype="bf16")
     m.load_state_dict(sa.make_state_dict(cfg, seed=61))
@@ -276,12 +271,12 @@ def _copies(m):
     return copy.deepcopy(m), torch.load(buf, weights_only=False)
 
 
-def _bits(t):
+def _bits(t):          # fp32 bit patterns; helpers.bf16_bits is the bf16 rounding
     return t.detach().cpu().view(torch.int32)
 
 
 def test_text_tower_copies():
-    dev = _gpu()
+    dev = gpu_device()
     torch.manual_seed(71)
     m = sa.SiglipTextModel(sa.SiglipTextConfig(vocab_size=32, hidden_size=64, intermediate_size=64, num_hidden_layers=1, num_attention_heads=2,
                                                max_position_embeddings=8), device=dev)
@@ -298,7 +293,7 @@ def test_text_tower_copies():
 
 
 def test_connector_copies():
-    dev = _gpu()
+    dev = gpu_device()
     torch.manual_seed(73)
     F, P = 2, 4
     m = sa.VideoTokenConnector(dict(mm_projector_type="mlp2x_gelu", mm_hidden_size=64, hidden_size=64, mm_spatial_pool_stride=2), device=dev)
@@ -318,7 +313,7 @@ def test_connector_copies():
 
 
 def test_detector_copies():
-    dev = _gpu()
+    dev = gpu_device()
     torch.manual_seed(75)
     d, L, W = 64, 4, 2                                        # the config of test_detector_forms
     m = sa.OnlineActionDetector(sa.OADConfig(VISUAL_SIZE=d, NUM_CLASSES=3, LINEAR_OUT_FEATURES=d, NUM_HEADS=2, DIM_FEEDFORWARD=64,

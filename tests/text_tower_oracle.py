@@ -22,6 +22,8 @@ import os
 import numpy as np
 import torch
 
+from tests.oracle_ops import activation, layernorm, operand_linear
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f18_text_tower.npz")
 
 CONFIGS = {
@@ -88,36 +90,6 @@ def make_ids_and_masks(cfg, seed, B=3):
     return torch.from_numpy(ids), torch.from_numpy(mask), torch.from_numpy(mask_last)
 
 
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
-def _linear(x, w, b, bf16_operands):
-    if bf16_operands == "x3":      # the accurate mode's products: x = xh + xl, w = wh + wl (bf16 each), xh wh + xh wl + xl wh, the xl wl term dropped
-        xh, wh = _bf16(x), _bf16(w)
-        xl, wl = _bf16(x - xh), _bf16(w - wh)
-        return xh @ wh.t() + xh @ wl.t() + xl @ wh.t() + b
-    if bf16_operands:
-        x, w = _bf16(x), _bf16(w)
-    return x @ w.t() + b
-
-
-def _ln(x, g, b, eps):
-    mu = x.mean(dim=-1, keepdim=True)
-    var = ((x - mu) ** 2).mean(dim=-1, keepdim=True)
-    return (x - mu) / torch.sqrt(var + eps) * g + b
-
-
-def _act(x, name):
-    if name == "gelu_pytorch_tanh":
-        return 0.5 * x * (1.0 + torch.tanh(math.sqrt(2.0 / math.pi) * (x + 0.044715 * x ** 3)))
-    if name == "gelu":
-        return 0.5 * x * (1.0 + torch.erf(x / math.sqrt(2.0)))
-    if name == "relu":
-        return torch.relu(x)
-    raise ValueError(name)
-
-
 def attention(qkv, mask, heads):
     """qkv [B, L, 3D] (q | k | v columns), mask [B, L] (0 = masked key) or None -> [B, L, D], in qkv's dtype."""
     B, L, D3 = qkv.shape
@@ -134,7 +106,7 @@ def pool(x, gamma, beta, eps, w, b, group=0):
     """x [B, L, D] -> head(LN(x[:, L - 1])) [B, P]; group >= 1: normalise rows, mean over ``group`` consecutive rows, normalise."""
     row = x[:, -1]
     if gamma is not None:
-        row = _ln(row, gamma, beta, eps)
+        row = layernorm(row, gamma, beta, eps)
     out = row @ w.t() + (b if b is not None else 0.0)
     if group:
         out = out / out.norm(dim=-1, keepdim=True)
@@ -151,15 +123,15 @@ def forward(sd, cfg, ids, mask=None, dtype=torch.float64, bf16_operands=False):
     x = W["embeddings.token_embedding.weight"][ids] + W["embeddings.position_embedding.weight"][:L][None]
     for i in range(cfg["num_hidden_layers"]):
         p = f"encoder.layers.{i}."
-        h = _ln(x, W[p + "layer_norm1.weight"], W[p + "layer_norm1.bias"], eps)
+        h = layernorm(x, W[p + "layer_norm1.weight"], W[p + "layer_norm1.bias"], eps)
         wqkv = torch.cat([W[p + f"self_attn.{n}_proj.weight"] for n in "qkv"], dim=0)
         bqkv = torch.cat([W[p + f"self_attn.{n}_proj.bias"] for n in "qkv"], dim=0)
-        ctx = attention(_linear(h, wqkv, bqkv, bf16_operands), mask, heads)
-        x = x + _linear(ctx, W[p + "self_attn.out_proj.weight"], W[p + "self_attn.out_proj.bias"], bf16_operands)
-        h = _ln(x, W[p + "layer_norm2.weight"], W[p + "layer_norm2.bias"], eps)
-        h = _act(_linear(h, W[p + "mlp.fc1.weight"], W[p + "mlp.fc1.bias"], bf16_operands), act)
-        x = x + _linear(h, W[p + "mlp.fc2.weight"], W[p + "mlp.fc2.bias"], bf16_operands)
-    last = _ln(x, W["final_layer_norm.weight"], W["final_layer_norm.bias"], eps)
+        ctx = attention(operand_linear(h, wqkv, bqkv, bf16_operands), mask, heads)
+        x = x + operand_linear(ctx, W[p + "self_attn.out_proj.weight"], W[p + "self_attn.out_proj.bias"], bf16_operands)
+        h = layernorm(x, W[p + "layer_norm2.weight"], W[p + "layer_norm2.bias"], eps)
+        h = activation(operand_linear(h, W[p + "mlp.fc1.weight"], W[p + "mlp.fc1.bias"], bf16_operands), act)
+        x = x + operand_linear(h, W[p + "mlp.fc2.weight"], W[p + "mlp.fc2.bias"], bf16_operands)
+    last = layernorm(x, W["final_layer_norm.weight"], W["final_layer_norm.bias"], eps)
     return last, last[:, -1] @ W["head.weight"].t() + W["head.bias"]
 
 

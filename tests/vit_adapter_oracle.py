@@ -25,6 +25,7 @@ from oracle import streamformer_oracle as O
 from streamformer_amd.configuration import StreamformerConfig
 from streamformer_amd.init_weights import make_state_dict
 from tests import msda_oracle as MO
+from tests.oracle_ops import bf16_round, operand_linear
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "f22_vit_adapter.npz")
 INPLANES = 64            # the reference builds SpatialPriorModule(inplanes=64) whatever conv_inplane says (adapter:500)
@@ -165,10 +166,6 @@ def reference_points(shapes):
 # ------------------------------------------------------------------------------------------------
 # the pieces
 # ------------------------------------------------------------------------------------------------
-def _bf16(t):
-    return t.to(torch.bfloat16).to(t.dtype)
-
-
 def _bn(x, sd, p):
     return F.batch_norm(x, sd[p + ".running_mean"], sd[p + ".running_var"], sd[p + ".weight"], sd[p + ".bias"], False, 0.0, BN_EPS)
 
@@ -250,8 +247,8 @@ def forward(sd, c, pixels, dtype=torch.float64, operands=False):
     cfg = config(c)
     sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in sd.items()}
     px = pixels.to(dtype)
-    lin = lambda x, w, b: MO.linear(x, w, b, operands)                    # noqa: E731
-    rnd = _bf16 if operands is True else (lambda t: t)
+    lin = lambda x, w, b: operand_linear(x, w, b, operands)                    # noqa: E731
+    rnd = bf16_round if operands is True else (lambda t: t)
     sample = MO.core_grid_sample if operands else MO.core
     B, T, _, H, W = px.shape
     Fr, D, (Hg, Wg) = B * T, cfg.hidden_size, (H // 16, W // 16)

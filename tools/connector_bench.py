@@ -12,7 +12,6 @@ Method: every timed window is a batch of calls between two HIP events (at least 
 median (min) over the windows is reported, every shape is warmed up first; outputs of both sides are compared before anything is timed.
 """
 import os
-import statistics
 import sys
 
 import torch
@@ -22,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import streamformer_amd as sa  # noqa: E402
+from tools._timing import compare  # noqa: E402
 
 D_IN, D_OUT, P, STRIDE = 768, 3584, 14, 2
 CONFIG = dict(mm_projector_type="mlp2x_gelu", mm_hidden_size=D_IN, hidden_size=D_OUT, mm_spatial_pool_stride=STRIDE,
@@ -36,30 +36,7 @@ def torch_tail(W, x):
     g = F.interpolate(g, size=[-(-P // STRIDE)] * 2, mode="bilinear").permute(0, 2, 3, 1)
     g = torch.cat([g, W["image_newline"].expand(n, g.shape[1], 1, c)], dim=2)
     return g.reshape(-1, c)
-
-
-def window_ms(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def compare(native, other, warmup=5, windows=9, target_ms=50.0):
-    """Alternating windows of the two callables; (median, min) milliseconds per call of each."""
-    for _ in range(warmup):
-        native()
-        other()
-    torch.cuda.synchronize()
-    calls = [max(3, int(target_ms / max(window_ms(f, 3), 1e-3))) for f in (native, other)]
-    a, b = [], []
-    for _ in range(windows):
-        a.append(window_ms(native, calls[0]))
-        b.append(window_ms(other, calls[1]))
-    return (statistics.median(a), min(a)), (statistics.median(b), min(b))
+WINDOWS = dict(warmup=5, windows=9, target_ms=50.0)
 
 
 def main():
@@ -86,7 +63,7 @@ def main():
                 assert got.shape == want.shape
                 lines.append(f"[{mode}] F = {n:2d}: {got.shape[0]} rows, max-abs against torch fp32 {float((got - want).abs().max()):.3e} (max |ref| {float(want.abs().max()):.2f})")
                 xt = x.to(tdtype)
-                nat_ms, t_ms = compare(lambda: m(x), lambda: torch_tail(W, xt))
+                nat_ms, t_ms = compare(lambda: m(x), lambda: torch_tail(W, xt), **WINDOWS)
                 lines.append(f"[{mode}] F = {n:2d}: native {nat_ms[0]:.3f} ({nat_ms[1]:.3f}) ms   torch {tdtype} {t_ms[0]:.3f} ({t_ms[1]:.3f}) ms   "
                              f"torch / native {t_ms[0] / nat_ms[0]:.2f}")
         # streaming: SigLIP-base tower (64-frame sliding cache), a returned window of 16 frames, both streams filled before anything is timed
@@ -118,7 +95,7 @@ def main():
         b = reference_push()
         assert a.shape == b.shape
         lines.append(f"[streaming] window of 16 frames: {a.shape[0]} rows, max-abs native push against tower + torch bf16 tail {float((a - b.float()).abs().max()):.3e}")
-        nat_ms, t_ms = compare(lambda: stream.push(frame), reference_push)
+        nat_ms, t_ms = compare(lambda: stream.push(frame), reference_push, **WINDOWS)
         lines.append(f"[streaming] one pushed frame, bf16: StreamingVideoTokens.push {nat_ms[0]:.3f} ({nat_ms[1]:.3f}) ms   tower + torch tail on the 16-frame window "
                      f"{t_ms[0]:.3f} ({t_ms[1]:.3f}) ms   ratio {t_ms[0] / nat_ms[0]:.2f}")
     text = "\n".join(lines) + "\n"

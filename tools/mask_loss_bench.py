@@ -13,7 +13,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -23,21 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from streamformer_amd import _native as nat  # noqa: E402
 from streamformer_amd.heads import DenseHeadProjection, MaskLossHead  # noqa: E402
-
-
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
+from tools._timing import timed  # noqa: E402
 
 
 def torch_sequence(x, tables, targets, ls, lb):
@@ -89,13 +74,13 @@ def main():
     loss, gx, gs = head.loss(x, tables, targets32)
     torch.cuda.synchronize()
     fused_peak = torch.cuda.max_memory_allocated() - base
-    med, lo, hi = timed(lambda: head.loss(x, tables, targets32), a.iters, a.warmup)
+    med, lo, hi = timed(lambda: head.loss(x, tables, targets32), warmup=a.warmup, iters=a.iters)
     ws = nat.lib.sf_mask_loss_workspace_bytes(B, T, N, L)
     print(f"sf_mask_loss forward + backward      {med:8.3f} ms [{lo:.3f}, {hi:.3f}]   workspace {ws / 2**20:.1f} MiB, peak allocated above the inputs "
           f"{fused_peak / 2**20:.1f} MiB (workspace + d x)")
     out["mask_loss_ms"] = med
     out["mask_loss_workspace_bytes"] = int(ws)
-    med1, lo1, hi1 = timed(lambda: head.loss(x, tables, targets32, need_grad=False), a.iters, a.warmup)
+    med1, lo1, hi1 = timed(lambda: head.loss(x, tables, targets32, need_grad=False), warmup=a.warmup, iters=a.iters)
     print(f"sf_mask_loss forward only            {med1:8.3f} ms [{lo1:.3f}, {hi1:.3f}]")
     out["mask_loss_forward_ms"] = med1
 
@@ -105,7 +90,7 @@ def main():
         tl, tgx = torch_sequence(x, tables, targets, ls, lb)
         torch.cuda.synchronize()
         peak = torch.cuda.max_memory_allocated() - base
-        medt, lot, hit = timed(lambda: torch_sequence(x, tables, targets, ls, lb), max(5, a.iters // 2), 2)
+        medt, lot, hit = timed(lambda: torch_sequence(x, tables, targets, ls, lb), warmup=2, iters=max(5, a.iters // 2))
         err = float((gx - tgx).abs().max() / tgx.abs().max())
         print(f"torch operator sequence (fp32)       {medt:8.3f} ms [{lot:.3f}, {hit:.3f}]   peak allocated above the inputs {peak / 2**20:.1f} MiB "
               f"(upsampled logits of one clip: {T * L * H * W * 4 / 2**20:.0f} MiB)")
@@ -125,8 +110,8 @@ def main():
     def fb():
         proj.forward(x, params)
         proj.backward(go)
-    medf, lof, hif = timed(lambda: proj.forward(x, params), a.iters, a.warmup)
-    medd, lod, hid = timed(fb, a.iters, a.warmup)
+    medf, lof, hif = timed(lambda: proj.forward(x, params), warmup=a.warmup, iters=a.iters)
+    medd, lod, hid = timed(fb, warmup=a.warmup, iters=a.iters)
     wsd = nat.lib.sf_dense_head_workspace_bytes(M, D, I)
     print(f"dense projection forward             {medf:8.3f} ms [{lof:.3f}, {hif:.3f}]   M = {M} rows")
     print(f"dense projection forward + backward  {medd:8.3f} ms [{lod:.3f}, {hid:.3f}]   workspace {wsd / 2**20:.0f} MiB")

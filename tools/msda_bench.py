@@ -20,7 +20,6 @@ Method: every timed window is a batch of calls between two HIP events (at least 
 median (min) over the windows is reported, everything is warmed up first; results are compared before anything is timed.
 """
 import os
-import statistics
 import sys
 
 import torch
@@ -30,6 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import streamformer_amd as sa  # noqa: E402
+from tools._timing import compare  # noqa: E402
 
 ATOMIC_RATE = 1.3e12
 
@@ -65,30 +65,6 @@ def torch_module(m, query, ref, flat, shapes):
     return m.output_proj(torch_core(value, shapes, loc, w))
 
 
-def window_ms(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def compare(native, other, warmup=3, windows=7, target_ms=50.0):
-    """Alternating windows of the two callables; (median, min) milliseconds per call of each."""
-    for _ in range(warmup):
-        native()
-        other()
-    torch.cuda.synchronize()
-    calls = [max(2, int(target_ms / max(window_ms(f, 2), 1e-3))) for f in (native, other)]
-    a, b = [], []
-    for _ in range(windows):
-        a.append(window_ms(native, calls[0]))
-        b.append(window_ms(other, calls[1]))
-    return (statistics.median(a), min(a)), (statistics.median(b), min(b))
-
-
 def row(label, nat_ms, t_ms, extra=""):
     return (f"  {label}: native {nat_ms[0]:.3f} ({nat_ms[1]:.3f}) ms   torch {t_ms[0]:.3f} ({t_ms[1]:.3f}) ms   torch / native "
             f"{t_ms[0] / nat_ms[0]:.2f}{extra}")
@@ -98,7 +74,7 @@ def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     smoke = "--smoke" in sys.argv
     dev = torch.device("cuda:0")
-    kw = dict(warmup=1, windows=2, target_ms=2.0) if smoke else {}
+    kw = dict(warmup=1, windows=2, target_ms=2.0, probe=2) if smoke else dict(warmup=3, windows=7, target_ms=50.0, probe=2)
     lines = [f"multi-scale deformable attention, {P} points; {torch.cuda.get_device_name(0)}",
              "milliseconds per call: median (min) over alternating windows between HIP events; torch = the reference's sequence without its "
              "CUDA extension (per-level grid_sample + weighted sum, autograd backward), fp32, same GPU, same process"]

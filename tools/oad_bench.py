@@ -16,7 +16,6 @@ Method: every timed window is a batch of steps between two HIP events (at least 
 median (min) over the windows is reported, everything is warmed up first; the scores of both sides are compared before anything is timed.
 """
 import os
-import statistics
 import sys
 
 import torch
@@ -26,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import streamformer_amd as sa  # noqa: E402
+from tools._timing import compare  # noqa: E402
 
 CFG = sa.OADConfig()      # the THUMOS shapes are the defaults
 D, H, L, W_, DIN = CFG.d_model, CFG.NUM_HEADS, CFG.LONG_MEMORY_NUM_SAMPLES, CFG.WORK_MEMORY_NUM_SAMPLES, CFG.VISUAL_SIZE
@@ -109,30 +109,6 @@ class TorchStream:
         return F.linear(self.ln(x, "dec_modules.norm"), self.W["classifier.weight"], self.W["classifier.bias"])
 
 
-def window_ms(fn, calls):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def compare(native, other, warmup=5, windows=9, target_ms=50.0):
-    """Alternating windows of the two callables; (median, min) milliseconds per call of each."""
-    for _ in range(warmup):
-        native()
-        other()
-    torch.cuda.synchronize()
-    calls = [max(3, int(target_ms / max(window_ms(f, 3), 1e-3))) for f in (native, other)]
-    a, b = [], []
-    for _ in range(windows):
-        a.append(window_ms(native, calls[0]))
-        b.append(window_ms(other, calls[1]))
-    return (statistics.median(a), min(a)), (statistics.median(b), min(b))
-
-
 def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = torch.device("cuda:0")
@@ -179,7 +155,7 @@ def main():
                     def reference():
                         return [r.step(wt[i], None if lg is None else nt[i], mk_t if lg is not None else None) for i, r in enumerate(refs)]
 
-                    nat_ms, t_ms = compare(native, reference)
+                    nat_ms, t_ms = compare(native, reference, warmup=5, windows=9, target_ms=50.0)
                     lines.append(f"[{mode}] {n} stream(s), {label}: native {nat_ms[0]:.3f} ({nat_ms[1]:.3f}) ms   torch {tdtype} {t_ms[0]:.3f} ({t_ms[1]:.3f}) ms   "
                                  f"torch / native {t_ms[0] / nat_ms[0]:.2f}")
     text = "\n".join(lines) + "\n"

@@ -16,7 +16,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import statistics
 import sys
 
 import torch
@@ -25,21 +24,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from streamformer_amd import _native as nat  # noqa: E402
-
-
-def timed(fn, iters, warmup):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms), min(ms), max(ms)
+from tools._timing import timed  # noqa: E402
 
 
 def torch_grounding(pooler, text, labels, ls, lb):
@@ -88,8 +73,8 @@ def main():
     def grounding():
         nat.check(nat.lib.sf_grounding_loss(pooler.data_ptr(), text.data_ptr(), labels.data_ptr(), B, T, D, ls.data_ptr(), lb.data_ptr(),
                                             loss.data_ptr(), gp.data_ptr(), gs.data_ptr(), lg.data_ptr(), ws.data_ptr(), ws.numel(), stream))
-    med, lo, hi = timed(grounding, a.iters, a.warmup)
-    medt, lot, hit = timed(lambda: torch_grounding(pooler, text, labels, ls[0], lb[0]), a.iters, a.warmup)
+    med, lo, hi = timed(grounding, warmup=a.warmup, iters=a.iters)
+    medt, lot, hit = timed(lambda: torch_grounding(pooler, text, labels, ls[0], lb[0]), warmup=a.warmup, iters=a.iters)
     tl, tgp, tlg = torch_grounding(pooler, text, labels, ls[0], lb[0])
     torch.cuda.synchronize()
     print(f"sf_grounding_loss forward + backward   {med * 1e3:9.1f} us [{lo * 1e3:.1f}, {hi * 1e3:.1f}]   2 launches")
@@ -106,8 +91,8 @@ def main():
 
     def logits():
         nat.check(nat.lib.sf_dense_text_logits(nxt().data_ptr(), text.data_ptr(), M, D, n, ls.data_ptr(), lb.data_ptr(), o.data_ptr(), stream))
-    med, lo, hi = timed(logits, a.iters, a.warmup)
-    medt, lot, hit = timed(lambda: torch_logits(nxt(), text, ls[0], lb[0]), a.iters, a.warmup)
+    med, lo, hi = timed(logits, warmup=a.warmup, iters=a.iters)
+    medt, lot, hit = timed(lambda: torch_logits(nxt(), text, ls[0], lb[0]), warmup=a.warmup, iters=a.iters)
     turn[0] = len(xs) - 1
     logits()
     to = torch_logits(x, text, ls[0], lb[0])

@@ -10,7 +10,6 @@ HIP events around the calls, median of the timed repetitions.  The torch side ru
 (fp32, and bf16 weights / activations for the bf16 mode's neighbour), key-padding mask as an additive bias.
 """
 import os
-import statistics
 import sys
 
 import torch
@@ -21,6 +20,7 @@ sys.path.insert(0, ROOT)
 
 import streamformer_amd as sa  # noqa: E402
 from streamformer_amd.text import PROMPTS_PER_CALL  # noqa: E402
+from tools._timing import timed  # noqa: E402
 
 
 def torch_tower(sd, cfg, ids, mask, dtype):
@@ -58,21 +58,6 @@ def native_table(m, ids, G, per_call):
     return torch.cat([m.encode_groups(ids[i:i + per_call * G], G) for i in range(0, ids.shape[0], per_call * G)])
 
 
-def timed(fn, warmup, reps):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms), min(ms)
-
-
 def main():
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = torch.device("cuda:0")
@@ -98,11 +83,11 @@ def main():
             got = m(ids8, attention_mask=mask8)[1]
             want = torch_tower(sd, cfg, ids8, mask8, torch.float32)
             lines.append(f"[{mode}] 8 captions, pooled max-abs against torch fp32: {float((got - want).abs().max()):.3e} (max |ref| {float(want.abs().max()):.2f})")
-            n_ms = timed(lambda: m(ids8, attention_mask=mask8), 5, 30)
-            t_ms = timed(lambda: torch_tower(sd, cfg, ids8, mask8, tdtype), 5, 30)
+            n_ms = timed(lambda: m(ids8, attention_mask=mask8), warmup=5, iters=30)
+            t_ms = timed(lambda: torch_tower(sd, cfg, ids8, mask8, tdtype), warmup=5, iters=30)
             lines.append(f"[{mode}] per-step case, 8 captions x 64 tokens, masked: native {n_ms[0]:.3f} ({n_ms[1]:.3f}) ms   torch {tdtype} {t_ms[0]:.3f} ({t_ms[1]:.3f}) ms")
-            n_ms = timed(lambda: native_table(m, ids_tab, G, per_call), 1, 3)
-            t_ms = timed(lambda: torch_table(sd, cfg, ids_tab, G, tdtype, per_call), 1, 3)
+            n_ms = timed(lambda: native_table(m, ids_tab, G, per_call), warmup=1, iters=3)
+            t_ms = timed(lambda: torch_table(sd, cfg, ids_tab, G, tdtype, per_call), warmup=1, iters=3)
             lines.append(f"[{mode}] class-table case, {labels} labels x {G} templates, {per_call * G} prompts per call: native {n_ms[0]:.1f} ({n_ms[1]:.1f}) ms   "
                          f"torch {tdtype} {t_ms[0]:.1f} ({t_ms[1]:.1f}) ms")
         del m

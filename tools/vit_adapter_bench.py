@@ -21,6 +21,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import streamformer_amd as sa      # noqa: E402
+from tools._timing import timed  # noqa: E402
 
 
 def composed_forward(m, pixel_values):
@@ -68,21 +69,6 @@ def composed_forward(m, pixel_values):
     return {"res2": m.norm1(m1), "res3": m.norm2(m2), "res4": m.norm3(m3), "res5": m.norm4(m4)}
 
 
-def timed(fn, warmup, iters):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return statistics.median(ms)
-
-
 def split(m, pixels, iters):
     """Median milliseconds per stage over `iters` forwards, from the module's own event marks."""
     per = {}
@@ -122,9 +108,9 @@ def main():
         for B, T in shapes:
             pixels = torch.randn(B, T, 3, size, size, device=dev)
             with torch.no_grad():
-                native = timed(lambda: m(pixels), args.warmup, args.iters)
+                native = timed(lambda: m(pixels), warmup=args.warmup, iters=args.iters)[0]
                 parts = split(m, pixels, args.iters)
-                composed = timed(lambda: composed_forward(m, pixels), args.warmup, args.iters)
+                composed = timed(lambda: composed_forward(m, pixels), warmup=args.warmup, iters=args.iters)[0]
                 a, b = m(pixels), composed_forward(m, pixels)
             worst = max(float((a[k] - b[k]).abs().max()) / float(b[k].abs().max()) for k in a)
             lines.append(f"{mode} B={B} T={T}: native {native:.2f} (" + ", ".join(f"{k} {v:.2f}" for k, v in parts.items()) +
