@@ -630,6 +630,77 @@ int sf_op_adapter_dwconv_gelu(const float* x_dev, const float* w_dev, const floa
 int sf_op_adapter_fuse(int level, const float* tokens_dev, long long tokens_frame_stride, const float* vit_dev, const float* c1_dev,
                        const float* scale_dev, const float* shift_dev, float* out_dev, int F, int H, int W, int D, sf_stream stream);
 
+/* ---- Mask2Former pixel decoder: mask features and multi-scale features from res2..res5 -------------------------------------------
+ * The reference's MSDeformAttnPixelDecoder (downstream/OVIS/mask2former/modeling/pixel_decoder/msdeformattn.py): 1 x 1 input projections
+ * + GroupNorm(32), a deformable-attention transformer encoder over the chosen levels (post-norm, ReLU, sine position table + level
+ * embedding), FPN levels (lateral 1 x 1, bilinear upsample + add, 3 x 3, GroupNorm, ReLU) for the finer ones and the 1 x 1 mask_features
+ * convolution.  Same protocol as the connector: create (the width rules are checked there, the field named), stage the weights under
+ * the reference's state-dict names (a leading "sem_seg_head.pixel_decoder." is dropped), finalize in a compute mode (weights rounded /
+ * split once; the convolution weights re-laid out for the GEMMs there).  Inference only, no padding masks.  Kernels: csrc/sf_pixdec.hip. */
+typedef struct sf_pixdec sf_pixdec;
+#define SF_PIXDEC_MAX_LEVELS 4
+#define SF_PIXDEC_NORM_GN 0
+typedef struct {
+  int32_t num_levels;                          /* input levels (res2 .. res5), 1..4, listed by increasing stride              */
+  int32_t channels[SF_PIXDEC_MAX_LEVELS];      /* multiples of 64                                                             */
+  int32_t strides[SF_PIXDEC_MAX_LEVELS];
+  int32_t in_transformer[SF_PIXDEC_MAX_LEVELS];/* 1: the level enters the transformer encoder                                 */
+  int32_t conv_dim, mask_dim, nheads, dim_feedforward, enc_layers, enc_n_points, common_stride;
+  int32_t norm;                                /* SF_PIXDEC_NORM_GN                                                           */
+  int32_t im2col_chunk_rows;                   /* pixels per gathered 3 x 3 operand; 0: the library's default (16384)         */
+} sf_pixdec_config;
+int sf_pixdec_create(const sf_pixdec_config* cfg, int device, sf_pixdec** out);
+void sf_pixdec_destroy(sf_pixdec* dec);
+/* host_ptr: contiguous host memory of dtype SF_F32, SF_F64 or SF_BF16 with exactly the reference's shape (convolutions [O, I, kh, kw]). */
+int sf_pixdec_load_tensor(sf_pixdec* dec, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+/* Makes the handle's device current and leaves it so. */
+int sf_pixdec_finalize(sf_pixdec* dec, int compute);
+int sf_pixdec_missing_weights(sf_pixdec* dec);              /* count; names via sf_last_error() */
+/* How many entries of the reference's `out` list sf_pixdec_forward returns (min(3, transformer levels + FPN levels)) and how many FPN
+ * levels the strides ask for.  Either pointer may be NULL.                                                                          */
+int sf_pixdec_num_outputs(sf_pixdec* dec, int* num_multi_scale, int* num_fpn_levels);
+/* level_shapes: HOST array of (H, W) per input level, independent of each other (no halving is assumed).  After sf_pixdec_finalize. */
+int sf_pixdec_workspace_bytes(sf_pixdec* dec, int F, const int32_t* level_shapes, int num_levels, size_t* out);
+/* features_dev: HOST array of num_levels device pointers, level l fp32 [F, channels[l], H_l, W_l] (a level neither the transformer nor an
+ * FPN level reads may be NULL).  mask_features_dev fp32 [F, mask_dim, H, W] of the finest level the decoder reaches.  multi_scale_dev:
+ * HOST array of num_multi_scale device pointers, fp32 [F, conv_dim, H, W] each: the first entries of the reference's `out`, i.e. the
+ * transformer's levels coarsest first, then the FPN levels coarse to fine; entry 0 is the reference's transformer_encoder_features.
+ * No allocation, no host synchronisation, one workspace (256-byte aligned), the caller's stream; bit-reproducible.  Refused before
+ * anything is launched: not finalized (SF_ERR_STATE), a level count other than the config's, F outside 1..65535, a NULL or not 16-byte
+ * aligned buffer (SF_ERR_INVALID), a short workspace (SF_ERR_WORKSPACE), activations above 2^31 - 1 elements (SF_ERR_CAPACITY).      */
+int sf_pixdec_forward(sf_pixdec* dec, const float* const* features_dev, int F, const int32_t* level_shapes, int num_levels,
+                      float* mask_features_dev, float* const* multi_scale_dev, int num_multi_scale, void* workspace_dev,
+                      size_t workspace_bytes, sf_stream stream);
+/* The decoder's kernels alone.  "rows" are fp32 [F, H W, C] with channels contiguous, "planes" the same as bf16 hi (+ lo = bf16(x - hi),
+ * may be NULL) bit patterns, the A operand of the GEMMs.  Every buffer 16-byte aligned.
+ * NCHW fp32 [F, C, HW] -> planes (C % 8 == 0), and rows (frame f at rows_dev + f * frame_stride floats) -> NCHW fp32 (C % 4 == 0).  */
+int sf_op_pixdec_nchw_to_planes(const float* x_dev, uint16_t* hi_dev, uint16_t* lo_dev, int F, int C, int HW, sf_stream stream);
+int sf_op_pixdec_rows_to_nchw(const float* rows_dev, long long frame_stride, float* out_dev, int F, int C, int HW, sf_stream stream);
+/* GroupNorm(32, C) (eps 1e-5) over rows x_dev per (frame, group), two-pass shifted statistics into stats_dev [F, 32, 4] (shift, mean - shift, rstd, 0), then
+ * y = gn(x) [ReLU] [+ bilinear upsample of prev_dev rows [F, Hp Wp, C] to H x W, F.interpolate(align_corners=False)'s rule].  Outputs,
+ * any subset: y_dev rows, y planes, q planes = y + pos_dev[pixel] (pos_dev fp32 [H W, C]).  C % 64 == 0.                              */
+int sf_op_pixdec_groupnorm(const float* x_dev, const float* gamma_dev, const float* beta_dev, int relu, const float* prev_dev, int Hp,
+                           int Wp, const float* pos_dev, float* stats_dev, float* y_dev, uint16_t* y_hi_dev, uint16_t* y_lo_dev,
+                           uint16_t* q_hi_dev, uint16_t* q_lo_dev, int F, int H, int W, int C, sf_stream stream);
+/* pos_dev [S, C] = PositionEmbeddingSine(C / 2, normalize=True) of an all-false mask + level_embed_dev[l] over the L levels of
+ * level_shapes (HOST (H, W) pairs), S = sum H W; ref_dev [F, S, L, 2] = ((x + 0.5) / W, (y + 0.5) / H) repeated over levels.          */
+int sf_op_pixdec_pos_ref(const float* level_embed_dev, const int32_t* level_shapes, int L, int F, int C, float* pos_dev, float* ref_dev,
+                         sf_stream stream);
+/* LayerNorm of rows x_dev [rows, C] (the residual already added): any subset of y_dev fp32, y planes, q planes = y + pos_dev[row % pos_rows]. */
+int sf_op_pixdec_postln(const float* x_dev, const float* gamma_dev, const float* beta_dev, float eps, const float* pos_dev, int pos_rows,
+                        float* y_dev, uint16_t* y_hi_dev, uint16_t* y_lo_dev, uint16_t* q_hi_dev, uint16_t* q_lo_dev, int rows, int C,
+                        sf_stream stream);
+/* The nine 3 x 3 taps (padding 1) of pixel rows [row0, row0 + rows) of planes [F, H W, C] side by side: out planes [rows, 9 C] in
+ * (dy, dx, c) order.  A tap outside its frame's grid is written as zero and never read.  C % 64 == 0.                                */
+int sf_op_pixdec_im2col(const uint16_t* in_hi_dev, const uint16_t* in_lo_dev, int F, int H, int W, int C, long long row0, int rows,
+                        uint16_t* out_hi_dev, uint16_t* out_lo_dev, sf_stream stream);
+/* The 3 x 3 convolution as the decoder runs it: that gather in chunks of chunk_rows pixels (0: the default), each followed by one GEMM
+ * with K = 9 C against w planes [N, 9 C] in (dy, dx, c_in) order; out_dev fp32 rows [F H W, N].  With lo planes the accurate mode.      */
+size_t sf_op_pixdec_conv3x3_workspace_bytes(int F, int H, int W, int C, int chunk_rows);
+int sf_op_pixdec_conv3x3(const uint16_t* in_hi_dev, const uint16_t* in_lo_dev, const uint16_t* w_hi_dev, const uint16_t* w_lo_dev, int F,
+                         int H, int W, int C, int N, int chunk_rows, float* out_dev, void* workspace_dev, size_t workspace_bytes,
+                         sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

@@ -52,6 +52,14 @@ class SfOadConfig(C.Structure):
         ("dec_layers", C.c_int32), ("dec_norm", C.c_int32), ("eps", C.c_float)]
 
 
+class SfPixdecConfig(C.Structure):
+    """sf_pixdec_config: the Mask2Former pixel decoder's fields as plain ints; per input level (by increasing stride) its channels, its
+    stride and whether it enters the transformer encoder (norm 0 = "GN"; im2col_chunk_rows 0 = the library's default)."""
+    _fields_ = [("num_levels", C.c_int32)] + [(n, C.c_int32 * 4) for n in ("channels", "strides", "in_transformer")] + [
+        (n, C.c_int32) for n in ("conv_dim", "mask_dim", "nheads", "dim_feedforward", "enc_layers", "enc_n_points", "common_stride", "norm",
+                                 "im2col_chunk_rows")]
+
+
 SF_OAD_MAX_CALL_STREAMS = 64
 SF_STREAM_BLOB_KV1 = 0x31564B53
 
@@ -178,6 +186,22 @@ SIGNATURES = {
     "sf_op_msda_backward": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_adapter_dwconv_gelu": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sf_op_adapter_fuse": (_I, [_I, _P, C.c_longlong, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_pixdec_create": (_I, [C.POINTER(SfPixdecConfig), _I, C.POINTER(_P)]),
+    "sf_pixdec_destroy": (None, [_P]),
+    "sf_pixdec_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
+    "sf_pixdec_finalize": (_I, [_P, _I]),
+    "sf_pixdec_missing_weights": (_I, [_P]),
+    "sf_pixdec_num_outputs": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "sf_pixdec_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int32), _I, C.POINTER(_SZ)]),
+    "sf_pixdec_forward": (_I, [_P, C.POINTER(_P), _I, C.POINTER(C.c_int32), _I, _P, C.POINTER(_P), _I, _P, _SZ, _P]),
+    "sf_op_pixdec_nchw_to_planes": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "sf_op_pixdec_rows_to_nchw": (_I, [_P, C.c_longlong, _P, _I, _I, _I, _P]),
+    "sf_op_pixdec_groupnorm": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_op_pixdec_pos_ref": (_I, [_P, C.POINTER(C.c_int32), _I, _I, _I, _P, _P, _P]),
+    "sf_op_pixdec_postln": (_I, [_P, _P, _P, _F, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sf_op_pixdec_im2col": (_I, [_P, _P, _I, _I, _I, _I, C.c_longlong, _I, _P, _P, _P]),
+    "sf_op_pixdec_conv3x3_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sf_op_pixdec_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
