@@ -17,19 +17,13 @@
 //                                   convolution's GEMM output read through the 2 x 2 pixel shuffle) + the bilinear resampling of the kept
 //                                   ViT stream (x4, x2, x1, x0.5 by F.interpolate(align_corners=False)'s rule, edge clamping included)
 //                                   [+ the spatial prior's c1 at res2], then the eval BatchNorm as a folded affine, written NCHW.  Inputs
-//                                   are channel-contiguous and the output is pixel-contiguous: a 64-pixel x 64-channel tile is gathered
-//                                   with lanes along channels (float4, 256 B per pixel), passes through LDS with rows padded to 65 floats
-//                                   (a column read then touches 64 different banks), and leaves with lanes along pixels (256 B per
-//                                   channel row).  c1, which is NCHW already, is added on the way out.
-#include "sf_common.h"
+//                                   are channel-contiguous and the output is pixel-contiguous: the sums enter sf_nchw_tile.h's tile on
+//                                   its rows side and leave on its NCHW side.  c1, which is NCHW already, is added on the way out.
 #include "sf_internal.h"
-#include "sf_launch.h"
+#include "sf_nchw_tile.h"
 
 #define ADW_THREADS 256
 #define ADW_PIXELS_PER_THREAD 4
-#define AFU_THREADS 256
-#define AFU_TILE 64                      // pixels and channels of one transpose tile
-#define AFU_LD (AFU_TILE + 1)
 
 struct SfAdapterDw {
   const float* x; const float* w; const float* b; float* y;
@@ -89,28 +83,11 @@ struct SfAdapterFuse {
   float ratio;                           // source pixels per output pixel: 1 / scale_factor
 };
 
-// one axis of F.interpolate(mode="bilinear", align_corners=False): source index pair and the weight of the second
-SF_DEVICE void afu_axis(int dst, float ratio, int in, int* i0, int* i1, float* l1) {
-  float src = ratio * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  int a = (int)src;
-  a = a > in - 1 ? in - 1 : a;
-  *i0 = a;
-  *i1 = a + 1 <= in - 1 ? a + 1 : in - 1;
-  const float l = src - (float)a;
-  *l1 = l > 1.f ? 1.f : l;
-}
-
-__global__ __launch_bounds__(AFU_THREADS) void sf_adapter_fuse_kernel(SfAdapterFuse p) {
-  __shared__ float tile[AFU_TILE * AFU_LD];                       // [pixel][channel], rows padded
-  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * AFU_TILE, p0 = (int)blockIdx.x * AFU_TILE;
+__global__ __launch_bounds__(SF_TILE_THREADS) void sf_adapter_fuse_kernel(SfAdapterFuse p) {
+  __shared__ float tile[SF_TILE_CELLS];
+  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * SF_TILE, p0 = (int)blockIdx.x * SF_TILE;
   const int pixels = p.Ho * p.Wo;
-  // gather: 16 lanes of float4 along the channels of one pixel, 16 pixels per step
-  const int lane_c = ((int)threadIdx.x % 16) * 4, lane_p = (int)threadIdx.x / 16;
-  const int c = c0 + lane_c;
-  for (int pp = lane_p; pp < AFU_TILE; pp += AFU_THREADS / 16) {
-    const int pix = p0 + pp;
-    if (pix >= pixels || c >= p.D) continue;
+  sf_tile_gather_rows(tile, p0, c0, pixels, p.D, [&](int pix, int c) {
     const int y = pix / p.Wo, x = pix - y * p.Wo;
     f32x4_t v;
     if (p.level == 0) {                  // row of the [.., 2Hv * 2Wv, 4 D] GEMM output, column block (dy, dx)
@@ -122,8 +99,8 @@ __global__ __launch_bounds__(AFU_THREADS) void sf_adapter_fuse_kernel(SfAdapterF
     if (p.vit) {
       int y0, y1, x0, x1;
       float ly, lx;
-      afu_axis(y, p.ratio, p.Hv, &y0, &y1, &ly);
-      afu_axis(x, p.ratio, p.Wv, &x0, &x1, &lx);
+      sf_bilinear_axis(y, p.ratio, p.Hv, &y0, &y1, &ly);
+      sf_bilinear_axis(x, p.ratio, p.Wv, &x0, &x1, &lx);
       const float* src = p.vit + (size_t)f * p.Hv * p.Wv * p.D + c;
       const f32x4_t v00 = *reinterpret_cast<const f32x4_t*>(src + (size_t)(y0 * p.Wv + x0) * p.D);
       const f32x4_t v01 = *reinterpret_cast<const f32x4_t*>(src + (size_t)(y0 * p.Wv + x1) * p.D);
@@ -132,21 +109,14 @@ __global__ __launch_bounds__(AFU_THREADS) void sf_adapter_fuse_kernel(SfAdapterF
       const float hy = 1.f - ly, hx = 1.f - lx;
       v += hy * (hx * v00 + lx * v01) + ly * (hx * v10 + lx * v11);
     }
-    float* row = tile + pp * AFU_LD + lane_c;
-    row[0] = v[0]; row[1] = v[1]; row[2] = v[2]; row[3] = v[3];
-  }
+    return v;
+  });
   __syncthreads();
-  // scatter: 64 lanes along the pixels of one channel row, four rows per step
-  const int lane = (int)threadIdx.x % 64, pix = p0 + lane;
-  if (pix >= pixels) return;
-  for (int cc = (int)threadIdx.x / 64; cc < AFU_TILE; cc += AFU_THREADS / 64) {
-    const int ch = c0 + cc;
-    if (ch >= p.D) break;
-    const size_t o = ((size_t)f * p.D + ch) * pixels + pix;
-    float v = tile[lane * AFU_LD + cc];
+  sf_tile_nchw(f, p0, c0, pixels, p.D, [&](int cell, int ch, size_t o) {
+    float v = tile[cell];
     if (p.c1) v += p.c1[o];
     p.out[o] = p.scale[ch] * v + p.shift[ch];
-  }
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -192,8 +162,8 @@ extern "C" int sf_op_adapter_fuse(int level, const float* tokens_dev, long long 
   if (((uintptr_t)tokens_dev | (uintptr_t)vit_dev) & 15) return sf_set_err(SF_ERR_INVALID, "%s: tokens and vit must be 16-byte aligned", who);
   p.tok = tokens_dev; p.vit = vit_dev; p.c1 = c1_dev; p.scale = scale_dev; p.shift = shift_dev; p.out = out_dev;
   p.tok_frame_stride = tokens_frame_stride;
-  const dim3 grid((unsigned)((pixels + AFU_TILE - 1) / AFU_TILE), (unsigned)((D + AFU_TILE - 1) / AFU_TILE), (unsigned)F);
-  if (grid.y > 65535) return sf_set_err(SF_ERR_INVALID, "%s: D = %d exceeds one grid", who, D);
-  HIP_TRY(sf_launch(sf_adapter_fuse_kernel, grid, dim3(AFU_THREADS), 0, (hipStream_t)stream, p));
+  dim3 grid;
+  if (!sf_tile_grid(F, D, pixels, &grid)) return sf_set_err(SF_ERR_INVALID, "%s: D = %d exceeds one grid", who, D);
+  HIP_TRY(sf_launch(sf_adapter_fuse_kernel, grid, dim3(SF_TILE_THREADS), 0, (hipStream_t)stream, p));
   return SF_OK;
 }

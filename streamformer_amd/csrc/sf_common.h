@@ -55,6 +55,22 @@ SF_DEVICE void split_bf(float x, unsigned int& hi, unsigned int& lo) {
   hi = f2bf(x);
   lo = f2bf(x - bf2f(hi));
 }
+// four / eight fp32 values -> elements o.. of the bf16 planes: hi = bf16(v) and, unless lo is null, lo = bf16(v - hi); one 8- / 16-byte
+// store per plane (o a multiple of 4 / 8 on planes aligned likewise)
+SF_DEVICE void store_planes4(f32x4_t v, bf16_t* hi, bf16_t* lo, size_t o) {
+  unsigned int hb[4], lb[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) split_bf(v[j], hb[j], lb[j]);
+  *reinterpret_cast<u32x2_t*>(hi + o) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
+  if (lo) *reinterpret_cast<u32x2_t*>(lo + o) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
+}
+SF_DEVICE void store_planes8(const float v[8], bf16_t* hi, bf16_t* lo, size_t o) {
+  unsigned int hb[8], lb[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) split_bf(v[j], hb[j], lb[j]);
+  *reinterpret_cast<u32x4_t*>(hi + o) = (u32x4_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16), hb[4] | (hb[5] << 16), hb[6] | (hb[7] << 16)};
+  if (lo) *reinterpret_cast<u32x4_t*>(lo + o) = (u32x4_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16), lb[4] | (lb[5] << 16), lb[6] | (lb[7] << 16)};
+}
 
 // LayerNorm folded into the consumer at small M (LNF): A = bf16(x) of the residual stream, W' = W * gamma.  The wave adds
 // up sum x and sum x^2 of its 16 rows from the very A fragments it feeds to the MFMAs (v_dot2c_f32_bf16: two VALU ops
@@ -340,6 +356,20 @@ hipError_t sf_launch_layernorm(const float* x, const float* gamma, const float* 
                                bf16_t* y_hi, bf16_t* y_lo, int rows, int D, float eps, hipStream_t s, const bf16_t* xp_hi = nullptr,
                                const bf16_t* xp_lo = nullptr, const bf16_t* xp_lo2 = nullptr, float* const* y_f32_ind = nullptr);
                                // y_f32_ind: the fp32 destination is read from device memory (the streamed frame's caller tensor)
+// The tail models' row pass: y = [ReLU] [LN] (x [+ r[row % r_mod]]) and q = y + pe[row % pe_mod], each as fp32 and / or bf16 planes.
+// One wave per row, two-pass statistics over x (+ r) re-read from memory; D any multiple of 4.  y may alias x or r: a row belongs to
+// one wave and each element is read by the lane that writes it.
+struct SfRowArgs {
+  const float* x;                                  // [rows, D]
+  const float* r; int r_mod;                       // + r[row % r_mod] (r_mod 0: r[row]); null: none
+  const float* gamma; const float* beta; float eps;      // LayerNorm; gamma null: none
+  int relu;                                        // r, gamma and relu pick the kernel's instantiation (sf_launch_row)
+  const float* pe; int pe_mod;                     // the q outputs' addend, after the activation; null: no q output
+  float* y; bf16_t* y_hi; bf16_t* y_lo;            // any of them null
+  float* q; bf16_t* q_hi; bf16_t* q_lo;            // any of them null
+  int rows, D;
+};
+hipError_t sf_launch_row(const SfRowArgs& p, hipStream_t s);      // pointers 16-byte aligned, D % 4 == 0, rows >= 1: checked by the callers
 // pixels [F,C,H,W] -> patch matrix [F*N, C*P*P] bf16 (+lo), columns (c,ph,pw).
 // pixel_kind 0 fp32, 1 bf16, 2 uint8 raw frames normalised on the fly: y = x * scale[c] + shift[c]
 struct SfPixelNorm { float scale[4]; float shift[4]; };

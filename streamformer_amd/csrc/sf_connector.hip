@@ -138,12 +138,7 @@ __global__ __launch_bounds__(256) void sf_connector_pool_kernel(SfConnPool p) {
     } else if (OUT == 1) {
       *reinterpret_cast<u32x4_t*>(p.out_bf16 + o) = (u32x4_t){pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
     } else {
-      unsigned int hb[8], lb[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) split_bf(y[j], hb[j], lb[j]);
-      *reinterpret_cast<u32x4_t*>(p.out_hi + o) = (u32x4_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16), hb[4] | (hb[5] << 16), hb[6] | (hb[7] << 16)};
-      if (p.out_lo)
-        *reinterpret_cast<u32x4_t*>(p.out_lo + o) = (u32x4_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16), lb[4] | (lb[5] << 16), lb[6] | (lb[7] << 16)};
+      store_planes8(y, p.out_hi, p.out_lo, o);
     }
   }
 }
@@ -190,14 +185,9 @@ static hipError_t conn_launch_pool(const SfConnPool& q, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // handle
 // ------------------------------------------------------------------------------------------------
-struct sf_connector {
+struct sf_connector : SfModelHandle {         // weights: image_newline is accepted by every layout and required by those that place it
   sf_connector_config cfg;
-  int device = 0;
   int pool = CONN_POOL_NONE;                  // cfg.pool_mode with stride 1 folded to none
-  SfWeightStore weights;                      // image_newline is accepted by every layout and required by those that place it
-  bool finalized = false;
-  int compute = SF_COMPUTE_BF16;
-  SfDeviceAllocs dev;
   std::vector<SfDevLinear> lin;
   const float* newline = nullptr;             // [out_dim] or null
 };
@@ -238,44 +228,18 @@ extern "C" int sf_connector_create(const sf_connector_config* cfg, int device, s
   return SF_OK;
 }
 
-static void conn_free_device(sf_connector* c) {
-  c->dev.free_all();
-  c->lin.clear();
-  c->newline = nullptr;
-}
-
-extern "C" void sf_connector_destroy(sf_connector* c) {
-  if (!c) return;
-  conn_free_device(c);
-  delete c;
-}
+extern "C" void sf_connector_destroy(sf_connector* c) { delete c; }
 
 extern "C" int sf_connector_load_tensor(sf_connector* c, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  if (!c || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_connector_load_tensor: null argument");
-  std::string err;
-  const int rc = c->weights.load(key, host_ptr, dtype, shape, ndim, &err);
-  if (rc) return sf_set_err(rc, "%s", err.c_str());
-  c->finalized = false;
-  return SF_OK;
+  return sf_model_load_tensor(c, "sf_connector_load_tensor", key, host_ptr, dtype, shape, ndim);
 }
 
-extern "C" int sf_connector_missing_weights(sf_connector* c) {
-  if (!c) return sf_set_err(SF_ERR_INVALID, "null handle");
-  std::string err;
-  const int missing = c->weights.missing(&err);
-  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
-  return missing;
-}
+extern "C" int sf_connector_missing_weights(sf_connector* c) { return sf_model_missing_weights(c); }
 
 // the weights rounded (bf16 mode) or split into hi + lo planes (bf16x3) ONCE, here: no per-call conversion of 3584^2 fp32 values.
 // Makes the handle's device current and leaves it so, as the encoder's and the text tower's finalize do (stated in the header).
 extern "C" int sf_connector_finalize(sf_connector* c, int compute) {
-  if (!c) return sf_set_err(SF_ERR_INVALID, "null handle");
-  SF_TRY(sf_check_compute_mode(compute));
-  if (sf_connector_missing_weights(c)) return SF_ERR_STATE;
-  HIP_TRY(hipSetDevice(c->device));
-  conn_free_device(c);
-  c->compute = compute;
+  SF_TRY(sf_model_begin_finalize(c, compute));
   c->lin.assign(c->cfg.depth, SfDevLinear());
   for (int i = 0; i < c->cfg.depth; ++i) {
     const std::string p = conn_linear_key(c, i);
@@ -341,7 +305,7 @@ static ConnWorkspace conn_carve(const sf_connector* c, const ConnPlan& pl, void*
     }
     w.y = cv.take<float>(Mp * Dout);
   }
-  w.bytes = (cv.off + 255) & ~(size_t)255;
+  w.bytes = cv.bytes();
   if (w.bytes == 0) w.bytes = 256;
   return w;
 }
@@ -360,7 +324,7 @@ extern "C" int sf_connector_workspace_bytes(sf_connector* c, int F, int P, size_
   ConnPlan pl;
   int rc = conn_plan(c, F, P, &pl);
   if (rc) return rc;
-  if (!c->finalized) return sf_set_err(SF_ERR_STATE, "sf_connector_finalize has not run (the workspace depends on the compute mode)");
+  SF_TRY(sf_model_check_finalized(c, "sf_connector", true));
   *out = conn_carve(c, pl, nullptr).bytes;
   return SF_OK;
 }
@@ -370,14 +334,12 @@ extern "C" int sf_connector_forward(sf_connector* c, const float* feats_dev, int
   ConnPlan pl;
   int rc = conn_plan(c, F, P, &pl);
   if (rc) return rc;
-  if (!c->finalized) return sf_set_err(SF_ERR_STATE, "sf_connector_finalize has not run (or weights were loaded after it)");
+  SF_TRY(sf_model_check_finalized(c, "sf_connector"));
   if (!feats_dev || !out_dev || !workspace_dev) return sf_set_err(SF_ERR_INVALID, "sf_connector_forward: null buffer");
   if (out_dtype != SF_F32 && out_dtype != SF_BF16) return sf_set_err(SF_ERR_INVALID, "sf_connector_forward: out_dtype %d (SF_F32 or SF_BF16)", out_dtype);
   if (((uintptr_t)feats_dev & 15) || ((uintptr_t)out_dev & 15)) return sf_set_err(SF_ERR_INVALID, "sf_connector_forward: features and output must be 16-byte aligned");
-  if ((uintptr_t)workspace_dev & 255) return sf_set_err(SF_ERR_INVALID, "sf_connector_forward: workspace must be 256-byte aligned");
   const ConnWorkspace ws = conn_carve(c, pl, workspace_dev);
-  if (workspace_bytes < ws.bytes)
-    return sf_set_err(SF_ERR_WORKSPACE, "sf_connector_forward: workspace %zu < %zu bytes (sf_connector_workspace_bytes)", workspace_bytes, ws.bytes);
+  SF_TRY(sf_check_workspace("sf_connector_forward", "sf_connector_workspace_bytes", workspace_dev, workspace_bytes, ws.bytes));
   hipStream_t s = (hipStream_t)stream;
   const sf_connector_config& cfg = c->cfg;
   const bool split = c->compute == SF_COMPUTE_BF16X3;

@@ -1,5 +1,7 @@
-// Device side of a native model's handle, shared by sf_encoder, sf_text, sf_connector and sf_oad: the device allocations a finalize
-// owns, a Linear's bf16 planes and their upload, and the GEMM arguments every Linear starts from.  The host half is sf_weights.h.
+// Device side of a native model's handle, shared by sf_encoder, sf_text, sf_connector, sf_oad and sf_pixdec: the device allocations a
+// finalize owns, a Linear's bf16 planes and their upload, the GEMM arguments every Linear starts from, and SfModelHandle, the part of
+// a tail model's handle (everything but the encoder's) and of its entry points that does not depend on the model.  The host half is
+// sf_weights.h.
 #pragma once
 #include "sf_common.h"
 #include "sf_internal.h"
@@ -54,6 +56,71 @@ struct SfDeviceAllocs {
     uploaded = 0;
   }
 };
+
+// ------------------------------------------------------------------------------------------------
+// What sf_text, sf_connector, sf_oad and sf_pixdec share: a handle derives from SfModelHandle and brings its config validation, its
+// expected-key table, its uploads, its plan, carve and launch sequence.  `family` below is the prefix of its entry points ("sf_text").
+// ------------------------------------------------------------------------------------------------
+struct SfModelHandle {
+  int device = 0;
+  SfWeightStore weights;
+  bool finalized = false;       // set at the end of *_finalize, cleared by every staged tensor
+  int compute = SF_COMPUTE_BF16;
+  SfDeviceAllocs dev;
+  ~SfModelHandle() { dev.free_all(); }
+};
+
+// *_load_tensor in two steps, for a family that stages some key by a rule of its own between them
+static inline int sf_model_load_args(const SfModelHandle* h, const char* who, const char* key, const void* host_ptr, const int64_t* shape, int ndim) {
+  if (!h || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "%s: null argument", who);
+  return SF_OK;
+}
+static inline int sf_model_staged(SfModelHandle* h, int rc, const std::string& err) {      // rc, err: what weights.load / stage gave
+  if (rc) return sf_set_err(rc, "%s", err.c_str());
+  h->finalized = false;
+  return SF_OK;
+}
+static inline int sf_model_load_tensor(SfModelHandle* h, const char* who, const char* key, const void* host_ptr, int dtype, const int64_t* shape,
+                                       int ndim) {
+  SF_TRY(sf_model_load_args(h, who, key, host_ptr, shape, ndim));
+  std::string err;
+  const int rc = h->weights.load(key, host_ptr, dtype, shape, ndim, &err);
+  return sf_model_staged(h, rc, err);
+}
+
+static inline int sf_model_missing_weights(SfModelHandle* h) {
+  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
+  std::string err;
+  const int missing = h->weights.missing(&err);
+  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
+  return missing;
+}
+
+// The opening of every *_finalize: refuses a null handle, an unknown mode and missing weights, makes the handle's device current and
+// leaves it so, frees what the last finalize put on the device and records the mode.  The handle counts as not finalized until the
+// caller sets h->finalized after its last upload, so a finalize that fails half-way leaves no freed pointer in use.
+static inline int sf_model_begin_finalize(SfModelHandle* h, int compute) {
+  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
+  SF_TRY(sf_check_compute_mode(compute));
+  if (sf_model_missing_weights(h)) return SF_ERR_STATE;
+  HIP_TRY(hipSetDevice(h->device));
+  h->dev.free_all();
+  h->finalized = false;
+  h->compute = compute;
+  return SF_OK;
+}
+
+// The refusals of a forward entry.  sizing: the wording of the *_workspace_bytes entry points.
+static inline int sf_model_check_finalized(const SfModelHandle* h, const char* family, bool sizing = false) {
+  if (h->finalized) return SF_OK;
+  return sf_set_err(SF_ERR_STATE, sizing ? "%s_finalize has not run (the workspace depends on the compute mode)" : "%s_finalize has not run (or weights were loaded after it)", family);
+}
+// who: the entry point; sizer: the function that tells `need`
+static inline int sf_check_workspace(const char* who, const char* sizer, const void* workspace, size_t given, size_t need) {
+  if ((uintptr_t)workspace & 255) return sf_set_err(SF_ERR_INVALID, "%s: workspace must be 256-byte aligned", who);
+  if (given < need) return sf_set_err(SF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (%s)", who, given, need, sizer);
+  return SF_OK;
+}
 
 // [N, K] weight (+ bias) -> bf16 hi (+ lo) planes on the device, uploaded in the order hi, lo, bias.  Np >= N zero-pads rows and bias
 // (out->N = Np); without want_lo, out->w_lo is null.  The rounding happens ONCE, here: no per-call conversion of the weights.

@@ -14,10 +14,10 @@
 //                              and the mask are indexed by the window position j.  A key whose mask is -inf is staged as ZERO rows and
 //                              scored -inf: it contributes exactly zero whatever its rows hold.  A query without a visible key gets zeros
 //                              (never a division by a zero sum).  One owner per output element, fixed order: bit-reproducible.
-//   sf_oad_row_kernel          y = [ReLU] [LN] (x [+ r[row % r_mod]]) [+ pe[row % pe_mod]] -> fp32 and bf16 hi / lo planes (the next GEMM's
-//                              operand).  One wave per row, two-pass statistics.  Serves the post-LN residual rows LN(x + sublayer(x)), the
-//                              feature head ReLU(LN(x)) (+ pe) and the identity feature head (x + pe).  In-place use (y == r) is safe: a row
-//                              belongs to one wave and each element is read by the lane that writes it.
+//   (sf_rowwise.hip)           the row pass sf_row_kernel, through oad_launch_row: [ReLU] [LN] (x [+ r[row % r_mod]]) [+ pe[row % pe_mod]] ->
+//                              fp32 and bf16 hi / lo planes (the next GEMM's operand).  Serves the post-LN residual rows
+//                              LN(x + sublayer(x)), in place (y == r), the feature head ReLU(LN(x)) (+ pe) and the identity feature
+//                              head (x + pe).
 //   sf_oad_rows_kernel         row gather / scatter by a table passed by value (fp32 -> fp32 and / or planes): the new K | V rows into the
 //                              rings, stage 0's result into the state, the cached compressed memory of a call's streams into one matrix,
 //                              query embeddings replicated per stream.
@@ -166,70 +166,7 @@ __global__ __launch_bounds__(64) void sf_oad_attention_kernel(SfOadAttn p) {
     if (d < HD) {                                   // HD % 4 == 0: the four dims of a lane are all inside or all outside
       const of4_t o = o_acc[t] * inv;
       if (p.ctx_f32) *reinterpret_cast<of4_t*>(p.ctx_f32 + ob + d) = o;
-      if (p.ctx_hi) {
-        unsigned int hb[4], lb[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) split_bf(o[r], hb[r], lb[r]);
-        *reinterpret_cast<u32x2_t*>(p.ctx_hi + ob + d) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-        if (p.ctx_lo) *reinterpret_cast<u32x2_t*>(p.ctx_lo + ob + d) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
-      }
-    }
-  }
-}
-
-struct SfOadRow {
-  const float* x;                                  // [rows, D]
-  const float* r; int r_mod;                       // + r[row % r_mod] (r_mod 0: r[row]); null: none
-  const float* gamma; const float* beta; float eps;      // LayerNorm; gamma null: none
-  int relu;
-  const float* pe; int pe_mod;                     // + pe[row % pe_mod] after the activation; null: none
-  float* y; bf16_t* y_hi; bf16_t* y_lo;            // any of them null
-  int rows, D;
-};
-
-__global__ __launch_bounds__(256) void sf_oad_row_kernel(SfOadRow p) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= p.rows) return;
-  const int nv = p.D >> 2;
-  const of4_t* x = reinterpret_cast<const of4_t*>(p.x + (size_t)row * p.D);
-  const of4_t* r = p.r ? reinterpret_cast<const of4_t*>(p.r + (size_t)(p.r_mod ? row % p.r_mod : row) * p.D) : nullptr;
-  float mean = 0.f, rstd = 1.f;
-  if (p.gamma) {
-    float s = 0.f;
-    for (int c = lane; c < nv; c += 64) {
-      of4_t v = x[c];
-      if (r) v += r[c];
-      s += (v[0] + v[1]) + (v[2] + v[3]);
-    }
-    mean = wave_sum(s) / (float)p.D;
-    float q = 0.f;
-    for (int c = lane; c < nv; c += 64) {
-      of4_t v = x[c];
-      if (r) v += r[c];
-      v -= mean;
-      q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-    }
-    rstd = 1.0f / sqrtf(wave_sum(q) / (float)p.D + p.eps);
-  }
-  const of4_t* pe = p.pe ? reinterpret_cast<const of4_t*>(p.pe + (size_t)(row % p.pe_mod) * p.D) : nullptr;
-  for (int c = lane; c < nv; c += 64) {
-    of4_t v = x[c];
-    if (r) v += r[c];
-    if (p.gamma) {
-      const of4_t gm = reinterpret_cast<const of4_t*>(p.gamma)[c], bt = reinterpret_cast<const of4_t*>(p.beta)[c];
-      v = (v - mean) * rstd * gm + bt;
-    }
-    if (p.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-    if (pe) v += pe[c];
-    const size_t o = (size_t)row * p.D + (size_t)c * 4;
-    if (p.y) *reinterpret_cast<of4_t*>(p.y + o) = v;
-    if (p.y_hi) {
-      unsigned int hb[4], lb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) split_bf(v[j], hb[j], lb[j]);
-      *reinterpret_cast<u32x2_t*>(p.y_hi + o) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-      if (p.y_lo) *reinterpret_cast<u32x2_t*>(p.y_lo + o) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
+      if (p.ctx_hi) store_planes4(o, p.ctx_hi, p.ctx_lo, ob + d);
     }
   }
 }
@@ -245,13 +182,7 @@ __global__ __launch_bounds__(256) void sf_oad_rows_kernel(const float* __restric
   for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     const of4_t v = reinterpret_cast<const of4_t*>(src)[s0 + i];
     if (dst) reinterpret_cast<of4_t*>(dst)[d0 + i] = v;
-    if (hi) {
-      unsigned int hb[4], lb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) split_bf(v[j], hb[j], lb[j]);
-      reinterpret_cast<u32x2_t*>(hi)[d0 + i] = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-      if (lo) reinterpret_cast<u32x2_t*>(lo)[d0 + i] = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
-    }
+    if (hi) store_planes4(v, hi, lo, (d0 + i) * 4);
   }
 }
 
@@ -301,10 +232,10 @@ static hipError_t oad_launch_attention(const SfOadAttn& p, hipStream_t s) {
   }
 }
 
-static hipError_t oad_launch_row(const SfOadRow& p, hipStream_t s) {
+static hipError_t oad_launch_row(const SfRowArgs& p, hipStream_t s) {
   if (p.rows <= 0) return hipSuccess;
   if (p.D < 4 || p.D % 4 || p.D > OAD_MAX_D || !p.x || (p.pe && p.pe_mod < 1) || (!p.gamma) != (!p.beta)) return hipErrorInvalidValue;
-  return sf_launch(sf_oad_row_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(256), 0, s, p);
+  return sf_launch_row(p, s);
 }
 
 static hipError_t oad_launch_rows(const float* src, float* dst, bf16_t* hi, bf16_t* lo, int D, const SfOadRows& t, hipStream_t s) {
@@ -345,14 +276,9 @@ struct OadWorkspace {
 };
 }  // namespace
 
-struct sf_oad {
+struct sf_oad : SfModelHandle {
   sf_oad_config cfg;
-  int device = 0;
   int d = 0, hd = 0, Cp = 0, Q0 = 0, maxT = 0;      // Cp: classes padded to 16 columns; maxT: longest sequence of any stage
-  SfWeightStore weights;
-  bool finalized = false;
-  int compute = SF_COMPUTE_BF16;
-  SfDeviceAllocs dev;
   SfDevLinear fh_long, fh_work, cls;
   SfDevLN fh_long_ln, fh_work_ln;
   std::vector<OadModule> enc;
@@ -441,42 +367,22 @@ extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out)
   return SF_OK;
 }
 
-static void oad_free_device(sf_oad* h) {
-  h->dev.free_all();
-  h->enc.clear();
-  h->dec = OadModule();
-}
-
-extern "C" void sf_oad_destroy(sf_oad* h) {
-  if (!h) return;
-  oad_free_device(h);
-  delete h;
-}
+extern "C" void sf_oad_destroy(sf_oad* h) { delete h; }
 
 extern "C" int sf_oad_load_tensor(sf_oad* h, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  if (!h || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_oad_load_tensor: null argument");
+  const char* who = "sf_oad_load_tensor";
+  SF_TRY(sf_model_load_args(h, who, key, host_ptr, shape, ndim));
+  if (strcmp(key, "pos_encoding.pe")) return sf_model_load_tensor(h, who, key, host_ptr, dtype, shape, ndim);
+  // the reference's buffer [max_len, 1, d]: the first L + W rows are kept
+  const int64_t rows = h->weights.expected.at(key)[0];
+  const bool ok = (ndim == 2 || (ndim == 3 && shape[1] == 1)) && shape[ndim - 1] == h->d && shape[0] >= rows;
+  if (!ok) return sf_set_err(SF_ERR_INVALID, "'%s': [rows >= %lld, d_model] or [rows, 1, d_model] expected", key, (long long)rows);
   std::string err;
-  int rc;
-  if (!strcmp(key, "pos_encoding.pe")) {      // the reference's buffer [max_len, 1, d]: the first L + W rows are kept
-    const int64_t rows = h->weights.expected.at(key)[0];
-    const bool ok = (ndim == 2 || (ndim == 3 && shape[1] == 1)) && shape[ndim - 1] == h->d && shape[0] >= rows;
-    if (!ok) return sf_set_err(SF_ERR_INVALID, "'%s': [rows >= %lld, d_model] or [rows, 1, d_model] expected", key, (long long)rows);
-    rc = h->weights.stage(key, host_ptr, dtype, (size_t)rows * h->d, shape, ndim, &err);
-  } else {
-    rc = h->weights.load(key, host_ptr, dtype, shape, ndim, &err);
-  }
-  if (rc) return sf_set_err(rc, "%s", err.c_str());
-  h->finalized = false;
-  return SF_OK;
+  const int rc = h->weights.stage(key, host_ptr, dtype, (size_t)rows * h->d, shape, ndim, &err);
+  return sf_model_staged(h, rc, err);
 }
 
-extern "C" int sf_oad_missing_weights(sf_oad* h) {
-  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  std::string err;
-  const int missing = h->weights.missing(&err);
-  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
-  return missing;
-}
+extern "C" int sf_oad_missing_weights(sf_oad* h) { return sf_model_missing_weights(h); }
 
 static SfDevLinear oad_rows_of(const SfDevLinear& l, int row0, int rows, bool with_bias) {
   SfDevLinear v = l;
@@ -528,7 +434,7 @@ static OadWorkspace oad_carve(const sf_oad* h, void* base, int n) {
   w.ctx_hi = c.take<bf16_t>(R * d); w.ctx_lo = c.take<bf16_t>(R * d);
   w.mid_hi = c.take<bf16_t>(R * F); w.mid_lo = c.take<bf16_t>(R * F);
   w.scores = c.take<float>((size_t)n * h->cfg.work_samples * h->Cp);
-  w.bytes = (c.off + 255) & ~(size_t)255;
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -550,7 +456,7 @@ struct OadRun {
   }
   // y = LN(x + r[row % r_mod]) -> fp32 + planes (y.f may be r)
   int add_ln(const float* x, const float* r, int r_mod, const SfDevLN& ln, const OadAct& y, int rows) {
-    SfOadRow p;
+    SfRowArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.r = r; p.r_mod = r_mod; p.gamma = ln.g; p.beta = ln.b; p.eps = h->cfg.eps;
     p.y = y.f; p.y_hi = y.hi; p.y_lo = acc ? y.lo : nullptr; p.rows = rows; p.D = h->d;
@@ -608,12 +514,7 @@ struct OadRun {
 
 // Makes the handle's device current and leaves it so, as the other handles' finalize do.
 extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
-  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  SF_TRY(sf_check_compute_mode(compute));
-  if (sf_oad_missing_weights(h)) return SF_ERR_STATE;
-  HIP_TRY(hipSetDevice(h->device));
-  oad_free_device(h);
-  h->compute = compute;
+  SF_TRY(sf_model_begin_finalize(h, compute));
   const sf_oad_config& c = h->cfg;
   const int d = h->d, L = c.long_samples, Q0 = h->Q0;
   auto H = [&](const std::string& k) -> std::vector<float>& { return h->weights.data(k); };
@@ -677,7 +578,7 @@ extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
 
 extern "C" int sf_oad_workspace_bytes(sf_oad* h, int streams, size_t* out) {
   if (!h || !out) return sf_set_err(SF_ERR_INVALID, "null argument");
-  if (!h->finalized) return sf_set_err(SF_ERR_STATE, "sf_oad_finalize has not run (the workspace depends on the compute mode)");
+  SF_TRY(sf_model_check_finalized(h, "sf_oad", true));
   if (streams < 1 || streams > OAD_MAX_S) return sf_set_err(SF_ERR_INVALID, "sf_oad: %d streams per call outside 1..%d", streams, OAD_MAX_S);
   *out = oad_carve(h, nullptr, streams).bytes;
   return SF_OK;
@@ -750,7 +651,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
                            const int32_t* long_rows, const float* mask_dev, float* out_dev, int probs, void* workspace, size_t workspace_bytes,
                            sf_stream stream) {
   if (!h || !st || st->det != h) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: null handle, or a state of another detector");
-  if (!h->finalized) return sf_set_err(SF_ERR_STATE, "sf_oad_finalize has not run (or weights were loaded after it)");
+  SF_TRY(sf_model_check_finalized(h, "sf_oad"));
   if (n < 1 || n > OAD_MAX_S) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: %d streams per call outside 1..%d", n, OAD_MAX_S);
   if (!ids || !long_rows || !work_dev || !out_dev || !workspace) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: null buffer");
   const sf_oad_config& c = h->cfg;
@@ -768,20 +669,22 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
   }
   if (Rl && !long_dev) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: long samples announced but long_dev is null");
   if (((uintptr_t)work_dev | (uintptr_t)long_dev | (uintptr_t)mask_dev | (uintptr_t)out_dev) & 15) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: buffers must be 16-byte aligned");
-  if ((uintptr_t)workspace & 255) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: workspace must be 256-byte aligned");
   OadRun r{h, oad_carve(h, workspace, n), (hipStream_t)stream, h->compute == SF_COMPUTE_BF16X3};
-  if (workspace_bytes < r.ws.bytes) return sf_set_err(SF_ERR_WORKSPACE, "sf_oad_step: workspace %zu < %zu bytes (sf_oad_workspace_bytes)", workspace_bytes, r.ws.bytes);
+  SF_TRY(sf_check_workspace("sf_oad_step", "sf_oad_workspace_bytes", workspace, workspace_bytes, r.ws.bytes));
   const OadWorkspace& ws = r.ws;
   hipStream_t s = r.s;
   int rc;
   OadAct x = ws.a[0], mem = ws.a[1], spare = ws.a[2];
   auto row_head = [&](const float* in, const SfDevLN* ln, const float* pe, int pe_mod, const OadAct& y, bool want_f32, int rows) {
-    SfOadRow p;
+    SfRowArgs p;
     memset(&p, 0, sizeof(p));
     p.x = in; p.eps = c.eps; p.rows = rows; p.D = d;
     if (ln) { p.gamma = ln->g; p.beta = ln->b; p.relu = 1; }
     p.pe = pe; p.pe_mod = pe_mod;
-    p.y = want_f32 ? y.f : nullptr; p.y_hi = y.hi; p.y_lo = r.acc ? y.lo : nullptr;
+    float* f32 = want_f32 ? y.f : nullptr;
+    bf16_t* lo = r.acc ? y.lo : nullptr;
+    if (pe) { p.q = f32; p.q_hi = y.hi; p.q_lo = lo; }      // the one output is the row with its position added
+    else { p.y = f32; p.y_hi = y.hi; p.y_lo = lo; }
     return oad_launch_row(p, s);
   };
   // ---- work memory: feature head + pe[L : L + W] ----

@@ -9,12 +9,10 @@
 // Layouts.  "rows": [F, H W, C] fp32, channels contiguous (what a GEMM writes).  "planes": the same as bf16 hi (+ lo in the accurate mode)
 // [rows, C], the A operand of a GEMM.  NCHW only at the two ends.
 //
-//   sf_pixdec_nchw_planes_kernel   NCHW fp32 -> planes.  A 64-pixel x 64-channel tile is read with lanes along pixels (256 B per channel
-//                                  row), passes through LDS with rows padded to 65 floats (a column read then touches 64 banks), and
+//   sf_pixdec_nchw_planes_kernel   NCHW fp32 -> planes.  sf_nchw_tile.h's 64-pixel x 64-channel tile is read on its NCHW side and
 //                                  leaves with 8 lanes x 16 bytes along the channels of a pixel.
-//   sf_pixdec_rows_nchw_kernel     rows -> NCHW fp32, the same tile the other way round (as sf_adapter_fuse_kernel): 16 lanes of float4
-//                                  along channels in, 64 lanes along pixels out.  A frame stride lets it read one level's slice of the
-//                                  flattened [F, S, C] tensor.
+//   sf_pixdec_rows_nchw_kernel     rows -> NCHW fp32, the tile's two sides as they are.  A frame stride lets it read one level's slice
+//                                  of the flattened [F, S, C] tensor.
 //   sf_pixdec_gn_stats_kernel      GroupNorm statistics: one workgroup per (frame, group), TWO passes over the group's H W x C / G values,
 //                                  both SHIFTED by a sample of the group (sum of x - shift, then of the squared deviations from the
 //                                  mean), and the mean is kept as shift + delta, never added up: the error does not grow with
@@ -26,20 +24,19 @@
 //   sf_pixdec_pos_ref_kernel       PositionEmbeddingSine(C / 2, normalize=True) of an all-false mask + level_embed[l] -> pos [S, C], and
 //                                  the reference points ((x + 0.5) / W, (y + 0.5) / H) repeated over levels -> [F, S, L, 2].  The angle
 //                                  is formed in fp64 and rounded once (accurate sin / cos, never the fast intrinsics).
-//   sf_pixdec_postln_kernel        LayerNorm of a row (the residual was added by the GEMM epilogue in front): the fp32 row, its planes and
-//                                  the planes of y + pos[row % S] in one pass, so nothing stands between an encoder layer and the next
-//                                  one's two GEMMs.  One wave per row, two-pass statistics (the layout of sf_oad.hip's row kernel).
+//   (sf_rowwise.hip)               the row pass sf_row_kernel, through pxd_launch_postln: LayerNorm of a row (the residual was added by
+//                                  the GEMM epilogue in front): the fp32 row, its planes and the planes of y + pos[row % S] in one
+//                                  pass, so nothing stands between an encoder layer and the next one's two GEMMs.
 //   sf_pixdec_im2col_kernel        3 x 3 gather: the nine taps of each pixel side by side, [rows, 9 C] planes in (dy, dx, c) order, 16-byte
-//                                  vectors.  Boundary rule (sf_msda.hip's, sf_adapter.hip's): a tap is addressed only after its
+//                                  vectors.  Boundary rule (the one sf_msda.hip and sf_adapter.hip state): a tap is addressed only after its
 //                                  coordinates passed the range test against the frame's OWN grid; a tap outside is written as zero
 //                                  and never read, so it cannot land on the neighbouring row or the next frame.
 //
 // The 3 x 3 convolution is that gather followed by ONE GEMM with K = 9 C, in chunks of im2col_chunk_rows pixels so that the gathered
 // planes stay bounded (SfGemmArgs has no A row pitch; a chunk is a contiguous [rows, 9 C] operand).
 #include "sf_handle.h"
+#include "sf_nchw_tile.h"
 
-#define PXD_TILE 64
-#define PXD_LD (PXD_TILE + 1)
 #define PXD_THREADS 256
 #define PXD_MAX_LEVELS 4
 #define PXD_GROUPS 32
@@ -56,50 +53,27 @@ struct SfPxdMove {
   int C, HW;
 };
 
-__global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_nchw_planes_kernel(SfPxdMove p) {
-  __shared__ float tile[PXD_TILE * PXD_LD];                        // [pixel][channel], rows padded
-  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * PXD_TILE, p0 = (int)blockIdx.x * PXD_TILE;
-  const int lane = (int)threadIdx.x % 64;
-  if (p0 + lane < p.HW) {
-    for (int cc = (int)threadIdx.x / 64; cc < PXD_TILE; cc += PXD_THREADS / 64) {
-      if (c0 + cc >= p.C) break;
-      tile[lane * PXD_LD + cc] = p.in[((size_t)f * p.C + c0 + cc) * p.HW + p0 + lane];
-    }
-  }
+__global__ __launch_bounds__(SF_TILE_THREADS) void sf_pixdec_nchw_planes_kernel(SfPxdMove p) {
+  __shared__ float tile[SF_TILE_CELLS];
+  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * SF_TILE, p0 = (int)blockIdx.x * SF_TILE;
+  sf_tile_nchw(f, p0, c0, p.HW, p.C, [&](int cell, int, size_t o) { tile[cell] = p.in[o]; });
   __syncthreads();
   const int c8 = ((int)threadIdx.x % 8) * 8;
   if (c0 + c8 >= p.C) return;
-  for (int pp = (int)threadIdx.x / 8; pp < PXD_TILE; pp += PXD_THREADS / 8) {
+  for (int pp = (int)threadIdx.x / 8; pp < SF_TILE; pp += SF_TILE_THREADS / 8) {
     if (p0 + pp >= p.HW) break;
-    unsigned int hb[8], lb[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) split_bf(tile[pp * PXD_LD + c8 + j], hb[j], lb[j]);
-    const size_t o = ((size_t)f * p.HW + p0 + pp) * p.C + c0 + c8;
-    *reinterpret_cast<u32x4_t*>(p.out_hi + o) = (u32x4_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16), hb[4] | (hb[5] << 16), hb[6] | (hb[7] << 16)};
-    if (p.out_lo)
-      *reinterpret_cast<u32x4_t*>(p.out_lo + o) = (u32x4_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16), lb[4] | (lb[5] << 16), lb[6] | (lb[7] << 16)};
+    store_planes8(tile + pp * SF_TILE_LD + c8, p.out_hi, p.out_lo, ((size_t)f * p.HW + p0 + pp) * p.C + c0 + c8);
   }
 }
 
-__global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_rows_nchw_kernel(SfPxdMove p) {
-  __shared__ float tile[PXD_TILE * PXD_LD];
-  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * PXD_TILE, p0 = (int)blockIdx.x * PXD_TILE;
-  const int lane_c = ((int)threadIdx.x % 16) * 4, lane_p = (int)threadIdx.x / 16;
-  if (c0 + lane_c < p.C) {
-    for (int pp = lane_p; pp < PXD_TILE; pp += PXD_THREADS / 16) {
-      if (p0 + pp >= p.HW) break;
-      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(p.in + (size_t)f * p.frame_stride + (size_t)(p0 + pp) * p.C + c0 + lane_c);
-      float* row = tile + pp * PXD_LD + lane_c;
-      row[0] = v[0]; row[1] = v[1]; row[2] = v[2]; row[3] = v[3];
-    }
-  }
+__global__ __launch_bounds__(SF_TILE_THREADS) void sf_pixdec_rows_nchw_kernel(SfPxdMove p) {
+  __shared__ float tile[SF_TILE_CELLS];
+  const int f = (int)blockIdx.z, c0 = (int)blockIdx.y * SF_TILE, p0 = (int)blockIdx.x * SF_TILE;
+  sf_tile_gather_rows(tile, p0, c0, p.HW, p.C, [&](int pix, int c) {
+    return *reinterpret_cast<const f32x4_t*>(p.in + (size_t)f * p.frame_stride + (size_t)pix * p.C + c);
+  });
   __syncthreads();
-  const int lane = (int)threadIdx.x % 64;
-  if (p0 + lane >= p.HW) return;
-  for (int cc = (int)threadIdx.x / 64; cc < PXD_TILE; cc += PXD_THREADS / 64) {
-    if (c0 + cc >= p.C) break;
-    p.out[((size_t)f * p.C + c0 + cc) * p.HW + p0 + lane] = tile[lane * PXD_LD + cc];
-  }
+  sf_tile_nchw(f, p0, c0, p.HW, p.C, [&](int cell, int, size_t o) { p.out[o] = tile[cell]; });
 }
 
 static int pxd_move_check(const char* who, int F, int C, int HW, int cmul) {
@@ -107,7 +81,8 @@ static int pxd_move_check(const char* who, int F, int C, int HW, int cmul) {
   if (C < cmul || C % cmul) return sf_set_err(SF_ERR_INVALID, "%s: C = %d must be a positive multiple of %d", who, C, cmul);
   if (HW < 1) return sf_set_err(SF_ERR_INVALID, "%s: %d pixels per frame", who, HW);
   if ((long long)F * HW * C > 0x7fffffffLL) return sf_set_err(SF_ERR_CAPACITY, "%s: %d frames of %d x %d exceed 2^31 - 1 elements", who, F, HW, C);
-  if ((C + PXD_TILE - 1) / PXD_TILE > 65535) return sf_set_err(SF_ERR_INVALID, "%s: C = %d exceeds one grid", who, C);
+  dim3 grid;
+  if (!sf_tile_grid(F, C, HW, &grid)) return sf_set_err(SF_ERR_INVALID, "%s: C = %d exceeds one grid", who, C);
   return SF_OK;
 }
 
@@ -115,16 +90,18 @@ static hipError_t pxd_launch_nchw_planes(const float* x, bf16_t* hi, bf16_t* lo,
   SfPxdMove p;
   memset(&p, 0, sizeof(p));
   p.in = x; p.out_hi = hi; p.out_lo = lo; p.C = C; p.HW = HW;
-  const dim3 grid((unsigned)((HW + PXD_TILE - 1) / PXD_TILE), (unsigned)((C + PXD_TILE - 1) / PXD_TILE), (unsigned)F);
-  return sf_launch(sf_pixdec_nchw_planes_kernel, grid, dim3(PXD_THREADS), 0, s, p);
+  dim3 grid;
+  if (!sf_tile_grid(F, C, HW, &grid)) return hipErrorInvalidValue;
+  return sf_launch(sf_pixdec_nchw_planes_kernel, grid, dim3(SF_TILE_THREADS), 0, s, p);
 }
 
 static hipError_t pxd_launch_rows_nchw(const float* rows, long long frame_stride, float* out, int F, int C, int HW, hipStream_t s) {
   SfPxdMove p;
   memset(&p, 0, sizeof(p));
   p.in = rows; p.out = out; p.frame_stride = frame_stride; p.C = C; p.HW = HW;
-  const dim3 grid((unsigned)((HW + PXD_TILE - 1) / PXD_TILE), (unsigned)((C + PXD_TILE - 1) / PXD_TILE), (unsigned)F);
-  return sf_launch(sf_pixdec_rows_nchw_kernel, grid, dim3(PXD_THREADS), 0, s, p);
+  dim3 grid;
+  if (!sf_tile_grid(F, C, HW, &grid)) return hipErrorInvalidValue;
+  return sf_launch(sf_pixdec_rows_nchw_kernel, grid, dim3(SF_TILE_THREADS), 0, s, p);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -173,30 +150,10 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_stats_kernel(SfPxdGn
   }
 }
 
-// one axis of F.interpolate(mode="bilinear", align_corners=False): source index pair and the weight of the second
-SF_DEVICE void pxd_axis(int dst, float ratio, int in, int* i0, int* i1, float* l1) {
-  float src = ratio * ((float)dst + 0.5f) - 0.5f;
-  src = src < 0.f ? 0.f : src;
-  int a = (int)src;
-  a = a > in - 1 ? in - 1 : a;
-  *i0 = a;
-  *i1 = a + 1 <= in - 1 ? a + 1 : in - 1;
-  const float l = src - (float)a;
-  *l1 = l > 1.f ? 1.f : l;
-}
-
 SF_DEVICE void pxd_load8(const float* q, float v[8]) {
   const f32x4_t a = *reinterpret_cast<const f32x4_t*>(q), b = *reinterpret_cast<const f32x4_t*>(q + 4);
 #pragma unroll
   for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-}
-
-SF_DEVICE void pxd_store_planes8(const float v[8], bf16_t* hi, bf16_t* lo, size_t o) {
-  unsigned int hb[8], lb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) split_bf(v[j], hb[j], lb[j]);
-  *reinterpret_cast<u32x4_t*>(hi + o) = (u32x4_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16), hb[4] | (hb[5] << 16), hb[6] | (hb[7] << 16)};
-  if (lo) *reinterpret_cast<u32x4_t*>(lo + o) = (u32x4_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16), lb[4] | (lb[5] << 16), lb[6] | (lb[7] << 16)};
 }
 
 __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn p) {
@@ -218,8 +175,8 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn
       const int y = pix / p.W, x = pix - y * p.W;
       int y0, y1, x0, x1;
       float ly, lx;
-      pxd_axis(y, p.ry, p.Hp, &y0, &y1, &ly);
-      pxd_axis(x, p.rx, p.Wp, &x0, &x1, &lx);
+      sf_bilinear_axis(y, p.ry, p.Hp, &y0, &y1, &ly);
+      sf_bilinear_axis(x, p.rx, p.Wp, &x0, &x1, &lx);
       const float* src = p.prev + (size_t)f * p.prev_frame_stride + c;
       float v00[8], v01[8], v10[8], v11[8];
       pxd_load8(src + (size_t)(y0 * p.Wp + x0) * p.C, v00); pxd_load8(src + (size_t)(y0 * p.Wp + x1) * p.C, v01);
@@ -233,13 +190,13 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn
       *reinterpret_cast<f32x4_t*>(p.y + o) = (f32x4_t){v[0], v[1], v[2], v[3]};
       *reinterpret_cast<f32x4_t*>(p.y + o + 4) = (f32x4_t){v[4], v[5], v[6], v[7]};
     }
-    if (p.y_hi) pxd_store_planes8(v, p.y_hi, p.y_lo, o);
+    if (p.y_hi) store_planes8(v, p.y_hi, p.y_lo, o);
     if (p.q_hi) {
       float e[8];
       pxd_load8(p.pos + (size_t)(p.out_row0 + pix) * p.C + c, e);
 #pragma unroll
       for (int j = 0; j < 8; ++j) e[j] += v[j];
-      pxd_store_planes8(e, p.q_hi, p.q_lo, o);
+      store_planes8(e, p.q_hi, p.q_lo, o);
     }
   }
 }
@@ -333,53 +290,16 @@ static hipError_t pxd_launch_pos_ref(const SfPxdPos& p, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // post-LN with planes
 // ------------------------------------------------------------------------------------------------
-struct SfPxdLn {
-  const float* x; const float* gamma; const float* beta; float eps;
-  const float* pos; int pos_mod;         // q = y + pos[row % pos_mod]
-  float* y; bf16_t* y_hi; bf16_t* y_lo; bf16_t* q_hi; bf16_t* q_lo;      // any of them null
-  int rows, C;
-};
-
-__global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_postln_kernel(SfPxdLn p) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= p.rows) return;
-  const int nv = p.C >> 2;
-  const f32x4_t* x = reinterpret_cast<const f32x4_t*>(p.x + (size_t)row * p.C);
-  float s = 0.f;
-  for (int c = lane; c < nv; c += 64) { const f32x4_t v = x[c]; s += (v[0] + v[1]) + (v[2] + v[3]); }
-  const float mean = wave_sum(s) / (float)p.C;
-  float q = 0.f;
-  for (int c = lane; c < nv; c += 64) {
-    const f32x4_t v = x[c] - mean;
-    q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)p.C + p.eps);
-  const f32x4_t* pe = p.q_hi ? reinterpret_cast<const f32x4_t*>(p.pos + (size_t)(row % p.pos_mod) * p.C) : nullptr;
-  for (int c = lane; c < nv; c += 64) {
-    const f32x4_t gm = reinterpret_cast<const f32x4_t*>(p.gamma)[c], bt = reinterpret_cast<const f32x4_t*>(p.beta)[c];
-    const f32x4_t v = (x[c] - mean) * rstd * gm + bt;
-    const size_t o = (size_t)row * p.C + (size_t)c * 4;
-    if (p.y) *reinterpret_cast<f32x4_t*>(p.y + o) = v;
-    unsigned int hb[4], lb[4];
-    if (p.y_hi) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) split_bf(v[j], hb[j], lb[j]);
-      *reinterpret_cast<u32x2_t*>(p.y_hi + o) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-      if (p.y_lo) *reinterpret_cast<u32x2_t*>(p.y_lo + o) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
-    }
-    if (pe) {
-      const f32x4_t e = v + pe[c];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) split_bf(e[j], hb[j], lb[j]);
-      *reinterpret_cast<u32x2_t*>(p.q_hi + o) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-      if (p.q_lo) *reinterpret_cast<u32x2_t*>(p.q_lo + o) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
-    }
-  }
-}
-
-static hipError_t pxd_launch_postln(const SfPxdLn& p, hipStream_t s) {
-  return sf_launch(sf_pixdec_postln_kernel, dim3((unsigned)((p.rows + 3) / 4)), dim3(PXD_THREADS), 0, s, p);
+// LayerNorm always; the q planes (y + pos[row % pos_mod]) only where q_hi is given.  Shapes and alignment: checked by the callers.
+static hipError_t pxd_launch_postln(const float* x, const SfDevLN& ln, float eps, const float* pos, int pos_mod, float* y, bf16_t* y_hi, bf16_t* y_lo,
+                                    bf16_t* q_hi, bf16_t* q_lo, int rows, int C, hipStream_t s) {
+  if (!x || !ln.g || !ln.b || rows < 1 || (q_hi && (!pos || pos_mod < 1))) return hipErrorInvalidValue;
+  SfRowArgs p;
+  memset(&p, 0, sizeof(p));
+  p.x = x; p.gamma = ln.g; p.beta = ln.b; p.eps = eps; p.rows = rows; p.D = C;
+  p.y = y; p.y_hi = y_hi; p.y_lo = y_lo;
+  if (q_hi) { p.pe = pos; p.pe_mod = pos_mod; p.q_hi = q_hi; p.q_lo = q_lo; }
+  return sf_launch_row(p, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -456,15 +376,10 @@ struct PxdEncLayer {
 };
 struct PxdFpn { SfDevLinear lateral, conv; SfDevLN lateral_norm, conv_norm; };
 
-struct sf_pixdec {
+struct sf_pixdec : SfModelHandle {
   sf_pixdec_config cfg;
-  int device = 0;
   int n_tr = 0, n_fpn = 0;
   int tr_level[PXD_MAX_LEVELS];              // input level of transformer level j, coarsest first
-  SfWeightStore weights;
-  bool finalized = false;
-  int compute = SF_COMPUTE_BF16;
-  SfDeviceAllocs dev;
   std::vector<SfDevLinear> proj;             // input_proj.{j}.0
   std::vector<SfDevLN> proj_norm;            // input_proj.{j}.1
   const float* level_embed = nullptr;
@@ -571,45 +486,18 @@ extern "C" int sf_pixdec_create(const sf_pixdec_config* cfg, int device, sf_pixd
   return SF_OK;
 }
 
-static void pxd_free_device(sf_pixdec* h) {
-  h->dev.free_all();
-  h->proj.clear(); h->proj_norm.clear(); h->layers.clear(); h->fpn.clear();
-  h->level_embed = nullptr;
-  h->mask = SfDevLinear();
-}
-
-extern "C" void sf_pixdec_destroy(sf_pixdec* h) {
-  if (!h) return;
-  pxd_free_device(h);
-  delete h;
-}
+extern "C" void sf_pixdec_destroy(sf_pixdec* h) { delete h; }
 
 extern "C" int sf_pixdec_load_tensor(sf_pixdec* h, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  if (!h || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_pixdec_load_tensor: null argument");
-  std::string err;
-  const int rc = h->weights.load(key, host_ptr, dtype, shape, ndim, &err);
-  if (rc) return sf_set_err(rc, "%s", err.c_str());
-  h->finalized = false;
-  return SF_OK;
+  return sf_model_load_tensor(h, "sf_pixdec_load_tensor", key, host_ptr, dtype, shape, ndim);
 }
 
-extern "C" int sf_pixdec_missing_weights(sf_pixdec* h) {
-  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  std::string err;
-  const int missing = h->weights.missing(&err);
-  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
-  return missing;
-}
+extern "C" int sf_pixdec_missing_weights(sf_pixdec* h) { return sf_model_missing_weights(h); }
 
 // Weights rounded (bf16 mode) or split into hi + lo planes (bf16x3) ONCE, here; the 1 x 1 convolutions are [O, I] as they are, the 3 x 3
 // ones are re-laid out [O, (dy, dx, c_in)] for the gathered operand.  Makes the handle's device current and leaves it so.
 extern "C" int sf_pixdec_finalize(sf_pixdec* h, int compute) {
-  if (!h) return sf_set_err(SF_ERR_INVALID, "null handle");
-  SF_TRY(sf_check_compute_mode(compute));
-  if (sf_pixdec_missing_weights(h)) return SF_ERR_STATE;
-  HIP_TRY(hipSetDevice(h->device));
-  pxd_free_device(h);
-  h->compute = compute;
+  SF_TRY(sf_model_begin_finalize(h, compute));
   const bool lo = compute == SF_COMPUTE_BF16X3;
   const sf_pixdec_config& c = h->cfg;
   const int C = c.conv_dim, Fd = c.dim_feedforward;
@@ -761,7 +649,7 @@ static PxdWorkspace pxd_carve(const sf_pixdec* h, const PxdPlan& pl, void* base)
     w.fo[1] = cv.take<float>(Mf * C);
   }
   w.mf = cv.take<float>((h->n_fpn ? Mf : Mt) * h->cfg.mask_dim);
-  w.bytes = (cv.off + 255) & ~(size_t)255;
+  w.bytes = cv.bytes();
   return w;
 }
 
@@ -769,7 +657,7 @@ extern "C" int sf_pixdec_workspace_bytes(sf_pixdec* h, int F, const int32_t* lev
   if (!out) return sf_set_err(SF_ERR_INVALID, "null argument");
   PxdPlan pl;
   SF_TRY(pxd_plan(h, F, level_shapes, num_levels, &pl));
-  if (!h->finalized) return sf_set_err(SF_ERR_STATE, "sf_pixdec_finalize has not run (the workspace depends on the compute mode)");
+  SF_TRY(sf_model_check_finalized(h, "sf_pixdec", true));
   *out = pxd_carve(h, pl, nullptr).bytes;
   return SF_OK;
 }
@@ -787,7 +675,7 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   const char* who = "sf_pixdec_forward";
   PxdPlan pl;
   SF_TRY(pxd_plan(h, F, level_shapes, num_levels, &pl));
-  if (!h->finalized) return sf_set_err(SF_ERR_STATE, "sf_pixdec_finalize has not run (or weights were loaded after it)");
+  SF_TRY(sf_model_check_finalized(h, "sf_pixdec"));
   if (!features_dev || !mask_features_dev || !multi_scale_dev || !workspace_dev) return sf_set_err(SF_ERR_INVALID, "%s: null buffer", who);
   if (num_multi_scale != pl.n_out) return sf_set_err(SF_ERR_INVALID, "%s: %d multi-scale outputs given, this decoder returns %d (sf_pixdec_num_outputs)", who, num_multi_scale, pl.n_out);
   const sf_pixdec_config& cfg = h->cfg;
@@ -802,9 +690,8 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
     bits |= (uintptr_t)multi_scale_dev[i];
   }
   if (bits & 15) return sf_set_err(SF_ERR_INVALID, "%s: features and outputs must be 16-byte aligned", who);
-  if ((uintptr_t)workspace_dev & 255) return sf_set_err(SF_ERR_INVALID, "%s: workspace must be 256-byte aligned", who);
   const PxdWorkspace ws = pxd_carve(h, pl, workspace_dev);
-  if (workspace_bytes < ws.bytes) return sf_set_err(SF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (sf_pixdec_workspace_bytes)", who, workspace_bytes, ws.bytes);
+  SF_TRY(sf_check_workspace(who, "sf_pixdec_workspace_bytes", workspace_dev, workspace_bytes, ws.bytes));
   hipStream_t s = (hipStream_t)stream;
   const bool split = h->compute == SF_COMPUTE_BF16X3;
   const int C = cfg.conv_dim, S = pl.S, L = h->n_tr, Mt = (int)pl.Mt;
@@ -849,20 +736,15 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
     g = sf_linear_args(ly.out, ws.c_hi, ws.c_lo, Mt, SF_EPI_RESID_F32, 0, split);
     g.resid = ws.src; g.out_f32 = ws.tmp;
     HIP_TRY(sf_launch_gemm(g, split, s));
-    SfPxdLn n;
-    memset(&n, 0, sizeof(n));
-    n.x = ws.tmp; n.gamma = ly.norm1.g; n.beta = ly.norm1.b; n.eps = PXD_LN_EPS; n.rows = Mt; n.C = C;
-    n.y = ws.src; n.y_hi = ws.a_hi; n.y_lo = split ? ws.a_lo : nullptr;
-    HIP_TRY(pxd_launch_postln(n, s));
+    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm1, PXD_LN_EPS, nullptr, 0, ws.src, ws.a_hi, split ? ws.a_lo : nullptr, nullptr, nullptr, Mt, C, s));
     g = sf_linear_args(ly.lin1, ws.a_hi, ws.a_lo, Mt, SF_EPI_ACT_BF16, 2, split);
     g.out_hi = ws.h_hi; g.out_lo = split ? ws.h_lo : nullptr;
     HIP_TRY(sf_launch_gemm(g, split, s));
     g = sf_linear_args(ly.lin2, ws.h_hi, ws.h_lo, Mt, SF_EPI_RESID_F32, 0, split);
     g.resid = ws.src; g.out_f32 = ws.tmp;
     HIP_TRY(sf_launch_gemm(g, split, s));
-    n.gamma = ly.norm2.g; n.beta = ly.norm2.b;
-    if (!last) { n.pos = ws.pos; n.pos_mod = S; n.q_hi = ws.q_hi; n.q_lo = split ? ws.q_lo : nullptr; }
-    HIP_TRY(pxd_launch_postln(n, s));
+    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm2, PXD_LN_EPS, ws.pos, S, ws.src, ws.a_hi, split ? ws.a_lo : nullptr, last ? nullptr : ws.q_hi,
+                              split ? ws.q_lo : nullptr, Mt, C, s));
   }
   // ---- the transformer's levels among the outputs ----
   for (int j = 0; j < L && j < pl.n_out; ++j) {
@@ -985,11 +867,9 @@ extern "C" int sf_op_pixdec_postln(const float* x_dev, const float* gamma_dev, c
   if (((uintptr_t)x_dev | (uintptr_t)gamma_dev | (uintptr_t)beta_dev | (uintptr_t)pos_dev | (uintptr_t)y_dev | (uintptr_t)y_hi_dev | (uintptr_t)y_lo_dev |
        (uintptr_t)q_hi_dev | (uintptr_t)q_lo_dev) & 15)
     return sf_set_err(SF_ERR_INVALID, "%s: every buffer must be 16-byte aligned", who);
-  SfPxdLn n;
-  memset(&n, 0, sizeof(n));
-  n.x = x_dev; n.gamma = gamma_dev; n.beta = beta_dev; n.eps = eps; n.pos = pos_dev; n.pos_mod = pos_rows > 0 ? pos_rows : 1; n.rows = rows; n.C = C;
-  n.y = y_dev; n.y_hi = y_hi_dev; n.y_lo = y_lo_dev; n.q_hi = q_hi_dev; n.q_lo = q_lo_dev;
-  HIP_TRY(pxd_launch_postln(n, (hipStream_t)stream));
+  SfDevLN ln;
+  ln.g = gamma_dev; ln.b = beta_dev;
+  HIP_TRY(pxd_launch_postln(x_dev, ln, eps, pos_dev, pos_rows, y_dev, y_hi_dev, y_lo_dev, q_hi_dev, q_lo_dev, rows, C, (hipStream_t)stream));
   return SF_OK;
 }
 
@@ -1031,10 +911,7 @@ extern "C" int sf_op_pixdec_conv3x3(const uint16_t* in_hi_dev, const uint16_t* i
   if (chunk_rows < 0) return sf_set_err(SF_ERR_INVALID, "%s: chunk_rows %d must be >= 0 (0: the library's default)", who, chunk_rows);
   if (((uintptr_t)in_hi_dev | (uintptr_t)in_lo_dev | (uintptr_t)w_hi_dev | (uintptr_t)w_lo_dev | (uintptr_t)out_dev) & 15)
     return sf_set_err(SF_ERR_INVALID, "%s: every buffer must be 16-byte aligned", who);
-  if ((uintptr_t)workspace_dev & 255) return sf_set_err(SF_ERR_INVALID, "%s: workspace must be 256-byte aligned", who);
-  if (workspace_bytes < sf_op_pixdec_conv3x3_workspace_bytes(F, H, W, C, chunk_rows))
-    return sf_set_err(SF_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes (sf_op_pixdec_conv3x3_workspace_bytes)", who, workspace_bytes,
-                      sf_op_pixdec_conv3x3_workspace_bytes(F, H, W, C, chunk_rows));
+  SF_TRY(sf_check_workspace(who, "sf_op_pixdec_conv3x3_workspace_bytes", workspace_dev, workspace_bytes, sf_op_pixdec_conv3x3_workspace_bytes(F, H, W, C, chunk_rows)));
   long long chunk = pxd_chunk_rows(chunk_rows, C);
   if (chunk > (long long)F * H * W) chunk = (long long)F * H * W;
   SfCarver cv(workspace_dev);

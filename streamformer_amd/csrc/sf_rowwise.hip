@@ -99,6 +99,69 @@ hipError_t sf_launch_layernorm(const float* x, const float* gamma, const float* 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The tail models' row pass (SfRowArgs): the detector's post-LN residual rows LN(x + sublayer(x)) and feature heads ReLU(LN(x)) + pe
+// or x + pe, the pixel decoder's LayerNorm that also emits the next layer's query operand y + pos.  Any width, so the row is re-read
+// from memory in each pass instead of living in registers.  Order: addend, statistics, normalise, ReLU, then the positional addend.
+// ADD (p.r), LN (p.gamma) and RELU are template flags: as run-time tests they cost the pixel decoder's post-LN 2.6 % (82.9 against
+// 80.8 us per launch at 131 712 rows of 256, MI355X); which outputs are written stays a run-time test, as in both kernels this replaced.
+// ------------------------------------------------------------------------------------------------
+template <bool ADD, bool LN, bool RELU>
+__global__ __launch_bounds__(256) void sf_row_kernel(SfRowArgs p) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= p.rows) return;
+  const int nv = p.D >> 2;
+  const f32x4_t* x = reinterpret_cast<const f32x4_t*>(p.x + (size_t)row * p.D);
+  const f32x4_t* r = ADD ? reinterpret_cast<const f32x4_t*>(p.r + (size_t)(p.r_mod ? row % p.r_mod : row) * p.D) : nullptr;
+  float mean = 0.f, rstd = 1.f;
+  if (LN) {
+    float s = 0.f;
+    for (int c = lane; c < nv; c += 64) {
+      f32x4_t v = x[c];
+      if (ADD) v += r[c];
+      s += (v[0] + v[1]) + (v[2] + v[3]);
+    }
+    mean = wave_sum(s) / (float)p.D;
+    float q = 0.f;
+    for (int c = lane; c < nv; c += 64) {
+      f32x4_t v = x[c];
+      if (ADD) v += r[c];
+      v -= mean;
+      q += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    }
+    rstd = 1.0f / sqrtf(wave_sum(q) / (float)p.D + p.eps);
+  }
+  const f32x4_t* pe = p.pe ? reinterpret_cast<const f32x4_t*>(p.pe + (size_t)(row % p.pe_mod) * p.D) : nullptr;
+  for (int c = lane; c < nv; c += 64) {
+    f32x4_t v = x[c];
+    if (ADD) v += r[c];
+    if (LN) {
+      const f32x4_t gm = reinterpret_cast<const f32x4_t*>(p.gamma)[c], bt = reinterpret_cast<const f32x4_t*>(p.beta)[c];
+      v = (v - mean) * rstd * gm + bt;
+    }
+    if (RELU) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+    const size_t o = (size_t)row * p.D + (size_t)c * 4;
+    if (p.y) *reinterpret_cast<f32x4_t*>(p.y + o) = v;
+    if (p.y_hi) store_planes4(v, p.y_hi, p.y_lo, o);
+    if (pe) {
+      const f32x4_t e = v + pe[c];
+      if (p.q) *reinterpret_cast<f32x4_t*>(p.q + o) = e;
+      if (p.q_hi) store_planes4(e, p.q_hi, p.q_lo, o);
+    }
+  }
+}
+
+template <bool ADD, bool LN>
+static hipError_t sf_launch_row_as(const SfRowArgs& p, hipStream_t s) {
+  const dim3 grid((unsigned)((p.rows + 3) / 4)), block(256);
+  return p.relu ? sf_launch(sf_row_kernel<ADD, LN, true>, grid, block, 0, s, p) : sf_launch(sf_row_kernel<ADD, LN, false>, grid, block, 0, s, p);
+}
+hipError_t sf_launch_row(const SfRowArgs& p, hipStream_t s) {
+  if (p.r) return p.gamma ? sf_launch_row_as<true, true>(p, s) : sf_launch_row_as<true, false>(p, s);
+  return p.gamma ? sf_launch_row_as<false, true>(p, s) : sf_launch_row_as<false, false>(p, s);
+}
+
+// ------------------------------------------------------------------------------------------------
 // patchify: pixels [F,C,H,W] -> A[F*N, C*P*P] (bf16 hi/lo), column = (c*P + ph)*P + pw,
 // patch n = prow*(W/P) + pcol.  One thread moves 8 consecutive pw pixels (16 B of bf16 out).
 // IN = 0 fp32, 1 bf16 (already normalised frames), 2 uint8 raw frames: the image processor's

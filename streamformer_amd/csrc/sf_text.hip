@@ -153,13 +153,7 @@ __global__ __launch_bounds__(256) void sf_text_attention_kernel(SfTextAttn p) {
       if (d < HD) {                                 // HD % 4 == 0: the four dims of a lane are all inside or all outside
         const tf4_t o = o_acc[t] * inv;
         if (p.ctx_f32) *reinterpret_cast<tf4_t*>(p.ctx_f32 + ob + d) = o;
-        if (p.ctx_hi) {
-          unsigned int hb[4], lb[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) split_bf(o[r], hb[r], lb[r]);
-          *reinterpret_cast<u32x2_t*>(p.ctx_hi + ob + d) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
-          if (p.ctx_lo) *reinterpret_cast<u32x2_t*>(p.ctx_lo + ob + d) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
-        }
+        if (p.ctx_hi) store_planes4(o, p.ctx_hi, p.ctx_lo, ob + d);
       }
     }
   }
@@ -291,14 +285,9 @@ static hipError_t text_launch_pool(const float* x, int B, int L, int D, const fl
 // ------------------------------------------------------------------------------------------------
 struct TextLayer { SfDevLN ln1, ln2; SfDevLinear qkv, out, fc1, fc2; };
 
-struct sf_text {
+struct sf_text : SfModelHandle {              // weights: q / k / v arrive separately and are packed at finalize
   sf_text_config cfg;
-  int device = 0;
   int D = 0, I = 0, hd = 0;                   // I: intermediate_size padded to a multiple of 64 (zero weights, act(0) = 0)
-  SfWeightStore weights;                      // q / k / v arrive separately and are packed at finalize
-  bool finalized = false;
-  int compute = SF_COMPUTE_BF16;
-  SfDeviceAllocs dev;
   const float* tok = nullptr; const float* pos = nullptr;
   std::vector<TextLayer> layers;
   SfDevLN final_ln;
@@ -321,7 +310,7 @@ static TextWorkspace text_carve(const sf_text* t, void* base, int B, int L) {
   w.xn_hi = c.take<bf16_t>(M * D); w.xn_lo = c.take<bf16_t>(M * D);
   w.ctx_hi = c.take<bf16_t>(M * D); w.ctx_lo = c.take<bf16_t>(M * D);
   w.mid_hi = c.take<bf16_t>(M * I); w.mid_lo = c.take<bf16_t>(M * I);
-  w.bytes = (c.off + 255) & ~(size_t)255;
+  w.bytes = c.bytes();
   return w;
 }
 
@@ -376,36 +365,16 @@ extern "C" int sf_text_create(const sf_text_config* cfg, int device, sf_text** o
   return SF_OK;
 }
 
-extern "C" void sf_text_destroy(sf_text* t) {
-  if (!t) return;
-  t->dev.free_all();
-  delete t;
-}
+extern "C" void sf_text_destroy(sf_text* t) { delete t; }
 
 extern "C" int sf_text_load_tensor(sf_text* t, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim) {
-  if (!t || !key || !host_ptr || ndim < 0 || (ndim && !shape)) return sf_set_err(SF_ERR_INVALID, "sf_text_load_tensor: null argument");
-  std::string err;
-  const int rc = t->weights.load(key, host_ptr, dtype, shape, ndim, &err);
-  if (rc) return sf_set_err(rc, "%s", err.c_str());
-  t->finalized = false;
-  return SF_OK;
+  return sf_model_load_tensor(t, "sf_text_load_tensor", key, host_ptr, dtype, shape, ndim);
 }
 
-extern "C" int sf_text_missing_weights(sf_text* t) {
-  if (!t) return sf_set_err(SF_ERR_INVALID, "null handle");
-  std::string err;
-  const int missing = t->weights.missing(&err);
-  if (missing) sf_set_err(SF_ERR_STATE, "%s", err.c_str());
-  return missing;
-}
+extern "C" int sf_text_missing_weights(sf_text* t) { return sf_model_missing_weights(t); }
 
 extern "C" int sf_text_finalize(sf_text* t, int compute) {
-  if (!t) return sf_set_err(SF_ERR_INVALID, "null handle");
-  SF_TRY(sf_check_compute_mode(compute));
-  if (sf_text_missing_weights(t)) return SF_ERR_STATE;
-  HIP_TRY(hipSetDevice(t->device));
-  t->dev.free_all();
-  t->compute = compute;
+  SF_TRY(sf_model_begin_finalize(t, compute));
   const int D = t->D, I = t->I, Ir = t->cfg.intermediate;
   const bool split = compute == SF_COMPUTE_BF16X3;
   SfDeviceAllocs& dev = t->dev;
@@ -452,7 +421,7 @@ extern "C" int sf_text_finalize(sf_text* t, int compute) {
 
 static int text_check_call(const sf_text* t, int B, int L) {
   if (!t) return sf_set_err(SF_ERR_INVALID, "null handle");
-  if (!t->finalized) return sf_set_err(SF_ERR_STATE, "sf_text_finalize has not run (or weights were loaded after it)");
+  SF_TRY(sf_model_check_finalized(t, "sf_text"));
   if (B <= 0 || L <= 0) return sf_set_err(SF_ERR_INVALID, "sf_text: bad shape B=%d L=%d", B, L);
   if (L > t->cfg.positions) return sf_set_err(SF_ERR_CAPACITY, "sf_text: sequence length %d > %d positions", L, t->cfg.positions);
   if ((size_t)B * L * 3 * t->D > (size_t)0x7fffffff || (size_t)B * L * t->I > (size_t)0x7fffffff)
@@ -475,9 +444,8 @@ static int text_forward(sf_text* t, const int32_t* ids, const uint8_t* mask, int
   if (rc) return rc;
   if (!ids || !pooled_out || !workspace) return sf_set_err(SF_ERR_INVALID, "sf_text_forward: null buffer");
   if (group < 0 || (group && B % group)) return sf_set_err(SF_ERR_INVALID, "sf_text: %d captions are not whole groups of %d", B, group);
-  if ((uintptr_t)workspace & 255) return sf_set_err(SF_ERR_INVALID, "sf_text_forward: workspace must be 256-byte aligned");
   const TextWorkspace ws = text_carve(t, workspace, B, L);
-  if (workspace_bytes < ws.bytes) return sf_set_err(SF_ERR_WORKSPACE, "sf_text_forward: workspace %zu < %zu bytes (sf_text_workspace_bytes)", workspace_bytes, ws.bytes);
+  SF_TRY(sf_check_workspace("sf_text_forward", "sf_text_workspace_bytes", workspace, workspace_bytes, ws.bytes));
   const sf_text_config& c = t->cfg;
   const int D = t->D, M = B * L;
   const bool acc = t->compute == SF_COMPUTE_BF16X3;

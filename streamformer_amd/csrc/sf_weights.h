@@ -166,4 +166,5 @@ struct SfCarver {
     off += n * sizeof(T);
     return p;
   }
+  size_t bytes() const { return (off + 255) & ~(size_t)255; }      // what a workspace holding every piece taken so far needs
 };

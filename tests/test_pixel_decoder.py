@@ -75,8 +75,8 @@ def rows_of(x):
 # ------------------------------------------------------------------------------------------------
 # 1. NCHW -> planes and rows -> NCHW
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("HW", [1, 6, 49, 240])
-@pytest.mark.parametrize("C_", [64, 192])
+@pytest.mark.parametrize("HW", [1, 6, 49, 65, 240])
+@pytest.mark.parametrize("C_", [8, 64, 72, 192])
 def test_layout_moves(C_, HW):
     nat, dev = _nat(), gpu_device()
     x = _draw(np.random.RandomState(2700 + C_ + HW), FRAMES, C_, HW)
@@ -213,8 +213,8 @@ def test_position_table_and_reference_points(C_):
 # ------------------------------------------------------------------------------------------------
 # 4. post-LN with planes
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,pos_rows", [(1, 1), (65, 13), (2 * 86, 86)])
-@pytest.mark.parametrize("C_", [64, 256])
+@pytest.mark.parametrize("rows,pos_rows", [(1, 1), (5, 1), (65, 13), (2 * 86, 86)])
+@pytest.mark.parametrize("C_", [4, 64, 256, 260])
 def test_postln_with_planes(C_, rows, pos_rows):
     nat, dev = _nat(), gpu_device()
     rs = np.random.RandomState(2760 + C_ + rows)
@@ -222,20 +222,23 @@ def test_postln_with_planes(C_, rows, pos_rows):
     gamma, beta, pos = 1.0 + 0.1 * _draw(rs, C_), 0.1 * _draw(rs, C_), _draw(rs, pos_rows, C_)
     xd, gd, bd, pd = x.to(dev), gamma.to(dev), beta.to(dev), pos.to(dev)
 
-    def run():
+    def run(lo=True, q=True):
         by, y = guarded(dev, rows, C_)
-        planes = [guarded_bits(dev, rows, C_) for _ in range(4)]
-        nat.check(nat.lib.sf_op_pixdec_postln(xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), PO.LN_EPS, pd.data_ptr(), pos_rows, y.data_ptr(),
-                                              *[v.data_ptr() for _, v in planes], rows, C_, _stream()))
+        planes = [guarded_bits(dev, rows, C_) if asked else None for asked in (True, lo, q, q and lo)]      # y_hi, y_lo, q_hi, q_lo
+        nat.check(nat.lib.sf_op_pixdec_postln(xd.data_ptr(), gd.data_ptr(), bd.data_ptr(), PO.LN_EPS, pd.data_ptr() if q else None, pos_rows if q else 0,
+                                              y.data_ptr(), *[p[1].data_ptr() if p else None for p in planes], rows, C_, _stream()))
         torch.cuda.synchronize()
-        return (read_guarded(by, y),) + tuple(read_guarded_bits(b, v) for b, v in planes)
+        return (read_guarded(by, y),) + tuple(read_guarded_bits(*p) if p else None for p in planes)
 
     y, y_hi, y_lo, q_hi, q_lo = run()
     check_against_floor(f"post-LN rows={rows} C={C_}", y, layernorm(x, gamma, beta, PO.LN_EPS), layernorm(x.double(), gamma.double(), beta.double(), PO.LN_EPS))
     assert torch.equal(y_hi, split_bits(y)[0]) and torch.equal(y_lo, split_bits(y)[1])
     q = y + pos.repeat(rows // pos_rows, 1)               # the pos row index wraps per frame
     assert torch.equal(q_hi, split_bits(q)[0]) and torch.equal(q_lo, split_bits(q)[1])
-    assert all(torch.equal(a, b) for a, b in zip(run(), (y, y_hi, y_lo, q_hi, q_lo))), "two runs differ"
+    full = (y, y_hi, y_lo, q_hi, q_lo)
+    assert all(torch.equal(a, b) for a, b in zip(run(), full)), "two runs differ"
+    for lo, q in ((False, True), (True, False), (False, False)):      # without the lo planes, without the positional addend: the rest stays
+        assert all(a is None or torch.equal(a, b) for a, b in zip(run(lo, q), full)), (lo, q)
 
 
 # ------------------------------------------------------------------------------------------------

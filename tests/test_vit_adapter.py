@@ -135,7 +135,11 @@ def _op_fuse(level, H, W, D, inp, with_vit):
     c1 = None
     if level == 0:
         t64 = t64 + s64 * inp["up_b"].double()
-        tok = _linear_gpu(inp["c2"].reshape(-1, D), inp["up_w"].permute(2, 3, 1, 0).reshape(4 * D, D))      # a real GEMM output [F * 2H * 2W, 4 D]
+        wl = inp["up_w"].permute(2, 3, 1, 0).reshape(4 * D, D)
+        if D % 32 == 0:
+            tok = _linear_gpu(inp["c2"].reshape(-1, D), wl)      # a real GEMM output [F * 2H * 2W, 4 D]
+        else:                                                    # a width the GEMM does not take: the same product at its operand precision
+            tok = operand_linear(inp["c2"].reshape(-1, D), wl, None, "x3").to(dev).contiguous()
         tok_ptr, stride = tok.data_ptr(), 4 * H * W * 4 * D
         c1 = inp["c1"].to(dev).contiguous()
     else:
@@ -150,8 +154,9 @@ def _op_fuse(level, H, W, D, inp, with_vit):
     return read_guarded(buf, out)
 
 
-@pytest.mark.parametrize("D", [64, 96])
-@pytest.mark.parametrize("H,W", GRIDS)
+# D 8 and 72: less than one tile of channels, and one tile and a part; (10, 26): 65 pixels at res5, one tile and one pixel
+@pytest.mark.parametrize("D", [8, 64, 72, 96])
+@pytest.mark.parametrize("H,W", GRIDS + [(10, 26)])
 @pytest.mark.parametrize("level", [0, 1, 2, 3])
 def test_fuse_vs_fp64(level, H, W, D):
     inp, want, floor = _fuse_case(level, H, W, D, 2700 + 1000 * level + 10 * H + W + D)
