@@ -701,6 +701,69 @@ int sf_op_pixdec_conv3x3(const uint16_t* in_hi_dev, const uint16_t* in_lo_dev, c
                          int H, int W, int C, int N, int chunk_rows, float* out_dev, void* workspace_dev, size_t workspace_bytes,
                          sf_stream stream);
 
+/* ---- Mask2Former masked-attention decoder: queries -> class logits, masks, re-identification embeddings ----------------------------
+ * The reference's MultiScaleMaskedTransformerDecoder (downstream/OVIS/mask2former/modeling/transformer_decoder/
+ * mask2former_transformer_decoder.py) and its CTVIS subclass CLMultiScaleMaskedTransformerDecoder (reid_layers >= 0: reid_embed,
+ * pred_queries, pred_bboxes): per layer masked cross-attention over one of three feature levels, self-attention, FFN (post-norm, ReLU),
+ * and after every layer the prediction heads, whose thresholded low-resolution mask is the next layer's attention mask.  The consumer of
+ * sf_pixdec_forward's four outputs as they are.  Same protocol as sf_pixdec: create (the width rules are checked there, the field
+ * named), stage the weights under the reference's state-dict names (a leading "sem_seg_head.predictor." is dropped), finalize in a
+ * compute mode.  Inference only, post-norm only, no padding masks.  Kernels: csrc/sf_maskdec.hip.                                   */
+typedef struct sf_maskdec sf_maskdec;
+#define SF_MASKDEC_LEVELS 3
+typedef struct {
+  int32_t in_channels, hidden_dim, num_queries, nheads, dim_feedforward, dec_layers, mask_dim, num_classes;   /* widths: multiples of 64 */
+  int32_t enforce_input_project;               /* input_proj is a 1 x 1 convolution iff this or in_channels != hidden_dim          */
+  int32_t pre_norm;                            /* must be 0                                                                         */
+  int32_t mask_classification;                 /* must be 1                                                                         */
+  int32_t reid_layers;                         /* -1: no reid_embed (the base class); 0: identity; n: an MLP of n layers            */
+  int32_t reid_hidden_dim;                     /* read when reid_layers > 1                                                         */
+} sf_maskdec_config;
+/* Device buffers of one forward, fp32 unless said otherwise; M = F * num_queries rows.  pred_logits [M, num_classes + 1] and pred_masks
+ * [M, H, W] are required; pred_queries [M, hidden_dim] (decoder_norm's rows), pred_embeds [M, hidden_dim] (reid_layers >= 0 only) and
+ * pred_bboxes [M, 4] ((min x, min y, max x + 1, max y + 1) / (W, H, W, H) over the pixels of pred_masks above zero, zeros without one)
+ * may be NULL.  aux_*: the same per entry of the reference's aux_outputs, [dec_layers, ...] each, or NULL (nothing of it is computed
+ * then).  attn_masks: uint32, every layer's packed attention mask one after the other, layer i [M, ceil(h w / 32)] words at the
+ * resolution of level i % 3, bit (j & 31) of word j / 32 set = key j hidden, or NULL.                                               */
+typedef struct {
+  float* pred_logits; float* pred_masks; float* pred_queries; float* pred_embeds; float* pred_bboxes;
+  float* aux_logits; float* aux_masks; float* aux_queries; float* aux_embeds;
+  uint32_t* attn_masks;
+} sf_maskdec_outputs;
+int sf_maskdec_create(const sf_maskdec_config* cfg, int device, sf_maskdec** out);
+void sf_maskdec_destroy(sf_maskdec* dec);
+/* host_ptr: contiguous host memory of dtype SF_F32, SF_F64 or SF_BF16 with exactly the reference's shape. */
+int sf_maskdec_load_tensor(sf_maskdec* dec, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int ndim);
+/* Makes the handle's device current and leaves it so. */
+int sf_maskdec_finalize(sf_maskdec* dec, int compute);
+int sf_maskdec_missing_weights(sf_maskdec* dec);            /* count; names via sf_last_error() */
+/* level_shapes: HOST array of three (h, w) pairs, the multi-scale features in the order they are passed; H, W: mask_features. */
+int sf_maskdec_workspace_bytes(sf_maskdec* dec, int F, const int32_t* level_shapes, int H, int W, size_t* out);
+/* x_dev: HOST array of three device pointers, level l fp32 [F, in_channels, h_l, w_l]; mask_features_dev fp32 [F, mask_dim, H, W]:
+ * what sf_pixdec_forward wrote, no layout change between the two.  No allocation, no host synchronisation, one workspace (256-byte
+ * aligned), the caller's stream; bit-reproducible.  Refused before anything is launched: not finalized (SF_ERR_STATE), F outside
+ * 1..65535, a NULL or not 16-byte aligned buffer (SF_ERR_INVALID), a short workspace (SF_ERR_WORKSPACE), activations above 2^31 - 1
+ * elements (SF_ERR_CAPACITY).                                                                                                       */
+int sf_maskdec_forward(sf_maskdec* dec, const float* const* x_dev, const float* mask_features_dev, int F, const int32_t* level_shapes, int H,
+                       int W, const sf_maskdec_outputs* outputs, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+/* The decoder's kernels alone (parity tests).  Masked attention, fp32: ctx[f, q, h, :] = softmax_j(q . (k_j + k_pos_j) / sqrt(head_dim)
+ * over the keys whose mask bit is clear) v_j.  q_dev rows [F Q] of q_pitch floats, k_dev / v_dev rows [F HW] of kv_pitch floats, a
+ * head's columns at h * head_dim; k_pos_dev [HW] rows of pos_pitch floats or NULL; mask_dev uint32 [F, Q, ceil(HW / 32)] shared by the
+ * heads, or NULL (nothing hidden).  A query without a visible key gets zeros.  A 16-key tile hidden from all 16 queries of a workgroup
+ * is skipped without being loaded unless no_skip is set; both ways give the same bits.  Outputs, any subset: ctx_dev fp32
+ * [F Q, heads * head_dim], the same as bf16 hi (+ lo) planes.  head_dim a multiple of 8 in 8..128, buffers 16-byte aligned.           */
+int sf_op_maskdec_attention(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const float* k_pos_dev,
+                            int pos_pitch, const uint32_t* mask_dev, float* ctx_dev, uint16_t* ctx_hi_dev, uint16_t* ctx_lo_dev, int F, int Q,
+                            int HW, int heads, int head_dim, int no_skip, sf_stream stream);
+/* Mask logits mask_embed_dev [F, Q, mask_dim] . mask_features_dev [F, mask_dim, H, W], fp32.  bits_dev (or NULL): the packed attention
+ * mask [F, Q, ceil(h w / 32)] at resolution h x w, bit set iff the logit of the features resampled to h x w by
+ * F.interpolate(bilinear, align_corners=False)'s rule is below zero, and a row with every bit set cleared; the resampled features go
+ * through workspace_dev (sf_op_maskdec_mask_workspace_bytes).  logits_dev (or NULL): the logits at H x W, [F, Q, H, W]; boxes_dev (or
+ * NULL, needs logits_dev): [F, Q, 4] as pred_bboxes above.  mask_dim a multiple of 4 up to 1024.                                     */
+size_t sf_op_maskdec_mask_workspace_bytes(int F, int mask_dim, int h, int w);
+int sf_op_maskdec_mask(const float* mask_embed_dev, const float* mask_features_dev, int F, int Q, int mask_dim, int H, int W, int h, int w,
+                       uint32_t* bits_dev, float* logits_dev, float* boxes_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

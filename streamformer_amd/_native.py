@@ -60,6 +60,20 @@ class SfPixdecConfig(C.Structure):
                                  "im2col_chunk_rows")]
 
 
+class SfMaskdecConfig(C.Structure):
+    """sf_maskdec_config: the Mask2Former transformer decoder's fields as plain ints (reid_layers -1 = the base class without
+    ``reid_embed``, 0 = identity, n = an MLP of n layers)."""
+    _fields_ = [(n, C.c_int32) for n in ("in_channels", "hidden_dim", "num_queries", "nheads", "dim_feedforward", "dec_layers", "mask_dim",
+                                         "num_classes", "enforce_input_project", "pre_norm", "mask_classification", "reid_layers",
+                                         "reid_hidden_dim")]
+
+
+class SfMaskdecOutputs(C.Structure):
+    """sf_maskdec_outputs: device addresses of one forward's outputs (0: not wanted)."""
+    _fields_ = [(n, C.c_void_p) for n in ("pred_logits", "pred_masks", "pred_queries", "pred_embeds", "pred_bboxes", "aux_logits", "aux_masks",
+                                          "aux_queries", "aux_embeds", "attn_masks")]
+
+
 SF_OAD_MAX_CALL_STREAMS = 64
 SF_STREAM_BLOB_KV1 = 0x31564B53
 
@@ -202,6 +216,16 @@ SIGNATURES = {
     "sf_op_pixdec_im2col": (_I, [_P, _P, _I, _I, _I, _I, C.c_longlong, _I, _P, _P, _P]),
     "sf_op_pixdec_conv3x3_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sf_op_pixdec_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "sf_maskdec_create": (_I, [C.POINTER(SfMaskdecConfig), _I, C.POINTER(_P)]),
+    "sf_maskdec_destroy": (None, [_P]),
+    "sf_maskdec_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
+    "sf_maskdec_finalize": (_I, [_P, _I]),
+    "sf_maskdec_missing_weights": (_I, [_P]),
+    "sf_maskdec_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_SZ)]),
+    "sf_maskdec_forward": (_I, [_P, C.POINTER(_P), _P, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(SfMaskdecOutputs), _P, _SZ, _P]),
+    "sf_op_maskdec_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "sf_op_maskdec_mask_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_maskdec_mask": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
