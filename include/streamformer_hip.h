@@ -233,6 +233,37 @@ int sf_op_linear(const float* x_dev, const float* w_dev, const float* b_dev, con
                  float alpha, int gelu, float* y_dev, int M, int N, int K, int compute,
                  void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 size_t sf_op_linear_workspace_bytes(int M, int N, int K);
+/* One forward GEMM, C[M,N] = A[M,K] W[N,K]^T + fused epilogue, with every field the forward sets (csrc/sf_common.h, SfGemmArgs, field
+ * for field and under the same names), on operand planes the CALLER rounded: bf16 bit patterns, hi = bf16(v), lo = bf16(v - hi).
+ *   split        0: bf16 mode (a_lo = w_lo = NULL); 1: the three-product accurate mode
+ *   epi          0 F32: out_f32 = acc + bias;  1 BF16 / 2 ACT_BF16: out_hi (+ out_lo) = [act](acc + bias), act 0 erf GELU, 1 tanh GELU,
+ *                2 ReLU;  3 RESID_F32: resid + alpha (acc + bias), resid fp32 (row m % resid_mod of a table when resid_mod > 0) to
+ *                out_f32, or planes resid_hi + resid_lo (+ resid_lo2) to out_hi + out_lo (+ out_lo2);  4 EMBED_F32: out_f32 = acc + bias
+ *                + pos[m % Np] + time_rows[(m / Np) % Tn]
+ *   ldc          row pitch, in elements, of every output AND of resid / resid_hi / resid_lo / resid_lo2 (>= N; pos, time_rows: N)
+ *   grp_*        grp_rows > 0: row m is written at (m / grp_rows) * grp_stride + grp_off + m % grp_rows
+ *   ln_stats_out producer of a LayerNorm fold: {sum x, sum x^2} pairs of the new residual rows, 4 floats per row, 8 when ln_stats_wide
+ *   ln_stats, ln_s, ln_eps   consumer: y = rstd (acc - mean ln_s[n]) + bias, w = W gamma, ln_s[n] = sum_k bf16(w)[n,k], bias = b + W beta;
+ *                ln_inkernel = 1: no ln_stats, the kernel sums the rows of A it reads
+ * family 0 dispatches as the forward does; 1 skinny, 2 tile, 3 panel, 4 256^2, 5 128^2 name a family, which runs only if its own
+ * support check accepts the call.  *family_taken (may be NULL): what ran; 6 = the 256-column kernel + a 128-column tail on the 128^2
+ * kernel.  A call no kernel takes, a null buffer its epilogue needs, or a field the chosen kernel does not read is SF_ERR_INVALID
+ * with nothing launched.                                                                                                        */
+typedef struct {
+  int32_t split;
+  const uint16_t* a_hi; const uint16_t* a_lo;      /* [M,K] */
+  const uint16_t* w_hi; const uint16_t* w_lo;      /* [N,K] */
+  const float* bias;                               /* [N] or NULL */
+  int32_t M, N, K, epi, act;
+  float alpha;
+  const float* resid; int32_t resid_mod;
+  const uint16_t* resid_hi; const uint16_t* resid_lo; const uint16_t* resid_lo2;
+  const float* pos; const float* time_rows; int32_t Np, Tn;
+  float* out_f32; uint16_t* out_hi; uint16_t* out_lo; uint16_t* out_lo2; int32_t ldc;
+  int32_t grp_rows, grp_stride, grp_off;
+  float* ln_stats_out; const float* ln_stats; const float* ln_s; float ln_eps; int32_t ln_stats_wide, ln_inkernel;
+} sf_gemm_desc;
+int sf_op_gemm(const sf_gemm_desc* d, int family, int* family_taken, sf_stream stream);
 /* softmax(q k^T / sqrt(d)) v per head over `groups` independent sequences
  * (modeling:688-717 spatial; :575-615 temporal with causal=1 and past offset).
  * qkv fp32 [groups, Lq|Lk, 3*D] packed as the qkv Linear emits it; ctx fp32 [groups, Lq, D].

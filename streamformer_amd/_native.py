@@ -85,6 +85,21 @@ class SfCacheStreamMeta(C.Structure):
         "elem_bytes")] + [("packing", C.c_uint64), ("blob_bytes", C.c_uint64)]
 
 
+class SfGemmDesc(C.Structure):
+    """sf_gemm_desc: one forward GEMM with every field the forward sets (device addresses; 0: absent)."""
+    _fields_ = [("split", C.c_int32)] + [(n, C.c_void_p) for n in ("a_hi", "a_lo", "w_hi", "w_lo", "bias")] + [
+        (n, C.c_int32) for n in ("M", "N", "K", "epi", "act")] + [("alpha", C.c_float), ("resid", C.c_void_p), ("resid_mod", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("resid_hi", "resid_lo", "resid_lo2", "pos", "time_rows")] + [("Np", C.c_int32), ("Tn", C.c_int32)] + [
+        (n, C.c_void_p) for n in ("out_f32", "out_hi", "out_lo", "out_lo2")] + [
+        (n, C.c_int32) for n in ("ldc", "grp_rows", "grp_stride", "grp_off")] + [
+        (n, C.c_void_p) for n in ("ln_stats_out", "ln_stats", "ln_s")] + [("ln_eps", C.c_float), ("ln_stats_wide", C.c_int32),
+                                                                          ("ln_inkernel", C.c_int32)]
+
+
+SF_GEMM_DISPATCH, SF_GEMM_SKINNY, SF_GEMM_TILE, SF_GEMM_PANEL, SF_GEMM_G256, SF_GEMM_G128, SF_GEMM_COLSPLIT = range(7)
+SF_EPI_F32, SF_EPI_BF16, SF_EPI_ACT_BF16, SF_EPI_RESID_F32, SF_EPI_EMBED_F32 = range(5)
+
+
 class NativeError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"streamformer_hip error {code}: {msg}")
@@ -127,6 +142,7 @@ SIGNATURES = {
     "sf_op_layernorm": (_I, [_P, _P, _P, _P, _I, _I, _F, _P]),
     "sf_op_linear": (_I, [_P, _P, _P, _P, _F, _I, _P, _I, _I, _I, _I, _P, _SZ, _P]),
     "sf_op_linear_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "sf_op_gemm": (_I, [C.POINTER(SfGemmDesc), _I, C.POINTER(_I), _P]),
     "sf_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "sf_op_attention_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_loss_workspace_bytes": (_SZ, [_I, _I]),

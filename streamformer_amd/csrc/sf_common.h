@@ -298,7 +298,17 @@ SF_DEVICE size_t sf_out_row(const SfGemmArgs& p, int m) {
 }
 // nanoseconds -> ticks of wall_clock64() on the current device (s_memrealtime: 100 MHz on MI355X; queried once)
 int sf_wall_clock_ticks(int ns);
-hipError_t sf_launch_gemm(const SfGemmArgs& a, bool split, hipStream_t s);      // dispatches skinny / panel / 256^2 / 128^2
+// the GEMM families of the forward; the values 1 .. 5 are the `family` argument of sf_op_gemm (include/streamformer_hip.h)
+enum SfGemmFamily {
+  SF_GEMM_FAM_NONE = 0,       // no kernel takes the call
+  SF_GEMM_FAM_SKINNY = 1, SF_GEMM_FAM_TILE = 2, SF_GEMM_FAM_PANEL = 3, SF_GEMM_FAM_G256 = 4, SF_GEMM_FAM_G128 = 5,
+  SF_GEMM_FAM_COLSPLIT = 6,   // N = 256 j + 128: the 256-column kernel on the first 256 j columns, the 128^2 kernel on the last 128
+  SF_GEMM_FAM_LAB_PIPE = 7, SF_GEMM_FAM_LAB_PP = 8,      // lab library only
+};
+SfGemmFamily sf_gemm_family(const SfGemmArgs& a, bool split);                    // sf_gemm.hip: what sf_launch_gemm will run (no launch)
+hipError_t sf_launch_gemm_family(SfGemmFamily fam, const SfGemmArgs& a, bool split, hipStream_t s);
+hipError_t sf_launch_gemm(const SfGemmArgs& a, bool split, hipStream_t s);      // = sf_launch_gemm_family(sf_gemm_family(a, split), ...)
+bool sf_gemm128_supported(const SfGemmArgs& a, bool split);                      // sf_gemm.hip
 hipError_t sf_launch_gemm128(const SfGemmArgs& a, bool split, hipStream_t s);   // sf_gemm.hip
 bool sf_gemm256_supported(const SfGemmArgs& a, bool split);                      // sf_gemm256.hip
 bool sf_gemm256_aux_supported(const SfGemmArgs& a);                              // aux_mode epilogues

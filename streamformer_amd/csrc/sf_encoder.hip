@@ -1787,6 +1787,102 @@ extern "C" int sf_op_linear(const float* x, const float* w, const float* b, cons
   return SF_OK;
 }
 
+// One forward GEMM with every field of SfGemmArgs the forward sets, on the operand planes as given: the parity tests' way to each
+// family and epilogue alone.  Everything the host can check is checked before anything is launched; a named family launches only what
+// its own sf_gemm_*_supported accepts.
+static const char* gemm_family_name(int f) {
+  static const char* const names[] = {"none", "skinny", "tile", "panel", "256^2", "128^2", "256-column + 128-column tail", "lab pipe", "lab pp"};
+  return f >= 0 && f <= 8 ? names[f] : "?";
+}
+extern "C" int sf_op_gemm(const sf_gemm_desc* d, int family, int* family_taken, sf_stream stream) {
+  if (family_taken) *family_taken = SF_GEMM_FAM_NONE;
+  if (!d) return set_err(SF_ERR_INVALID, "sf_op_gemm: null descriptor");
+  if (family < 0 || family > SF_GEMM_FAM_G128) return set_err(SF_ERR_INVALID, "sf_op_gemm: family %d is not one of 0 (dispatch) .. 5", family);
+  const bool split = d->split != 0;
+  if (d->M <= 0 || d->N <= 0 || d->K <= 0) return set_err(SF_ERR_INVALID, "sf_op_gemm: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
+  if (d->ldc < d->N) return set_err(SF_ERR_INVALID, "sf_op_gemm: ldc %d < N %d", d->ldc, d->N);
+  if (!d->a_hi || !d->w_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: a_hi and w_hi are required");
+  if (split && (!d->a_lo || !d->w_lo)) return set_err(SF_ERR_INVALID, "sf_op_gemm: split needs a_lo and w_lo");
+  if (!split && (d->a_lo || d->w_lo)) return set_err(SF_ERR_INVALID, "sf_op_gemm: a_lo / w_lo given without split");
+  if (d->act < 0 || d->act > 2) return set_err(SF_ERR_INVALID, "sf_op_gemm: act %d is not 0 (erf GELU), 1 (tanh GELU) or 2 (ReLU)", d->act);
+  if (d->resid_mod < 0) return set_err(SF_ERR_INVALID, "sf_op_gemm: resid_mod %d < 0", d->resid_mod);
+  if (d->resid_mod > 0 && !d->resid) return set_err(SF_ERR_INVALID, "sf_op_gemm: resid_mod needs the fp32 resid table");
+  if ((d->resid_hi != nullptr) != (d->resid_lo != nullptr)) return set_err(SF_ERR_INVALID, "sf_op_gemm: resid_hi and resid_lo come together");
+  if (d->resid_lo2 && !d->resid_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: resid_lo2 needs resid_hi and resid_lo");
+  if (d->resid && d->resid_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: resid and resid_hi / resid_lo are two forms of one operand: give one");
+  if (d->out_lo && !d->out_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: out_lo needs out_hi");
+  if (d->out_lo2 && !d->out_lo) return set_err(SF_ERR_INVALID, "sf_op_gemm: out_lo2 needs out_hi and out_lo");
+  if (!d->ln_inkernel && (d->ln_stats != nullptr) != (d->ln_s != nullptr))
+    return set_err(SF_ERR_INVALID, "sf_op_gemm: ln_stats and ln_s come together");
+  if (d->ln_inkernel && !d->ln_s) return set_err(SF_ERR_INVALID, "sf_op_gemm: ln_inkernel needs ln_s");
+  if (d->ln_inkernel && d->ln_stats) return set_err(SF_ERR_INVALID, "sf_op_gemm: ln_inkernel and ln_stats are two forms of one fold: give one");
+  if ((d->ln_stats || d->ln_inkernel) && d->ln_stats_out) return set_err(SF_ERR_INVALID, "sf_op_gemm: a fold consumer does not produce statistics");
+  if (d->grp_rows < 0 || (d->grp_rows > 0 && (d->grp_stride < d->grp_rows || d->grp_off < 0)))
+    return set_err(SF_ERR_INVALID, "sf_op_gemm: row remap grp_rows=%d grp_stride=%d grp_off=%d (stride >= rows > 0, off >= 0)", d->grp_rows, d->grp_stride, d->grp_off);
+  switch (d->epi) {
+    case SF_EPI_F32:
+      if (!d->out_f32) return set_err(SF_ERR_INVALID, "sf_op_gemm: SF_EPI_F32 needs out_f32");
+      break;
+    case SF_EPI_BF16: case SF_EPI_ACT_BF16:
+      if (!d->out_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: a bf16 epilogue needs out_hi");
+      break;
+    case SF_EPI_RESID_F32:
+      if (!d->resid && !d->resid_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: SF_EPI_RESID_F32 needs resid or resid_hi / resid_lo");
+      if (d->resid && !d->out_f32) return set_err(SF_ERR_INVALID, "sf_op_gemm: an fp32 residual needs out_f32");
+      if (d->resid_hi && (!d->out_hi || !d->out_lo)) return set_err(SF_ERR_INVALID, "sf_op_gemm: a plane-form residual needs out_hi and out_lo");
+      break;
+    case SF_EPI_EMBED_F32:
+      if (!d->out_f32 || !d->pos || !d->time_rows || d->Np <= 0 || d->Tn <= 0)
+        return set_err(SF_ERR_INVALID, "sf_op_gemm: SF_EPI_EMBED_F32 needs out_f32, pos, time_rows, Np > 0 and Tn > 0");
+      break;
+    default: return set_err(SF_ERR_INVALID, "sf_op_gemm: unknown epilogue %d", d->epi);
+  }
+  if (d->epi != SF_EPI_RESID_F32 && (d->resid || d->resid_hi)) return set_err(SF_ERR_INVALID, "sf_op_gemm: a residual is given to epilogue %d", d->epi);
+  if (d->ln_stats_out && !d->out_hi) return set_err(SF_ERR_INVALID, "sf_op_gemm: ln_stats_out comes with the bf16 plane out_hi the consumer reads");
+  SfGemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.a_hi = d->a_hi; g.a_lo = d->a_lo; g.w_hi = d->w_hi; g.w_lo = d->w_lo; g.bias = d->bias;
+  g.M = d->M; g.N = d->N; g.K = d->K; g.epi = d->epi; g.act = d->act; g.alpha = d->alpha;
+  g.resid = d->resid; g.resid_mod = d->resid_mod; g.resid_hi = d->resid_hi; g.resid_lo = d->resid_lo; g.resid_lo2 = d->resid_lo2;
+  g.pos = d->pos; g.time_rows = d->time_rows; g.Np = d->Np; g.Tn = d->Tn;
+  g.out_f32 = d->out_f32; g.out_hi = d->out_hi; g.out_lo = d->out_lo; g.out_lo2 = d->out_lo2; g.ldc = d->ldc;
+  g.grp_rows = d->grp_rows; g.grp_stride = d->grp_stride; g.grp_off = d->grp_off;
+  g.ln_stats_out = d->ln_stats_out; g.ln_stats = d->ln_stats; g.ln_s = d->ln_s; g.ln_eps = d->ln_eps;
+  g.ln_stats_wide = d->ln_stats_wide; g.ln_inkernel = d->ln_inkernel;
+  SfGemmFamily fam = SF_GEMM_FAM_NONE;
+  if (family == 0) {
+    fam = sf_gemm_family(g, split);
+    if (fam == SF_GEMM_FAM_NONE) return set_err(SF_ERR_INVALID, "sf_op_gemm: no GEMM family takes this call");
+  } else {
+    bool ok = false;
+    switch (family) {
+      case SF_GEMM_FAM_SKINNY: ok = sf_gemm_skinny_supported(g, split); break;
+      case SF_GEMM_FAM_TILE: ok = sf_gemm_tile_supported(g, split); break;
+      case SF_GEMM_FAM_PANEL: ok = sf_gemm_panel_supported(g, split); break;
+      case SF_GEMM_FAM_G256: ok = sf_gemm256_supported(g, split); break;
+      default: ok = sf_gemm128_supported(g, split); break;
+    }
+    if (!ok) return set_err(SF_ERR_INVALID, "sf_op_gemm: the %s family does not take this call (its sf_gemm_*_supported says no)", gemm_family_name(family));
+    fam = (SfGemmFamily)family;
+  }
+  // fields that only some kernels read: the others would ignore them (or read a null buffer in their place), so the call is refused
+  const bool p256 = fam == SF_GEMM_FAM_PANEL || fam == SF_GEMM_FAM_G256;
+  const char* stray = nullptr;
+  if (g.resid_mod > 0 && fam != SF_GEMM_FAM_PANEL) stray = "resid_mod (panel kernel only)";
+  else if (g.resid_hi && !p256) stray = "resid_hi / resid_lo (panel and 256^2 kernels only)";
+  else if ((g.resid_lo2 || g.out_lo2) && fam != SF_GEMM_FAM_G256) stray = "resid_lo2 / out_lo2 (256^2 kernel only)";
+  else if (g.ln_stats && fam != SF_GEMM_FAM_G256) stray = "ln_stats (256^2 kernel only)";
+  else if (g.ln_stats_out && !p256 && fam != SF_GEMM_FAM_TILE) stray = "ln_stats_out (tile, panel and 256^2 kernels only)";
+  else if (g.ln_inkernel && fam != SF_GEMM_FAM_SKINNY && fam != SF_GEMM_FAM_TILE) stray = "ln_inkernel (skinny and tile kernels only)";
+  else if (g.grp_rows > 0 && (fam == SF_GEMM_FAM_PANEL || fam == SF_GEMM_FAM_TILE) && g.epi != SF_EPI_BF16 && g.epi != SF_EPI_ACT_BF16) stray = "the row remap (not on this kernel's fp32 epilogues)";
+  else if ((fam == SF_GEMM_FAM_G128 || fam == SF_GEMM_FAM_COLSPLIT) && !sf_gemm128_supported(g, split)) stray = "a field the 128^2 kernel does not read";
+  else if (fam == SF_GEMM_FAM_SKINNY && g.epi == SF_EPI_RESID_F32 && !g.resid) stray = "a plane-form residual";
+  if (stray) return set_err(SF_ERR_INVALID, "sf_op_gemm: the %s family does not read %s", gemm_family_name(fam), stray);
+  HIP_TRY(sf_launch_gemm_family(fam, g, split, (hipStream_t)stream));
+  if (family_taken) *family_taken = (int)fam;
+  return SF_OK;
+}
+
 extern "C" size_t sf_op_attention_workspace_bytes(int groups, int L, int heads, int head_dim) {
   const size_t rows = (size_t)groups * L, D = (size_t)heads * head_dim;
   return rows * 3 * D * 2 * 2 + rows * D * 2 * 2 + 4096;     // qkv hi (+ lo) planes, ctx hi + lo

@@ -233,27 +233,45 @@ int sf_infold_max_rows() {
   return a > b ? a : b;
 }
 
-hipError_t sf_launch_gemm(const SfGemmArgs& a, bool split, hipStream_t s) {
-  if (a.aux_mode) return sf_gemm256_aux_supported(a) && !split ? sf_launch_gemm256(a, s) : hipErrorInvalidValue;
+// The forward's choice of a GEMM family for one call: pure (no launch), the checks in the order the launch has always made them.
+SfGemmFamily sf_gemm_family(const SfGemmArgs& a, bool split) {
+  if (a.aux_mode) return sf_gemm256_aux_supported(a) && !split ? SF_GEMM_FAM_G256 : SF_GEMM_FAM_NONE;
   if (a.ln_inkernel) {
-    if (sf_gemm_skinny_supported(a, split)) return sf_launch_gemm_skinny(a, split, s);
-    return sf_gemm_tile_supported(a, split) ? sf_launch_gemm_tile(a, s) : hipErrorInvalidValue;
+    if (sf_gemm_skinny_supported(a, split)) return SF_GEMM_FAM_SKINNY;
+    return sf_gemm_tile_supported(a, split) ? SF_GEMM_FAM_TILE : SF_GEMM_FAM_NONE;
   }
-  if (sf_gemm_skinny_supported(a, split) && !sf_sw(SW_DISABLE_SKINNY)) return sf_launch_gemm_skinny(a, split, s);
-  if (sf_gemm_tile_supported(a, split)) return sf_launch_gemm_tile(a, s);
+  if (sf_gemm_skinny_supported(a, split) && !sf_sw(SW_DISABLE_SKINNY)) return SF_GEMM_FAM_SKINNY;
+  if (sf_gemm_tile_supported(a, split)) return SF_GEMM_FAM_TILE;
 #ifdef SF_LAB      // round-4 epilogue-overlap experiments (profiles/r04_panel_overlap_lab.txt): lab library only, behind SF_PANEL_PIPE / SF_PANEL_PP
-  if (sf_gemm_pipe_supported(a, split)) return sf_launch_gemm_pipe(a, s);
-  if (sf_gemm_pp_supported(a, split)) return sf_launch_gemm_pp(a, s);
+  if (sf_gemm_pipe_supported(a, split)) return SF_GEMM_FAM_LAB_PIPE;
+  if (sf_gemm_pp_supported(a, split)) return SF_GEMM_FAM_LAB_PP;
 #endif
-  if (sf_gemm_panel_supported(a, split)) return sf_launch_gemm_panel(a, s);
-  if (sf_gemm256_supported(a, split)) return sf_launch_gemm256(a, s);
-  if (a.resid_hi) return hipErrorInvalidValue;      // plane-form residual: panel kernel only
+  if (sf_gemm_panel_supported(a, split)) return SF_GEMM_FAM_PANEL;
+  if (sf_gemm256_supported(a, split)) return SF_GEMM_FAM_G256;
+  if (a.resid_hi) return SF_GEMM_FAM_NONE;      // plane-form residual: panel kernel only
   // N = 256 j + 128 (SigLIP-so400m: 1152, 3456): the first 256 j columns on the 256-column kernel, the last 128 on the 128^2 kernel — two
   // launches on disjoint column ranges of the same rows (every epilogue here is column-local), instead of the whole problem on 128^2 tiles
   if (a.N % 256 == 128 && a.N > 256 && !a.ln_stats && !a.ln_stats_out && a.epi != SF_EPI_EMBED_F32 && !sf_sw(SW_DISABLE_GEMM_COLSPLIT)) {
     SfGemmArgs m = a;
     m.N = a.N - 128;
-    if (sf_gemm256_supported(m, split)) {
+    if (sf_gemm256_supported(m, split)) return SF_GEMM_FAM_COLSPLIT;
+  }
+  return SF_GEMM_FAM_G128;
+}
+
+hipError_t sf_launch_gemm_family(SfGemmFamily fam, const SfGemmArgs& a, bool split, hipStream_t s) {
+  switch (fam) {
+    case SF_GEMM_FAM_SKINNY: return sf_launch_gemm_skinny(a, split, s);
+    case SF_GEMM_FAM_TILE: return sf_launch_gemm_tile(a, s);
+#ifdef SF_LAB
+    case SF_GEMM_FAM_LAB_PIPE: return sf_launch_gemm_pipe(a, s);
+    case SF_GEMM_FAM_LAB_PP: return sf_launch_gemm_pp(a, s);
+#endif
+    case SF_GEMM_FAM_PANEL: return sf_launch_gemm_panel(a, s);
+    case SF_GEMM_FAM_G256: return sf_launch_gemm256(a, s);
+    case SF_GEMM_FAM_COLSPLIT: {
+      SfGemmArgs m = a;
+      m.N = a.N - 128;
       SfGemmArgs t = a;
       const size_t n0 = (size_t)m.N;
       t.N = 128;
@@ -268,8 +286,26 @@ hipError_t sf_launch_gemm(const SfGemmArgs& a, bool split, hipStream_t s) {
       if (e != hipSuccess) return e;
       return sf_launch_gemm128(t, split, s);
     }
+    case SF_GEMM_FAM_G128: return sf_launch_gemm128(a, split, s);
+    default: return hipErrorInvalidValue;
   }
-  return sf_launch_gemm128(a, split, s);
+}
+
+hipError_t sf_launch_gemm(const SfGemmArgs& a, bool split, hipStream_t s) { return sf_launch_gemm_family(sf_gemm_family(a, split), a, split, s); }
+
+// what the 128^2 kernel reads and writes: every epilogue with its own buffers, no LayerNorm fold, no plane-form or table residual
+bool sf_gemm128_supported(const SfGemmArgs& a, bool split) {
+  const int bk = split ? 32 : 64;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % bk) || (a.N % 4) || (a.ldc % 4)) return false;
+  if (split && (!a.a_lo || !a.w_lo)) return false;
+  if (a.aux_mode || a.ln_stats || a.ln_stats_out || a.ln_inkernel || a.resid_hi || a.resid_mod > 0 || a.out_lo2) return false;
+  switch (a.epi) {
+    case SF_EPI_F32: return a.out_f32 != nullptr;
+    case SF_EPI_RESID_F32: return a.out_f32 && a.resid;
+    case SF_EPI_EMBED_F32: return a.out_f32 && a.pos && a.time_rows && a.Np > 0 && a.Tn > 0;
+    case SF_EPI_BF16: case SF_EPI_ACT_BF16: return a.out_hi != nullptr;
+    default: return false;
+  }
 }
 
 hipError_t sf_launch_gemm128(const SfGemmArgs& a, bool split, hipStream_t s) {

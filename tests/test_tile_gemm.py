@@ -1,5 +1,6 @@
 """The tile GEMM family of one to a few clips per call (sf_gemm_tile.hip; 2560 < M <= SF_TILE_MAX_M): every candidate tile
-shape forced in turn (lab switch SF_TILE_SHAPE, read once per process -> each case runs in its own interpreter) on ragged
+shape forced in turn (switch SF_TILE_SHAPE; each case runs in its own interpreter, though since the switch table it could be
+flipped in process with the `switches` fixture, as tests/test_gemm_families.py does) on ragged
 row counts, every epilogue sf_op_linear reaches (plain fp32, residual read-modify-write, erf-GELU bf16), and the whole
 SigLIP-base forward of ONE clip (README.md:55-71: LayerNorm-folded consumers, embedding epilogue, KV-cache row remap of the
 temporal qkv) against the reference's outputs (fixture F2)."""
