@@ -795,6 +795,31 @@ size_t sf_op_maskdec_mask_workspace_bytes(int F, int mask_dim, int h, int w);
 int sf_op_maskdec_mask(const float* mask_embed_dev, const float* mask_features_dev, int F, int Q, int mask_dim, int H, int W, int h, int w,
                        uint32_t* bits_dev, float* logits_dev, float* boxes_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- video instance segmentation: the kernels between the mask decoder and a list of instances ---------------------------------
+ * (the CTVIS SimpleTracker's frame-local front and CTVISModel.inference_video; streamformer_amd/vis.py runs the association loop on
+ * the host).  All fp32, bit-reproducible, the caller's stream, no allocation, no host synchronisation.                              */
+/* Rows of logits_dev [rows, classes + 1]: softmax over the row without its last column.  max_scores_dev [rows] and labels_dev [rows]
+ * (the first index of the largest score); scores_dev (or NULL): all [rows, classes] scores.                                         */
+int sf_op_vis_scores(const float* logits_dev, long long rows, int classes_plus_one, float* max_scores_dev, int32_t* labels_dev,
+                     float* scores_dev, sf_stream stream);
+/* masks_dev [rows, pixels] -> bits_dev [rows, ceil(pixels / 32)], bit p & 31 of word p / 32 set iff x[p] > 0, tail bits zero, and
+ * area_dev [rows], the number of set bits.                                                                                          */
+int sf_op_vis_pack_masks(const float* masks_dev, long long rows, int pixels, uint32_t* bits_dev, int32_t* area_dev, sf_stream stream);
+/* bits_dev [F, Q, ceil(pixels / 32)] as sf_op_vis_pack_masks wrote it -> inter_dev [F, Q, Q], popcount(row i & row j) inside each
+ * frame.  The IoU (i + 1e-6) / (area_i + area_j - i + 1e-6) and the NMS scan are the host's.  pixels up to 524288.                  */
+int sf_op_vis_mask_iou(const uint32_t* bits_dev, int F, int Q, int pixels, int32_t* inter_dev, sf_stream stream);
+/* masks_dev [R, h, w], the detections' mask logits; index_dev int32 [K, F], a row of masks_dev or -1 (absent: zeros, adds nothing).
+ * Per (k, f): resample h x w to Hp x Wp, keep the top left Hc x Wc, resample that to H x W, both by F.interpolate(bilinear,
+ * align_corners=False)'s rule, composed in one pass; the second resample clamps at the crop's edge.  Outputs, any subset (NULL: not
+ * wanted, at least one of the first two): out_masks_dev [K, F, H, W] bytes, 1 where the logit is above zero; out_logits_dev fp32
+ * [K, F, H, W]; numerator_dev fp32 [K], the sum of sigmoid(logit) over the set pixels, with denominator_dev int64 [K], their number
+ * (both or neither; they need the workspace, 256-byte aligned).  Hp = Hc = H = h (and the same for w) gathers rows unchanged.
+ * K * F up to 65535; SF_ERR_CAPACITY when a 16 x 256 output tile reaches more than 63 KB of source pixels (a strong downscale).     */
+size_t sf_op_vis_postprocess_workspace_bytes(int K, int F, int H, int W);
+int sf_op_vis_postprocess(const float* masks_dev, int R, int h, int w, const int32_t* index_dev, int K, int F, int Hp, int Wp, int Hc, int Wc,
+                          int H, int W, uint8_t* out_masks_dev, float* out_logits_dev, float* numerator_dev, int64_t* denominator_dev,
+                          void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

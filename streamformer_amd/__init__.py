@@ -31,6 +31,7 @@ from .msda import MSDeformAttn, MSDeformAttnFunction, as_compiled_op, ms_deform_
 from .adapter import TimesformerMultiTaskingModelSigLIPViTAdapter  # noqa: F401
 from .pixel_decoder import MSDeformAttnPixelDecoder, ShapeSpec  # noqa: F401
 from .mask_decoder import CLMultiScaleMaskedTransformerDecoder, MultiScaleMaskedTransformerDecoder  # noqa: F401
+from .vis import SimpleTracker, VideoInstanceSegmenter, postprocess_video_masks  # noqa: F401
 from .processing import TimesformerImageProcessor  # noqa: F401
 
 __version__ = "0.1.0"

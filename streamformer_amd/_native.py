@@ -242,6 +242,11 @@ SIGNATURES = {
     "sf_op_maskdec_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_maskdec_mask_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_op_maskdec_mask": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
+    "sf_op_vis_scores": (_I, [_P, C.c_longlong, _I, _P, _P, _P, _P]),
+    "sf_op_vis_pack_masks": (_I, [_P, C.c_longlong, _I, _P, _P, _P]),
+    "sf_op_vis_mask_iou": (_I, [_P, _I, _I, _I, _P, _P]),
+    "sf_op_vis_postprocess_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_vis_postprocess": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
