@@ -820,6 +820,28 @@ int sf_op_vis_postprocess(const float* masks_dev, int R, int h, int w, const int
                           int H, int W, uint8_t* out_masks_dev, float* out_logits_dev, float* numerator_dev, int64_t* denominator_dev,
                           void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- image segmentation: the kernels between the mask decoder and MaskFormer's semantic and panoptic results ---------------------
+ * (semantic_inference and panoptic_inference of mask2former/maskformer_model.py; streamformer_amd/segmentation.py runs the segment rule
+ * on the host; instance inference is sf_op_vis_scores + sf_op_vis_postprocess with an index table [K, 1]).  All fp32, bit-reproducible,
+ * the caller's stream, no allocation, no host synchronisation.  The geometry arguments are sf_op_vis_postprocess's: masks_dev [Q, h, w]
+ * resampled to Hp x Wp, cropped to the top left Hc x Wc, resampled to H x W, composed per output pixel: r_q(y, x).                  */
+/* out_dev [C, H, W] = sum over q of probs_dev [Q, C] (what sf_op_vis_scores writes to scores_dev) times sigmoid(r_q), in query order on
+ * fp32 MFMA.  Q up to 512, C up to 256; SF_ERR_CAPACITY above, and when a 1 x 64 output tile reaches more source pixels per query than
+ * the LDS holds for a chunk of 32 queries (a strong downscale).                                                                      */
+int sf_op_seg_semantic(const float* masks_dev, const float* probs_dev, int Q, int C, int h, int w, int Hp, int Wp, int Hc, int Wc, int H, int W,
+                       float* out_dev, sf_stream stream);
+/* Query q is kept iff labels_dev[q] != num_classes and max_scores_dev[q] > object_mask_threshold (decided on the device).  code_dev
+ * int32 [H, W]: 2 q + (r_q >= 0) of the kept query with the largest max_scores[q] * sigmoid(r_q), the first index on ties, or -1 when no
+ * query is kept.  counts_dev int32 [Q, 3] (zeroed here): pixels won, pixels with r_q >= 0, pixels with both; zeros for a query that is
+ * not kept.  Q up to 512; SF_ERR_CAPACITY above, and when a 4 x 64 output tile reaches more source pixels than the LDS holds.        */
+int sf_op_seg_panoptic_argmax(const float* masks_dev, const float* max_scores_dev, const int32_t* labels_dev, int Q, int num_classes,
+                              float object_mask_threshold, int h, int w, int Hp, int Wp, int Hc, int Wc, int H, int W, int32_t* code_dev,
+                              int32_t* counts_dev, sf_stream stream);
+/* panoptic_dev int32 [pixels] = segment_of_query_dev[q] (int32 [Q], 0 = dropped) where code_dev holds 2 q + 1, else 0.  panoptic_dev may
+ * be code_dev.                                                                                                                        */
+int sf_op_seg_panoptic_relabel(const int32_t* code_dev, const int32_t* segment_of_query_dev, int Q, long long pixels, int32_t* panoptic_dev,
+                               sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

@@ -32,6 +32,14 @@ from .adapter import TimesformerMultiTaskingModelSigLIPViTAdapter  # noqa: F401
 from .pixel_decoder import MSDeformAttnPixelDecoder, ShapeSpec  # noqa: F401
 from .mask_decoder import CLMultiScaleMaskedTransformerDecoder, MultiScaleMaskedTransformerDecoder  # noqa: F401
 from .vis import SimpleTracker, VideoInstanceSegmenter, postprocess_video_masks  # noqa: F401
+from .segmentation import (  # noqa: F401
+    ImageSegmenter,
+    SegmentationInstances,
+    instance_inference,
+    panoptic_inference,
+    panoptic_segments_host,
+    semantic_inference,
+)
 from .processing import TimesformerImageProcessor  # noqa: F401
 
 __version__ = "0.1.0"

@@ -247,6 +247,9 @@ SIGNATURES = {
     "sf_op_vis_mask_iou": (_I, [_P, _I, _I, _I, _P, _P]),
     "sf_op_vis_postprocess_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_op_vis_postprocess": (_I, [_P, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "sf_op_seg_semantic": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "sf_op_seg_panoptic_argmax": (_I, [_P, _P, _P, _I, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "sf_op_seg_panoptic_relabel": (_I, [_P, _P, _I, C.c_longlong, _P, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),

@@ -24,6 +24,7 @@
 #include "sf_common.h"
 #include "sf_launch.h"
 #include "sf_handle.h"
+#include "sf_vis_axis.h"      // vis_axis, vis_reach: the coordinate arithmetic, shared with sf_seg.hip
 
 #define VIS_THREADS 256
 #define VIS_WAVES (VIS_THREADS / 64)
@@ -32,18 +33,6 @@
 #define VIS_PX 16                         // pixels of a row per thread
 #define VIS_INTER_MAX_WORDS 16384         // row i in 64 KB of LDS
 #define VIS_BOX_MAX_BYTES (63 * 1024)     // a tile's source box: what a kernel gets without raising its dynamic-LDS limit, less the static words
-
-// F.interpolate(bilinear, align_corners=False) along one axis: output index -> the two source indices and the second one's weight
-__host__ __device__ static inline void vis_axis(int dst, float ratio, int in, int* i0, int* i1, float* l1) {
-  float src = fmaf(ratio, (float)dst + 0.5f, -0.5f);        // one correctly rounded operation: the same bits on the host and on the device
-  src = src < 0.f ? 0.f : src;
-  int a = (int)src;
-  a = a > in - 1 ? in - 1 : a;
-  *i0 = a;
-  *i1 = a < in - 1 ? a + 1 : a;
-  const float l = src - (float)a;
-  *l1 = l > 1.f ? 1.f : l;
-}
 
 // ------------------------------------------------------------------------------------------------
 // a. scores
@@ -141,18 +130,6 @@ struct SfVisPost {
   float ry1, rx1, ry2, rx2;               // source pixels per padded pixel; cropped pixels per output pixel
   int lds_floats;
 };
-
-// the source rows (columns) that output rows (columns) a..b reach: both maps are non-decreasing
-__host__ __device__ static inline void vis_reach(int a, int b, float r2, int crop, float r1, int in, int* lo, int* hi) {
-  int m0, m1, s0, s1;
-  float l;
-  vis_axis(a, r2, crop, &m0, &m1, &l);
-  vis_axis(m0, r1, in, &s0, &s1, &l);
-  *lo = s0;
-  vis_axis(b, r2, crop, &m0, &m1, &l);
-  vis_axis(m1, r1, in, &s0, &s1, &l);
-  *hi = s1;
-}
 
 __global__ __launch_bounds__(VIS_THREADS) void sf_vis_postprocess_kernel(SfVisPost p) {
   extern __shared__ __attribute__((aligned(16))) float box[];
