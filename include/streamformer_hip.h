@@ -842,6 +842,55 @@ int sf_op_seg_panoptic_argmax(const float* masks_dev, const float* max_scores_de
 int sf_op_seg_panoptic_relabel(const int32_t* code_dev, const int32_t* segment_of_query_dev, int Q, long long pixels, int32_t* panoptic_dev,
                                sf_stream stream);
 
+/* ---- Mask2Former criterion (mask2former/modeling/matcher.py, criterion.py): every decoder layer of a training step per call --------
+ * All fp32, the caller's stream, no allocation, no host synchronisation.  Layers travel as HOST arrays of L device pointers (the final
+ * layer and the auxiliary ones are separate tensors of one shape): pred_logits[l] [B, Q, C1] with C1 = classes + 1, pred_masks[l]
+ * [B, Q, H, W].  Targets travel as HOST arrays over the B images: tgt_masks[b] device fp32 [G_b, H_b, W_b], tgt_labels[b] device int64
+ * [G_b], tgt_G / tgt_H / tgt_W host int32 (an image with G_b = 0 may have null pointers).  Points are (x, y) in [0, 1) and are sampled
+ * by F.grid_sample(bilinear, zeros, align_corners=False)'s rule, every corner bounds-checked on its own.  Limits (SF_ERR_CAPACITY, before
+ * any launch): L up to 16, B up to 32, G_b up to 128, Q and C1 up to 4096.                                                            */
+/* cost_dev [L, B, Q, G_max] = w_mask cost_mask + w_class cost_class + w_dice cost_dice of HungarianMatcher.memory_efficient_forward at
+ * the points coords_dev [L, B, K, 2]; columns >= G_b are NOT written.  The two [Q, K] x [K, G] contractions run on fp32 MFMA over
+ * chunks of 512 points whose partials a second kernel adds in chunk order: bit-reproducible, no [Q, K] tensor in memory.              */
+size_t sf_op_crit_costs_workspace_bytes(int L, int B, int Q, int G_max, int K);
+int sf_op_crit_costs(const float* const* pred_logits, const float* const* pred_masks, int L, int B, int Q, int C1, int H, int W,
+                     const float* const* tgt_masks, const int64_t* const* tgt_labels, const int32_t* tgt_G, const int32_t* tgt_H,
+                     const int32_t* tgt_W, const float* coords_dev, int K, int G_max, float w_class, float w_mask, float w_dice,
+                     float* cost_dev, void* workspace, size_t workspace_bytes, sf_stream stream);
+/* SetCriterion.loss_masks of the N matched pairs of all layers: pairs_dev int32 [N, 4] = (layer, image, query, target), grouped by
+ * layer, layer_start host int32 [L + 1].  Per pair one workgroup keeps the predicted mask at the K_over points over_dev [N, K_over, 2] in
+ * LDS (K_over up to sf_op_crit_losses_capacity() = 39424, SF_ERR_CAPACITY above), selects the K_uncertain points of smallest |x| by a
+ * radix select on the bit pattern (ties at the threshold go to the LOWER index; chosen points are emitted in index order), appends
+ * rand_dev [N, K - K_uncertain, 2], samples the target (coordinates scale by the batch's largest mask, reads outside a mask's own extent
+ * are zero, as nested_tensor_from_tensor_list pads) and reduces in a fixed order: bit-reproducible.  losses_dev[l * losses_stride + 0 / 1]
+ * = loss_mask / loss_dice of layer l (sum over its pairs in pair order, over num_masks).  coords_out_dev [N, K, 2] and sums_dev [N, 4]
+ * (sum sigmoid, sum t, sum sigmoid t, 0) are what the backward needs; idx_out_dev int32 [N, K_uncertain] (may be null) the chosen
+ * indices.                                                                                                                            */
+int sf_op_crit_losses_capacity(void);
+size_t sf_op_crit_losses_workspace_bytes(int N);
+int sf_op_crit_losses(const float* const* pred_masks, int L, int B, int Q, int H, int W, const float* const* tgt_masks, const int32_t* tgt_G,
+                      const int32_t* tgt_H, const int32_t* tgt_W, const int32_t* pairs_dev, const int32_t* layer_start, int N,
+                      const float* over_dev, const float* rand_dev, int K, int K_over, int K_uncertain, float num_masks,
+                      float* losses_dev, int losses_stride, float* coords_out_dev, float* sums_dev, int32_t* idx_out_dev, void* workspace,
+                      size_t workspace_bytes, sf_stream stream);
+/* grad_pred_masks_dev [L, B, Q, H, W] (zeroed here: planes of unmatched queries stay zero) from the saved coordinates and sums and
+ * upstream_dev [L, 2] = d / d loss_mask_l, d / d loss_dice_l.  A pair's plane of up to 32768 pixels is accumulated in LDS and flushed
+ * once, a larger one goes straight to memory; float atomics either way, so the sums are in arrival order: NOT bit-reproducible (as
+ * grad_value of sf_op_msda_backward).  No workspace.                                                                                  */
+int sf_op_crit_losses_backward(const float* const* pred_masks, int L, int B, int Q, int H, int W, const float* const* tgt_masks,
+                               const int32_t* tgt_G, const int32_t* tgt_H, const int32_t* tgt_W, const int32_t* pairs_dev, int N,
+                               const float* coords_dev, const float* sums_dev, int K, float num_masks, const float* upstream_dev,
+                               float* grad_pred_masks_dev, sf_stream stream);
+/* SetCriterion.loss_labels of all layers: F.cross_entropy(weight = weight_dev [C1], mean reduction) of the L B Q rows, the target class
+ * of a row being its pair's label and C1 - 1 (no-object) for an unmatched query or a label outside the table.  losses_dev[l *
+ * losses_stride] = loss_ce of layer l; grad_dev [L, B, Q, C1] (may be null) its gradient; target_classes_out_dev int32 [L, B, Q] (may be
+ * null) the target classes.  One wave per row, per-layer sums in a fixed order: bit-reproducible.                                     */
+size_t sf_op_crit_class_loss_workspace_bytes(int L, int B, int Q);
+int sf_op_crit_class_loss(const float* const* pred_logits, int L, int B, int Q, int C1, const int32_t* pairs_dev, int N,
+                          const int64_t* const* tgt_labels, const int32_t* tgt_G, const float* weight_dev, float* losses_dev,
+                          int losses_stride, float* grad_dev, int32_t* target_classes_out_dev, void* workspace, size_t workspace_bytes,
+                          sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

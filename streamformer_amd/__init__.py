@@ -40,6 +40,7 @@ from .segmentation import (  # noqa: F401
     panoptic_segments_host,
     semantic_inference,
 )
+from .criterion import HungarianMatcher, SetCriterion  # noqa: F401
 from .processing import TimesformerImageProcessor  # noqa: F401
 
 __version__ = "0.1.0"

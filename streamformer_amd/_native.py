@@ -250,6 +250,18 @@ SIGNATURES = {
     "sf_op_seg_semantic": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     "sf_op_seg_panoptic_argmax": (_I, [_P, _P, _P, _I, _I, _F, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sf_op_seg_panoptic_relabel": (_I, [_P, _P, _I, C.c_longlong, _P, _P]),
+    "sf_op_crit_costs_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
+    "sf_op_crit_costs": (_I, [C.POINTER(_P), C.POINTER(_P), _I, _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_int32),
+                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _I, _I, _F, _F, _F, _P, _P, _SZ, _P]),
+    "sf_op_crit_losses_capacity": (_I, []),
+    "sf_op_crit_losses_workspace_bytes": (_SZ, [_I]),
+    "sf_op_crit_losses": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_int32), _P, C.POINTER(C.c_int32), _I, _P, _P, _I, _I, _I, _F, _P, _I, _P, _P, _P, _P, _SZ, _P]),
+    "sf_op_crit_losses_backward": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, C.POINTER(_P), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), _P, _I, _P, _P, _I, _F, _P, _P, _P]),
+    "sf_op_crit_class_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "sf_op_crit_class_loss": (_I, [C.POINTER(_P), _I, _I, _I, _I, _P, _I, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _I, _P, _P, _P, _SZ,
+                                   _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
