@@ -217,8 +217,7 @@ extern "C" int sf_connector_create(const sf_connector_config* cfg, int device, s
   w.all_required = false;
   for (int i = 0; i < c.depth; ++i) {
     const std::string p = conn_linear_key(h, i);
-    w.expected[p + "weight"] = {c.out_dim, i ? c.out_dim : c.in_dim};
-    w.expected[p + "bias"] = {c.out_dim};
+    w.expect_linear(p, c.out_dim, i ? c.out_dim : c.in_dim);
     w.required.push_back(p + "weight");
     w.required.push_back(p + "bias");
   }
@@ -277,9 +276,9 @@ static int conn_plan(const sf_connector* c, int F, int P, ConnPlan* pl) {
 }
 
 struct ConnWorkspace {
-  bf16_t *x_hi, *x_lo;                 // the split input [M, in_dim]
-  bf16_t *act_hi[2], *act_lo[2];       // GELU outputs [M, out_dim], ping-pong from depth 3 up
-  bf16_t *pool_hi, *pool_lo;           // role (a) output [Mp, K of the last Linear]
+  SfPlanes x;                          // the split input [M, in_dim]
+  SfPlanes act[2];                     // GELU outputs [M, out_dim], ping-pong from depth 3 up
+  SfPlanes pool;                       // role (a) output [Mp, K of the last Linear]
   float* y;                            // the last Linear's output [Mp, out_dim]
   size_t bytes;
 };
@@ -287,22 +286,13 @@ struct ConnWorkspace {
 static ConnWorkspace conn_carve(const sf_connector* c, const ConnPlan& pl, void* base) {
   ConnWorkspace w;
   memset(&w, 0, sizeof(w));
-  SfCarver cv(base);
+  SfCarver cv(base, c->compute == SF_COMPUTE_BF16X3);
   const size_t M = (size_t)pl.M, Mp = (size_t)pl.Mp, Din = c->cfg.in_dim, Dout = c->cfg.out_dim;
-  const bool split = c->compute == SF_COMPUTE_BF16X3;
   const int depth = c->cfg.depth;
   if (depth >= 1) {
-    w.x_hi = cv.take<bf16_t>(M * Din);
-    if (split) w.x_lo = cv.take<bf16_t>(M * Din);
-    for (int i = 0; i < (depth >= 3 ? 2 : depth >= 2 ? 1 : 0); ++i) {
-      w.act_hi[i] = cv.take<bf16_t>(M * Dout);
-      if (split) w.act_lo[i] = cv.take<bf16_t>(M * Dout);
-    }
-    if (pl.pool_first) {
-      const size_t K = depth == 1 ? Din : Dout;
-      w.pool_hi = cv.take<bf16_t>(Mp * K);
-      if (split) w.pool_lo = cv.take<bf16_t>(Mp * K);
-    }
+    w.x = cv.planes(M * Din);
+    for (int i = 0; i < (depth >= 3 ? 2 : depth >= 2 ? 1 : 0); ++i) w.act[i] = cv.planes(M * Dout);
+    if (pl.pool_first) w.pool = cv.planes(Mp * (depth == 1 ? Din : Dout));
     w.y = cv.take<float>(Mp * Dout);
   }
   w.bytes = cv.bytes();
@@ -342,7 +332,7 @@ extern "C" int sf_connector_forward(sf_connector* c, const float* feats_dev, int
   SF_TRY(sf_check_workspace("sf_connector_forward", "sf_connector_workspace_bytes", workspace_dev, workspace_bytes, ws.bytes));
   hipStream_t s = (hipStream_t)stream;
   const sf_connector_config& cfg = c->cfg;
-  const bool split = c->compute == SF_COMPUTE_BF16X3;
+  const SfLinearCaller lin{c->compute == SF_COMPUTE_BF16X3, 0, s};      // act 0: erf GELU (nn.GELU() of the reference builder)
   const int depth = cfg.depth;
 
   SfConnPool place;                      // role (b): the last launch of every schedule
@@ -355,31 +345,23 @@ extern "C" int sf_connector_forward(sf_connector* c, const float* feats_dev, int
     HIP_TRY(conn_launch_pool(place, s));
     return SF_OK;
   }
-  HIP_TRY(sf_launch_split(feats_dev, ws.x_hi, ws.x_lo, (size_t)pl.M * cfg.in_dim, s));
-  const bf16_t* a_hi = ws.x_hi;
-  const bf16_t* a_lo = ws.x_lo;
-  auto linear = [&](const SfDevLinear& l, int M, int epi) { return sf_linear_args(l, a_hi, a_lo, M, epi, 0, split); };      // act 0: erf GELU (nn.GELU() of the reference builder)
+  HIP_TRY(sf_launch_split(feats_dev, ws.x.hi, ws.x.lo, (size_t)pl.M * cfg.in_dim, s));
+  SfPlanes a = ws.x;
   for (int i = 0; i + 1 < depth; ++i) {
-    SfGemmArgs g = linear(c->lin[i], (int)pl.M, SF_EPI_ACT_BF16);
-    g.out_hi = ws.act_hi[i & 1]; g.out_lo = split ? ws.act_lo[i & 1] : nullptr;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-    a_hi = ws.act_hi[i & 1]; a_lo = ws.act_lo[i & 1];
+    HIP_TRY(lin.planes(c->lin[i], a, (int)pl.M, ws.act[i & 1], true));
+    a = ws.act[i & 1];
   }
   const SfDevLinear& last = c->lin[depth - 1];
   if (pl.pool_first) {                   // role (a): P^2 -> P'^2 rows per frame in front of the last Linear
     SfConnPool q;
     memset(&q, 0, sizeof(q));
-    q.in_hi = a_hi; q.in_lo = split ? a_lo : nullptr;
-    q.out_hi = ws.pool_hi; q.out_lo = split ? ws.pool_lo : nullptr;
+    q.in_hi = a.hi; q.in_lo = a.lo;
+    q.out_hi = ws.pool.hi; q.out_lo = ws.pool.lo;
     q.F = F; q.P = P; q.C = last.K; q.mode = c->pool; q.stride = cfg.pool_stride; q.nl = CONN_NL_NONE;
     HIP_TRY(conn_launch_pool(q, s));
-    a_hi = ws.pool_hi; a_lo = ws.pool_lo;
+    a = ws.pool;
   }
-  {
-    SfGemmArgs g = linear(last, (int)pl.Mp, SF_EPI_F32);
-    g.out_f32 = ws.y;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-  }
+  HIP_TRY(lin.f32(last, a, (int)pl.Mp, ws.y));
   place.in_f32 = ws.y;
   if (pl.pool_first) { place.P = pl.Po; place.mode = CONN_POOL_NONE; place.stride = 1; }      // identity taps: rows are placed only
   else { place.P = P; place.mode = c->pool; place.stride = cfg.pool_stride; }

@@ -1,6 +1,7 @@
-// Device side of a native model's handle, shared by sf_encoder, sf_text, sf_connector, sf_oad and sf_pixdec: the device allocations a
-// finalize owns, a Linear's bf16 planes and their upload, the GEMM arguments every Linear starts from, and SfModelHandle, the part of
-// a tail model's handle (everything but the encoder's) and of its entry points that does not depend on the model.  The host half is
+// Device side of a native model's handle, shared by sf_encoder, sf_text, sf_connector, sf_oad, sf_pixdec and sf_maskdec: the device
+// allocations a finalize owns, a Linear's bf16 planes and a LayerNorm's affine pair with their uploads, the GEMM arguments every Linear
+// starts from and SfLinearCaller, the three calls most Linears are, and SfModelHandle, the part of a tail model's handle (everything but
+// the encoder's) and of its entry points that does not depend on the model.  The host half, SfPlanes and the carver included, is
 // sf_weights.h.
 #pragma once
 #include "sf_common.h"
@@ -58,8 +59,8 @@ struct SfDeviceAllocs {
 };
 
 // ------------------------------------------------------------------------------------------------
-// What sf_text, sf_connector, sf_oad and sf_pixdec share: a handle derives from SfModelHandle and brings its config validation, its
-// expected-key table, its uploads, its plan, carve and launch sequence.  `family` below is the prefix of its entry points ("sf_text").
+// What sf_text, sf_connector, sf_oad, sf_pixdec and sf_maskdec share: a handle derives from SfModelHandle and brings its config
+// validation, its expected-key table, its uploads, its plan, carve and launch sequence.  `family` below is the prefix of its entry points ("sf_text").
 // ------------------------------------------------------------------------------------------------
 struct SfModelHandle {
   int device = 0;
@@ -143,6 +144,21 @@ static inline int sf_upload_linear(SfDeviceAllocs& dev, const std::vector<float>
   return SF_OK;
 }
 
+static inline int sf_upload_ln(SfDeviceAllocs& dev, SfWeightStore& w, const std::string& prefix, SfDevLN* out) {      // weight, then bias
+  SF_TRY(dev.upload(w.data(prefix + "weight"), &out->g));
+  return dev.upload(w.data(prefix + "bias"), &out->b);
+}
+
+// rows [row0, row0 + rows) of an uploaded Linear as a Linear of their own (a packed in_proj's q, k | v, ...), with the bias given
+static inline SfDevLinear sf_linear_rows(const SfDevLinear& lin, int row0, int rows, const float* bias) {
+  SfDevLinear o = lin;
+  o.w_hi = lin.w_hi + (size_t)row0 * lin.K;
+  o.w_lo = lin.w_lo ? lin.w_lo + (size_t)row0 * lin.K : nullptr;
+  o.bias = bias;
+  o.N = rows;
+  return o;
+}
+
 // The fields every Linear's GEMM shares; a call site then sets what is special about it (outputs, residual, LayerNorm fold, row
 // remap) by field name and launches with the same `split`.
 static inline SfGemmArgs sf_linear_args(const SfDevLinear& lin, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, int act, bool split) {
@@ -155,3 +171,29 @@ static inline SfGemmArgs sf_linear_args(const SfDevLinear& lin, const bf16_t* a_
   g.epi = epi; g.act = act; g.alpha = 1.f;
   return g;
 }
+
+// A model's forward says its compute mode, its activation (0 erf GELU, 1 tanh GELU, 2 ReLU: read by the activated epilogue only) and
+// its stream once, and then runs a Linear on `rows` rows of the planes `a` in one of three ways.  A GEMM that needs a field these do
+// not set starts from sf_linear_args itself.
+struct SfLinearCaller {
+  bool split;
+  int act;
+  hipStream_t stream;
+
+  hipError_t f32(const SfDevLinear& lin, const SfPlanes& a, int rows, float* out, int ldc = 0) const {      // ldc 0: lin.N, dense rows
+    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, SF_EPI_F32, act, split);
+    g.out_f32 = out;
+    if (ldc) g.ldc = ldc;
+    return sf_launch_gemm(g, split, stream);
+  }
+  hipError_t planes(const SfDevLinear& lin, const SfPlanes& a, int rows, const SfPlanes& out, bool activated) const {
+    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, activated ? SF_EPI_ACT_BF16 : SF_EPI_BF16, act, split);
+    g.out_hi = out.hi; g.out_lo = out.lo;
+    return sf_launch_gemm(g, split, stream);
+  }
+  hipError_t resid(const SfDevLinear& lin, const SfPlanes& a, int rows, const float* resid, float* out) const {      // out = resid + a W^T + b
+    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, SF_EPI_RESID_F32, act, split);
+    g.resid = resid; g.out_f32 = out;
+    return sf_launch_gemm(g, split, stream);
+  }
+};

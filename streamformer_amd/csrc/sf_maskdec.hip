@@ -441,21 +441,19 @@ extern "C" int sf_maskdec_create(const sf_maskdec_config* cfg, int device, sf_ma
   w.noun = "mask decoder";
   w.prefix = "sem_seg_head.predictor.";
   w.dtype_msg = "sf_maskdec_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
-  auto affine = [&](const std::string& p) { w.expected[p + "weight"] = {C}; w.expected[p + "bias"] = {C}; };
-  auto linear = [&](const std::string& p, int64_t o, int64_t i) { w.expected[p + "weight"] = {o, i}; w.expected[p + "bias"] = {o}; };
   for (int i = 0; i < c.dec_layers; ++i) {
     for (const std::string& p : {mkd_idx("transformer_self_attention_layers.", i, ".self_attn."), mkd_idx("transformer_cross_attention_layers.", i, ".multihead_attn.")}) {
       w.expected[p + "in_proj_weight"] = {3 * C, C};
       w.expected[p + "in_proj_bias"] = {3 * C};
-      linear(p + "out_proj.", C, C);
+      w.expect_linear(p + "out_proj.", C, C);
     }
-    affine(mkd_idx("transformer_self_attention_layers.", i, ".norm."));
-    affine(mkd_idx("transformer_cross_attention_layers.", i, ".norm."));
-    linear(mkd_idx("transformer_ffn_layers.", i, ".linear1."), Fd, C);
-    linear(mkd_idx("transformer_ffn_layers.", i, ".linear2."), C, Fd);
-    affine(mkd_idx("transformer_ffn_layers.", i, ".norm."));
+    w.expect_affine(mkd_idx("transformer_self_attention_layers.", i, ".norm."), C);
+    w.expect_affine(mkd_idx("transformer_cross_attention_layers.", i, ".norm."), C);
+    w.expect_linear(mkd_idx("transformer_ffn_layers.", i, ".linear1."), Fd, C);
+    w.expect_linear(mkd_idx("transformer_ffn_layers.", i, ".linear2."), C, Fd);
+    w.expect_affine(mkd_idx("transformer_ffn_layers.", i, ".norm."), C);
   }
-  affine("decoder_norm.");
+  w.expect_affine("decoder_norm.", C);
   w.expected["query_feat.weight"] = {c.num_queries, C};
   w.expected["query_embed.weight"] = {c.num_queries, C};
   w.expected["level_embed.weight"] = {MKD_LEVELS, C};
@@ -464,12 +462,12 @@ extern "C" int sf_maskdec_create(const sf_maskdec_config* cfg, int device, sf_ma
       w.expected[mkd_idx("input_proj.", l, ".weight")] = {C, c.in_channels, 1, 1};
       w.expected[mkd_idx("input_proj.", l, ".bias")] = {C};
     }
-  linear("class_embed.", c.num_classes + 1, C);
-  linear("mask_embed.layers.0.", C, C);
-  linear("mask_embed.layers.1.", C, C);
-  linear("mask_embed.layers.2.", c.mask_dim, C);
+  w.expect_linear("class_embed.", c.num_classes + 1, C);
+  w.expect_linear("mask_embed.layers.0.", C, C);
+  w.expect_linear("mask_embed.layers.1.", C, C);
+  w.expect_linear("mask_embed.layers.2.", c.mask_dim, C);
   for (int n = 0; n < c.reid_layers; ++n)
-    linear(mkd_idx("reid_embed.layers.", n, "."), n + 1 == c.reid_layers ? C : c.reid_hidden_dim, n == 0 ? C : c.reid_hidden_dim);
+    w.expect_linear(mkd_idx("reid_embed.layers.", n, "."), n + 1 == c.reid_layers ? C : c.reid_hidden_dim, n == 0 ? C : c.reid_hidden_dim);
   *out = h;
   return SF_OK;
 }
@@ -482,15 +480,6 @@ extern "C" int sf_maskdec_load_tensor(sf_maskdec* h, const char* key, const void
 
 extern "C" int sf_maskdec_missing_weights(sf_maskdec* h) { return sf_model_missing_weights(h); }
 
-static SfDevLinear mkd_rows_of(const SfDevLinear& l, int row0, int rows, const float* bias) {
-  SfDevLinear o = l;
-  o.w_hi = l.w_hi + (size_t)row0 * l.K;
-  o.w_lo = l.w_lo ? l.w_lo + (size_t)row0 * l.K : nullptr;
-  o.bias = bias;
-  o.N = rows;
-  return o;
-}
-
 // Weights rounded (bf16 mode) or split into hi + lo planes (bf16x3) ONCE, here.  Makes the handle's device current and leaves it so.
 extern "C" int sf_maskdec_finalize(sf_maskdec* h, int compute) {
   SF_TRY(sf_model_begin_finalize(h, compute));
@@ -500,10 +489,6 @@ extern "C" int sf_maskdec_finalize(sf_maskdec* h, int compute) {
   SfWeightStore& w = h->weights;
   auto linear = [&](const std::string& p, int N, int K, int Np, SfDevLinear* out) {
     return sf_upload_linear(h->dev, w.data(p + "weight"), &w.data(p + "bias"), N, K, Np, lo, out);
-  };
-  auto norm = [&](const std::string& p, SfDevLN* out) {
-    SF_TRY(h->dev.upload(w.data(p + "weight"), &out->g));
-    return h->dev.upload(w.data(p + "bias"), &out->b);
   };
   const std::vector<float>& le = w.data("level_embed.weight");
   if (h->proj) {
@@ -537,26 +522,26 @@ extern "C" int sf_maskdec_finalize(sf_maskdec* h, int compute) {
       SF_TRY(h->dev.upload(bq, &dq));
       SF_TRY(h->dev.upload(bk, &dk));
       SF_TRY(h->dev.upload(bkv, &dkv));
-      L.cq = mkd_rows_of(all, 0, C, dq);
-      L.ck = mkd_rows_of(all, C, C, dk);
-      L.ckv = mkd_rows_of(all, C, 2 * C, dkv);
+      L.cq = sf_linear_rows(all, 0, C, dq);
+      L.ck = sf_linear_rows(all, C, C, dk);
+      L.ckv = sf_linear_rows(all, C, 2 * C, dkv);
       SF_TRY(linear(p + "out_proj.", C, C, C, &L.co));
-      SF_TRY(norm(mkd_idx("transformer_cross_attention_layers.", i, ".norm."), &L.cnorm));
+      SF_TRY(sf_upload_ln(h->dev, w, mkd_idx("transformer_cross_attention_layers.", i, ".norm."), &L.cnorm));
     }
     {
       const std::string p = mkd_idx("transformer_self_attention_layers.", i, ".self_attn.");
       SfDevLinear all;
       SF_TRY(sf_upload_linear(h->dev, w.data(p + "in_proj_weight"), &w.data(p + "in_proj_bias"), 3 * C, C, 3 * C, lo, &all));
-      L.sqk = mkd_rows_of(all, 0, 2 * C, all.bias);
-      L.sv = mkd_rows_of(all, 2 * C, C, all.bias + 2 * C);
+      L.sqk = sf_linear_rows(all, 0, 2 * C, all.bias);
+      L.sv = sf_linear_rows(all, 2 * C, C, all.bias + 2 * C);
       SF_TRY(linear(p + "out_proj.", C, C, C, &L.so));
-      SF_TRY(norm(mkd_idx("transformer_self_attention_layers.", i, ".norm."), &L.snorm));
+      SF_TRY(sf_upload_ln(h->dev, w, mkd_idx("transformer_self_attention_layers.", i, ".norm."), &L.snorm));
     }
     SF_TRY(linear(mkd_idx("transformer_ffn_layers.", i, ".linear1."), Fd, C, Fd, &L.lin1));
     SF_TRY(linear(mkd_idx("transformer_ffn_layers.", i, ".linear2."), C, Fd, C, &L.lin2));
-    SF_TRY(norm(mkd_idx("transformer_ffn_layers.", i, ".norm."), &L.fnorm));
+    SF_TRY(sf_upload_ln(h->dev, w, mkd_idx("transformer_ffn_layers.", i, ".norm."), &L.fnorm));
   }
-  SF_TRY(norm("decoder_norm.", &h->dnorm));
+  SF_TRY(sf_upload_ln(h->dev, w, "decoder_norm.", &h->dnorm));
   SF_TRY(h->dev.upload(w.data("query_feat.weight"), &h->query_feat));
   SF_TRY(h->dev.upload(w.data("query_embed.weight"), &h->query_embed));
   SF_TRY(linear("class_embed.", c.num_classes + 1, C, h->Cp, &h->cls));
@@ -609,13 +594,12 @@ static int mkd_plan(const sf_maskdec* h, int F, const int32_t* level_shapes, int
   return SF_OK;
 }
 
-struct MkdPlanes { bf16_t* hi = nullptr; bf16_t* lo = nullptr; };
 struct MkdWorkspace {
   float *pos, *ref, *kpos;
-  MkdPlanes pos_p, xin, src[MKD_LEVELS];
+  SfPlanes pos_p, xin, src[MKD_LEVELS];
   float* feat[MKD_LEVELS];               // mask_features at the level's resolution [F, Dm, hw]
   float *kv, *out, *tmp, *qkv, *dn, *me, *cls, *embeds;
-  MkdPlanes y, q, ctx, hid, dnp, ma, mb, ra, rb;
+  SfPlanes y, q, ctx, hid, dnp, ma, mb, ra, rb;
   uint32_t* bits;
   size_t bytes;
 };
@@ -623,18 +607,16 @@ struct MkdWorkspace {
 static MkdWorkspace mkd_carve(const sf_maskdec* h, const MkdPlan& pl, void* base) {
   MkdWorkspace w;
   memset(&w, 0, sizeof(w));
-  SfCarver cv(base);
-  const bool split = h->compute == SF_COMPUTE_BF16X3;
+  SfCarver cv(base, h->compute == SF_COMPUTE_BF16X3);
   const sf_maskdec_config& c = h->cfg;
   const size_t C = c.hidden_dim, M = (size_t)pl.F * c.num_queries;
-  auto planes = [&](size_t n) { MkdPlanes p; p.hi = cv.take<bf16_t>(n); if (split) p.lo = cv.take<bf16_t>(n); return p; };
   w.pos = cv.take<float>((size_t)pl.S * C);
   w.ref = cv.take<float>((size_t)pl.S * MKD_LEVELS * 2);
   w.kpos = cv.take<float>(std::max<size_t>(pl.kpos_rows, 1) * C);
-  w.pos_p = planes((size_t)pl.S * C);
-  if (h->proj) w.xin = planes((size_t)pl.F * pl.max_hw * c.in_channels);
+  w.pos_p = cv.planes((size_t)pl.S * C);
+  if (h->proj) w.xin = cv.planes((size_t)pl.F * pl.max_hw * c.in_channels);
   for (int l = 0; l < MKD_LEVELS; ++l) {
-    w.src[l] = planes((size_t)pl.F * pl.hw[l] * C);
+    w.src[l] = cv.planes((size_t)pl.F * pl.hw[l] * C);
     w.feat[l] = cv.take<float>((size_t)pl.F * c.mask_dim * pl.hw[l]);
   }
   w.kv = cv.take<float>((size_t)pl.F * pl.max_hw * 2 * C);
@@ -645,9 +627,9 @@ static MkdWorkspace mkd_carve(const sf_maskdec* h, const MkdPlan& pl, void* base
   w.me = cv.take<float>(M * c.mask_dim);
   w.cls = cv.take<float>(M * h->Cp);
   w.embeds = cv.take<float>(M * C);
-  w.y = planes(M * C); w.q = planes(M * C); w.ctx = planes(M * C); w.dnp = planes(M * C); w.ma = planes(M * C); w.mb = planes(M * C);
-  w.hid = planes(M * c.dim_feedforward);
-  if (c.reid_layers > 1) { w.ra = planes(M * c.reid_hidden_dim); w.rb = planes(M * c.reid_hidden_dim); }
+  w.y = cv.planes(M * C); w.q = cv.planes(M * C); w.ctx = cv.planes(M * C); w.dnp = cv.planes(M * C); w.ma = cv.planes(M * C); w.mb = cv.planes(M * C);
+  w.hid = cv.planes(M * c.dim_feedforward);
+  if (c.reid_layers > 1) { w.ra = cv.planes(M * c.reid_hidden_dim); w.rb = cv.planes(M * c.reid_hidden_dim); }
   int words = 1;
   for (int l = 0; l < MKD_LEVELS; ++l) words = std::max(words, pl.words[l]);
   w.bits = cv.take<uint32_t>(M * words);
@@ -690,49 +672,31 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
   const bool split = h->compute == SF_COMPUTE_BF16X3;
   const int C = c.hidden_dim, Q = c.num_queries, M = F * Q, Dm = c.mask_dim, heads = c.nheads, hd = h->hd, L = c.dec_layers, K1 = c.num_classes + 1;
   const float scale = 1.0f / sqrtf((float)hd);
-  auto lo_of = [&](const MkdPlanes& p) { return split ? p.lo : nullptr; };
-  auto gemm_f32 = [&](const SfDevLinear& lin, const MkdPlanes& a, int rows, float* out, int ldc) {
-    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, SF_EPI_F32, 0, split);
-    g.out_f32 = out; g.ldc = ldc;
-    return sf_launch_gemm(g, split, s);
-  };
-  auto gemm_planes = [&](const SfDevLinear& lin, const MkdPlanes& a, int rows, const MkdPlanes& out, bool relu) {
-    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, relu ? SF_EPI_ACT_BF16 : SF_EPI_BF16, 2, split);
-    g.out_hi = out.hi; g.out_lo = lo_of(out);
-    return sf_launch_gemm(g, split, s);
-  };
-  auto gemm_resid = [&](const SfDevLinear& lin, const MkdPlanes& a, int rows, const float* resid, float* out) {
-    SfGemmArgs g = sf_linear_args(lin, a.hi, a.lo, rows, SF_EPI_RESID_F32, 0, split);
-    g.resid = resid; g.out_f32 = out;
-    return sf_launch_gemm(g, split, s);
-  };
+  const SfLinearCaller lin{split, 2, s};      // act 2: ReLU
 
   // ---- what depends on the shapes only: the sine table (+ level_embed without input_proj) and its k projection per layer ----
   SF_TRY(sf_op_pixdec_pos_ref(h->pos_level, pl.shapes, MKD_LEVELS, 1, C, ws.pos, ws.ref, stream));
-  HIP_TRY(sf_launch_split(ws.pos, ws.pos_p.hi, lo_of(ws.pos_p), (size_t)pl.S * C, s));
+  HIP_TRY(sf_launch_split(ws.pos, ws.pos_p.hi, ws.pos_p.lo, (size_t)pl.S * C, s));
   std::vector<const float*> kpos(L);
   {
     size_t row = 0;
     for (int i = 0; i < L; ++i) {
       const int l = i % MKD_LEVELS;
-      MkdPlanes a;
-      a.hi = ws.pos_p.hi + (size_t)pl.start[l] * C;
-      a.lo = split ? ws.pos_p.lo + (size_t)pl.start[l] * C : nullptr;
       float* dst = ws.kpos + row * C;
-      HIP_TRY(gemm_f32(h->layers[i].ck, a, pl.hw[l], dst, C));
+      HIP_TRY(lin.f32(h->layers[i].ck, ws.pos_p.at((size_t)pl.start[l] * C), pl.hw[l], dst));
       kpos[i] = dst;
       row += (size_t)pl.hw[l];
     }
   }
   // ---- per level: src as GEMM operand planes, and mask_features at the level's resolution ----
-  MkdPlanes src[MKD_LEVELS];
+  SfPlanes src[MKD_LEVELS];
   for (int l = 0; l < MKD_LEVELS; ++l) {
     src[l] = ws.src[l];
     if (h->proj) {
-      SF_TRY(sf_op_pixdec_nchw_to_planes(x_dev[l], ws.xin.hi, lo_of(ws.xin), F, c.in_channels, pl.hw[l], stream));
-      HIP_TRY(gemm_planes(h->in_proj[l], ws.xin, F * pl.hw[l], src[l], false));
+      SF_TRY(sf_op_pixdec_nchw_to_planes(x_dev[l], ws.xin.hi, ws.xin.lo, F, c.in_channels, pl.hw[l], stream));
+      HIP_TRY(lin.planes(h->in_proj[l], ws.xin, F * pl.hw[l], src[l], false));
     } else {
-      SF_TRY(sf_op_pixdec_nchw_to_planes(x_dev[l], src[l].hi, lo_of(src[l]), F, C, pl.hw[l], stream));
+      SF_TRY(sf_op_pixdec_nchw_to_planes(x_dev[l], src[l].hi, src[l].lo, F, C, pl.hw[l], stream));
     }
     bool used = L > 0 && l == 0;                         // the mask of layer i has the resolution of level i % 3
     for (int i = 1; i < L; ++i) used = used || i % MKD_LEVELS == l;
@@ -740,7 +704,7 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
   }
   // ---- queries: query_feat replicated over the frames, and the planes of query_feat + query_embed ----
   HIP_TRY(hipMemsetAsync(ws.tmp, 0, (size_t)M * C * sizeof(float), s));
-  HIP_TRY(mkd_row(ws.tmp, h->query_feat, Q, nullptr, h->query_embed, Q, ws.out, nullptr, nullptr, ws.q.hi, lo_of(ws.q), M, C, s));
+  HIP_TRY(mkd_row(ws.tmp, h->query_feat, Q, nullptr, h->query_embed, Q, ws.out, nullptr, nullptr, ws.q.hi, ws.q.lo, M, C, s));
 
   size_t mask_off = 0;                                   // words of the exported masks so far
   for (int i = 0; i <= L; ++i) {
@@ -750,55 +714,55 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
       const int l = (i - 1) % MKD_LEVELS, hw = pl.hw[l];
       const uint32_t* mask = o.attn_masks ? o.attn_masks + (mask_off - (size_t)M * pl.words[l]) : ws.bits;
       // cross-attention
-      HIP_TRY(gemm_f32(ly.cq, ws.q, M, ws.qkv, C));
-      HIP_TRY(gemm_f32(ly.ckv, src[l], F * hw, ws.kv, 2 * C));
+      HIP_TRY(lin.f32(ly.cq, ws.q, M, ws.qkv, C));
+      HIP_TRY(lin.f32(ly.ckv, src[l], F * hw, ws.kv, 2 * C));
       SfMkdAttn a;
       memset(&a, 0, sizeof(a));
       a.q = ws.qkv; a.k = ws.kv; a.v = ws.kv + C; a.kpos = kpos[i - 1]; a.mask = mask;
-      a.ctx_hi = ws.ctx.hi; a.ctx_lo = lo_of(ws.ctx);
+      a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
       a.q_pitch = C; a.k_pitch = 2 * C; a.v_pitch = 2 * C; a.pos_pitch = C;
       a.F = F; a.Tq = Q; a.Tk = hw; a.heads = heads; a.hd = hd; a.words = pl.words[l]; a.scale = scale;
       HIP_TRY(mkd_launch_attention(a, s));
-      HIP_TRY(gemm_resid(ly.co, ws.ctx, M, ws.out, ws.tmp));
-      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.cnorm, h->query_embed, Q, ws.out, ws.y.hi, lo_of(ws.y), ws.q.hi, lo_of(ws.q), M, C, s));
+      HIP_TRY(lin.resid(ly.co, ws.ctx, M, ws.out, ws.tmp));
+      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.cnorm, h->query_embed, Q, ws.out, ws.y.hi, ws.y.lo, ws.q.hi, ws.q.lo, M, C, s));
       // self-attention: q = k = x + query_embed, v = x
-      HIP_TRY(gemm_f32(ly.sqk, ws.q, M, ws.qkv, 3 * C));
-      HIP_TRY(gemm_f32(ly.sv, ws.y, M, ws.qkv + 2 * C, 3 * C));
+      HIP_TRY(lin.f32(ly.sqk, ws.q, M, ws.qkv, 3 * C));
+      HIP_TRY(lin.f32(ly.sv, ws.y, M, ws.qkv + 2 * C, 3 * C));
       memset(&a, 0, sizeof(a));
       a.q = ws.qkv; a.k = ws.qkv + C; a.v = ws.qkv + 2 * C;
-      a.ctx_hi = ws.ctx.hi; a.ctx_lo = lo_of(ws.ctx);
+      a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
       a.q_pitch = 3 * C; a.k_pitch = 3 * C; a.v_pitch = 3 * C;
       a.F = F; a.Tq = Q; a.Tk = Q; a.heads = heads; a.hd = hd; a.scale = scale;
       HIP_TRY(mkd_launch_attention(a, s));
-      HIP_TRY(gemm_resid(ly.so, ws.ctx, M, ws.out, ws.tmp));
-      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.snorm, nullptr, 0, ws.out, ws.y.hi, lo_of(ws.y), nullptr, nullptr, M, C, s));
+      HIP_TRY(lin.resid(ly.so, ws.ctx, M, ws.out, ws.tmp));
+      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.snorm, nullptr, 0, ws.out, ws.y.hi, ws.y.lo, nullptr, nullptr, M, C, s));
       // FFN
-      HIP_TRY(gemm_planes(ly.lin1, ws.y, M, ws.hid, true));
-      HIP_TRY(gemm_resid(ly.lin2, ws.hid, M, ws.out, ws.tmp));
-      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.fnorm, h->query_embed, Q, ws.out, nullptr, nullptr, last ? nullptr : ws.q.hi, lo_of(ws.q), M, C, s));
+      HIP_TRY(lin.planes(ly.lin1, ws.y, M, ws.hid, true));
+      HIP_TRY(lin.resid(ly.lin2, ws.hid, M, ws.out, ws.tmp));
+      HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.fnorm, h->query_embed, Q, ws.out, nullptr, nullptr, last ? nullptr : ws.q.hi, ws.q.lo, M, C, s));
     }
     // ---- prediction heads on decoder_norm(output) ----
     float* dn = last ? (o.pred_queries ? o.pred_queries : ws.dn) : (o.aux_queries ? o.aux_queries + (size_t)i * M * C : ws.dn);
-    HIP_TRY(mkd_row(ws.out, nullptr, 0, &h->dnorm, nullptr, 0, dn, ws.dnp.hi, lo_of(ws.dnp), nullptr, nullptr, M, C, s));
+    HIP_TRY(mkd_row(ws.out, nullptr, 0, &h->dnorm, nullptr, 0, dn, ws.dnp.hi, ws.dnp.lo, nullptr, nullptr, M, C, s));
     float* logits = last ? o.pred_logits : (o.aux_logits ? o.aux_logits + (size_t)i * M * K1 : nullptr);
     if (logits) {
-      HIP_TRY(gemm_f32(h->cls, ws.dnp, M, ws.cls, h->Cp));
+      HIP_TRY(lin.f32(h->cls, ws.dnp, M, ws.cls, h->Cp));
       HIP_TRY(sf_launch(sf_maskdec_cut_kernel, dim3(mkd_stream_grid((size_t)M * K1)), dim3(256), 0, s, (const float*)ws.cls, logits, M, h->Cp, K1));
     }
     float* embeds = last ? o.pred_embeds : (o.aux_embeds ? o.aux_embeds + (size_t)i * M * C : nullptr);
     if (embeds) {
       if (c.reid_layers == 0) HIP_TRY(hipMemcpyAsync(embeds, dn, (size_t)M * C * sizeof(float), hipMemcpyDeviceToDevice, s));
-      MkdPlanes in = ws.dnp;
+      SfPlanes in = ws.dnp;
       for (int n = 0; n < c.reid_layers; ++n) {
-        if (n + 1 == c.reid_layers) { HIP_TRY(gemm_f32(h->reid[n], in, M, embeds, C)); break; }
-        const MkdPlanes out = n & 1 ? ws.rb : ws.ra;
-        HIP_TRY(gemm_planes(h->reid[n], in, M, out, true));
+        if (n + 1 == c.reid_layers) { HIP_TRY(lin.f32(h->reid[n], in, M, embeds, C)); break; }
+        const SfPlanes out = n & 1 ? ws.rb : ws.ra;
+        HIP_TRY(lin.planes(h->reid[n], in, M, out, true));
         in = out;
       }
     }
-    HIP_TRY(gemm_planes(h->mlp[0], ws.dnp, M, ws.ma, true));
-    HIP_TRY(gemm_planes(h->mlp[1], ws.ma, M, ws.mb, true));
-    HIP_TRY(gemm_f32(h->mlp[2], ws.mb, M, ws.me, Dm));
+    HIP_TRY(lin.planes(h->mlp[0], ws.dnp, M, ws.ma, true));
+    HIP_TRY(lin.planes(h->mlp[1], ws.ma, M, ws.mb, true));
+    HIP_TRY(lin.f32(h->mlp[2], ws.mb, M, ws.me, Dm));
     SfMkdMask m;
     memset(&m, 0, sizeof(m));
     m.me = ws.me; m.F = F; m.Q = Q; m.Dm = Dm;

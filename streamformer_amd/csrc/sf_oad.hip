@@ -265,12 +265,12 @@ struct OadModule {
   SfDevLN fn;
   const float* qw = nullptr;           // enc_queries.j.weight [queries, d]
 };
-struct OadAct { float* f = nullptr; bf16_t* hi = nullptr; bf16_t* lo = nullptr; };      // an activation [rows, d]: fp32 + the GEMM operand planes
+struct OadAct { float* f = nullptr; SfPlanes p; };      // an activation [rows, d]: fp32 + the GEMM operand planes
 struct OadWorkspace {
   OadAct a[3];                         // rotating activations [R, d]
-  bf16_t *in_hi, *in_lo;               // split inputs [R, d_in]
+  SfPlanes in;                         // split inputs [R, d_in]
   float *tmp, *qkv, *q, *kv;           // GEMM outputs [R, d], [R, 3d], [R, d], [R, 2d]
-  bf16_t *ctx_hi, *ctx_lo, *mid_hi, *mid_lo;      // [R, d], [R, ffn]
+  SfPlanes ctx, mid;                   // [R, d], [R, ffn]
   float* scores;                       // [n W, Cp]
   size_t bytes;
 };
@@ -299,18 +299,18 @@ struct sf_oad_state {
 
 static void oad_expect_layer(sf_oad* h, const std::string& p, bool decoder) {
   const int64_t d = h->d, F = h->cfg.ffn;
-  auto& e = h->weights.expected;
+  SfWeightStore& w = h->weights;
   for (const char* a : {"self_attn.", "multihead_attn."}) {
     if (!decoder && a[0] == 'm') continue;
-    e[p + a + "in_proj_weight"] = {3 * d, d}; e[p + a + "in_proj_bias"] = {3 * d};
-    e[p + a + "out_proj.weight"] = {d, d}; e[p + a + "out_proj.bias"] = {d};
+    w.expected[p + a + "in_proj_weight"] = {3 * d, d};
+    w.expected[p + a + "in_proj_bias"] = {3 * d};
+    w.expect_linear(p + a + "out_proj.", d, d);
   }
-  e[p + "linear1.weight"] = {F, d}; e[p + "linear1.bias"] = {F};
-  e[p + "linear2.weight"] = {d, F}; e[p + "linear2.bias"] = {d};
-  for (const char* n : {"norm1.", "norm2.", "norm3."}) {
-    if (!decoder && n[4] == '3') continue;
-    e[p + n + "weight"] = {d}; e[p + n + "bias"] = {d};
-  }
+  w.expect_linear(p + "linear1.", F, d);
+  w.expect_linear(p + "linear2.", d, F);
+  w.expect_affine(p + "norm1.", d);
+  w.expect_affine(p + "norm2.", d);
+  if (decoder) w.expect_affine(p + "norm3.", d);
 }
 
 extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out) {
@@ -343,12 +343,13 @@ extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out)
   const int64_t d = h->d;
   h->weights.noun = "detector";
   h->weights.dtype_msg = "sf_oad_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
-  auto& e = h->weights.expected;
+  SfWeightStore& w = h->weights;
+  auto& e = w.expected;
   if (c.linear_enabled)
     for (const char* fh : {"feature_head_long.", "feature_head_work."}) {
       const std::string p = std::string(fh) + "visual_linear.";
-      e[p + "0.weight"] = {d, c.d_in}; e[p + "0.bias"] = {d};
-      e[p + "1.weight"] = {d}; e[p + "1.bias"] = {d};
+      w.expect_linear(p + "0.", d, c.d_in);
+      w.expect_affine(p + "1.", d);
     }
   for (int j = 0; j < c.enc_modules; ++j) {
     const std::string m = "enc_modules." + std::to_string(j) + ".";
@@ -357,11 +358,11 @@ extern "C" int sf_oad_create(const sf_oad_config* cfg, int device, sf_oad** out)
       if (c.enc_queries[j] > h->maxT) h->maxT = c.enc_queries[j];
     }
     for (int l = 0; l < c.enc_layers[j]; ++l) oad_expect_layer(h, m + "layers." + std::to_string(l) + ".", c.enc_queries[j] > 0);
-    if (c.enc_norm[j]) { e[m + "norm.weight"] = {d}; e[m + "norm.bias"] = {d}; }
+    if (c.enc_norm[j]) w.expect_affine(m + "norm.", d);
   }
   for (int l = 0; l < c.dec_layers; ++l) oad_expect_layer(h, "dec_modules.layers." + std::to_string(l) + ".", true);
-  if (c.dec_norm) { e["dec_modules.norm.weight"] = {d}; e["dec_modules.norm.bias"] = {d}; }
-  e["classifier.weight"] = {c.classes, d}; e["classifier.bias"] = {c.classes};
+  if (c.dec_norm) w.expect_affine("dec_modules.norm.", d);
+  w.expect_linear("classifier.", c.classes, d);
   e["pos_encoding.pe"] = {c.long_samples + c.work_samples, d};      // at least that many rows; [rows, 1, d] accepted
   *out = h;
   return SF_OK;
@@ -384,20 +385,6 @@ extern "C" int sf_oad_load_tensor(sf_oad* h, const char* key, const void* host_p
 
 extern "C" int sf_oad_missing_weights(sf_oad* h) { return sf_model_missing_weights(h); }
 
-static SfDevLinear oad_rows_of(const SfDevLinear& l, int row0, int rows, bool with_bias) {
-  SfDevLinear v = l;
-  v.w_hi = l.w_hi + (size_t)row0 * l.K;
-  v.w_lo = l.w_lo ? l.w_lo + (size_t)row0 * l.K : nullptr;
-  v.bias = with_bias ? l.bias + row0 : nullptr;
-  v.N = rows;
-  return v;
-}
-
-static int oad_upload_ln(sf_oad* h, const std::string& p, SfDevLN* ln) {
-  SF_TRY(h->dev.upload(h->weights.data(p + "weight"), &ln->g));
-  return h->dev.upload(h->weights.data(p + "bias"), &ln->b);
-}
-
 // [N, K] weight + bias -> the planes of the handle's compute mode; rows zero-padded to Np
 static int oad_upload_linear(sf_oad* h, const std::vector<float>& w, const std::vector<float>& bias, int N, int K, int Np, SfDevLinear* out) {
   return sf_upload_linear(h->dev, w, &bias, N, K, Np, h->compute == SF_COMPUTE_BF16X3, out);
@@ -412,27 +399,27 @@ static int oad_upload_layer(sf_oad* h, const std::string& p, bool decoder, bool 
   if (decoder) {
     SfDevLinear in;
     SF_TRY(oad_upload_linear(h, H("multihead_attn.in_proj_weight"), H("multihead_attn.in_proj_bias"), 3 * d, d, 3 * d, &in));
-    l->cross_q = oad_rows_of(in, 0, d, true);
-    l->cross_kv = oad_rows_of(in, d, 2 * d, !stage0);      // stage 0: the bias belongs to k_pos | v_pos
+    l->cross_q = sf_linear_rows(in, 0, d, in.bias);
+    l->cross_kv = sf_linear_rows(in, d, 2 * d, stage0 ? nullptr : in.bias + d);      // stage 0: the bias belongs to k_pos | v_pos
     SF_TRY(oad_upload_linear(h, H("multihead_attn.out_proj.weight"), H("multihead_attn.out_proj.bias"), d, d, d, &l->cross_out));
   }
   SF_TRY(oad_upload_linear(h, H("linear1.weight"), H("linear1.bias"), F, d, F, &l->lin1));
   SF_TRY(oad_upload_linear(h, H("linear2.weight"), H("linear2.bias"), d, F, d, &l->lin2));
-  SF_TRY(oad_upload_ln(h, p + "norm1.", &l->n1));
-  SF_TRY(oad_upload_ln(h, p + "norm2.", &l->n2));
-  if (decoder) SF_TRY(oad_upload_ln(h, p + "norm3.", &l->n3));
+  SF_TRY(sf_upload_ln(h->dev, h->weights, p + "norm1.", &l->n1));
+  SF_TRY(sf_upload_ln(h->dev, h->weights, p + "norm2.", &l->n2));
+  if (decoder) SF_TRY(sf_upload_ln(h->dev, h->weights, p + "norm3.", &l->n3));
   return SF_OK;
 }
 
 static OadWorkspace oad_carve(const sf_oad* h, void* base, int n) {
   OadWorkspace w;
-  SfCarver c(base);
+  SfCarver c(base, h->compute == SF_COMPUTE_BF16X3, true);      // the lo planes are set aside in either mode
   const size_t R = (size_t)n * h->maxT, d = h->d, F = h->cfg.ffn;
-  for (int i = 0; i < 3; ++i) { w.a[i].f = c.take<float>(R * d); w.a[i].hi = c.take<bf16_t>(R * d); w.a[i].lo = c.take<bf16_t>(R * d); }
-  w.in_hi = c.take<bf16_t>(R * h->cfg.d_in); w.in_lo = c.take<bf16_t>(R * h->cfg.d_in);
+  for (int i = 0; i < 3; ++i) { w.a[i].f = c.take<float>(R * d); w.a[i].p = c.planes(R * d); }
+  w.in = c.planes(R * h->cfg.d_in);
   w.tmp = c.take<float>(R * d); w.qkv = c.take<float>(R * 3 * d); w.q = c.take<float>(R * d); w.kv = c.take<float>(R * 2 * d);
-  w.ctx_hi = c.take<bf16_t>(R * d); w.ctx_lo = c.take<bf16_t>(R * d);
-  w.mid_hi = c.take<bf16_t>(R * F); w.mid_lo = c.take<bf16_t>(R * F);
+  w.ctx = c.planes(R * d);
+  w.mid = c.planes(R * F);
   w.scores = c.take<float>((size_t)n * h->cfg.work_samples * h->Cp);
   w.bytes = c.bytes();
   return w;
@@ -446,27 +433,23 @@ struct OadRun {
   sf_oad* h;
   OadWorkspace ws;
   hipStream_t s;
-  bool acc;
+  SfLinearCaller lin;
 
-  int gemm(const SfDevLinear& l, const bf16_t* a_hi, const bf16_t* a_lo, int M, int epi, float* out_f32, bf16_t* out_hi, bf16_t* out_lo) {
-    SfGemmArgs g = sf_linear_args(l, a_hi, a_lo, M, epi, h->cfg.act, acc);
-    g.out_f32 = out_f32; g.out_hi = out_hi; g.out_lo = acc ? out_lo : nullptr;
-    HIP_TRY(sf_launch_gemm(g, acc, s));
-    return SF_OK;
-  }
+  OadRun(sf_oad* det, void* workspace, int n, hipStream_t stream)
+      : h(det), ws(oad_carve(det, workspace, n)), s(stream), lin{det->compute == SF_COMPUTE_BF16X3, det->cfg.act, stream} {}
   // y = LN(x + r[row % r_mod]) -> fp32 + planes (y.f may be r)
   int add_ln(const float* x, const float* r, int r_mod, const SfDevLN& ln, const OadAct& y, int rows) {
     SfRowArgs p;
     memset(&p, 0, sizeof(p));
     p.x = x; p.r = r; p.r_mod = r_mod; p.gamma = ln.g; p.beta = ln.b; p.eps = h->cfg.eps;
-    p.y = y.f; p.y_hi = y.hi; p.y_lo = acc ? y.lo : nullptr; p.rows = rows; p.D = h->d;
+    p.y = y.f; p.y_hi = y.p.hi; p.y_lo = y.p.lo; p.rows = rows; p.D = h->d;
     HIP_TRY(oad_launch_row(p, s));
     return SF_OK;
   }
   SfOadAttn attn_args(int n, int Tq, int Tk, int causal) {
     SfOadAttn a;
     memset(&a, 0, sizeof(a));
-    a.ctx_hi = ws.ctx_hi; a.ctx_lo = acc ? ws.ctx_lo : nullptr;
+    a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
     a.streams = n; a.Tq = Tq; a.Tk = Tk; a.heads = h->cfg.heads; a.hd = h->hd; a.causal = causal;
     a.scale = 1.0f / sqrtf((float)h->hd);
     for (int i = 0; i < n; ++i) { a.kv_row0[i] = i * Tk; a.mask_row[i] = i; }
@@ -475,38 +458,35 @@ struct OadRun {
   // x = LN1(x + out_proj(attention(in_proj(x))))
   int self_block(const OadLayer& l, const OadAct& x, int n, int T, int causal) {
     const int d = h->d, M = n * T;
-    int rc;
-    if ((rc = gemm(l.self_in, x.hi, x.lo, M, SF_EPI_F32, ws.qkv, nullptr, nullptr))) return rc;
+    HIP_TRY(lin.f32(l.self_in, x.p, M, ws.qkv));
     SfOadAttn a = attn_args(n, T, T, causal);
     a.q = ws.qkv; a.k = ws.qkv + d; a.v = ws.qkv + 2 * d;
     a.q_pitch = a.kv_pitch = 3 * d; a.q_sstride = (long long)T * 3 * d;
     HIP_TRY(oad_launch_attention(a, s));
-    if ((rc = gemm(l.self_out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+    HIP_TRY(lin.f32(l.self_out, ws.ctx, M, ws.tmp));
     return add_ln(ws.tmp, x.f, 0, l.n1, x, M);
   }
   // x = LN2(x + out_proj(attention(q(x), kv(mem))))
   int cross_block(const OadLayer& l, const OadAct& x, int n, int T, const OadAct& mem, int Tm) {
     const int d = h->d, M = n * T;
-    int rc;
-    if ((rc = gemm(l.cross_q, x.hi, x.lo, M, SF_EPI_F32, ws.q, nullptr, nullptr))) return rc;
-    if ((rc = gemm(l.cross_kv, mem.hi, mem.lo, n * Tm, SF_EPI_F32, ws.kv, nullptr, nullptr))) return rc;
+    HIP_TRY(lin.f32(l.cross_q, x.p, M, ws.q));
+    HIP_TRY(lin.f32(l.cross_kv, mem.p, n * Tm, ws.kv));
     SfOadAttn a = attn_args(n, T, Tm, 0);
     a.q = ws.q; a.q_pitch = d; a.q_sstride = (long long)T * d;
     a.k = ws.kv; a.v = ws.kv + d; a.kv_pitch = 2 * d;
     HIP_TRY(oad_launch_attention(a, s));
-    if ((rc = gemm(l.cross_out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+    HIP_TRY(lin.f32(l.cross_out, ws.ctx, M, ws.tmp));
     return add_ln(ws.tmp, x.f, 0, l.n2, x, M);
   }
   // x = LN(x + linear2(act(linear1(x))))
   int ffn_block(const OadLayer& l, const SfDevLN& ln, const OadAct& x, int M) {
-    int rc;
-    if ((rc = gemm(l.lin1, x.hi, x.lo, M, SF_EPI_ACT_BF16, nullptr, ws.mid_hi, ws.mid_lo))) return rc;
-    if ((rc = gemm(l.lin2, ws.mid_hi, ws.mid_lo, M, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+    HIP_TRY(lin.planes(l.lin1, x.p, M, ws.mid, true));
+    HIP_TRY(lin.f32(l.lin2, ws.mid, M, ws.tmp));
     return add_ln(ws.tmp, x.f, 0, ln, x, M);
   }
   // the module's final norm, out of place on the encoder's LayerNorm kernel
   int final_norm(const SfDevLN& ln, const OadAct& x, const OadAct& y, int M) {
-    HIP_TRY(sf_launch_layernorm(x.f, ln.g, ln.b, y.f, y.hi, acc ? y.lo : nullptr, M, h->d, h->cfg.eps, s));
+    HIP_TRY(sf_launch_layernorm(x.f, ln.g, ln.b, y.f, y.p.hi, y.p.lo, M, h->d, h->cfg.eps, s));
     return SF_OK;
   }
 };
@@ -521,8 +501,8 @@ extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
   if (c.linear_enabled) {
     SF_TRY(oad_upload_linear(h, H("feature_head_long.visual_linear.0.weight"), H("feature_head_long.visual_linear.0.bias"), d, c.d_in, d, &h->fh_long));
     SF_TRY(oad_upload_linear(h, H("feature_head_work.visual_linear.0.weight"), H("feature_head_work.visual_linear.0.bias"), d, c.d_in, d, &h->fh_work));
-    SF_TRY(oad_upload_ln(h, "feature_head_long.visual_linear.1.", &h->fh_long_ln));
-    SF_TRY(oad_upload_ln(h, "feature_head_work.visual_linear.1.", &h->fh_work_ln));
+    SF_TRY(sf_upload_ln(h->dev, h->weights, "feature_head_long.visual_linear.1.", &h->fh_long_ln));
+    SF_TRY(sf_upload_ln(h->dev, h->weights, "feature_head_work.visual_linear.1.", &h->fh_work_ln));
   }
   h->enc.assign(c.enc_modules, OadModule());
   for (int j = 0; j < c.enc_modules; ++j) {
@@ -533,39 +513,40 @@ extern "C" int sf_oad_finalize(sf_oad* h, int compute) {
     if (m.queries > 0) SF_TRY(h->dev.upload(H("enc_queries." + std::to_string(j) + ".weight"), &m.qw));
     m.layers.assign(c.enc_layers[j], OadLayer());
     for (int l = 0; l < c.enc_layers[j]; ++l) SF_TRY(oad_upload_layer(h, p + "layers." + std::to_string(l) + ".", m.queries > 0, j == 0, &m.layers[l]));
-    if (m.norm) SF_TRY(oad_upload_ln(h, p + "norm.", &m.fn));
+    if (m.norm) SF_TRY(sf_upload_ln(h->dev, h->weights, p + "norm.", &m.fn));
   }
   h->dec.norm = c.dec_norm != 0;
   h->dec.layers.assign(c.dec_layers, OadLayer());
   for (int l = 0; l < c.dec_layers; ++l) SF_TRY(oad_upload_layer(h, "dec_modules.layers." + std::to_string(l) + ".", true, false, &h->dec.layers[l]));
-  if (h->dec.norm) SF_TRY(oad_upload_ln(h, "dec_modules.norm.", &h->dec.fn));
+  if (h->dec.norm) SF_TRY(sf_upload_ln(h->dev, h->weights, "dec_modules.norm.", &h->dec.fn));
   SF_TRY(oad_upload_linear(h, H("classifier.weight"), H("classifier.bias"), c.classes, d, h->Cp, &h->cls));
   SF_TRY(h->dev.upload(H("pos_encoding.pe"), &h->pe));
   // ---- what does not depend on the input: k_pos | v_pos = W_kv pe[:L] + b_kv; tgt0 = norm1(queries + self_attn(queries)); q0 = W_q tgt0 + b_q ----
   {
     SF_TRY(h->dev.alloc((size_t)L * 2 * d * 4, (void**)&h->pos_kv));
     SF_TRY(h->dev.alloc((size_t)Q0 * d * 4, (void**)&h->tgt0.f));
-    SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.hi));
-    SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.lo));
+    SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.p.hi));
+    h->tgt0.p.lo = nullptr;
+    if (compute == SF_COMPUTE_BF16X3) SF_TRY(h->dev.alloc((size_t)Q0 * d * 2, (void**)&h->tgt0.p.lo));
     SF_TRY(h->dev.alloc((size_t)Q0 * d * 4, (void**)&h->q0));
     void* wsp = nullptr;
     const size_t bytes = oad_carve(h, nullptr, 1).bytes;
     HIP_TRY(hipMalloc(&wsp, bytes));
-    OadRun r{h, oad_carve(h, wsp, 1), (hipStream_t)0, compute == SF_COMPUTE_BF16X3};
+    OadRun r(h, wsp, 1, (hipStream_t)0);
     const OadLayer& l0 = h->enc[0].layers[0];
     int rc = SF_OK;
     do {
       hipError_t e;
-      if ((e = sf_launch_split(h->pe, r.ws.a[0].hi, r.ws.a[0].lo, (size_t)L * d, r.s)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
+      if ((e = sf_launch_split(h->pe, r.ws.a[0].p.hi, r.ws.a[0].p.lo, (size_t)L * d, r.s)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
       SfDevLinear kvb = l0.cross_kv;
       kvb.bias = l0.cross_q.bias + d;      // the k | v rows of in_proj_bias
-      if ((rc = r.gemm(kvb, r.ws.a[0].hi, r.ws.a[0].lo, L, SF_EPI_F32, h->pos_kv, nullptr, nullptr))) break;
+      if ((e = r.lin.f32(kvb, r.ws.a[0].p, L, h->pos_kv)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
       SfOadRows t;
       memset(&t, 0, sizeof(t));
       t.n = 1; t.cnt[0] = Q0;
-      if ((e = oad_launch_rows(h->enc[0].qw, h->tgt0.f, h->tgt0.hi, h->tgt0.lo, d, t, r.s)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
+      if ((e = oad_launch_rows(h->enc[0].qw, h->tgt0.f, h->tgt0.p.hi, h->tgt0.p.lo, d, t, r.s)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
       if ((rc = r.self_block(l0, h->tgt0, 1, Q0, 0))) break;
-      if ((rc = r.gemm(l0.cross_q, h->tgt0.hi, h->tgt0.lo, Q0, SF_EPI_F32, h->q0, nullptr, nullptr))) break;
+      if ((e = r.lin.f32(l0.cross_q, h->tgt0.p, Q0, h->q0)) != hipSuccess) { rc = sf_set_err(SF_ERR_HIP, "sf_oad_finalize: %s", hipGetErrorString(e)); break; }
     } while (0);
     const hipError_t es = hipDeviceSynchronize();
     (void)hipFree(wsp);
@@ -669,7 +650,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
   }
   if (Rl && !long_dev) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: long samples announced but long_dev is null");
   if (((uintptr_t)work_dev | (uintptr_t)long_dev | (uintptr_t)mask_dev | (uintptr_t)out_dev) & 15) return sf_set_err(SF_ERR_INVALID, "sf_oad_step: buffers must be 16-byte aligned");
-  OadRun r{h, oad_carve(h, workspace, n), (hipStream_t)stream, h->compute == SF_COMPUTE_BF16X3};
+  OadRun r(h, workspace, n, (hipStream_t)stream);
   SF_TRY(sf_check_workspace("sf_oad_step", "sf_oad_workspace_bytes", workspace, workspace_bytes, r.ws.bytes));
   const OadWorkspace& ws = r.ws;
   hipStream_t s = r.s;
@@ -682,15 +663,14 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
     if (ln) { p.gamma = ln->g; p.beta = ln->b; p.relu = 1; }
     p.pe = pe; p.pe_mod = pe_mod;
     float* f32 = want_f32 ? y.f : nullptr;
-    bf16_t* lo = r.acc ? y.lo : nullptr;
-    if (pe) { p.q = f32; p.q_hi = y.hi; p.q_lo = lo; }      // the one output is the row with its position added
-    else { p.y = f32; p.y_hi = y.hi; p.y_lo = lo; }
+    if (pe) { p.q = f32; p.q_hi = y.p.hi; p.q_lo = y.p.lo; }      // the one output is the row with its position added
+    else { p.y = f32; p.y_hi = y.p.hi; p.y_lo = y.p.lo; }
     return oad_launch_row(p, s);
   };
   // ---- work memory: feature head + pe[L : L + W] ----
   if (c.linear_enabled) {
-    HIP_TRY(sf_launch_split(work_dev, ws.in_hi, r.acc ? ws.in_lo : nullptr, (size_t)n * W * c.d_in, s));
-    if ((rc = r.gemm(h->fh_work, ws.in_hi, ws.in_lo, n * W, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+    HIP_TRY(sf_launch_split(work_dev, ws.in.hi, ws.in.lo, (size_t)n * W * c.d_in, s));
+    HIP_TRY(r.lin.f32(h->fh_work, ws.in, n * W, ws.tmp));
     HIP_TRY(row_head(ws.tmp, &h->fh_work_ln, h->pe + (size_t)L * d, W, x, true, n * W));
   } else {
     HIP_TRY(row_head(work_dev, nullptr, h->pe + (size_t)L * d, W, x, true, n * W));
@@ -698,14 +678,14 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
   // ---- long memory: feature head of the new samples, W_k x | W_v x into the rings, compression stage 0 ----
   if (Rl) {
     if (c.linear_enabled) {
-      HIP_TRY(sf_launch_split(long_dev, ws.in_hi, r.acc ? ws.in_lo : nullptr, (size_t)Rl * c.d_in, s));
-      if ((rc = r.gemm(h->fh_long, ws.in_hi, ws.in_lo, Rl, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+      HIP_TRY(sf_launch_split(long_dev, ws.in.hi, ws.in.lo, (size_t)Rl * c.d_in, s));
+      HIP_TRY(r.lin.f32(h->fh_long, ws.in, Rl, ws.tmp));
       HIP_TRY(row_head(ws.tmp, &h->fh_long_ln, nullptr, 0, spare, false, Rl));
     } else {
-      HIP_TRY(sf_launch_split(long_dev, spare.hi, r.acc ? spare.lo : nullptr, (size_t)Rl * d, s));
+      HIP_TRY(sf_launch_split(long_dev, spare.p.hi, spare.p.lo, (size_t)Rl * d, s));
     }
     const OadLayer& l0 = h->enc[0].layers[0];
-    if ((rc = r.gemm(l0.cross_kv, spare.hi, spare.lo, Rl, SF_EPI_F32, ws.kv, nullptr, nullptr))) return rc;
+    HIP_TRY(r.lin.f32(l0.cross_kv, spare.p, Rl, ws.kv));
     SfOadRows put, keep;
     memset(&put, 0, sizeof(put));
     memset(&keep, 0, sizeof(keep));
@@ -730,7 +710,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
     a.kpos = h->pos_kv; a.vpos = h->pos_kv + d; a.pos_pitch = 2 * d;
     a.mask = mask_dev;
     HIP_TRY(oad_launch_attention(a, s));
-    if ((rc = r.gemm(l0.cross_out, ws.ctx_hi, ws.ctx_lo, n0 * Q0, SF_EPI_F32, ws.tmp, nullptr, nullptr))) return rc;
+    HIP_TRY(r.lin.f32(l0.cross_out, ws.ctx, n0 * Q0, ws.tmp));
     if ((rc = r.add_ln(ws.tmp, h->tgt0.f, Q0, l0.n2, mem, n0 * Q0))) return rc;
     if ((rc = r.ffn_block(l0, l0.n3, mem, n0 * Q0))) return rc;
     if (h->enc[0].norm) {
@@ -749,7 +729,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
     memset(&get, 0, sizeof(get));
     get.n = n;
     for (int i = 0; i < n; ++i) { get.src[i] = ids[i] * Q0; get.dst[i] = i * Q0; get.cnt[i] = Q0; }
-    HIP_TRY(oad_launch_rows(st->mem0, mem.f, mem.hi, r.acc ? mem.lo : nullptr, d, get, s));
+    HIP_TRY(oad_launch_rows(st->mem0, mem.f, mem.p.hi, mem.p.lo, d, get, s));
   }
   // ---- later compression stages ----
   for (size_t j = 1; j < h->enc.size(); ++j) {
@@ -760,7 +740,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
       memset(&rep, 0, sizeof(rep));
       rep.n = n;
       for (int i = 0; i < n; ++i) { rep.src[i] = 0; rep.dst[i] = i * Q; rep.cnt[i] = Q; }
-      HIP_TRY(oad_launch_rows(m.qw, spare.f, spare.hi, r.acc ? spare.lo : nullptr, d, rep, s));
+      HIP_TRY(oad_launch_rows(m.qw, spare.f, spare.p.hi, spare.p.lo, d, rep, s));
       for (const OadLayer& l : m.layers) {
         if ((rc = r.self_block(l, spare, n, Q, 0))) return rc;
         if ((rc = r.cross_block(l, spare, n, Q, mem, Tm))) return rc;
@@ -789,7 +769,7 @@ extern "C" int sf_oad_step(sf_oad* h, sf_oad_state* st, const int32_t* ids, int 
     if ((rc = r.final_norm(h->dec.fn, x, spare, n * W))) return rc;
     std::swap(x, spare);
   }
-  if ((rc = r.gemm(h->cls, x.hi, x.lo, n * W, SF_EPI_F32, ws.scores, nullptr, nullptr))) return rc;
+  HIP_TRY(r.lin.f32(h->cls, x.p, n * W, ws.scores));
   HIP_TRY(sf_launch(sf_oad_scores_kernel, dim3((unsigned)((n * W + 3) / 4)), dim3(256), 0, s, ws.scores, out_dev, n * W, h->Cp, c.classes, probs));
   return SF_OK;
 }

@@ -353,16 +353,14 @@ static int pxd_chunk_rows(int requested, int C) {
   return (int)(rows < cap ? rows : cap);
 }
 
-// out [F H W, N] fp32 = conv3x3(in planes, w [N, 9 C] in (dy, dx, c) order), padding 1, no bias; col_*: [chunk, 9 C] planes
-static int pxd_conv3x3(const bf16_t* in_hi, const bf16_t* in_lo, const SfDevLinear& w, int F, int H, int W, int C, int chunk, bf16_t* col_hi,
-                       bf16_t* col_lo, float* out, bool split, hipStream_t s) {
+// out [F H W, N] fp32 = conv3x3(in planes, w [N, 9 C] in (dy, dx, c) order), padding 1, no bias; col: [chunk, 9 C] planes
+static int pxd_conv3x3(const SfPlanes& in, const SfDevLinear& w, int F, int H, int W, int C, int chunk, const SfPlanes& col, float* out,
+                       const SfLinearCaller& lin) {
   const long long rows = (long long)F * H * W;
   for (long long r0 = 0; r0 < rows; r0 += chunk) {
     const int n = (int)(rows - r0 < chunk ? rows - r0 : chunk);
-    HIP_TRY(pxd_launch_im2col(in_hi, split ? in_lo : nullptr, col_hi, split ? col_lo : nullptr, H, W, C, r0, n, s));
-    SfGemmArgs g = sf_linear_args(w, col_hi, col_lo, n, SF_EPI_F32, 0, split);
-    g.out_f32 = out + (size_t)r0 * w.N;
-    HIP_TRY(sf_launch_gemm(g, split, s));
+    HIP_TRY(pxd_launch_im2col(in.hi, in.lo, col.hi, col.lo, H, W, C, r0, n, lin.stream));
+    HIP_TRY(lin.f32(w, col, n, out + (size_t)r0 * w.N));
   }
   return SF_OK;
 }
@@ -448,28 +446,19 @@ extern "C" int sf_pixdec_create(const sf_pixdec_config* cfg, int device, sf_pixd
     const std::string p = "input_proj." + std::to_string(j) + ".";
     w.expected[p + "0.weight"] = {C, c.channels[h->tr_level[j]], 1, 1};
     w.expected[p + "0.bias"] = {C};
-    w.expected[p + "1.weight"] = {C};
-    w.expected[p + "1.bias"] = {C};
+    w.expect_affine(p + "1.", C);
   }
   w.expected["transformer.level_embed"] = {h->n_tr, C};
   for (int i = 0; i < c.enc_layers; ++i) {
     const std::string p = "transformer.encoder.layers." + std::to_string(i) + ".";
-    w.expected[p + "self_attn.sampling_offsets.weight"] = {2 * n_front, C};
-    w.expected[p + "self_attn.sampling_offsets.bias"] = {2 * n_front};
-    w.expected[p + "self_attn.attention_weights.weight"] = {n_front, C};
-    w.expected[p + "self_attn.attention_weights.bias"] = {n_front};
-    for (const char* n : {"self_attn.value_proj", "self_attn.output_proj"}) {
-      w.expected[p + n + ".weight"] = {C, C};
-      w.expected[p + n + ".bias"] = {C};
-    }
-    w.expected[p + "linear1.weight"] = {Fd, C};
-    w.expected[p + "linear1.bias"] = {Fd};
-    w.expected[p + "linear2.weight"] = {C, Fd};
-    w.expected[p + "linear2.bias"] = {C};
-    for (const char* n : {"norm1", "norm2"}) {
-      w.expected[p + n + ".weight"] = {C};
-      w.expected[p + n + ".bias"] = {C};
-    }
+    w.expect_linear(p + "self_attn.sampling_offsets.", 2 * n_front, C);
+    w.expect_linear(p + "self_attn.attention_weights.", n_front, C);
+    w.expect_linear(p + "self_attn.value_proj.", C, C);
+    w.expect_linear(p + "self_attn.output_proj.", C, C);
+    w.expect_linear(p + "linear1.", Fd, C);
+    w.expect_linear(p + "linear2.", C, Fd);
+    w.expect_affine(p + "norm1.", C);
+    w.expect_affine(p + "norm2.", C);
   }
   w.expected["mask_features.weight"] = {c.mask_dim, C, 1, 1};
   w.expected["mask_features.bias"] = {c.mask_dim};
@@ -477,10 +466,8 @@ extern "C" int sf_pixdec_create(const sf_pixdec_config* cfg, int device, sf_pixd
     const std::string a = "adapter_" + std::to_string(k + 1) + ".", l = "layer_" + std::to_string(k + 1) + ".";
     w.expected[a + "weight"] = {C, c.channels[k], 1, 1};
     w.expected[l + "weight"] = {C, C, 3, 3};
-    for (const std::string& p : {a, l}) {
-      w.expected[p + "norm.weight"] = {C};
-      w.expected[p + "norm.bias"] = {C};
-    }
+    w.expect_affine(a + "norm.", C);
+    w.expect_affine(l + "norm.", C);
   }
   *out = h;
   return SF_OK;
@@ -505,16 +492,12 @@ extern "C" int sf_pixdec_finalize(sf_pixdec* h, int compute) {
   auto linear = [&](const std::string& p, int N, int K, bool bias, SfDevLinear* out) {
     return sf_upload_linear(h->dev, w.data(p + "weight"), bias ? &w.data(p + "bias") : nullptr, N, K, N, lo, out);
   };
-  auto norm = [&](const std::string& p, SfDevLN* out) {
-    SF_TRY(h->dev.upload(w.data(p + "weight"), &out->g));
-    return h->dev.upload(w.data(p + "bias"), &out->b);
-  };
   h->proj.assign(h->n_tr, SfDevLinear());
   h->proj_norm.assign(h->n_tr, SfDevLN());
   for (int j = 0; j < h->n_tr; ++j) {
     const std::string p = "input_proj." + std::to_string(j) + ".";
     SF_TRY(linear(p + "0.", C, c.channels[h->tr_level[j]], true, &h->proj[j]));
-    SF_TRY(norm(p + "1.", &h->proj_norm[j]));
+    SF_TRY(sf_upload_ln(h->dev, w, p + "1.", &h->proj_norm[j]));
   }
   SF_TRY(h->dev.upload(w.data("transformer.level_embed"), &h->level_embed));
   h->layers.assign(c.enc_layers, PxdEncLayer());
@@ -531,8 +514,8 @@ extern "C" int sf_pixdec_finalize(sf_pixdec* h, int compute) {
     SF_TRY(linear(p + "self_attn.output_proj.", C, C, true, &L.out));
     SF_TRY(linear(p + "linear1.", Fd, C, true, &L.lin1));
     SF_TRY(linear(p + "linear2.", C, Fd, true, &L.lin2));
-    SF_TRY(norm(p + "norm1.", &L.norm1));
-    SF_TRY(norm(p + "norm2.", &L.norm2));
+    SF_TRY(sf_upload_ln(h->dev, w, p + "norm1.", &L.norm1));
+    SF_TRY(sf_upload_ln(h->dev, w, p + "norm2.", &L.norm2));
   }
   SF_TRY(linear("mask_features.", c.mask_dim, C, true, &h->mask));
   h->fpn.assign(h->n_fpn, PxdFpn());
@@ -545,8 +528,8 @@ extern "C" int sf_pixdec_finalize(sf_pixdec* h, int compute) {
       for (int i = 0; i < C; ++i)
         for (int t = 0; t < 9; ++t) re[((size_t)o * 9 + t) * C + i] = src[((size_t)o * C + i) * 9 + t];
     SF_TRY(sf_upload_linear(h->dev, re, nullptr, C, 9 * C, C, lo, &h->fpn[k].conv));
-    SF_TRY(norm(a + "norm.", &h->fpn[k].lateral_norm));
-    SF_TRY(norm(l + "norm.", &h->fpn[k].conv_norm));
+    SF_TRY(sf_upload_ln(h->dev, w, a + "norm.", &h->fpn[k].lateral_norm));
+    SF_TRY(sf_upload_ln(h->dev, w, l + "norm.", &h->fpn[k].conv_norm));
   }
   h->finalized = true;
   return SF_OK;
@@ -604,11 +587,11 @@ static int pxd_plan(const sf_pixdec* h, int F, const int32_t* level_shapes, int 
 
 struct PxdWorkspace {
   float *pos, *ref, *stats;
-  bf16_t *in_hi, *in_lo;                 // an input level as planes
+  SfPlanes in;                           // an input level as planes
   float* pre;                            // a GEMM's output in front of its GroupNorm [max rows, C]
   float *src, *tmp, *value, *front, *ctx;
-  bf16_t *a_hi, *a_lo, *q_hi, *q_lo, *c_hi, *c_lo, *h_hi, *h_lo;
-  bf16_t *sum_hi, *sum_lo, *col_hi, *col_lo, *fo_hi, *fo_lo;
+  SfPlanes a, q, c, h;                   // GEMM operands: src, src + pos, the attention's output, the FFN's hidden rows
+  SfPlanes sum, col, fo_p;               // FPN: lateral + upsampled, the gathered 3 x 3 operand, the finest output
   float* fo[2];                          // FPN outputs, ping-pong: the previous level is the next one's upsample source
   float* mf;                             // mask_features as rows
   size_t bytes;
@@ -617,34 +600,31 @@ struct PxdWorkspace {
 static PxdWorkspace pxd_carve(const sf_pixdec* h, const PxdPlan& pl, void* base) {
   PxdWorkspace w;
   memset(&w, 0, sizeof(w));
-  SfCarver cv(base);
-  const bool split = h->compute == SF_COMPUTE_BF16X3;
+  SfCarver cv(base, h->compute == SF_COMPUTE_BF16X3);
   const size_t C = h->cfg.conv_dim, Fd = h->cfg.dim_feedforward, Mt = (size_t)pl.Mt, Mf = (size_t)pl.Mf;
   const size_t NF = (size_t)3 * h->cfg.nheads * h->n_tr * h->cfg.enc_n_points;
   w.pos = cv.take<float>((size_t)pl.S * C);
   w.ref = cv.take<float>(Mt * h->n_tr * 2);
   w.stats = cv.take<float>((size_t)pl.F * PXD_GROUPS * 4);
-  w.in_hi = cv.take<bf16_t>((size_t)pl.Min);
-  if (split) w.in_lo = cv.take<bf16_t>((size_t)pl.Min);
+  w.in = cv.planes((size_t)pl.Min);
   w.pre = cv.take<float>(std::max(Mt, Mf) * C);
   w.src = cv.take<float>(Mt * C);
-  w.a_hi = cv.take<bf16_t>(Mt * C);
-  if (split) w.a_lo = cv.take<bf16_t>(Mt * C);
+  w.a = cv.planes(Mt * C);
   if (h->cfg.enc_layers) {
     w.tmp = cv.take<float>(Mt * C);
     w.value = cv.take<float>(Mt * C);
     w.front = cv.take<float>(Mt * NF);
     w.ctx = cv.take<float>(Mt * C);
-    w.q_hi = cv.take<bf16_t>(Mt * C);
-    w.c_hi = cv.take<bf16_t>(Mt * C);
-    w.h_hi = cv.take<bf16_t>(Mt * Fd);
-    if (split) { w.q_lo = cv.take<bf16_t>(Mt * C); w.c_lo = cv.take<bf16_t>(Mt * C); w.h_lo = cv.take<bf16_t>(Mt * Fd); }
+    w.q.hi = cv.take<bf16_t>(Mt * C);      // the three hi planes, then the three lo planes
+    w.c.hi = cv.take<bf16_t>(Mt * C);
+    w.h.hi = cv.take<bf16_t>(Mt * Fd);
+    w.q.lo = cv.lo(Mt * C); w.c.lo = cv.lo(Mt * C); w.h.lo = cv.lo(Mt * Fd);
   }
   if (h->n_fpn) {
-    w.sum_hi = cv.take<bf16_t>(Mf * C);
-    w.col_hi = cv.take<bf16_t>((size_t)pl.chunk * 9 * C);
-    w.fo_hi = cv.take<bf16_t>(Mf * C);
-    if (split) { w.sum_lo = cv.take<bf16_t>(Mf * C); w.col_lo = cv.take<bf16_t>((size_t)pl.chunk * 9 * C); w.fo_lo = cv.take<bf16_t>(Mf * C); }
+    w.sum.hi = cv.take<bf16_t>(Mf * C);
+    w.col.hi = cv.take<bf16_t>((size_t)pl.chunk * 9 * C);
+    w.fo_p.hi = cv.take<bf16_t>(Mf * C);
+    w.sum.lo = cv.lo(Mf * C); w.col.lo = cv.lo((size_t)pl.chunk * 9 * C); w.fo_p.lo = cv.lo(Mf * C);
     w.fo[0] = cv.take<float>(Mf * C);
     w.fo[1] = cv.take<float>(Mf * C);
   }
@@ -693,7 +673,7 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   const PxdWorkspace ws = pxd_carve(h, pl, workspace_dev);
   SF_TRY(sf_check_workspace(who, "sf_pixdec_workspace_bytes", workspace_dev, workspace_bytes, ws.bytes));
   hipStream_t s = (hipStream_t)stream;
-  const bool split = h->compute == SF_COMPUTE_BF16X3;
+  const SfLinearCaller lin{h->compute == SF_COMPUTE_BF16X3, 2, s};      // act 2: ReLU
   const int C = cfg.conv_dim, S = pl.S, L = h->n_tr, Mt = (int)pl.Mt;
 
   // ---- position table (+ level_embed) and reference points ----
@@ -706,16 +686,14 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   // ---- input projections: 1 x 1 convolution + GroupNorm into the level's slice of [F, S, C], coarsest first ----
   for (int j = 0; j < L; ++j) {
     const int l = h->tr_level[j], HW = pl.H[l] * pl.W[l];
-    HIP_TRY(pxd_launch_nchw_planes(features_dev[l], ws.in_hi, split ? ws.in_lo : nullptr, F, cfg.channels[l], HW, s));
-    SfGemmArgs g = sf_linear_args(h->proj[j], ws.in_hi, ws.in_lo, F * HW, SF_EPI_F32, 0, split);
-    g.out_f32 = ws.pre;
-    HIP_TRY(sf_launch_gemm(g, split, s));
+    HIP_TRY(pxd_launch_nchw_planes(features_dev[l], ws.in.hi, ws.in.lo, F, cfg.channels[l], HW, s));
+    HIP_TRY(lin.f32(h->proj[j], ws.in, F * HW, ws.pre));
     SfPxdGn n;
     memset(&n, 0, sizeof(n));
     n.x = ws.pre; n.stats = ws.stats; n.gamma = h->proj_norm[j].g; n.beta = h->proj_norm[j].b;
     n.F = F; n.H = pl.H[l]; n.W = pl.W[l]; n.C = C;
-    n.y = ws.src; n.y_hi = ws.a_hi; n.y_lo = split ? ws.a_lo : nullptr;
-    if (cfg.enc_layers) { n.pos = ws.pos; n.q_hi = ws.q_hi; n.q_lo = split ? ws.q_lo : nullptr; }
+    n.y = ws.src; n.y_hi = ws.a.hi; n.y_lo = ws.a.lo;
+    if (cfg.enc_layers) { n.pos = ws.pos; n.q_hi = ws.q.hi; n.q_lo = ws.q.lo; }
     n.out_frame_rows = S; n.out_row0 = pl.geom.start[j];
     HIP_TRY(pxd_launch_groupnorm(n, s));
   }
@@ -724,27 +702,16 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   for (int i = 0; i < cfg.enc_layers; ++i) {
     const PxdEncLayer& ly = h->layers[i];
     const bool last = i + 1 == cfg.enc_layers;
-    SfGemmArgs g = sf_linear_args(ly.value, ws.a_hi, ws.a_lo, Mt, SF_EPI_F32, 0, split);
-    g.out_f32 = ws.value;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-    g = sf_linear_args(ly.front, ws.q_hi, ws.q_lo, Mt, SF_EPI_F32, 0, split);
-    g.out_f32 = ws.front;
-    HIP_TRY(sf_launch_gemm(g, split, s));
+    HIP_TRY(lin.f32(ly.value, ws.a, Mt, ws.value));
+    HIP_TRY(lin.f32(ly.front, ws.q, Mt, ws.front));
     SF_TRY(sf_op_msda_forward_fused(ws.value, nullptr, pl.tr_shapes, pl.tr_start, ws.front, 3 * n_front, ws.front + 2 * n_front, 3 * n_front, ws.ref, 2,
                                     ws.ctx, F, S, cfg.nheads, C / cfg.nheads, S, L, cfg.enc_n_points, stream));
-    HIP_TRY(sf_launch_split(ws.ctx, ws.c_hi, split ? ws.c_lo : nullptr, (size_t)Mt * C, s));
-    g = sf_linear_args(ly.out, ws.c_hi, ws.c_lo, Mt, SF_EPI_RESID_F32, 0, split);
-    g.resid = ws.src; g.out_f32 = ws.tmp;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm1, PXD_LN_EPS, nullptr, 0, ws.src, ws.a_hi, split ? ws.a_lo : nullptr, nullptr, nullptr, Mt, C, s));
-    g = sf_linear_args(ly.lin1, ws.a_hi, ws.a_lo, Mt, SF_EPI_ACT_BF16, 2, split);
-    g.out_hi = ws.h_hi; g.out_lo = split ? ws.h_lo : nullptr;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-    g = sf_linear_args(ly.lin2, ws.h_hi, ws.h_lo, Mt, SF_EPI_RESID_F32, 0, split);
-    g.resid = ws.src; g.out_f32 = ws.tmp;
-    HIP_TRY(sf_launch_gemm(g, split, s));
-    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm2, PXD_LN_EPS, ws.pos, S, ws.src, ws.a_hi, split ? ws.a_lo : nullptr, last ? nullptr : ws.q_hi,
-                              split ? ws.q_lo : nullptr, Mt, C, s));
+    HIP_TRY(sf_launch_split(ws.ctx, ws.c.hi, ws.c.lo, (size_t)Mt * C, s));
+    HIP_TRY(lin.resid(ly.out, ws.c, Mt, ws.src, ws.tmp));
+    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm1, PXD_LN_EPS, nullptr, 0, ws.src, ws.a.hi, ws.a.lo, nullptr, nullptr, Mt, C, s));
+    HIP_TRY(lin.planes(ly.lin1, ws.a, Mt, ws.h, true));
+    HIP_TRY(lin.resid(ly.lin2, ws.h, Mt, ws.src, ws.tmp));
+    HIP_TRY(pxd_launch_postln(ws.tmp, ly.norm2, PXD_LN_EPS, ws.pos, S, ws.src, ws.a.hi, ws.a.lo, last ? nullptr : ws.q.hi, ws.q.lo, Mt, C, s));
   }
   // ---- the transformer's levels among the outputs ----
   for (int j = 0; j < L && j < pl.n_out; ++j) {
@@ -758,24 +725,22 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   for (int k = h->n_fpn - 1, idx = 0; k >= 0; --k, ++idx) {
     const PxdFpn& fp = h->fpn[k];
     const int H = pl.H[k], W = pl.W[k], M = F * H * W;
-    HIP_TRY(pxd_launch_nchw_planes(features_dev[k], ws.in_hi, split ? ws.in_lo : nullptr, F, cfg.channels[k], H * W, s));
-    SfGemmArgs g = sf_linear_args(fp.lateral, ws.in_hi, ws.in_lo, M, SF_EPI_F32, 0, split);
-    g.out_f32 = ws.pre;
-    HIP_TRY(sf_launch_gemm(g, split, s));
+    HIP_TRY(pxd_launch_nchw_planes(features_dev[k], ws.in.hi, ws.in.lo, F, cfg.channels[k], H * W, s));
+    HIP_TRY(lin.f32(fp.lateral, ws.in, M, ws.pre));
     SfPxdGn n;
     memset(&n, 0, sizeof(n));
     n.x = ws.pre; n.stats = ws.stats; n.gamma = fp.lateral_norm.g; n.beta = fp.lateral_norm.b;
     n.F = F; n.H = H; n.W = W; n.C = C;
     n.prev = prev; n.prev_frame_stride = prev_stride; n.Hp = Hp; n.Wp = Wp;
-    n.y_hi = ws.sum_hi; n.y_lo = split ? ws.sum_lo : nullptr; n.out_frame_rows = H * W;
+    n.y_hi = ws.sum.hi; n.y_lo = ws.sum.lo; n.out_frame_rows = H * W;
     HIP_TRY(pxd_launch_groupnorm(n, s));
-    SF_TRY(pxd_conv3x3(ws.sum_hi, ws.sum_lo, fp.conv, F, H, W, C, pl.chunk, ws.col_hi, ws.col_lo, ws.pre, split, s));
+    SF_TRY(pxd_conv3x3(ws.sum, fp.conv, F, H, W, C, pl.chunk, ws.col, ws.pre, lin));
     float* fo = ws.fo[idx & 1];
     memset(&n, 0, sizeof(n));
     n.x = ws.pre; n.stats = ws.stats; n.gamma = fp.conv_norm.g; n.beta = fp.conv_norm.b; n.relu = 1;
     n.F = F; n.H = H; n.W = W; n.C = C; n.out_frame_rows = H * W;
     n.y = fo;
-    if (k == 0) { n.y_hi = ws.fo_hi; n.y_lo = split ? ws.fo_lo : nullptr; }
+    if (k == 0) { n.y_hi = ws.fo_p.hi; n.y_lo = ws.fo_p.lo; }
     HIP_TRY(pxd_launch_groupnorm(n, s));
     if (L + idx < pl.n_out) HIP_TRY(pxd_launch_rows_nchw(fo, (long long)H * W * C, multi_scale_dev[L + idx], F, C, H * W, s));
     prev = fo; prev_stride = (long long)H * W * C; Hp = H; Wp = W;
@@ -784,9 +749,7 @@ extern "C" int sf_pixdec_forward(sf_pixdec* h, const float* const* features_dev,
   {
     const bool fpn = h->n_fpn > 0;
     const int M = fpn ? F * Hp * Wp : Mt;      // without an FPN level: all rows of [F, S, C]; the finest level's slice leaves
-    SfGemmArgs g = sf_linear_args(h->mask, fpn ? ws.fo_hi : ws.a_hi, fpn ? ws.fo_lo : ws.a_lo, M, SF_EPI_F32, 0, split);
-    g.out_f32 = ws.mf;
-    HIP_TRY(sf_launch_gemm(g, split, s));
+    HIP_TRY(lin.f32(h->mask, fpn ? ws.fo_p : ws.a, M, ws.mf));
     const float* rows = fpn ? ws.mf : ws.mf + (size_t)pl.geom.start[L - 1] * cfg.mask_dim;
     const long long stride = fpn ? (long long)Hp * Wp * cfg.mask_dim : (long long)S * cfg.mask_dim;
     HIP_TRY(pxd_launch_rows_nchw(rows, stride, mask_features_dev, F, cfg.mask_dim, Hp * Wp, s));
@@ -914,10 +877,11 @@ extern "C" int sf_op_pixdec_conv3x3(const uint16_t* in_hi_dev, const uint16_t* i
   SF_TRY(sf_check_workspace(who, "sf_op_pixdec_conv3x3_workspace_bytes", workspace_dev, workspace_bytes, sf_op_pixdec_conv3x3_workspace_bytes(F, H, W, C, chunk_rows)));
   long long chunk = pxd_chunk_rows(chunk_rows, C);
   if (chunk > (long long)F * H * W) chunk = (long long)F * H * W;
-  SfCarver cv(workspace_dev);
-  bf16_t* col_hi = cv.take<bf16_t>((size_t)chunk * 9 * C);
-  bf16_t* col_lo = cv.take<bf16_t>((size_t)chunk * 9 * C);
+  const SfLinearCaller lin{in_lo_dev != nullptr, 0, (hipStream_t)stream};
+  SfCarver cv(workspace_dev, lin.split, true);      // the workspace holds both planes in either mode
+  SfPlanes in;                                       // read only
+  in.hi = const_cast<uint16_t*>(in_hi_dev); in.lo = const_cast<uint16_t*>(in_lo_dev);
   SfDevLinear w;
   w.w_hi = w_hi_dev; w.w_lo = w_lo_dev; w.N = N; w.K = 9 * C;
-  return pxd_conv3x3(in_hi_dev, in_lo_dev, w, F, H, W, C, (int)chunk, col_hi, col_lo, out_dev, in_lo_dev != nullptr, (hipStream_t)stream);
+  return pxd_conv3x3(in, w, F, H, W, C, (int)chunk, cv.planes((size_t)chunk * 9 * C), out_dev, lin);
 }

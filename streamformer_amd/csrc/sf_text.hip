@@ -296,20 +296,20 @@ struct sf_text : SfModelHandle {              // weights: q / k / v arrive separ
 
 struct TextWorkspace {
   float* resid; float* qkv; float* pooled;
-  bf16_t *xn_hi, *xn_lo, *ctx_hi, *ctx_lo, *mid_hi, *mid_lo;
+  SfPlanes xn, ctx, mid;      // GEMM operands: the normalised rows, the attention's output, the MLP's hidden rows
   size_t bytes;
 };
 
 static TextWorkspace text_carve(const sf_text* t, void* base, int B, int L) {
   TextWorkspace w;
-  SfCarver c(base);
+  SfCarver c(base, t->compute == SF_COMPUTE_BF16X3, true);      // the lo planes are set aside in either mode
   const size_t M = (size_t)B * L, D = t->D, I = t->I;
   w.resid = c.take<float>(M * D);
   w.qkv = c.take<float>(M * 3 * D);
   w.pooled = c.take<float>((size_t)B * t->cfg.projection);
-  w.xn_hi = c.take<bf16_t>(M * D); w.xn_lo = c.take<bf16_t>(M * D);
-  w.ctx_hi = c.take<bf16_t>(M * D); w.ctx_lo = c.take<bf16_t>(M * D);
-  w.mid_hi = c.take<bf16_t>(M * I); w.mid_lo = c.take<bf16_t>(M * I);
+  w.xn = c.planes(M * D);
+  w.ctx = c.planes(M * D);
+  w.mid = c.planes(M * I);
   w.bytes = c.bytes();
   return w;
 }
@@ -320,21 +320,19 @@ static void text_expected(sf_text* t) {
   t->weights.noun = "text model";
   t->weights.prefix = "text_model.";
   t->weights.dtype_msg = "sf_text_load_tensor: dtype %d unsupported (fp32, fp64, bf16)";
-  auto& e = t->weights.expected;
-  e["embeddings.token_embedding.weight"] = {c.vocab, D};
-  e["embeddings.position_embedding.weight"] = {c.positions, D};
+  SfWeightStore& w = t->weights;
+  w.expected["embeddings.token_embedding.weight"] = {c.vocab, D};
+  w.expected["embeddings.position_embedding.weight"] = {c.positions, D};
   for (int i = 0; i < c.layers; ++i) {
     const std::string p = "encoder.layers." + std::to_string(i) + ".";
-    for (const char* ln : {"layer_norm1", "layer_norm2"}) { e[p + ln + ".weight"] = {D}; e[p + ln + ".bias"] = {D}; }
-    for (const char* a : {"q_proj", "k_proj", "v_proj", "out_proj"}) {
-      e[p + "self_attn." + a + ".weight"] = {D, D};
-      e[p + "self_attn." + a + ".bias"] = {D};
-    }
-    e[p + "mlp.fc1.weight"] = {I, D}; e[p + "mlp.fc1.bias"] = {I};
-    e[p + "mlp.fc2.weight"] = {D, I}; e[p + "mlp.fc2.bias"] = {D};
+    w.expect_affine(p + "layer_norm1.", D);
+    w.expect_affine(p + "layer_norm2.", D);
+    for (const char* a : {"q_proj.", "k_proj.", "v_proj.", "out_proj."}) w.expect_linear(p + "self_attn." + a, D, D);
+    w.expect_linear(p + "mlp.fc1.", I, D);
+    w.expect_linear(p + "mlp.fc2.", D, I);
   }
-  e["final_layer_norm.weight"] = {D}; e["final_layer_norm.bias"] = {D};
-  e["head.weight"] = {c.projection, D}; e["head.bias"] = {c.projection};
+  w.expect_affine("final_layer_norm.", D);
+  w.expect_linear("head.", c.projection, D);
 }
 
 extern "C" int sf_text_create(const sf_text_config* cfg, int device, sf_text** out) {
@@ -385,8 +383,8 @@ extern "C" int sf_text_finalize(sf_text* t, int compute) {
   for (int i = 0; i < t->cfg.layers; ++i) {
     const std::string p = "encoder.layers." + std::to_string(i) + ".";
     TextLayer& l = t->layers[i];
-    SF_TRY(dev.upload(H(p + "layer_norm1.weight"), &l.ln1.g)); SF_TRY(dev.upload(H(p + "layer_norm1.bias"), &l.ln1.b));
-    SF_TRY(dev.upload(H(p + "layer_norm2.weight"), &l.ln2.g)); SF_TRY(dev.upload(H(p + "layer_norm2.bias"), &l.ln2.b));
+    SF_TRY(sf_upload_ln(dev, t->weights, p + "layer_norm1.", &l.ln1));
+    SF_TRY(sf_upload_ln(dev, t->weights, p + "layer_norm2.", &l.ln2));
     {   // q_proj | k_proj | v_proj -> one [3D, D] Linear
       std::vector<float> w, b;
       w.reserve((size_t)3 * D * D); b.reserve((size_t)3 * D);
@@ -411,8 +409,7 @@ extern "C" int sf_text_finalize(sf_text* t, int compute) {
       SF_TRY(sf_upload_linear(dev, w2, &H(p + "mlp.fc2.bias"), D, I, D, split, &l.fc2));
     }
   }
-  SF_TRY(dev.upload(H("final_layer_norm.weight"), &t->final_ln.g));
-  SF_TRY(dev.upload(H("final_layer_norm.bias"), &t->final_ln.b));
+  SF_TRY(sf_upload_ln(dev, t->weights, "final_layer_norm.", &t->final_ln));
   SF_TRY(dev.upload(H("head.weight"), &t->head_w));
   SF_TRY(dev.upload(H("head.bias"), &t->head_b));
   t->finalized = true;
@@ -448,38 +445,22 @@ static int text_forward(sf_text* t, const int32_t* ids, const uint8_t* mask, int
   SF_TRY(sf_check_workspace("sf_text_forward", "sf_text_workspace_bytes", workspace, workspace_bytes, ws.bytes));
   const sf_text_config& c = t->cfg;
   const int D = t->D, M = B * L;
-  const bool acc = t->compute == SF_COMPUTE_BF16X3;
+  const SfLinearCaller lin{t->compute == SF_COMPUTE_BF16X3, c.act, s};
   HIP_TRY(text_launch_embed(ids, t->tok, t->pos, ws.resid, M, L, D, c.vocab, s));
   for (const TextLayer& l : t->layers) {
-    HIP_TRY(sf_launch_layernorm(ws.resid, l.ln1.g, l.ln1.b, nullptr, ws.xn_hi, acc ? ws.xn_lo : nullptr, M, D, c.eps, s));
-    {
-      SfGemmArgs g = sf_linear_args(l.qkv, ws.xn_hi, ws.xn_lo, M, SF_EPI_F32, c.act, acc);
-      g.out_f32 = ws.qkv;
-      HIP_TRY(sf_launch_gemm(g, acc, s));
-    }
+    HIP_TRY(sf_launch_layernorm(ws.resid, l.ln1.g, l.ln1.b, nullptr, ws.xn.hi, ws.xn.lo, M, D, c.eps, s));
+    HIP_TRY(lin.f32(l.qkv, ws.xn, M, ws.qkv));
     {
       SfTextAttn a;
       memset(&a, 0, sizeof(a));
-      a.qkv = ws.qkv; a.mask = mask; a.ctx_hi = ws.ctx_hi; a.ctx_lo = acc ? ws.ctx_lo : nullptr;
+      a.qkv = ws.qkv; a.mask = mask; a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
       a.B = B; a.L = L; a.heads = c.heads; a.D = D; a.scale = 1.0f / sqrtf((float)t->hd);
       HIP_TRY(text_launch_attention(a, s));
     }
-    {
-      SfGemmArgs g = sf_linear_args(l.out, ws.ctx_hi, ws.ctx_lo, M, SF_EPI_RESID_F32, c.act, acc);
-      g.resid = ws.resid; g.out_f32 = ws.resid;
-      HIP_TRY(sf_launch_gemm(g, acc, s));
-    }
-    HIP_TRY(sf_launch_layernorm(ws.resid, l.ln2.g, l.ln2.b, nullptr, ws.xn_hi, acc ? ws.xn_lo : nullptr, M, D, c.eps, s));
-    {
-      SfGemmArgs g = sf_linear_args(l.fc1, ws.xn_hi, ws.xn_lo, M, SF_EPI_ACT_BF16, c.act, acc);
-      g.out_hi = ws.mid_hi; g.out_lo = acc ? ws.mid_lo : nullptr;
-      HIP_TRY(sf_launch_gemm(g, acc, s));
-    }
-    {
-      SfGemmArgs g = sf_linear_args(l.fc2, ws.mid_hi, ws.mid_lo, M, SF_EPI_RESID_F32, c.act, acc);
-      g.resid = ws.resid; g.out_f32 = ws.resid;
-      HIP_TRY(sf_launch_gemm(g, acc, s));
-    }
+    HIP_TRY(lin.resid(l.out, ws.ctx, M, ws.resid, ws.resid));
+    HIP_TRY(sf_launch_layernorm(ws.resid, l.ln2.g, l.ln2.b, nullptr, ws.xn.hi, ws.xn.lo, M, D, c.eps, s));
+    HIP_TRY(lin.planes(l.fc1, ws.xn, M, ws.mid, true));
+    HIP_TRY(lin.resid(l.fc2, ws.mid, M, ws.resid, ws.resid));
   }
   if (last_hidden) HIP_TRY(sf_launch_layernorm(ws.resid, t->final_ln.g, t->final_ln.b, last_hidden, nullptr, nullptr, M, D, c.eps, s));
   HIP_TRY(text_launch_pool(ws.resid, B, L, D, t->final_ln.g, t->final_ln.b, c.eps, t->head_w, t->head_b, c.projection, group, pooled_out,

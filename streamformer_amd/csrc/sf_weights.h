@@ -1,6 +1,7 @@
-// Host side of a native model's handle: staging of named weights, bf16 rounding, workspace carving.  Plain C++17 with nothing from
-// HIP: the four handles (sf_encoder, sf_text, sf_connector, sf_oad) share it, and tests/host/weight_store_main.cpp checks it on a CPU
-// under sanitizers.  The device half (uploads, GEMM arguments) is sf_handle.h.
+// Host side of a native model's handle: staging of named weights and their expected-key table, bf16 rounding, workspace carving and
+// the bf16 plane pair the carver hands out.  Plain C++17 with nothing from HIP: every handle built on SfWeightStore (sf_encoder, sf_text,
+// sf_connector, sf_oad, sf_pixdec, sf_maskdec) shares it, and tests/host/weight_store_main.cpp checks it on a CPU under sanitizers.  The
+// device half (uploads, GEMM arguments and calls) is sf_handle.h.
 #pragma once
 #include "../../include/streamformer_hip.h"
 
@@ -150,20 +151,56 @@ struct SfWeightStore {
   }
 
   std::vector<float>& data(const std::string& k) { return host[k].data; }
+
+  // the keys of an nn.Linear [N, K] under `p` ("....linear1."), and of a LayerNorm / GroupNorm affine pair over C channels
+  void expect_linear(const std::string& p, int64_t N, int64_t K, bool bias = true) {
+    expected[p + "weight"] = {N, K};
+    if (bias) expected[p + "bias"] = {N};
+  }
+  void expect_affine(const std::string& p, int64_t C) {
+    expected[p + "weight"] = {C};
+    expected[p + "bias"] = {C};
+  }
 };
 
 // ------------------------------------------------------------------------------------------------
 // workspace carving: 256-byte aligned pieces of one buffer.  A null base only counts (the *_workspace_bytes entry points).
 // ------------------------------------------------------------------------------------------------
+// An activation as the GEMMs read it: the bf16 plane hi and, in bf16x3 mode only, the plane lo of what hi rounded away.  lo is null in
+// bf16 mode, so a launch passes p.hi, p.lo as they are and a kernel that is handed a lo plane writes it.
+struct SfPlanes {
+  uint16_t* hi = nullptr;
+  uint16_t* lo = nullptr;
+  SfPlanes at(size_t elements) const {      // the same pair `elements` further on; null stays null (lo in bf16 mode, both while sizing)
+    SfPlanes p;
+    p.hi = hi ? hi + elements : nullptr;
+    p.lo = lo ? lo + elements : nullptr;
+    return p;
+  }
+};
+
 struct SfCarver {
   char* base;
   size_t off = 0;
-  explicit SfCarver(void* b) : base((char*)b) {}
+  bool split = false;           // bf16x3 mode: lo planes are handed out
+  bool reserve_lo = false;      // a lo plane's bytes are set aside in bf16 mode too (a workspace whose size does not depend on the mode)
+  explicit SfCarver(void* b, bool split_ = false, bool reserve_lo_ = false) : base((char*)b), split(split_), reserve_lo(reserve_lo_) {}
   template <typename T>
   T* take(size_t n) {
     off = (off + 255) & ~(size_t)255;
     T* p = base ? (T*)(base + off) : nullptr;
     off += n * sizeof(T);
+    return p;
+  }
+  // the lo plane of n elements: where a model takes several hi planes first and their lo planes after them
+  uint16_t* lo(size_t n) {
+    uint16_t* p = split || reserve_lo ? take<uint16_t>(n) : nullptr;
+    return split ? p : nullptr;
+  }
+  SfPlanes planes(size_t n) {      // hi, then lo
+    SfPlanes p;
+    p.hi = take<uint16_t>(n);
+    p.lo = lo(n);
     return p;
   }
   size_t bytes() const { return (off + 255) & ~(size_t)255; }      // what a workspace holding every piece taken so far needs

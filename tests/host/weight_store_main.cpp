@@ -240,7 +240,70 @@ static void test_carver() {
   std::free(raw);
 }
 
+// expect_linear / expect_affine against the pairs the handles wrote by hand
+static void test_expect() {
+  SfWeightStore got, want;
+  got.expect_linear("layers.0.linear1.", 128, 64);
+  want.expected["layers.0.linear1.weight"] = {128, 64};
+  want.expected["layers.0.linear1.bias"] = {128};
+  got.expect_linear("adapter_1.", 64, 192, false);
+  want.expected["adapter_1.weight"] = {64, 192};
+  got.expect_affine("layers.0.norm1.", 64);
+  want.expected["layers.0.norm1.weight"] = {64};
+  want.expected["layers.0.norm1.bias"] = {64};
+  got.expect_linear("", 3, 5);                           // the connector's depth-1 prefix ends in the dot itself; an empty one is legal too
+  want.expected["weight"] = {3, 5};
+  want.expected["bias"] = {3};
+  CHECK(got.expected == want.expected);
+  CHECK(got.expected.size() == 7 && got.expected.count("adapter_1.bias") == 0);
+  CHECK(got.required.empty() && got.host.empty());      // nothing but the table is touched
+}
+
+// the plane carve against the two takes it replaces, under both reservation rules, in both modes, counting and assigning
+static void test_planes() {
+  alignas(256) static char buf[8192];
+  const size_t n = 300, m = 77;                          // 600 and 154 bytes: neither a multiple of the 256-byte step
+  for (int reserve = 0; reserve < 2; ++reserve)
+    for (int split = 0; split < 2; ++split)
+      for (char* base : {(char*)nullptr, buf}) {
+        SfCarver old(base), cv(base, split != 0, reserve != 0);
+        float* f_old = old.take<float>(5);
+        uint16_t* hi_old = old.take<uint16_t>(n);
+        uint16_t* lo_old = (split || reserve) ? old.take<uint16_t>(n) : nullptr;
+        float* g_old = old.take<float>(3);
+        float* f = cv.take<float>(5);
+        const SfPlanes p = cv.planes(n);
+        float* g = cv.take<float>(3);
+        CHECK(f == f_old && p.hi == hi_old && g == g_old);
+        CHECK(p.lo == (split ? lo_old : nullptr));        // reserved bytes are not handed out in bf16 mode
+        CHECK(cv.off == old.off && cv.bytes() == old.bytes());
+        CHECK((p.hi == nullptr) == (base == nullptr));    // a sizing pass hands out nothing
+        if (!base) CHECK(p.lo == nullptr);
+        // several hi planes first, their lo planes after them
+        uint16_t* a_old = old.take<uint16_t>(n);
+        uint16_t* b_old = old.take<uint16_t>(m);
+        uint16_t* al_old = nullptr; uint16_t* bl_old = nullptr;
+        if (split || reserve) { al_old = old.take<uint16_t>(n); bl_old = old.take<uint16_t>(m); }
+        SfPlanes a, b;
+        a.hi = cv.take<uint16_t>(n); b.hi = cv.take<uint16_t>(m);
+        a.lo = cv.lo(n); b.lo = cv.lo(m);
+        CHECK(a.hi == a_old && b.hi == b_old);
+        CHECK(a.lo == (split ? al_old : nullptr) && b.lo == (split ? bl_old : nullptr));
+        CHECK(cv.bytes() == old.bytes() && cv.bytes() <= sizeof(buf));
+        if (base && split) { a.lo[n - 1] = 1; b.lo[m - 1] = 2; p.lo[n - 1] = 3; }      // inside the buffer (the sanitizer watches)
+        // at(): both planes move, null stays null
+        const SfPlanes q = p.at(17);
+        CHECK(q.hi == (p.hi ? p.hi + 17 : nullptr));
+        CHECK(q.lo == (p.lo ? p.lo + 17 : nullptr));
+        CHECK(p.at(0).hi == p.hi && p.at(0).lo == p.lo);
+      }
+  const SfPlanes none;
+  CHECK(none.hi == nullptr && none.lo == nullptr && none.at(1000).hi == nullptr && none.at(1000).lo == nullptr);
+}
+
 int main() {
+  test_expect();
+  test_planes();
   test_bf16();
   test_f16();
   test_convert();
