@@ -7,6 +7,7 @@
 // scalars are read from device memory and the row partials live in the caller's workspace, so a training step
 // has no host synchronisation and no library-side allocation here.
 #include "sf_common.h"
+#include "sf_internal.h"
 
 SF_DEVICE float log_sigmoid(float x) {  // matches F.logsigmoid: min(x,0) - log1p(exp(-|x|))
   return fminf(x, 0.f) - log1pf(expf(-fabsf(x)));
@@ -271,4 +272,36 @@ hipError_t sf_launch_grounding_loss(const float* pooler, const float* text, cons
                                  logit_bias, partial, grad_pooler, logits_out);
   if (e != hipSuccess) return e;
   return sf_launch(sf_loss_finish_kernel, dim3(1), dim3(64), 0, s, partial, B * T, loss, grad_scalars);
+}
+
+// ------------------------------------------------------------------------------------------------
+// C entry points (sf_grounding_loss: sf_text_heads.hip, beside its kernel)
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t sf_loss_workspace_bytes(int B, int T) {
+  return sf_loss_partial_bytes(B > 0 && T > 0 ? B * T : 1);
+}
+extern "C" int sf_retrieval_loss(const float* pooler, const float* text, int B, int T, int D, int Bt, int pos_offset,
+                                 const float* logit_scale, const float* logit_bias, float* loss, float* grad_pooler,
+                                 float* grad_scalars, void* workspace, size_t workspace_bytes, sf_stream stream) {
+  if (!pooler || !text || !loss || !logit_scale || !logit_bias || !workspace) return sf_set_err(SF_ERR_INVALID, "sf_retrieval_loss: null buffer");
+  if (B <= 0 || Bt <= 0 || T <= 0 || D <= 0) return sf_set_err(SF_ERR_INVALID, "sf_retrieval_loss: bad shape B=%d Bt=%d T=%d D=%d", B, Bt, T, D);
+  if (D > 2048) return sf_set_err(SF_ERR_CAPACITY, "sf_retrieval_loss: feature width %d > 2048 (256 threads x 8 features)", D);
+  if (pos_offset >= 0 && pos_offset + B > Bt)
+    return sf_set_err(SF_ERR_INVALID, "sf_retrieval_loss: positives %d..%d fall outside the %d text rows", pos_offset, pos_offset + B - 1, Bt);
+  if (workspace_bytes < sf_loss_partial_bytes(B)) return sf_set_err(SF_ERR_WORKSPACE, "loss workspace %zu < %zu bytes", workspace_bytes, sf_loss_partial_bytes(B));
+  HIP_TRY(sf_launch_retrieval_loss(pooler, text, B, T, D, Bt, pos_offset, logit_scale, logit_bias, loss, grad_pooler,
+                                   grad_scalars, (float*)workspace, (hipStream_t)stream));
+  return SF_OK;
+}
+extern "C" int sf_localization_loss(const float* pooler, const float* label_emb, const int32_t* labels, int B, int T,
+                                    int D, int L, const float* logit_scale, const float* logit_bias, float* loss,
+                                    float* grad_pooler, float* grad_scalars, void* workspace, size_t workspace_bytes,
+                                    sf_stream stream) {
+  if (!pooler || !label_emb || !labels || !loss || !logit_scale || !logit_bias || !workspace) return sf_set_err(SF_ERR_INVALID, "sf_localization_loss: null buffer");
+  if (B <= 0 || T <= 0 || D <= 0 || L <= 0) return sf_set_err(SF_ERR_INVALID, "sf_localization_loss: bad shape B=%d T=%d D=%d L=%d", B, T, D, L);
+  if (L > 4096) return sf_set_err(SF_ERR_CAPACITY, "sf_localization_loss: %d label classes > 4096 (one LDS row of similarities per frame)", L);
+  if (workspace_bytes < sf_loss_partial_bytes(B * T)) return sf_set_err(SF_ERR_WORKSPACE, "loss workspace %zu < %zu bytes", workspace_bytes, sf_loss_partial_bytes(B * T));
+  HIP_TRY(sf_launch_localization_loss(pooler, label_emb, labels, B, T, D, L, logit_scale, logit_bias, loss, grad_pooler,
+                                      grad_scalars, (float*)workspace, (hipStream_t)stream));
+  return SF_OK;
 }

@@ -30,7 +30,7 @@ ACC_CEIL = 5e-4
 # projects the tokens to k / v at all (sf_pool_head.hip: scores and weighted sums on the fp32 tokens, bf16x3 / fp32 arithmetic in both
 # modes), so what is left is exactly what the encoder's tokens carry: back to SURVEY's 2e-2 for every fixture.
 BF16_LHS, BF16_POOL = 4e-2, 2e-2
-# Accurate mode, per forward schedule (sf_encoder.hip: plan_forward decides which one a call takes; the table at ForwardPlan lists
+# Accurate mode, per forward schedule (sf_encoder.hip: plan_forward decides which one a call takes; the table at ForwardPlan, sf_encoder.h, lists
 # them all).  Each bound is about twice the largest max-abs against the oracle measured on an MI355X, written next to its test:
 #   xm      residual stream as hi + lo + lo2 bf16 planes, LayerNorm fold on the bf16x3 256^2 kernel: SigLIP-base from three clips
 #           (M > 6272), D = 1024 from 2048 rows.  Without the third plane (SF_ACC_TWO_PLANES) it measures 1.36e-4.

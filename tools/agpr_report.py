@@ -18,7 +18,7 @@ def report(src):
         rows.append((int(m.group(1)), int(m.group(3)), m.group(2)))
     return src, rows
 
-units = sys.argv[1:] or [s for s in B.SOURCES if s not in ("sf_switches.hip", "sf_encoder.hip", "sf_train.hip")]
+units = sys.argv[1:] or [s for s in B.SOURCES if s not in ("sf_switches.hip", "sf_encoder.hip", "sf_stream.hip", "sf_bench.hip", "sf_train.hip")]
 with ThreadPoolExecutor(max_workers=8) as ex:
     for src, rows in ex.map(report, units):
         used = [r for r in rows if r[0] > 0]

@@ -1,7 +1,8 @@
-"""The tail models on seeded weights and inputs, written to a file: the bit-identity check of a host-side change to their handles.
+"""The tail models and the encoder on seeded weights and inputs, written to a file: the bit-identity check of a host-side change.
 
     python tools/tail_dump.py --case pixdec_fpn_enc2 --out a.pt [--root OTHER_TREE]
     python tools/tail_dump.py --case maskdec --out a.pt          # a model's name: every case of that model, one after the other
+    python tools/tail_dump.py --case encoder --out a.pt          # enc_forward, enc_stream, enc_ops: the encoder's host code (below)
     python tools/tail_dump.py --compare a.pt b.pt
 
 A case builds one model (the smallest widths the GEMM k-step allows, a handful of rows), fills its parameters from a seeded generator,
@@ -116,6 +117,114 @@ def run_maskdec(sa, mode, g, dev, in_channels, reid, dec_layers):
     return {"plain": m(x, mask_features), "aux": m(x, mask_features, return_aux=True, return_attn_masks=True)}
 
 
+# ---------------------------------------------------------------------------------------------------- the encoder
+def small_encoder(sa, mode, dev):
+    """The small golden configuration (tests/helpers.small_cfg) on seeded weights."""
+    from streamformer_amd.init_weights import make_state_dict
+    cfg = sa.StreamformerConfig(image_size=48, patch_size=16, num_frames=16, hidden_size=128, num_hidden_layers=2, num_attention_heads=2,
+                                intermediate_size=256, enable_causal_temporal=True)
+    m = sa.TimesformerMultiTaskingModelSigLIP(cfg, compute_dtype=mode)
+    m.load_state_dict(make_state_dict(cfg, seed=4))
+    return m.to(dev).eval()
+
+
+def run_enc_forward(sa, mode, g, dev):
+    """sf_forward at B = 1 and 2 (with hidden states at B = 1), and sf_embed + sf_layers + sf_post_head staged."""
+    m = small_encoder(sa, mode, dev)
+    res = {}
+    for B in (1, 2):
+        x = torch.randn(B, 4, 3, 48, 48, generator=g).to(dev)
+        o = m(x, output_hidden_states=B == 1)
+        res[f"b{B}"] = {"last_hidden_state": o.last_hidden_state, "pooler_output": o.pooler_output, "hidden_states": o.hidden_states}
+    h = m.embeddings(x)
+    e = m.encoder(h, num_frames=4, output_attentions=True)
+    y = m.post_layernorm(e.last_hidden_state)
+    tok = y.reshape(B, 9, 4, 128).permute(0, 2, 1, 3).reshape(B * 4, 9, 128)      # patch-major tokens -> one row group per frame
+    res["staged"] = {"embeddings": h, "encoder": e.last_hidden_state, "attentions": e.attentions, "post_layernorm": y, "head": m.head(tok)}
+    return res
+
+
+def run_enc_stream(sa, mode, g, dev):
+    """Graphs on (the default): 6 single frames into a 4-frame sliding window; 3 streams staggered by one frame; one stream parked."""
+    m = small_encoder(sa, mode, dev)
+    pair = lambda o: {"last_hidden_state": o.last_hidden_state.clone(), "pooler_output": o.pooler_output.clone()}      # noqa: E731
+    x = torch.randn(3, 7, 3, 48, 48, generator=g).to(dev)
+    res = {}
+    cache = m.new_cache(1, 4, policy="slide")
+    for t in range(6):
+        res[f"slide.{t}"] = pair(m(x[:1, t:t + 1], past_key_values=cache))
+    cache = m.new_cache(3, 16)
+    for t in range(6):      # stream i joins at call i
+        ids = [i for i in range(3) if t >= i]
+        xs = torch.stack([x[i, t - i] for i in ids])[:, None]
+        res[f"ragged.{t}"] = pair(m(xs, past_key_values=cache, stream_ids=ids))
+    snap = cache.snapshot(1)
+    res["park.blob"] = snap.blob
+    other = m.new_cache(2, 16)
+    other.restore(snap, stream=1)
+    res["park.resumed"] = pair(m(x[1:2, 5:6], past_key_values=other, stream_ids=[1]))
+    res["park.prefill"] = pair(m(x[2:3, :3], past_key_values=other, stream_ids=[0]))      # several frames of one stream: the eager slab call
+    return res
+
+
+def gemm_call(nat, dev, g, family, M, N, K, split, resid):
+    """One sf_op_gemm call on seeded planes (fp32 epilogue, or residual + bf16 copy); a refusal is recorded as its message."""
+    import ctypes as C
+    planes = lambda *shape: torch.randint(0x3c00, 0x4000, shape, generator=g, dtype=torch.int32).to(torch.int16).to(dev)      # noqa: E731
+    a, w, bias, out = planes(M, K), planes(N, K), torch.randn(N, generator=g).to(dev), torch.zeros(M, N, device=dev)
+    lo = [planes(M, K) >> 8, planes(N, K) >> 8] if split else []
+    d = nat.SfGemmDesc()
+    d.split, d.a_hi, d.w_hi, d.bias = int(split), a.data_ptr(), w.data_ptr(), bias.data_ptr()
+    if split:
+        d.a_lo, d.w_lo = lo[0].data_ptr(), lo[1].data_ptr()
+    d.M, d.N, d.K, d.ldc, d.alpha, d.out_f32 = M, N, K, N, 0.75, out.data_ptr()
+    d.epi = 3 if resid else 0      # SF_EPI_RESID_F32 / SF_EPI_F32
+    if resid:
+        out.copy_(torch.randn(M, N, generator=g))
+        d.resid = out.data_ptr()
+    taken = C.c_int(-1)
+    rc = nat.lib.sf_op_gemm(C.byref(d), family, C.byref(taken), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize(dev)
+    if rc:
+        return {"refused": torch.tensor(list(nat.lib.sf_last_error()), dtype=torch.uint8)}
+    return {"out": out, "family": torch.tensor(taken.value)}
+
+
+def run_enc_ops(sa, mode, g, dev):
+    nat, heads = sa._native, sa.heads
+    cm = nat.compute_mode(mode)
+    stream = nat.current_stream_handle(dev)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)      # noqa: E731
+    res = {}
+    M, N, K = 33, 64, 64
+    x, w, b, r = rnd(M, K), rnd(N, K) / 8, rnd(N), rnd(M, N)
+    nb = nat.lib.sf_op_linear_workspace_bytes(M, N, K)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    for name, resid, gelu in (("plain", None, 0), ("gelu", None, 1), ("resid", r, 0)):
+        y = torch.empty(M, N, device=dev)
+        nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), nat.ptr(resid), 0.37 if resid is not None else 1.0, gelu, y.data_ptr(), M,
+                                       N, K, cm, ws.data_ptr(), nb, stream))
+        res[f"linear.{name}"] = y
+    # one call per family (1 skinny .. 5 128^2) and the dispatcher's own choice (0) at the same shape
+    for fam, shape in ((1, (33, 100, 64)), (2, (3136, 768, 128)), (3, (6272, 768, 128)), (4, (2048, 1024, 128)), (5, (600, 1000, 128))):
+        for family in (fam, 0):
+            for resid in (False, True):
+                res[f"gemm.{fam}.{family}.{int(resid)}"] = gemm_call(nat, dev, g, family, *shape, split=mode == "fp32", resid=resid)
+    for name, groups, L, temporal, causal, ntok, hd in (("spatial", 3, 17, 0, 0, 0, 64), ("temporal", 6, 5, 1, 1, 3, 64), ("spatial_hd32", 3, 17, 0, 0, 0, 32)):
+        D = 2 * hd
+        qkv, ctx = rnd(groups * L, 3 * D), torch.empty(groups * L, D, device=dev)
+        nb = nat.lib.sf_op_attention_workspace_bytes(groups, L, 2, hd)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        nat.check(nat.lib.sf_op_attention(qkv.data_ptr(), ctx.data_ptr(), groups, L, 2, hd, causal, temporal, ntok, cm, ws.data_ptr(), nb, stream))
+        res[f"attention.{name}"] = ctx
+    B, T, D = 2, 3, 64
+    unit = lambda t: t / t.norm(dim=-1, keepdim=True)      # noqa: E731
+    pooler = unit(rnd(B, T, D))
+    res["loss.retrieval"] = heads.RetrievalHead().loss(pooler, unit(rnd(B, D)))
+    res["loss.localization"] = heads.LocalizationHead(unit(rnd(5, D))).loss(pooler, torch.randint(0, 5, (B, T), generator=g))
+    return res
+
+
 CASES = {
     "text": (run_text, {}),
     "connector_depth1": (run_connector, dict(projector="linear")),
@@ -134,10 +243,15 @@ CASES = {
     "maskdec_noproj_base": (run_maskdec, dict(in_channels=64, reid=-1, dec_layers=4)),
     "maskdec_proj_layers0": (run_maskdec, dict(in_channels=128, reid=3, dec_layers=0)),
     "maskdec_noproj_reid1": (run_maskdec, dict(in_channels=64, reid=1, dec_layers=1)),
+    "enc_forward": (run_enc_forward, {}),
+    "enc_stream": (run_enc_stream, {}),
+    "enc_ops": (run_enc_ops, {}),
 }
-MODELS = ("text", "connector", "oad", "pixdec", "maskdec")
+MODELS = ("text", "connector", "oad", "pixdec", "maskdec", "enc")
+FAMILIES = {"encoder": "enc"}      # --case encoder: every enc_* case
 SIZERS = ("sf_text_workspace_bytes", "sf_connector_workspace_bytes", "sf_oad_workspace_bytes", "sf_pixdec_workspace_bytes",
-          "sf_maskdec_workspace_bytes")
+          "sf_maskdec_workspace_bytes", "sf_workspace_bytes", "sf_stream_workspace_bytes", "sf_cache_stream_blob_bytes")
+VALUE_SIZERS = ("sf_op_linear_workspace_bytes", "sf_op_attention_workspace_bytes", "sf_loss_workspace_bytes")      # the answer is the return value
 
 
 def record_sizes(nat, log):
@@ -148,6 +262,12 @@ def record_sizes(nat, log):
             log.append((_name, int(args[-1]._obj.value)))
             return rc
         setattr(nat.lib, name, wrapped)
+    for name in VALUE_SIZERS:
+        def valued(*args, _fn=getattr(nat.lib, name), _name=name):
+            n = _fn(*args)
+            log.append((_name, int(n)))
+            return n
+        setattr(nat.lib, name, valued)
 
 
 def compare(a_path, b_path):
@@ -169,7 +289,8 @@ def main():
     args = ap.parse_args()
     if args.compare:
         sys.exit(compare(*args.compare))
-    names = [c for n in args.case for c in CASES if c == n or (n in MODELS and c.startswith(n))]
+    wanted = [FAMILIES.get(n, n) for n in args.case]
+    names = [c for n in wanted for c in CASES if c == n or (n in MODELS and c.startswith(n))]
     if not names or not args.out:
         ap.error("--case needs known names and --out a file")
     sys.path.insert(0, os.path.abspath(args.root))
