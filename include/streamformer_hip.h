@@ -273,6 +273,27 @@ int sf_op_attention(const float* qkv_dev, float* ctx_dev, int groups, int L, int
                     int causal, int temporal_layout, int N_tokens, int compute,
                     void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 size_t sf_op_attention_workspace_bytes(int groups, int L, int heads, int head_dim);
+/* Temporal attention over a KV-cache the CALLER built: the streaming step (Tq = 1), chunked prefill (Tq > 1 behind a past), the position
+ * read from device memory and the table of a ragged call — the kernels of a stream, without an encoder around them.
+ * cache fp32 [slabs, cap, N_tokens, 3*D], q | k | v per row (the encoder's cache layout); it is converted to what `compute` keeps in a real
+ * stream (bf16 rows; the accurate mode reads the fp32 rows as they are).  ctx fp32 [B * Tq * N_tokens, D].
+ * Sequence (b, n): query t < Tq is row q_t0 + t of slab b, keys and values are rows 0 .. Tk - 1 of that slab; causal: key j is visible
+ * to query t iff j <= t_past + t.  Rows the call does not name are not read.
+ *   pos_dev  (Tq = 1) two ints {slot, tk} in device memory: the query row and the number of keys, all of them visible
+ *   tab      (Tq = 1) B entries in device memory: sequence b reads slab tab[b].stream, query row tab[b].slot, tab[b].tk keys, all
+ *            visible; its context row stays row b.  With either, Tk bounds every tk and picks the kernel instance; t_row is unused.
+ * *route_out (may be NULL): the kernel and instance that ran — 1..3 single query fp32 rows (64 / 128 / 256 keys), 4..5 single query
+ * bf16 whole lines (64 / 128), 6..8 single query bf16 lane = key (64 / 128 / 256), 9 DMA-staged bf16, 10 DMA-staged planes (not reached
+ * from here), 11..14 MFMA fp32 rows (32 / 64 / 128 / 256 keys), 15..18 MFMA bf16 rows, 19 the generic kernel (head_dim != 64).
+ * *waves_out (may be NULL): waves per workgroup of that launch.
+ * SF_ERR_INVALID, with nothing launched, for query rows or keys outside the cache, a device position outside it, tab / pos_dev with
+ * Tq != 1 or on a route that does not read them, and every call no kernel takes.                                                  */
+typedef struct { int32_t stream, t_row, slot, tk; } sf_stream_slot;
+int sf_op_attention_cached(const float* cache_dev, float* ctx_dev, int slabs, int cap, int N_tokens, int heads, int head_dim,
+                           int compute, int B, int Tq, int Tk, int q_t0, int t_past, int causal, const int* pos_dev,
+                           const sf_stream_slot* tab_dev, int* route_out, int* waves_out,
+                           void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+size_t sf_op_attention_cached_workspace_bytes(int slabs, int cap, int N_tokens, int heads, int head_dim, int B, int Tq);
 
 /* ---- loss heads of the multitask pre-training step (BASELINE config #3) ---------------------
  * retrieval: TimesformerVideoRetrievalHead.forward + SigLipLoss._loss (modeling:2324-2351,221-237)

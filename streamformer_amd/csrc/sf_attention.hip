@@ -1486,51 +1486,86 @@ bool sf_temporal_planes_ok(int Tq, int Tk) {
   return !off && Tq > 1 && Tq <= 16 && Tk <= 32;
 }
 
-hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipStream_t s) {
-  if (a.head_dim && a.head_dim != HD) return sf_launch_attention_generic(a, a.head_dim, true, s);       // sf_attention_generic.hip
-  if (a.D != a.heads * HD || a.Tq <= 0 || a.Tk <= 0 || a.B <= 0 || a.N <= 0) return hipErrorInvalidValue;
+// What sf_launch_temporal_attention runs for a call: decided here, launched by sf_launch_temporal_route (nothing else chooses a kernel).
+SfTemporalRoute sf_temporal_route(const SfAttnArgs& a, bool accurate) {
+  if (a.head_dim && a.head_dim != HD)                // sf_attention_generic.hip
+    return sf_attention_generic_supported(a, a.head_dim) && a.B > 0 && a.N > 0 && a.Tq > 0 && a.Tk > 0 && !a.probs ? SF_TROUTE_GENERIC : SF_TROUTE_NONE;
+  if (a.D != a.heads * HD || a.Tq <= 0 || a.Tk <= 0 || a.B <= 0 || a.N <= 0) return SF_TROUTE_NONE;
   // dropout on the probabilities (training forward): the DMA-staged whole-clip kernel only
-  if (a.drop.on && (accurate || a.Tq == 1 || a.Tq > 16 || a.Tk > 32 || (a.row_pitch_kv % 8) || sf_sw(SW_DISABLE_TEMPORAL_DMA))) return hipErrorInvalidValue;
+  if (a.drop.on && (accurate || a.Tq == 1 || a.Tq > 16 || a.Tk > 32 || (a.row_pitch_kv % 8) || sf_sw(SW_DISABLE_TEMPORAL_DMA))) return SF_TROUTE_NONE;
   const bool decode_off = sf_sw(SW_DISABLE_TEMPORAL_DECODE) != nullptr;
   if (a.Tq == 1 && a.Tk <= 256 && !decode_off) {        // one new frame per stream: the matrix-vector kernel
-    const int ntasks = a.B * a.N * a.heads;
-    const dim3 grid((ntasks + 3) / 4), block(256);
     const int kp = (a.Tk + 63) >> 6;
-#define SF_TD(F, KPV) return sf_launch(sf_temporal_decode_kernel<F, KPV>, grid, block, 0, s, a, ntasks)
-    if (accurate) { if (kp <= 1) SF_TD(true, 1); else if (kp <= 2) SF_TD(true, 2); else SF_TD(true, 4); }
-    else if (kp <= 2 && (a.row_pitch_kv % 8) == 0 && (a.row_pitch_q % 8) == 0 && !sf_sw(SW_TEMPORAL_DECODE_LANE_KEY)) {
-      // bf16 rows, <= 128 keys: whole cache lines per load instruction
-      if (kp <= 1) return sf_launch(sf_temporal_decode_lines_kernel<1>, grid, block, 0, s, a, ntasks);
-      return sf_launch(sf_temporal_decode_lines_kernel<2>, grid, block, 0, s, a, ntasks);
-    }
-    else { if (kp <= 1) SF_TD(false, 1); else if (kp <= 2) SF_TD(false, 2); else SF_TD(false, 4); }
-#undef SF_TD
+    if (accurate) return kp <= 1 ? SF_TROUTE_DECODE_F32_KP1 : kp <= 2 ? SF_TROUTE_DECODE_F32_KP2 : SF_TROUTE_DECODE_F32_KP4;
+    // bf16 rows, <= 128 keys: whole cache lines per load instruction
+    if (kp <= 2 && (a.row_pitch_kv % 8) == 0 && (a.row_pitch_q % 8) == 0 && !sf_sw(SW_TEMPORAL_DECODE_LANE_KEY))
+      return kp <= 1 ? SF_TROUTE_DECODE_LINES_KP1 : SF_TROUTE_DECODE_LINES_KP2;
+    return kp <= 1 ? SF_TROUTE_DECODE_BF16_KP1 : kp <= 2 ? SF_TROUTE_DECODE_BF16_KP2 : SF_TROUTE_DECODE_BF16_KP4;
   }
   const bool tdma_off = sf_sw(SW_DISABLE_TEMPORAL_DMA) != nullptr;
-  if (!accurate && !tdma_off && a.Tq <= 16 && a.Tk <= 32 && (a.row_pitch_kv % 8) == 0) {     // every full 16-frame clip
-    const int ntasks = a.B * a.N * a.heads;
-    return sf_launch(sf_temporal_attn_dma_kernel<false>, dim3((ntasks + 3) / 4), dim3(256), 4 * 10240, s, a, ntasks);
-  }
-  if (accurate && !a.in_is_f32) {        // hi + lo planes (sf_temporal_planes_ok)
-    if (a.Tq > 16 || a.Tk > 32 || a.lo_plane_off <= 0 || (a.row_pitch_kv % 8) || (a.lo_plane_off % 8)) return hipErrorInvalidValue;
-    const int ntasks = a.B * a.N * a.heads;
-    return sf_launch_big_lds(sf_temporal_attn_dma_kernel<true>, dim3((ntasks + 3) / 4), dim3(256), 4 * 20480, s, a, ntasks);
-  }
+  if (!accurate && !tdma_off && a.Tq <= 16 && a.Tk <= 32 && (a.row_pitch_kv % 8) == 0) return SF_TROUTE_DMA_BF16;     // every full 16-frame clip
+  if (accurate && !a.in_is_f32)          // hi + lo planes (sf_temporal_planes_ok)
+    return a.Tq > 16 || a.Tk > 32 || a.lo_plane_off <= 0 || (a.row_pitch_kv % 8) || (a.lo_plane_off % 8) ? SF_TROUTE_NONE : SF_TROUTE_DMA_PLANES;
   const int tkp = (a.Tk + 31) & ~31;
-  if (tkp > 32 * 8) return hipErrorInvalidValue;   // <= 256 cached frames per stream
-  const int vp = vt_pitch(tkp);
-  const size_t patch = (size_t)HD * vp * (accurate ? 2 : 1) + (accurate ? 4096 : 2048);
+  if (tkp > 32 * 8) return SF_TROUTE_NONE;   // <= 256 cached frames per stream
+  const int nt2 = tkp >> 5;
+  const int step = nt2 <= 1 ? 0 : nt2 <= 2 ? 1 : nt2 <= 4 ? 2 : 3;
+  return (SfTemporalRoute)((accurate ? SF_TROUTE_MFMA_ACC_NT1 : SF_TROUTE_MFMA_BF16_NT1) + step);
+}
+
+static bool troute_mfma(SfTemporalRoute r) { return r >= SF_TROUTE_MFMA_ACC_NT1 && r <= SF_TROUTE_MFMA_BF16_NT8; }
+static size_t troute_mfma_patch(SfTemporalRoute r, const SfAttnArgs& a) {      // LDS bytes per wave of the MFMA routes
+  const bool accurate = r <= SF_TROUTE_MFMA_ACC_NT8;
+  return (size_t)HD * vt_pitch((a.Tk + 31) & ~31) * (accurate ? 2 : 1) + (accurate ? 4096 : 2048);
+}
+int sf_temporal_route_waves(SfTemporalRoute r, const SfAttnArgs& a) {
+  if (!troute_mfma(r)) return 4;
+  const size_t patch = troute_mfma_patch(r, a);
   int waves = 4;
   while (waves > 1 && patch * waves > 150 * 1024) waves >>= 1;
-  const size_t lds = patch * waves;
+  return waves;
+}
+
+hipError_t sf_launch_temporal_route(SfTemporalRoute r, const SfAttnArgs& a, hipStream_t s) {
+  if (r == SF_TROUTE_NONE) return hipErrorInvalidValue;
+  if (r == SF_TROUTE_GENERIC) return sf_launch_attention_generic(a, a.head_dim, true, s);
   const int ntasks = a.B * a.N * a.heads;
-  const dim3 grid((ntasks + waves - 1) / waves), block(waves * 64);
+  if (troute_mfma(r)) {
+    const int vp = vt_pitch((a.Tk + 31) & ~31);
+    const int waves = sf_temporal_route_waves(r, a);
+    const size_t lds = troute_mfma_patch(r, a) * waves;
+    const dim3 grid((ntasks + waves - 1) / waves), block(waves * 64);
 #define SF_TL(ACCV, NT) return sf_launch_big_lds(sf_temporal_attn_kernel<ACCV, NT>, grid, block, lds, s, a, vp, ntasks)
-  const int nt2 = tkp >> 5;
-  if (accurate) {
-    if (nt2 <= 1) SF_TL(true, 1); else if (nt2 <= 2) SF_TL(true, 2); else if (nt2 <= 4) SF_TL(true, 4); else SF_TL(true, 8);
-  } else {
-    if (nt2 <= 1) SF_TL(false, 1); else if (nt2 <= 2) SF_TL(false, 2); else if (nt2 <= 4) SF_TL(false, 4); else SF_TL(false, 8);
-  }
+    switch (r) {
+      case SF_TROUTE_MFMA_ACC_NT1: SF_TL(true, 1);
+      case SF_TROUTE_MFMA_ACC_NT2: SF_TL(true, 2);
+      case SF_TROUTE_MFMA_ACC_NT4: SF_TL(true, 4);
+      case SF_TROUTE_MFMA_ACC_NT8: SF_TL(true, 8);
+      case SF_TROUTE_MFMA_BF16_NT1: SF_TL(false, 1);
+      case SF_TROUTE_MFMA_BF16_NT2: SF_TL(false, 2);
+      case SF_TROUTE_MFMA_BF16_NT4: SF_TL(false, 4);
+      default: SF_TL(false, 8);
+    }
 #undef SF_TL
+  }
+  const dim3 grid((ntasks + 3) / 4), block(256);
+#define SF_TD(F, KPV) return sf_launch(sf_temporal_decode_kernel<F, KPV>, grid, block, 0, s, a, ntasks)
+  switch (r) {
+    case SF_TROUTE_DECODE_F32_KP1: SF_TD(true, 1);
+    case SF_TROUTE_DECODE_F32_KP2: SF_TD(true, 2);
+    case SF_TROUTE_DECODE_F32_KP4: SF_TD(true, 4);
+    case SF_TROUTE_DECODE_LINES_KP1: return sf_launch(sf_temporal_decode_lines_kernel<1>, grid, block, 0, s, a, ntasks);
+    case SF_TROUTE_DECODE_LINES_KP2: return sf_launch(sf_temporal_decode_lines_kernel<2>, grid, block, 0, s, a, ntasks);
+    case SF_TROUTE_DECODE_BF16_KP1: SF_TD(false, 1);
+    case SF_TROUTE_DECODE_BF16_KP2: SF_TD(false, 2);
+    case SF_TROUTE_DECODE_BF16_KP4: SF_TD(false, 4);
+    case SF_TROUTE_DMA_BF16: return sf_launch(sf_temporal_attn_dma_kernel<false>, grid, block, 4 * 10240, s, a, ntasks);
+    case SF_TROUTE_DMA_PLANES: return sf_launch_big_lds(sf_temporal_attn_dma_kernel<true>, grid, block, 4 * 20480, s, a, ntasks);
+    default: return hipErrorInvalidValue;
+  }
+#undef SF_TD
+}
+
+hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipStream_t s) {
+  return sf_launch_temporal_route(sf_temporal_route(a, accurate), a, s);
 }

@@ -486,7 +486,21 @@ struct SfAttnArgs {
 hipError_t sf_launch_spatial_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);
 bool sf_spatial_planes_ok(int N, bool probs);
 bool sf_temporal_planes_ok(int Tq, int Tk);
-hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);
+// the kernels of the temporal attention and their instances; the values are the `route` of sf_op_attention_cached (include/streamformer_hip.h)
+enum SfTemporalRoute {
+  SF_TROUTE_NONE = 0,                                                            // no kernel takes the call
+  SF_TROUTE_DECODE_F32_KP1 = 1, SF_TROUTE_DECODE_F32_KP2 = 2, SF_TROUTE_DECODE_F32_KP4 = 3,      // single query, fp32 rows, 64 / 128 / 256 keys
+  SF_TROUTE_DECODE_LINES_KP1 = 4, SF_TROUTE_DECODE_LINES_KP2 = 5,                // single query, bf16 rows, whole lines per load, 64 / 128 keys
+  SF_TROUTE_DECODE_BF16_KP1 = 6, SF_TROUTE_DECODE_BF16_KP2 = 7, SF_TROUTE_DECODE_BF16_KP4 = 8,   // single query, bf16 rows, lane = key
+  SF_TROUTE_DMA_BF16 = 9, SF_TROUTE_DMA_PLANES = 10,                             // Tq <= 16, Tk <= 32: bf16 rows / hi + lo planes
+  SF_TROUTE_MFMA_ACC_NT1 = 11, SF_TROUTE_MFMA_ACC_NT2 = 12, SF_TROUTE_MFMA_ACC_NT4 = 13, SF_TROUTE_MFMA_ACC_NT8 = 14,      // fp32 rows, 32 / 64 / 128 / 256 keys
+  SF_TROUTE_MFMA_BF16_NT1 = 15, SF_TROUTE_MFMA_BF16_NT2 = 16, SF_TROUTE_MFMA_BF16_NT4 = 17, SF_TROUTE_MFMA_BF16_NT8 = 18,
+  SF_TROUTE_GENERIC = 19,                                                        // head_dim != 64: sf_attention_generic.hip
+};
+SfTemporalRoute sf_temporal_route(const SfAttnArgs& a, bool accurate);          // sf_attention.hip: what sf_launch_temporal_attention will run (no launch)
+int sf_temporal_route_waves(SfTemporalRoute r, const SfAttnArgs& a);            // waves per workgroup of that launch (the MFMA routes shrink it when the LDS patch is large)
+hipError_t sf_launch_temporal_route(SfTemporalRoute r, const SfAttnArgs& a, hipStream_t s);
+hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);      // = sf_launch_temporal_route(sf_temporal_route(a, accurate), ...)
 bool sf_attention_generic_supported(const SfAttnArgs& a, int head_dim);            // sf_attention_generic.hip: head_dim % 8 == 0, <= 128
 hipError_t sf_launch_attention_generic(const SfAttnArgs& a, int head_dim, bool temporal, hipStream_t s);
 

@@ -188,3 +188,85 @@ extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, 
   HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, cp.hi, cp.lo, ctx, rows * D));
   return SF_OK;
 }
+
+// Temporal attention over a KV-cache, alone: the streaming step, chunked prefill, the device-side position and the ragged call's table,
+// on a cache the CALLER built.  The cache is converted to what the mode keeps in a real stream (bf16 rows; the accurate mode reads the
+// caller's fp32 rows) and the arguments are filled as the encoder's layer fills them (forward_layer, sf_encoder.hip).
+extern "C" size_t sf_op_attention_cached_workspace_bytes(int slabs, int cap, int N_tokens, int heads, int head_dim, int B, int Tq) {
+  const size_t D = (size_t)heads * head_dim;
+  return (size_t)slabs * cap * N_tokens * 3 * D * 2 + (size_t)B * Tq * N_tokens * D * 2 * 2 + 4096;      // bf16 cache rows, ctx hi + lo
+}
+
+extern "C" int sf_op_attention_cached(const float* cache, float* ctx, int slabs, int cap, int N_tokens, int heads, int head_dim, int compute,
+                                      int B, int Tq, int Tk, int q_t0, int t_past, int causal, const int* pos_dev,
+                                      const sf_stream_slot* tab, int* route_out, int* waves_out, void* workspace, size_t workspace_bytes,
+                                      sf_stream stream) {
+  static_assert(sizeof(sf_stream_slot) == sizeof(SfStreamSlot), "sf_stream_slot is SfStreamSlot");
+  if (route_out) *route_out = SF_TROUTE_NONE;
+  if (waves_out) *waves_out = 0;
+  if (!cache || !ctx || ((uintptr_t)cache & 15) || ((uintptr_t)ctx & 15)) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: cache and ctx are 16-byte aligned device buffers");
+  if (head_dim < 8 || head_dim > 128 || head_dim % 8) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: head_dim must be a multiple of 8 in 8..128");
+  if (compute != SF_COMPUTE_BF16 && compute != SF_COMPUTE_BF16X3) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: compute %d is not bf16 (0) or bf16x3 (1)", compute);
+  if (slabs <= 0 || cap <= 0 || N_tokens <= 0 || heads <= 0 || B <= 0 || Tq <= 0 || Tk <= 0)
+    return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: bad shape slabs=%d cap=%d N_tokens=%d heads=%d B=%d Tq=%d Tk=%d", slabs, cap, N_tokens, heads, B, Tq, Tk);
+  if (q_t0 < 0 || q_t0 + Tq > cap) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: query rows q_t0 %d .. + Tq %d leave the cache (cap %d)", q_t0, Tq, cap);
+  if (Tk > cap) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: Tk %d > cap %d", Tk, cap);
+  if (t_past < 0) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: t_past %d < 0", t_past);
+  if (tab && pos_dev) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: tab and pos_dev are two forms of one position: give one");
+  if ((tab || pos_dev) && Tq != 1) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: tab / pos_dev serve the single-query kernels (Tq %d != 1)", Tq);
+  if (tab ? B > SF_MAX_CALL_STREAMS : B > slabs)
+    return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: B %d > %d (%s)", B, tab ? SF_MAX_CALL_STREAMS : slabs, tab ? "entries of a table" : "slabs");
+  if (workspace_bytes < sf_op_attention_cached_workspace_bytes(slabs, cap, N_tokens, heads, head_dim, B, Tq)) return sf_set_err(SF_ERR_WORKSPACE, "workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  // the device-side position is the caller's: every row it names is checked before a kernel follows it
+  if (tab || pos_dev) {
+    SfStreamSlot host[SF_MAX_CALL_STREAMS];
+    int nent = B;
+    if (tab) {
+      HIP_TRY(hipMemcpy(host, tab, sizeof(SfStreamSlot) * B, hipMemcpyDeviceToHost));
+    } else {
+      int two[2];
+      HIP_TRY(hipMemcpy(two, pos_dev, sizeof(two), hipMemcpyDeviceToHost));
+      host[0].stream = 0; host[0].t_row = 0; host[0].slot = two[0]; host[0].tk = two[1];
+      nent = 1;
+    }
+    for (int b = 0; b < nent; ++b) {
+      const SfStreamSlot& e = host[b];
+      if (e.stream < 0 || e.stream >= slabs || e.slot < 0 || e.slot >= cap || e.tk < 1 || e.tk > Tk)
+        return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: device position %d {stream %d, slot %d, tk %d} outside slabs %d, cap %d, Tk %d", b, e.stream,
+                          e.slot, e.tk, slabs, cap, Tk);
+    }
+  }
+  const bool acc = compute == SF_COMPUTE_BF16X3;
+  const int D = heads * head_dim;
+  const size_t rows = (size_t)B * Tq * N_tokens, cells = (size_t)slabs * cap * N_tokens * 3 * D;
+  SfCarver c(workspace, acc, true);
+  const SfPlanes cp = c.planes(rows * D);
+  bf16_t* qb = c.take<bf16_t>(cells);
+  const void* base = cache;
+  size_t esz = 4;
+  if (!acc) {
+    HIP_TRY(sf_launch_split(cache, qb, nullptr, cells, s));
+    base = qb;
+    esz = 2;
+  }
+  SfAttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = base; a.k = (const char*)base + (size_t)D * esz; a.v = (const char*)base + (size_t)2 * D * esz;
+  a.in_is_f32 = acc; a.lo_plane_off = 0;
+  a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = 1.0f / sqrtf((float)head_dim); a.head_dim = head_dim;
+  a.N = N_tokens; a.ctx_hi = cp.hi; a.ctx_lo = cp.lo; a.D = D;
+  a.B = B; a.Tq = Tq; a.Tk = Tk; a.Tcap = cap; a.t_past = t_past;
+  a.causal = causal; a.Tq_cap = cap; a.q_t0 = q_t0;
+  a.pos_dev = pos_dev; a.tab = reinterpret_cast<const SfStreamSlot*>(tab);
+  const SfTemporalRoute r = sf_temporal_route(a, acc);
+  if (r == SF_TROUTE_NONE) return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: no temporal attention kernel takes this call");
+  const bool single = (r >= SF_TROUTE_DECODE_F32_KP1 && r <= SF_TROUTE_DECODE_BF16_KP4) || r == SF_TROUTE_GENERIC;
+  if ((tab || pos_dev) && !single)
+    return sf_set_err(SF_ERR_INVALID, "sf_op_attention_cached: route %d does not read tab / pos_dev (single-query and generic kernels only)", (int)r);
+  HIP_TRY(sf_launch_temporal_route(r, a, s));
+  HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, cp.hi, cp.lo, ctx, rows * D));
+  if (route_out) *route_out = (int)r;
+  if (waves_out) *waves_out = sf_temporal_route_waves(r, a);
+  return SF_OK;
+}
