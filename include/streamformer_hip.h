@@ -912,6 +912,32 @@ int sf_op_crit_class_loss(const float* const* pred_logits, int L, int B, int Q, 
                           int losses_stride, float* grad_dev, int32_t* target_classes_out_dev, void* workspace, size_t workspace_bytes,
                           sf_stream stream);
 
+/* ---- CTVIS contrastive loss (ctvis/modeling/cl_plugin/ct_cl_plugin.py, CTCLPlugin): loss_reid and loss_aux_reid of a training step ----
+ * All fp32, the caller's stream, no allocation, no host synchronisation, a launch count independent of the shapes, no float atomics and
+ * fixed reduction orders (bit-reproducible).  embeds_dev [R, C] is pred_embeds with R = B F Q rows; C is a multiple of 8 up to 256
+ * (SF_ERR_CAPACITY otherwise), F at most 32.  The host decides the data-dependent bookkeeping and passes it as int32 device tables
+ * (streamformer_amd/cl_plugin.py builds them): track_rows [T, F] the matched row of a (video, instance) at the frames it is present in,
+ * else -1; track_items [T, F] the item anchored at (track, frame) or -1; items [I, 8] = (track, frame, anchor row, positive kind,
+ * positive index, first negative, negatives, positive frame) with kind 0 an embedding row and kind 1 row t F + f of sg; neg [NE] the
+ * items' negative rows; row_start [R + 1] / row_items [NE] per row the items listing it as a negative, in plan order.  max_neg is the
+ * largest negative count of an item (up to 4096).  An entry out of range reads row 0 and never outside a buffer.
+ * sf_op_clp_tracks: the similarity-guided embeddings sg_dev [T, F, C] (zeros before a track's first present frame, repeated over absent
+ * frames) and stats_dev [T, F, 2] = (sim, beta = max(0, sim)) per present frame, 0 elsewhere.                                          */
+int sf_op_clp_tracks(const float* embeds_dev, int R, int C, const int32_t* track_rows_dev, int T, int F, float* sg_dev, float* stats_dev,
+                     sf_stream stream);
+/* Per item log(1 + sum exp(d_neg - d_pos)) (maximum subtracted) and mean((cos - label)^2) over its 1 + n rows: item_out_dev [I, 4] =
+ * (contras, aux, d_pos, 1 / |anchor|); losses_dev [2] = their sums in item order over I (zeros when I = 0).                            */
+int sf_op_clp_items(const float* embeds_dev, int R, int C, const float* sg_dev, int T, int F, const int32_t* items_dev, int I,
+                    const int32_t* neg_dev, int NE, int max_neg, float* losses_dev, float* item_out_dev, sf_stream stream);
+/* grad_embeds_dev [R, C] for upstream_dev [2] = d / d (loss_reid, loss_aux_reid): a gather per row over the items that list it as a
+ * negative, then per track the anchor and positive terms and the recurrence of sg backwards (through beta where sim > 0).  Every row
+ * is written; rows nobody references are exact zeros.                                                                                */
+size_t sf_op_clp_backward_workspace_bytes(int I, int T, int F, int C);
+int sf_op_clp_backward(const float* embeds_dev, int R, int C, const float* sg_dev, const float* stats_dev, const int32_t* track_rows_dev,
+                       const int32_t* track_items_dev, int T, int F, const int32_t* items_dev, int I, const int32_t* neg_dev, int NE,
+                       int max_neg, const int32_t* row_start_dev, const int32_t* row_items_dev, const float* item_out_dev,
+                       const float* upstream_dev, float* grad_embeds_dev, void* workspace, size_t workspace_bytes, sf_stream stream);
+
 /* ---- introspection for bench/roofline ------------------------------------------------------- */
 /* Enqueue `iters` back-to-back launches of the dominant GEMM (the MLP up-projection shape of the
  * loaded model at M rows) between two HIP events on `stream` and return the mean launch time.   */

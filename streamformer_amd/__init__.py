@@ -41,6 +41,7 @@ from .segmentation import (  # noqa: F401
     semantic_inference,
 )
 from .criterion import HungarianMatcher, SetCriterion  # noqa: F401
+from .cl_plugin import CTCLPlugin, ctvis_train_losses  # noqa: F401
 from .processing import TimesformerImageProcessor  # noqa: F401
 
 __version__ = "0.1.0"

@@ -264,6 +264,10 @@ SIGNATURES = {
     "sf_op_crit_class_loss_workspace_bytes": (_SZ, [_I, _I, _I]),
     "sf_op_crit_class_loss": (_I, [C.POINTER(_P), _I, _I, _I, _I, _P, _I, C.POINTER(_P), C.POINTER(C.c_int32), _P, _P, _I, _P, _P, _P, _SZ,
                                    _P]),
+    "sf_op_clp_tracks": (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "sf_op_clp_items": (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "sf_op_clp_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_clp_backward": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "sf_reload_switches": (None, []),
     "sf_switch_info": (C.c_char_p, [_I, _I]),
     "sf_bench_launch_floor": (_I, [_I, _I, _I, _P, C.POINTER(_F)]),
