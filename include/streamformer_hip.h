@@ -816,6 +816,33 @@ size_t sf_op_maskdec_mask_workspace_bytes(int F, int mask_dim, int h, int w);
 int sf_op_maskdec_mask(const float* mask_embed_dev, const float* mask_features_dev, int F, int Q, int mask_dim, int H, int W, int h, int w,
                        uint32_t* bits_dev, float* logits_dev, float* boxes_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 
+/* ---- masked attention for training (streamformer_amd/masked_attention.py): the decoder's attention kernel with the row statistics a
+ * backward needs, that backward, and the mask packer.  All fp32 with exact products, no float atomics, bit-reproducible, the caller's
+ * stream, no allocation, no host synchronisation.  Rows as in sf_op_maskdec_attention: q_dev [F Q] rows of q_pitch floats, k_dev /
+ * v_dev [F HW] rows of kv_pitch floats (column ranges of one [rows, 3 C] buffer work), a head's columns at h * head_dim; mask_dev
+ * uint32 [F, Q, ceil(HW / 32)] shared by the heads, [F, heads, Q, ceil(HW / 32)] with mask_per_head, or NULL (nothing hidden); bits of
+ * keys at or past HW are never read.  Refused before any launch with SF_ERR_INVALID: a NULL required buffer, a buffer that is not
+ * 16-byte aligned, a pitch below heads * head_dim or not a multiple of 4, head_dim not a multiple of 8 in 8..128, F, Q or heads outside
+ * 1..65535, HW outside 1..2^24; SF_ERR_CAPACITY above 2^31 - 1 elements.                                                            */
+/* ctx_dev [F Q, heads * head_dim]: bit for bit what sf_op_maskdec_attention writes without k_pos_dev.  stats_dev [F, heads, Q] or
+ * NULL: the log-sum-exp of the scaled scores over the visible keys; +inf for a query without a visible key (its ctx is zeros).      */
+int sf_op_maskattn_forward(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const uint32_t* mask_dev,
+                           int mask_per_head, float* ctx_dev, float* stats_dev, int F, int Q, int HW, int heads, int head_dim, int no_skip,
+                           sf_stream stream);
+/* ctx_dev and stats_dev as the forward wrote them, d_ctx_dev [F Q, heads * head_dim].  With delta = rowsum(d_ctx o ctx) and
+ * P = exp(q . k / sqrt(head_dim) - stats) on the visible keys: dv = P^T d_ctx, dS = P o (d_ctx v^T - delta), dq = dS k / sqrt(head_dim),
+ * dk = dS^T q / sqrt(head_dim).  dq_dev [F Q] rows of dq_pitch floats, dk_dev / dv_dev [F HW] rows of dkv_pitch floats; every element
+ * of the heads' columns is written: exact zeros in dk / dv for a key no query sees and in dq for a query that sees no key.  Two
+ * launches; a key tile (dq) or query tile (dk, dv) with nothing visible is skipped without being loaded unless no_skip is set; both
+ * ways give the same bits.                                                                                                          */
+int sf_op_maskattn_backward(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const uint32_t* mask_dev,
+                            int mask_per_head, const float* ctx_dev, const float* stats_dev, const float* d_ctx_dev, float* dq_dev, int dq_pitch,
+                            float* dk_dev, float* dv_dev, int dkv_pitch, int F, int Q, int HW, int heads, int head_dim, int no_skip,
+                            sf_stream stream);
+/* mask_dev bytes [rows, HW] (a bool tensor, any leading shape flattened), non-zero = hidden -> bits_dev uint32 [rows, ceil(HW / 32)],
+ * bit (j & 31) of word j / 32 set = key j hidden: the layout sf_op_maskdec_mask writes.  The padding bits of the last word are set.  */
+int sf_op_maskattn_pack(const uint8_t* mask_dev, uint32_t* bits_dev, long long rows, int HW, sf_stream stream);
+
 /* ---- video instance segmentation: the kernels between the mask decoder and a list of instances ---------------------------------
  * (the CTVIS SimpleTracker's frame-local front and CTVISModel.inference_video; streamformer_amd/vis.py runs the association loop on
  * the host).  All fp32, bit-reproducible, the caller's stream, no allocation, no host synchronisation.                              */

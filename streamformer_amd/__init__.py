@@ -42,6 +42,14 @@ from .segmentation import (  # noqa: F401
 )
 from .criterion import HungarianMatcher, SetCriterion  # noqa: F401
 from .cl_plugin import CTCLPlugin, ctvis_train_losses  # noqa: F401
+from .masked_attention import (  # noqa: F401
+    MaskedAttentionFunction,
+    MaskedMultiheadAttention,
+    PackedAttentionMask,
+    masked_attention,
+    pack_attention_mask,
+    use_native_attention,
+)
 from .processing import TimesformerImageProcessor  # noqa: F401
 
 __version__ = "0.1.0"

@@ -242,6 +242,9 @@ SIGNATURES = {
     "sf_maskdec_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(_SZ)]),
     "sf_maskdec_forward": (_I, [_P, C.POINTER(_P), _P, _I, C.POINTER(C.c_int32), _I, _I, C.POINTER(SfMaskdecOutputs), _P, _SZ, _P]),
     "sf_op_maskdec_attention": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "sf_op_maskattn_forward": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "sf_op_maskattn_backward": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "sf_op_maskattn_pack": (_I, [_P, _P, C.c_longlong, _I, _P]),
     "sf_op_maskdec_mask_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_op_maskdec_mask": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "sf_op_vis_scores": (_I, [_P, C.c_longlong, _I, _P, _P, _P, _P]),

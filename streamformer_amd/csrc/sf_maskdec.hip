@@ -22,6 +22,8 @@
 //                                 hidden) is left out before K or V are loaded.  Run unskipped, such a tile scores -inf everywhere: the
 //                                 running max stays, the correction is expf(0) = 1, every weight is 0 and the staged rows are zeros, so the
 //                                 accumulators do not change: both paths give the same bits.  One owner per output element, fixed order.
+//                                 TRAIN (template flag, sf_op_maskattn_forward only): also stats[f, h, q] = m + log l for the backward of
+//                                 sf_maskattn.hip, and a mask per head; the decoder runs the instance without it, whose code is unchanged.
 //   sf_maskdec_interp_kernel      mask_features [F, Dm, H, W] -> [F, Dm, h w] by F.interpolate(bilinear, align_corners=False)'s rule.
 //                                 Interpolation is linear, so the FEATURES are resampled once per level and call, and every layer of the
 //                                 level thresholds mask_embed . resampled features: the [F, Q, H, W] logits of an intermediate layer are
@@ -64,11 +66,14 @@ struct SfMkdAttn {
   int q_pitch, k_pitch, v_pitch, pos_pitch;            // elements per row
   int F, Tq, Tk, heads, hd, words, no_skip;
   float scale;
+  // the training forward (sf_op_maskattn_forward) only; both unset, the kernel is the instance the decoder runs
+  float* stats;                                        // [F, heads, Tq]: log-sum-exp of the scaled scores over the visible keys, +inf without one
+  int mask_per_head;                                   // the mask is [F, heads, Tq, words]
 };
 
 SF_DEVICE mf4_t mk_mfma(float a, float b, mf4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
-template <int NT>      // NT = ceil(head_dim / 16) <= 8
+template <int NT, bool TRAIN>      // NT = ceil(head_dim / 16) <= 8; TRAIN: p.stats and p.mask_per_head are read
 __global__ __launch_bounds__(64 * MKD_WAVES) void sf_maskdec_attention_kernel(SfMkdAttn p) {
   extern __shared__ __attribute__((aligned(16))) float mk_smem[];
   const int HD = p.hd, LD = HD + 4, HDQ = HD >> 2, Tq = p.Tq, Tk = p.Tk;
@@ -88,6 +93,7 @@ __global__ __launch_bounds__(64 * MKD_WAVES) void sf_maskdec_attention_kernel(Sf
     for (int i = 0; i < NT * 4; ++i) qreg[i] = i < HDQ ? q[4 * i] : 0.f;
   }
   const uint32_t* mrow = p.mask ? p.mask + ((size_t)f * Tq + qrow) * p.words : nullptr;
+  if (TRAIN && p.mask && p.mask_per_head) mrow = p.mask + (((size_t)f * p.heads + h) * Tq + qrow) * p.words;
   const size_t kv0 = (size_t)f * Tk;
   mf4_t o_acc[NT];
 #pragma unroll
@@ -205,6 +211,8 @@ __global__ __launch_bounds__(64 * MKD_WAVES) void sf_maskdec_attention_kernel(Sf
     const size_t ob = ((size_t)f * Tq + qo) * ((size_t)p.heads * HD) + h * HD + d;
     if (p.ctx) *reinterpret_cast<mf4_t*>(p.ctx + ob) = o;
     if (p.ctx_hi) store_planes4(o, p.ctx_hi, p.ctx_lo, ob);
+    // m + log l; +inf for a query without a visible key, so that the backward's exp(s - stats) is 0 for it
+    if (TRAIN && p.stats && d == 0) p.stats[((size_t)f * p.heads + h) * Tq + qo] = l_all > 0.f ? m_all + logf(l_all) : INFINITY;
   }
 }
 
@@ -220,8 +228,12 @@ static hipError_t mkd_launch_attention(const SfMkdAttn& p, hipStream_t s) {
   if (blocks > 0x7fffffff) return hipErrorInvalidValue;
   const size_t lds = (size_t)MKD_WAVES * 2 * 16 * (p.hd + 4) * sizeof(float);      // 66 KB at head_dim 128
   const dim3 grid((unsigned)blocks), block(64 * MKD_WAVES);
+  if ((uintptr_t)p.stats & 3) return hipErrorInvalidValue;
+  const bool train = p.stats || p.mask_per_head;
   switch ((p.hd + 15) / 16) {
-#define MK_CASE(E) case E: return sf_launch_big_lds(sf_maskdec_attention_kernel<E>, grid, block, lds, s, p);
+#define MK_CASE(E) \
+  case E: return train ? sf_launch_big_lds(sf_maskdec_attention_kernel<E, true>, grid, block, lds, s, p) \
+                       : sf_launch_big_lds(sf_maskdec_attention_kernel<E, false>, grid, block, lds, s, p);
     MK_CASE(1) MK_CASE(2) MK_CASE(3) MK_CASE(4) MK_CASE(5) MK_CASE(6) MK_CASE(7) MK_CASE(8)
 #undef MK_CASE
     default: return hipErrorInvalidValue;
@@ -807,6 +819,32 @@ extern "C" int sf_op_maskdec_attention(const float* q_dev, int q_pitch, const fl
   a.q = q_dev; a.k = k_dev; a.v = v_dev; a.kpos = k_pos_dev; a.mask = mask_dev;
   a.ctx = ctx_dev; a.ctx_hi = ctx_hi_dev; a.ctx_lo = ctx_lo_dev;
   a.q_pitch = q_pitch; a.k_pitch = kv_pitch; a.v_pitch = kv_pitch; a.pos_pitch = k_pos_dev ? pos_pitch : 0;
+  a.F = F; a.Tq = Q; a.Tk = HW; a.heads = heads; a.hd = head_dim; a.words = (HW + 31) / 32; a.no_skip = no_skip ? 1 : 0;
+  a.scale = 1.0f / sqrtf((float)head_dim);
+  HIP_TRY(mkd_launch_attention(a, (hipStream_t)stream));
+  return SF_OK;
+}
+
+// The same kernel as the training forward of streamformer_amd/masked_attention.py: the row statistics the backward (sf_maskattn.hip)
+// recomputes the probabilities from, and a mask that may differ between the heads.  Without both it is sf_op_maskdec_attention.
+extern "C" int sf_op_maskattn_forward(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const uint32_t* mask_dev,
+                                      int mask_per_head, float* ctx_dev, float* stats_dev, int F, int Q, int HW, int heads, int head_dim, int no_skip,
+                                      sf_stream stream) {
+  const char* who = "sf_op_maskattn_forward";
+  if (!q_dev || !k_dev || !v_dev || !ctx_dev) return sf_set_err(SF_ERR_INVALID, "%s: null buffer", who);
+  if (F < 1 || F > 65535 || Q < 1 || Q > 65535 || HW < 1 || HW > (1 << 24) || heads < 1 || heads > 65535)
+    return sf_set_err(SF_ERR_INVALID, "%s: bad shape F=%d Q=%d HW=%d heads=%d", who, F, Q, HW, heads);
+  if (head_dim < 8 || head_dim > 128 || head_dim % 8) return sf_set_err(SF_ERR_INVALID, "%s: head_dim must be a multiple of 8 in 8..128", who);
+  const int D = heads * head_dim;
+  if (q_pitch < D || kv_pitch < D || ((q_pitch | kv_pitch) & 3))
+    return sf_set_err(SF_ERR_INVALID, "%s: row pitches must be multiples of 4 and at least heads * head_dim = %d", who, D);
+  if ((int64_t)F * (Q > HW ? Q : HW) * std::max(q_pitch, kv_pitch) > (int64_t)0x7fffffff) return sf_set_err(SF_ERR_CAPACITY, "%s: more than 2^31 - 1 elements", who);
+  if (((uintptr_t)q_dev | (uintptr_t)k_dev | (uintptr_t)v_dev | (uintptr_t)mask_dev | (uintptr_t)ctx_dev | (uintptr_t)stats_dev) & 15)
+    return sf_set_err(SF_ERR_INVALID, "%s: buffers must be 16-byte aligned", who);
+  SfMkdAttn a;
+  memset(&a, 0, sizeof(a));
+  a.q = q_dev; a.k = k_dev; a.v = v_dev; a.mask = mask_dev; a.ctx = ctx_dev; a.stats = stats_dev; a.mask_per_head = mask_dev && mask_per_head ? 1 : 0;
+  a.q_pitch = q_pitch; a.k_pitch = kv_pitch; a.v_pitch = kv_pitch;
   a.F = F; a.Tq = Q; a.Tk = HW; a.heads = heads; a.hd = head_dim; a.words = (HW + 31) / 32; a.no_skip = no_skip ? 1 : 0;
   a.scale = 1.0f / sqrtf((float)head_dim);
   HIP_TRY(mkd_launch_attention(a, (hipStream_t)stream));
