@@ -815,6 +815,8 @@ int sf_op_maskdec_attention(const float* q_dev, int q_pitch, const float* k_dev,
 size_t sf_op_maskdec_mask_workspace_bytes(int F, int mask_dim, int h, int w);
 int sf_op_maskdec_mask(const float* mask_embed_dev, const float* mask_features_dev, int F, int Q, int mask_dim, int H, int W, int h, int w,
                        uint32_t* bits_dev, float* logits_dev, float* boxes_dev, void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+/* The boxes alone, of masks_dev [rows, H, W] made elsewhere (sf_op_masklogits_forward): boxes_dev [rows, 4] as pred_bboxes above.    */
+int sf_op_maskdec_boxes(const float* masks_dev, float* boxes_dev, int rows, int H, int W, sf_stream stream);
 
 /* ---- masked attention for training (streamformer_amd/masked_attention.py): the decoder's attention kernel with the row statistics a
  * backward needs, that backward, and the mask packer.  All fp32 with exact products, no float atomics, bit-reproducible, the caller's
@@ -842,6 +844,27 @@ int sf_op_maskattn_backward(const float* q_dev, int q_pitch, const float* k_dev,
 /* mask_dev bytes [rows, HW] (a bool tensor, any leading shape flattened), non-zero = hidden -> bits_dev uint32 [rows, ceil(HW / 32)],
  * bit (j & 31) of word j / 32 set = key j hidden: the layout sf_op_maskdec_mask writes.  The padding bits of the last word are set.  */
 int sf_op_maskattn_pack(const uint8_t* mask_dev, uint32_t* bits_dev, long long rows, int HW, sf_stream stream);
+
+/* ---- mask logits for training (streamformer_amd/mask_decoder.py with trainable=True; csrc/sf_masklogits.hip): the product of every
+ * prediction head at full mask-feature resolution and its gradients.  All fp32 with exact products, one owner and one summation order
+ * per output element, no float atomics, bit-reproducible, the caller's stream, no allocation, no host synchronisation.  The grid is
+ * F x 64-pixel tiles (the backward: spans of them), whatever Q is.  mask_embed_dev [F, Q, mask_dim], mask_features_dev
+ * [F, mask_dim, P] with P = H W, logits [F, Q, P].  Refused before any launch with SF_ERR_INVALID: a NULL required buffer, a buffer
+ * that is not 16-byte aligned, mask_dim not a multiple of 4 in 4..1024, F or Q outside 1..65535, P outside 1..2^24; SF_ERR_CAPACITY
+ * when F max(Q, mask_dim) P or F Q mask_dim exceeds 2^31 - 1.  The bits are not those of sf_op_maskdec_mask's logits.               */
+/* logits_dev[f, q, p] = sum_c mask_embed[f, q, c] mask_features[f, c, p].                                                            */
+int sf_op_masklogits_forward(const float* mask_embed_dev, const float* mask_features_dev, float* logits_dev, int F, int Q, int mask_dim, int P,
+                             sf_stream stream);
+/* d_mask_embed_dev[f, q, c] = sum_p d_logits[f, q, p] mask_features[f, c, p] and d_mask_features_dev[f, c, p] =
+ * sum_q mask_embed[f, q, c] d_logits[f, q, p]; either may be NULL (not both).  accumulate != 0: d_mask_features_dev is added to, not
+ * overwritten (the heads of a decoder share one buffer; the order of the additions is the order of the calls); d_mask_embed_dev is
+ * always overwritten.  Each d_logits tile is read once for both products.  d_mask_embed_dev is summed over spans of pixel tiles:
+ * partial sums go to workspace_dev (sf_op_masklogits_backward_workspace_bytes; not needed without d_mask_embed_dev) and a second
+ * launch adds them in ascending order.                                                                                               */
+size_t sf_op_masklogits_backward_workspace_bytes(int F, int Q, int mask_dim, int P);
+int sf_op_masklogits_backward(const float* d_logits_dev, const float* mask_embed_dev, const float* mask_features_dev, float* d_mask_embed_dev,
+                              float* d_mask_features_dev, int accumulate, int F, int Q, int mask_dim, int P, void* workspace_dev,
+                              size_t workspace_bytes, sf_stream stream);
 
 /* ---- video instance segmentation: the kernels between the mask decoder and a list of instances ---------------------------------
  * (the CTVIS SimpleTracker's frame-local front and CTVISModel.inference_video; streamformer_amd/vis.py runs the association loop on

@@ -245,6 +245,10 @@ SIGNATURES = {
     "sf_op_maskattn_forward": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_maskattn_backward": (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_maskattn_pack": (_I, [_P, _P, C.c_longlong, _I, _P]),
+    "sf_op_maskdec_boxes": (_I, [_P, _P, _I, _I, _I, _P]),
+    "sf_op_masklogits_forward": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_op_masklogits_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_masklogits_backward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "sf_op_maskdec_mask_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "sf_op_maskdec_mask": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _SZ, _P]),
     "sf_op_vis_scores": (_I, [_P, C.c_longlong, _I, _P, _P, _P, _P]),

@@ -851,6 +851,17 @@ extern "C" int sf_op_maskattn_forward(const float* q_dev, int q_pitch, const flo
   return SF_OK;
 }
 
+// the box kernel alone, over masks some other kernel made (the training path's full-resolution logits)
+extern "C" int sf_op_maskdec_boxes(const float* masks_dev, float* boxes_dev, int rows, int H, int W, sf_stream stream) {
+  const char* who = "sf_op_maskdec_boxes";
+  if (!masks_dev || !boxes_dev) return sf_set_err(SF_ERR_INVALID, "%s: null buffer", who);
+  if (rows < 1 || H < 1 || W < 1 || H > 4096 || W > 4096) return sf_set_err(SF_ERR_INVALID, "%s: rows = %d, H = %d, W = %d", who, rows, H, W);
+  if ((long long)rows * H * W > 0x7fffffffLL) return sf_set_err(SF_ERR_CAPACITY, "%s: more than 2^31 - 1 elements", who);
+  if (((uintptr_t)masks_dev | (uintptr_t)boxes_dev) & 15) return sf_set_err(SF_ERR_INVALID, "%s: every buffer must be 16-byte aligned", who);
+  HIP_TRY(sf_launch(sf_maskdec_box_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, masks_dev, boxes_dev, rows, H, W));
+  return SF_OK;
+}
+
 extern "C" size_t sf_op_maskdec_mask_workspace_bytes(int F, int mask_dim, int h, int w) {
   if (F < 1 || mask_dim < 1 || h < 1 || w < 1) return 0;
   return ((size_t)F * mask_dim * h * w * sizeof(float) + 255) & ~(size_t)255;

@@ -16,7 +16,13 @@ runs in ``libstreamformer_hip.so`` (``sf_maskdec_forward``, kernels in ``csrc/sf
     mask_features, _, multi_scale_features = pix.forward_features(pyramid)
     out = dec(multi_scale_features, mask_features)        # pred_logits, pred_masks, pred_embeds, pred_bboxes, ...
 
-Out of scope: training and the losses (``aux_outputs`` is empty unless ``return_aux=True``), the CTVIS tracker and post-processing
+Training is an opt-in: ``trainable=True`` (constructor keyword or attribute) makes ``.train()`` run an autograd graph instead of the
+refusal: torch ops on the module's own parameters, attention through ``MaskedAttentionFunction``, each layer's packed attention mask
+from ``sf_op_maskdec_mask``, and the full-resolution mask logits of all ``dec_layers + 1`` heads through ``sf_op_masklogits_forward`` /
+``sf_op_masklogits_backward`` (``csrc/sf_masklogits.hip``), with ONE gradient buffer for ``mask_features`` shared by the heads.  The
+result feeds ``SetCriterion`` / ``ctvis_train_losses`` and ``.backward()``.  ``.eval()`` is the same native path either way.
+
+Out of scope: the losses themselves (in eval ``aux_outputs`` is empty unless ``return_aux=True``), the CTVIS tracker and post-processing
 (``ctvis_model.py``'s inference over ``pred_embeds``), ``StandardTransformerDecoder``, and padding masks (the reference deletes its
 ``mask`` argument itself; it is accepted and ignored here too).
 """
@@ -24,12 +30,17 @@ from __future__ import annotations
 
 import ctypes as C
 import logging
+import math
 from typing import Any, Dict, List, Optional, Sequence
 
 import torch
+import torch.nn.functional as TF
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
+from .masked_attention import MaskedAttentionFunction, PackedAttentionMask
 from .pixel_decoder import ConvNorm, _c2_xavier_fill, _staged_dtype
 
 __all__ = ["MultiScaleMaskedTransformerDecoder", "CLMultiScaleMaskedTransformerDecoder"]
@@ -42,6 +53,107 @@ def _xavier_matrices(module: nn.Module) -> None:
     for p in module.parameters():
         if p.dim() > 1:
             nn.init.xavier_uniform_(p)
+
+
+class _SharedGrad:
+    """The one gradient buffer of ``mask_features`` that the heads of a training forward add into."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None
+
+
+class _MaskFeatureHub(Function):
+    """Identity on ``mask_features``.  Every head reads the OUTPUT, so autograd runs this backward after the backward of every head;
+    the heads add their gradients into ``shared.buf`` (``sf_op_masklogits_backward``, ``accumulate``) and return none of their own, and
+    this hands the buffer back as the gradient of ``mask_features``: one full-size tensor instead of ``dec_layers + 1``."""
+
+    @staticmethod
+    def forward(ctx, mask_features, shared):
+        ctx.shared = shared
+        ctx.set_materialize_grads(False)
+        return mask_features.view_as(mask_features)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        buf, ctx.shared.buf = ctx.shared.buf, None
+        if grad is not None:                  # a reader of the hub's output that is not a head
+            buf = grad if buf is None else buf + grad
+        return buf, None
+
+
+class _MaskLogitsFunction(Function):
+    """``logits[f, q, h, w] = sum_c me[f, q, c] feat[f, c, h, w]`` on the HIP kernels; the gradient of ``feat`` goes to ``shared``."""
+
+    @staticmethod
+    def forward(ctx, me, feat, shared):
+        Fr, Q, Dm = me.shape
+        H, W = feat.shape[2:]
+        me = me.contiguous()
+        out = torch.empty(Fr, Q, H, W, device=me.device, dtype=torch.float32)
+        with torch.cuda.device(me.device):
+            nat.check(nat.lib.sf_op_masklogits_forward(me.data_ptr(), feat.data_ptr(), out.data_ptr(), Fr, Q, Dm, H * W,
+                                                       nat.current_stream_handle(me.device)))
+        ctx.save_for_backward(me, feat)
+        ctx.shared = shared
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        me, feat = ctx.saved_tensors
+        shared = ctx.shared
+        Fr, Q, Dm = me.shape
+        P = feat.shape[2] * feat.shape[3]
+        grad = grad.float().contiguous()
+        d_me = torch.empty_like(me) if ctx.needs_input_grad[0] else None
+        d_feat, accumulate = None, 0
+        if ctx.needs_input_grad[1]:
+            accumulate = int(shared.buf is not None)
+            if shared.buf is None:
+                shared.buf = torch.empty_like(feat)
+            d_feat = shared.buf
+        if d_me is None and d_feat is None:
+            return None, None, None
+        ws = None
+        if d_me is not None:
+            ws = torch.empty(max(nat.lib.sf_op_masklogits_backward_workspace_bytes(Fr, Q, Dm, P), 256), dtype=torch.uint8, device=me.device)
+        with torch.cuda.device(me.device):
+            nat.check(nat.lib.sf_op_masklogits_backward(grad.data_ptr(), me.data_ptr(), feat.data_ptr(), nat.ptr(d_me), nat.ptr(d_feat), accumulate,
+                                                        Fr, Q, Dm, P, nat.ptr(ws), 0 if ws is None else ws.numel(),
+                                                        nat.current_stream_handle(me.device)))
+        return d_me, None, None               # the hub returns the gradient of the features
+
+
+class _Reach(Function):
+    """Identity on ``out`` that gives ``others`` a zero gradient: with fewer than three layers a feature level is projected and never
+    attended to, and its ``input_proj`` / ``x[l]`` would be left without a gradient (``None``) where a training loop expects zeros."""
+
+    @staticmethod
+    def forward(ctx, out, *others):
+        ctx.meta = [(t.shape, t.dtype, t.device) for t in others]
+        return out.view_as(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad):
+        return (grad,) + tuple(torch.zeros(s, dtype=d, device=dev) for s, d, dev in ctx.meta)
+
+
+def _sine_table(h: int, w: int, C: int, device) -> torch.Tensor:
+    """PositionEmbeddingSine(C / 2, normalize=True) of an all-false mask as rows [h w, C], fp32 (computed in fp64, rounded once)."""
+    wd = torch.float64
+    npf = C // 2
+    y = torch.arange(1, h + 1, dtype=wd, device=device)[:, None].expand(h, w)
+    x = torch.arange(1, w + 1, dtype=wd, device=device)[None, :].expand(h, w)
+    y = y / (y[-1:, :] + 1e-6) * (2 * math.pi)
+    x = x / (x[:, -1:] + 1e-6) * (2 * math.pi)
+    dim_t = torch.arange(npf, dtype=wd, device=device)
+    dim_t = 10000 ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / npf)
+    px, py = x[:, :, None] / dim_t, y[:, :, None] / dim_t
+    px = torch.stack((px[:, :, 0::2].sin(), px[:, :, 1::2].cos()), dim=3).flatten(2)
+    py = torch.stack((py[:, :, 0::2].sin(), py[:, :, 1::2].cos()), dim=3).flatten(2)
+    return torch.cat((py, px), dim=2).reshape(h * w, C).float()
 
 
 class _SelfAttentionLayer(nn.Module):
@@ -86,10 +198,12 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
 
     def __init__(self, in_channels: int, mask_classification: bool = True, *, num_classes: int, hidden_dim: int, num_queries: int, nheads: int,
                  dim_feedforward: int, dec_layers: int, pre_norm: bool, mask_dim: int, enforce_input_project: bool,
-                 compute_dtype: Any = "fp32"):
+                 compute_dtype: Any = "fp32", trainable: bool = False):
         super().__init__()
         self._compute = nat.compute_mode(compute_dtype)
         self.compute_dtype = compute_dtype
+        self._trainable = False
+        self.trainable = trainable
         self.in_channels, self.mask_classification, self.pre_norm = int(in_channels), bool(mask_classification), bool(pre_norm)
         self.num_classes, self.hidden_dim, self.num_queries, self.num_heads = int(num_classes), int(hidden_dim), int(num_queries), int(nheads)
         self.dim_feedforward, self.num_layers, self.mask_dim = int(dim_feedforward), int(dec_layers), int(mask_dim)
@@ -170,16 +284,122 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         return self._native.get(dev, nat.weights_token(dev, [p for _, p in params]), params)
 
     # ------------------------------------------------------------------------------------ forward
-    @torch.no_grad()
+    @property
+    def trainable(self) -> bool:
+        """Whether ``.train()`` runs the autograd path (fp32 only) instead of refusing."""
+        return self._trainable
+
+    @trainable.setter
+    def trainable(self, value: bool) -> None:
+        if value and self._compute != nat.compute_mode("fp32"):
+            raise ValueError(f"trainable=True needs compute_dtype='fp32', got compute_dtype={self.compute_dtype!r} (there is no bf16 training mode)")
+        self._trainable = bool(value)
+
     def forward(self, x: Sequence[torch.Tensor], mask_features: torch.Tensor, mask: Optional[torch.Tensor] = None, *, return_aux: bool = False,
                 return_attn_masks: bool = False) -> Dict[str, Any]:
         """``x``: three fp32 (F, in_channels, h_l, w_l) feature maps, ``mask_features``: fp32 (F, mask_dim, H, W), both on the GPU, as the
         pixel decoder returns them.  Returns the reference's dict; ``aux_outputs`` is an empty list unless ``return_aux`` (the per-layer
         predictions are a training need).  ``return_attn_masks`` adds ``attn_masks``: per layer the bit-packed attention mask, int32
-        (F, Q, ceil(h w / 32)), bit ``j & 31`` of word ``j // 32`` set where key ``j`` is hidden."""
+        (F, Q, ceil(h w / 32)), bit ``j & 31`` of word ``j // 32`` set where key ``j`` is hidden.
+
+        In ``.train()`` with ``trainable=True`` the result is differentiable and ``aux_outputs`` is always populated."""
         del mask                          # the reference disables it too
-        if self.training:
+        if self.training and not self._trainable:
             raise RuntimeError("the native mask decoder is inference only: call .eval() (training and the losses are not part of it)")
+        if self.training:
+            return self._forward_train(*self._checked(x, mask_features), return_attn_masks)
+        with torch.no_grad():
+            return self._forward_eval(*self._checked(x, mask_features), return_aux, return_attn_masks)
+
+    # ------------------------------------------------------------------------------------ training forward
+    def _attend(self, mha: nn.MultiheadAttention, q_in, k_in, v_in, mask: Optional[PackedAttentionMask]):
+        """nn.MultiheadAttention's arithmetic on ``mha``'s own parameters, [F, T, C] tensors, the attention itself on the HIP kernels."""
+        Cd = self.hidden_dim
+        w, b = mha.in_proj_weight, mha.in_proj_bias
+        if q_in is k_in:                  # self-attention: q and k from one [F, T, 2 C] product, read in place by the kernel
+            qk = TF.linear(q_in, w[:2 * Cd], b[:2 * Cd])
+            q, k = qk[..., :Cd], qk[..., Cd:]
+        else:
+            q, k = TF.linear(q_in, w[:Cd], b[:Cd]), TF.linear(k_in, w[Cd:2 * Cd], b[Cd:2 * Cd])
+        v = TF.linear(v_in, w[2 * Cd:], b[2 * Cd:])
+        ctx = MaskedAttentionFunction.apply(q, k, v, mask, self.num_heads)
+        return TF.linear(ctx, mha.out_proj.weight, mha.out_proj.bias)
+
+    def _forward_train(self, xs, mf, return_attn_masks: bool) -> Dict[str, Any]:
+        dev = self.device
+        F, Dm, H, W = mf.shape
+        Q, Cd, L = self.num_queries, self.hidden_dim, self.num_layers
+        cl = self._reid_layers >= 0
+        stream = nat.current_stream_handle(dev)
+        shared = _SharedGrad()
+        feat = _MaskFeatureHub.apply(mf, shared)
+        mf_plain = mf.detach()
+        src, pos, sizes = [], [], []
+        for l, t in enumerate(xs):
+            h, w = t.shape[2:]
+            sizes.append((h, w))
+            rows = t.flatten(2).transpose(1, 2)
+            proj = self.input_proj[l]
+            if isinstance(proj, ConvNorm):
+                rows = TF.linear(rows, proj.weight.flatten(1), proj.bias)
+            src.append(rows + self.level_embed.weight[l])
+            pos.append(_sine_table(h, w, Cd, dev))
+        qe = self.query_embed.weight.unsqueeze(0).expand(F, -1, -1)
+        out = self.query_feat.weight.unsqueeze(0).expand(F, -1, -1)
+        if L < self.num_feature_levels:   # levels no layer attends to: zero gradients, not None
+            out = _Reach.apply(out, *src[L:])
+
+        def mlp(m: _MLP, v):
+            for j, layer in enumerate(m.layers):
+                v = layer(v)
+                if j < m.num_layers - 1:
+                    v = torch.relu(v)
+            return v
+
+        def heads_of(out, size):
+            """The prediction heads on decoder_norm(out), and the packed attention mask the next layer attends under (``size`` or None)."""
+            dn = self.decoder_norm(out)
+            pred = {"pred_logits": self.class_embed(dn)}
+            me = mlp(self.mask_embed, dn).contiguous()
+            pred["pred_masks"] = _MaskLogitsFunction.apply(me, feat, shared)
+            if cl:
+                pred["pred_queries"] = dn
+                pred["pred_embeds"] = mlp(self.reid_embed, dn) if isinstance(self.reid_embed, _MLP) else self.reid_embed(dn)
+            bits = None
+            if size is not None:
+                h, w = size
+                bits = torch.empty(F, Q, (h * w + 31) // 32, dtype=torch.int32, device=dev)
+                ws = self._native.workspace(nat.lib.sf_op_maskdec_mask_workspace_bytes(F, Dm, h, w), dev, key="train mask")
+                with torch.cuda.device(dev):
+                    nat.check(nat.lib.sf_op_maskdec_mask(me.detach().data_ptr(), mf_plain.data_ptr(), F, Q, Dm, H, W, h, w, bits.data_ptr(), None, None,
+                                                         ws.data_ptr(), ws.numel(), stream))
+            return pred, bits
+
+        preds, masks = [], []
+        pred, bits = heads_of(out, sizes[0] if L else None)
+        preds.append(pred)
+        for i in range(L):
+            l = i % self.num_feature_levels
+            masks.append(bits)
+            ca, sa, ffn = self.transformer_cross_attention_layers[i], self.transformer_self_attention_layers[i], self.transformer_ffn_layers[i]
+            out = ca.norm(out + self._attend(ca.multihead_attn, out + qe, src[l] + pos[l], src[l], PackedAttentionMask(bits, sizes[l][0] * sizes[l][1])))
+            x_pos = out + qe
+            out = sa.norm(out + self._attend(sa.self_attn, x_pos, x_pos, out, None))
+            out = ffn.norm(out + ffn.linear2(torch.relu(ffn.linear1(out))))
+            pred, bits = heads_of(out, sizes[(i + 1) % self.num_feature_levels] if i + 1 < L else None)
+            preds.append(pred)
+        res: Dict[str, Any] = dict(preds[-1])
+        if cl:
+            boxes = torch.empty(F, Q, 4, dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                nat.check(nat.lib.sf_op_maskdec_boxes(res["pred_masks"].detach().data_ptr(), boxes.data_ptr(), F * Q, H, W, stream))
+            res.update(pred_bboxes=boxes, query_pos_embeds=self.query_embed.weight.detach().unsqueeze(0).repeat(F, 1, 1))
+        res["aux_outputs"] = preds[:-1]
+        if return_attn_masks:
+            res["attn_masks"] = masks
+        return res
+
+    def _checked(self, x, mask_features):
         if len(x) != self.num_feature_levels:
             raise ValueError(f"x must hold {self.num_feature_levels} feature maps, got {len(x)}")
         dev = self.device
@@ -193,7 +413,11 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             if t.dim() != 4 or t.shape[0] != F or t.shape[1] != self.in_channels:
                 raise ValueError(f"x[{i}] must be ({F}, {self.in_channels}, h, w), got {tuple(t.shape)}")
             xs.append(t.to(device=dev, dtype=torch.float32).contiguous())
-        mf = mask_features.to(device=dev, dtype=torch.float32).contiguous()
+        return xs, mask_features.to(device=dev, dtype=torch.float32).contiguous()
+
+    def _forward_eval(self, xs, mf, return_aux: bool, return_attn_masks: bool) -> Dict[str, Any]:
+        dev = self.device
+        F, _, H, W = mf.shape
         h = self._handle()
         Q, Cd, L, K1 = self.num_queries, self.hidden_dim, self.num_layers, self.num_classes + 1
         cl = self._reid_layers >= 0
@@ -245,12 +469,12 @@ class CLMultiScaleMaskedTransformerDecoder(MultiScaleMaskedTransformerDecoder):
 
     def __init__(self, in_channels: int, mask_classification: bool = True, *, num_classes: int, hidden_dim: int, num_queries: int, nheads: int,
                  dim_feedforward: int, dec_layers: int, pre_norm: bool, mask_dim: int, enforce_input_project: bool, reid_hidden_dim: int,
-                 num_reid_head_layers: int, compute_dtype: Any = "fp32", **kwargs):
+                 num_reid_head_layers: int, compute_dtype: Any = "fp32", trainable: bool = False, **kwargs):
         self._reid_layers = max(int(num_reid_head_layers), 0)
         self._reid_hidden_dim = int(reid_hidden_dim)
         super().__init__(in_channels, mask_classification, num_classes=num_classes, hidden_dim=hidden_dim, num_queries=num_queries, nheads=nheads,
                          dim_feedforward=dim_feedforward, dec_layers=dec_layers, pre_norm=pre_norm, mask_dim=mask_dim,
-                         enforce_input_project=enforce_input_project, compute_dtype=compute_dtype)
+                         enforce_input_project=enforce_input_project, compute_dtype=compute_dtype, trainable=trainable)
         if num_reid_head_layers > 0:
             self.reid_embed = _MLP(hidden_dim, reid_hidden_dim, hidden_dim, num_reid_head_layers)
             for layer in self.reid_embed.layers:
