@@ -8,6 +8,7 @@ with the repo snapshot; nothing is JIT-built at import time.
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -57,9 +58,7 @@ def build(force: bool = False, verbose: bool = True, lab: bool = False, variant:
     os.makedirs(objdir, exist_ok=True)
     if lab and not os.path.isdir(LAB_DIR):
         raise RuntimeError("the lab kernels (tools/lab/) are not present in this checkout")
-    headers = [os.path.join(CSRC, "sf_common.h"), os.path.join(CSRC, "sf_launch.h"), os.path.join(CSRC, "sf_train.h"), os.path.join(CSRC, "sf_internal.h"), os.path.join(CSRC, "sf_pool_head.h"), os.path.join(CSRC, "sf_switches.h"),
-               os.path.join(CSRC, "sf_weights.h"), os.path.join(CSRC, "sf_handle.h"), os.path.join(CSRC, "sf_encoder.h"), os.path.join(CSRC, "sf_vis_axis.h"),
-               os.path.join(os.path.dirname(HERE), "include", "streamformer_hip.h")]
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "streamformer_hip.h")]
 
     def compile_one(src: str) -> str:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))

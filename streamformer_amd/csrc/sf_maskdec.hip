@@ -6,24 +6,10 @@
 // GEMM launchers (sf_launch_gemm, both compute modes, weights rounded / split ONCE at finalize), the row passes on sf_row_kernel; this
 // file adds the kernels those do not cover, the launch sequence and the C entry points.
 //
-//   sf_maskdec_attention_kernel   ctx[f, q, h, :] = softmax_j(scale Q . (K_j + kpos_j) | mask[f, q, j]) V_j in fp32 with exact products
-//                                 (v_mfma_f32_16x16x4_f32), arithmetic and lane layout of sf_oad_attention_kernel: expf, eight blocked score
-//                                 chains, running max / sum over 16-key tiles, zero-staged invisible keys, zeros for a query that sees no
-//                                 key.  The mask is bit-packed [F, Q, ceil(HW / 32)] (bit set = key hidden), shared by the heads; a null
-//                                 mask is the unmasked Q x Q self-attention.
-//                                 WORKGROUP SHAPE: 256 threads = 4 waves on ONE 16-query tile of one (frame, head); the key tiles are dealt
-//                                 round-robin to the waves (tile t -> wave t % 4), each wave keeps its own running max / sum / accumulator
-//                                 and its own K | V staging area in LDS, and the four partial results meet in LDS at the end in wave order
-//                                 (max, then sum of exp(m_w - max) weighted partials).  The grid is F x heads x ceil(Q / 16) workgroups, so
-//                                 F = 1, Q = 100, 8 heads is 56 workgroups x 4 waves = 224 waves: close to one per CU of the 256, where one
-//                                 wave per tile (sf_oad's shape) would occupy 56.  More waves per tile would leave 784 / 16 = 49 key tiles
-//                                 at fewer than 12 each and a merge as long as the work; splitting the 16 queries would halve the MFMA tile.
-//                                 SKIP: a key tile hidden from all 16 queries of the workgroup (mask words all set; keys past HW count as
-//                                 hidden) is left out before K or V are loaded.  Run unskipped, such a tile scores -inf everywhere: the
-//                                 running max stays, the correction is expf(0) = 1, every weight is 0 and the staged rows are zeros, so the
-//                                 accumulators do not change: both paths give the same bits.  One owner per output element, fixed order.
-//                                 TRAIN (template flag, sf_op_maskattn_forward only): also stats[f, h, q] = m + log l for the backward of
-//                                 sf_maskattn.hip, and a mask per head; the decoder runs the instance without it, whose code is unchanged.
+//   (sf_maskattn.hip)             sf_maskdec_attention_kernel through mka_launch_forward (sf_maskattn.h): ctx[f, q, h, :] =
+//                                 softmax_j(scale Q . (K_j + kpos_j) | mask[f, q, j]) V_j in fp32, the mask bit-packed [F, Q, ceil(HW / 32)]
+//                                 (bit set = key hidden) and shared by the heads; a null mask is the unmasked Q x Q self-attention.
+//                                 Workgroup shape, skip rule and the training path are described there.
 //   sf_maskdec_interp_kernel      mask_features [F, Dm, H, W] -> [F, Dm, h w] by F.interpolate(bilinear, align_corners=False)'s rule.
 //                                 Interpolation is linear, so the FEATURES are resampled once per level and call, and every layer of the
 //                                 level thresholds mask_embed . resampled features: the [F, Q, H, W] logits of an intermediate layer are
@@ -56,195 +42,11 @@ typedef __attribute__((ext_vector_type(4))) float mf4_t;
 #define MKD_MAX_MASK_DIM 1024
 
 // ------------------------------------------------------------------------------------------------
-// masked attention
-// ------------------------------------------------------------------------------------------------
-struct SfMkdAttn {
-  const float* q; const float* k; const float* v;      // fp32 rows; a head's columns at h * hd
-  const float* kpos;                                   // [Tk, pos_pitch] by key, or null
-  const uint32_t* mask;                                // [F, Tq, words], bit j & 31 of word j / 32 set: key j hidden; or null
-  float* ctx; bf16_t* ctx_hi; bf16_t* ctx_lo;          // [F Tq, heads * hd]; any of them null
-  int q_pitch, k_pitch, v_pitch, pos_pitch;            // elements per row
-  int F, Tq, Tk, heads, hd, words, no_skip;
-  float scale;
-  // the training forward (sf_op_maskattn_forward) only; both unset, the kernel is the instance the decoder runs
-  float* stats;                                        // [F, heads, Tq]: log-sum-exp of the scaled scores over the visible keys, +inf without one
-  int mask_per_head;                                   // the mask is [F, heads, Tq, words]
-};
-
-SF_DEVICE mf4_t mk_mfma(float a, float b, mf4_t c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-template <int NT, bool TRAIN>      // NT = ceil(head_dim / 16) <= 8; TRAIN: p.stats and p.mask_per_head are read
-__global__ __launch_bounds__(64 * MKD_WAVES) void sf_maskdec_attention_kernel(SfMkdAttn p) {
-  extern __shared__ __attribute__((aligned(16))) float mk_smem[];
-  const int HD = p.hd, LD = HD + 4, HDQ = HD >> 2, Tq = p.Tq, Tk = p.Tk;
-  const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63, l15 = lane & 15, g = lane >> 4;
-  const int area = 2 * 16 * LD;                        // floats of a wave's staging area
-  float* kt = mk_smem + wave * area;
-  float* vt = kt + 16 * LD;
-  const int qtiles = (Tq + 15) >> 4;
-  int b = (int)blockIdx.x;
-  const int qt = b % qtiles; b /= qtiles;
-  const int h = b % p.heads, f = b / p.heads;
-  const int qi = qt * 16 + l15, qrow = qi < Tq ? qi : Tq - 1;      // lanes past Tq repeat the last query, see no key and store nothing
-  float qreg[NT * 4];
-  {
-    const float* q = p.q + ((size_t)f * Tq + qrow) * p.q_pitch + h * HD + g;      // k-index (g, i) of the score MFMAs is dim 4 i + g
-#pragma unroll
-    for (int i = 0; i < NT * 4; ++i) qreg[i] = i < HDQ ? q[4 * i] : 0.f;
-  }
-  const uint32_t* mrow = p.mask ? p.mask + ((size_t)f * Tq + qrow) * p.words : nullptr;
-  if (TRAIN && p.mask && p.mask_per_head) mrow = p.mask + (((size_t)f * p.heads + h) * Tq + qrow) * p.words;
-  const size_t kv0 = (size_t)f * Tk;
-  mf4_t o_acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) o_acc[t] = (mf4_t){0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-  const int ntiles = (Tk + 15) >> 4, rounds = (ntiles + MKD_WAVES - 1) / MKD_WAVES;
-  for (int r = 0; r < rounds; ++r) {                   // every wave runs every round: the barriers below are reached by all of them
-    const int k0 = (r * MKD_WAVES + wave) * 16;
-    bool active = k0 < Tk;
-    unsigned vis = 0u, any = 0u;                       // bit j: key k0 + j is visible to this lane's query / to one of the 16 queries
-    if (active) {
-      const int nk = Tk - k0;
-      const unsigned valid = nk >= 16 ? 0xffffu : ((1u << nk) - 1u);
-      const unsigned hidden = mrow ? (mrow[k0 >> 5] >> (k0 & 31)) & 0xffffu : 0u;
-      vis = qi < Tq ? (~hidden & valid) : 0u;
-      any = vis;
-      any |= __shfl_xor(any, 1, 64); any |= __shfl_xor(any, 2, 64); any |= __shfl_xor(any, 4, 64); any |= __shfl_xor(any, 8, 64);
-      if (!p.no_skip && any == 0u) active = false;     // the same in every lane: the four 16-lane groups hold the same 16 queries
-    }
-    __syncthreads();
-    if (active) {
-      // ---- K + kpos and V of 16 keys; a key no query of the tile sees (and a row past Tk) is staged as zeros (0 * p stays finite) ----
-      for (int c = lane; c < 16 * HDQ; c += 64) {
-        const int row = c / HDQ, cc = c - row * HDQ;
-        mf4_t kv = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
-        if ((any >> row) & 1u) {
-          const size_t key = kv0 + k0 + row;
-          kv = *reinterpret_cast<const mf4_t*>(p.k + key * p.k_pitch + h * HD + cc * 4);
-          vv = *reinterpret_cast<const mf4_t*>(p.v + key * p.v_pitch + h * HD + cc * 4);
-          if (p.kpos) kv += *reinterpret_cast<const mf4_t*>(p.kpos + (size_t)(k0 + row) * p.pos_pitch + h * HD + cc * 4);
-        }
-        *reinterpret_cast<mf4_t*>(kt + row * LD + cc * 4) = kv;
-        *reinterpret_cast<mf4_t*>(vt + row * LD + cc * 4) = vv;
-      }
-    }
-    __syncthreads();
-    if (active) {
-      // S^T tile: keys k0 + l15 (A operand) x queries (B operand); lane (query l15, g) receives keys k0 + 4 g + r.  Eight chains, a tree.
-      mf4_t s4;
-      {
-        mf4_t part[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) part[j] = (mf4_t){0.f, 0.f, 0.f, 0.f};
-        const float* kr = kt + l15 * LD + g;
-#pragma unroll
-        for (int i = 0; i < NT * 4; ++i)
-          if (i < HDQ) part[i & 7] = mk_mfma(kr[4 * i], qreg[i], part[i & 7]);
-        s4 = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
-      }
-      float mx = -INFINITY;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const bool ok = (vis >> (4 * g + rr)) & 1u;
-        s4[rr] = ok ? s4[rr] * p.scale : -INFINITY;
-        mx = fmaxf(mx, s4[rr]);
-      }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float m_new = fmaxf(m_run, mx);
-      const float corr = m_new == -INFINITY ? 1.f : expf(m_run - m_new);      // no visible key so far: keep zeros
-      float psum = 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        s4[rr] = m_new == -INFINITY ? 0.f : expf(s4[rr] - m_new);
-        psum += s4[rr];
-      }
-      psum += __shfl_xor(psum, 16, 64);
-      psum += __shfl_xor(psum, 32, 64);
-      l_run = l_run * corr + psum;
-      m_run = m_new;
-      // O^T += V^T P^T: lane (dim l15 of the 16-dim tile, g) supplies V[k0 + 4 g + r][d]
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        o_acc[t] *= corr;
-        const int d = t * 16 + l15;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float v = d < HD ? vt[(4 * g + rr) * LD + d] : 0.f;
-          o_acc[t] = mk_mfma(v, s4[rr], o_acc[t]);
-        }
-      }
-    }
-  }
-  // ---- the four waves' partial results meet: each leaves (o [16][HD], m [16], l [16]) in its own staging area ----
-  __syncthreads();
-  {
-    float* po = kt;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int d = t * 16 + 4 * g;
-      if (d < HD) *reinterpret_cast<mf4_t*>(po + l15 * HD + d) = o_acc[t];
-    }
-    if (g == 0) { po[16 * HD + l15] = m_run; po[16 * HD + 16 + l15] = l_run; }
-  }
-  __syncthreads();
-  for (int idx = (int)threadIdx.x; idx < 16 * HDQ; idx += 64 * MKD_WAVES) {
-    const int qq = idx / HDQ, d = (idx - qq * HDQ) * 4;
-    const int qo = qt * 16 + qq;
-    if (qo >= Tq) continue;
-    float mw[MKD_WAVES], m_all = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < MKD_WAVES; ++w) { mw[w] = mk_smem[w * area + 16 * HD + qq]; m_all = fmaxf(m_all, mw[w]); }
-    mf4_t o = {0.f, 0.f, 0.f, 0.f};
-    float l_all = 0.f;
-    if (m_all != -INFINITY) {
-#pragma unroll
-      for (int w = 0; w < MKD_WAVES; ++w) {              // wave order: one fixed summation order
-        const float cf = expf(mw[w] - m_all);           // a wave without a visible key: expf(-inf) = 0
-        l_all += cf * mk_smem[w * area + 16 * HD + 16 + qq];
-        o += cf * *reinterpret_cast<const mf4_t*>(mk_smem + w * area + qq * HD + d);
-      }
-    }
-    const float inv = l_all > 0.f ? 1.0f / l_all : 0.f;      // no visible key: zeros
-    o *= inv;
-    const size_t ob = ((size_t)f * Tq + qo) * ((size_t)p.heads * HD) + h * HD + d;
-    if (p.ctx) *reinterpret_cast<mf4_t*>(p.ctx + ob) = o;
-    if (p.ctx_hi) store_planes4(o, p.ctx_hi, p.ctx_lo, ob);
-    // m + log l; +inf for a query without a visible key, so that the backward's exp(s - stats) is 0 for it
-    if (TRAIN && p.stats && d == 0) p.stats[((size_t)f * p.heads + h) * Tq + qo] = l_all > 0.f ? m_all + logf(l_all) : INFINITY;
-  }
-}
-
-// every pointer 16-byte aligned (planes 8), pitches multiples of 4, hd % 8 == 0 in 8..128: checked here
-static hipError_t mkd_launch_attention(const SfMkdAttn& p, hipStream_t s) {
-  if (p.F < 1 || p.Tq < 1 || p.Tk < 1 || p.heads < 1) return hipErrorInvalidValue;
-  if (p.hd < 8 || p.hd > 128 || p.hd % 8) return hipErrorInvalidValue;
-  if (!p.q || !p.k || !p.v || (p.mask && p.words < (p.Tk + 31) / 32)) return hipErrorInvalidValue;
-  if (((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.kpos | (uintptr_t)p.ctx) & 15) return hipErrorInvalidValue;
-  if (((uintptr_t)p.ctx_hi | (uintptr_t)p.ctx_lo) & 7 || ((uintptr_t)p.mask & 3)) return hipErrorInvalidValue;
-  if ((p.q_pitch | p.k_pitch | p.v_pitch | p.pos_pitch) & 3) return hipErrorInvalidValue;
-  const int64_t blocks = (int64_t)p.F * p.heads * ((p.Tq + 15) / 16);
-  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  const size_t lds = (size_t)MKD_WAVES * 2 * 16 * (p.hd + 4) * sizeof(float);      // 66 KB at head_dim 128
-  const dim3 grid((unsigned)blocks), block(64 * MKD_WAVES);
-  if ((uintptr_t)p.stats & 3) return hipErrorInvalidValue;
-  const bool train = p.stats || p.mask_per_head;
-  switch ((p.hd + 15) / 16) {
-#define MK_CASE(E) \
-  case E: return train ? sf_launch_big_lds(sf_maskdec_attention_kernel<E, true>, grid, block, lds, s, p) \
-                       : sf_launch_big_lds(sf_maskdec_attention_kernel<E, false>, grid, block, lds, s, p);
-    MK_CASE(1) MK_CASE(2) MK_CASE(3) MK_CASE(4) MK_CASE(5) MK_CASE(6) MK_CASE(7) MK_CASE(8)
-#undef MK_CASE
-    default: return hipErrorInvalidValue;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 // mask features at a level's resolution; mask logits -> packed attention mask, or fp32 masks; boxes; class columns
 // ------------------------------------------------------------------------------------------------
 struct SfMkdInterp { const float* in; float* out; int H, W, h, w; float ry, rx; size_t total; };      // total = F * Dm * h * w
 
+#include "sf_maskattn.h"
 __global__ __launch_bounds__(256) void sf_maskdec_interp_kernel(SfMkdInterp p) {
   const size_t hw = (size_t)p.h * p.w;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.total; i += (size_t)gridDim.x * blockDim.x) {
@@ -728,13 +530,13 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
       // cross-attention
       HIP_TRY(lin.f32(ly.cq, ws.q, M, ws.qkv, C));
       HIP_TRY(lin.f32(ly.ckv, src[l], F * hw, ws.kv, 2 * C));
-      SfMkdAttn a;
+      SfMkaFwd a;
       memset(&a, 0, sizeof(a));
       a.q = ws.qkv; a.k = ws.kv; a.v = ws.kv + C; a.kpos = kpos[i - 1]; a.mask = mask;
       a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
-      a.q_pitch = C; a.k_pitch = 2 * C; a.v_pitch = 2 * C; a.pos_pitch = C;
+      a.q_pitch = C; a.kv_pitch = 2 * C; a.pos_pitch = C;
       a.F = F; a.Tq = Q; a.Tk = hw; a.heads = heads; a.hd = hd; a.words = pl.words[l]; a.scale = scale;
-      HIP_TRY(mkd_launch_attention(a, s));
+      HIP_TRY(mka_launch_forward(a, s));
       HIP_TRY(lin.resid(ly.co, ws.ctx, M, ws.out, ws.tmp));
       HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.cnorm, h->query_embed, Q, ws.out, ws.y.hi, ws.y.lo, ws.q.hi, ws.q.lo, M, C, s));
       // self-attention: q = k = x + query_embed, v = x
@@ -743,9 +545,9 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
       memset(&a, 0, sizeof(a));
       a.q = ws.qkv; a.k = ws.qkv + C; a.v = ws.qkv + 2 * C;
       a.ctx_hi = ws.ctx.hi; a.ctx_lo = ws.ctx.lo;
-      a.q_pitch = 3 * C; a.k_pitch = 3 * C; a.v_pitch = 3 * C;
+      a.q_pitch = 3 * C; a.kv_pitch = 3 * C;
       a.F = F; a.Tq = Q; a.Tk = Q; a.heads = heads; a.hd = hd; a.scale = scale;
-      HIP_TRY(mkd_launch_attention(a, s));
+      HIP_TRY(mka_launch_forward(a, s));
       HIP_TRY(lin.resid(ly.so, ws.ctx, M, ws.out, ws.tmp));
       HIP_TRY(mkd_row(ws.tmp, nullptr, 0, &ly.snorm, nullptr, 0, ws.out, ws.y.hi, ws.y.lo, nullptr, nullptr, M, C, s));
       // FFN
@@ -798,59 +600,6 @@ extern "C" int sf_maskdec_forward(sf_maskdec* h, const float* const* x_dev, cons
 // ------------------------------------------------------------------------------------------------
 // the kernels alone (parity tests)
 // ------------------------------------------------------------------------------------------------
-extern "C" int sf_op_maskdec_attention(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const float* k_pos_dev,
-                                       int pos_pitch, const uint32_t* mask_dev, float* ctx_dev, uint16_t* ctx_hi_dev, uint16_t* ctx_lo_dev, int F, int Q,
-                                       int HW, int heads, int head_dim, int no_skip, sf_stream stream) {
-  const char* who = "sf_op_maskdec_attention";
-  if (!q_dev || !k_dev || !v_dev) return sf_set_err(SF_ERR_INVALID, "%s: null buffer", who);
-  if (!ctx_dev && !ctx_hi_dev) return sf_set_err(SF_ERR_INVALID, "%s: no output", who);
-  if (ctx_lo_dev && !ctx_hi_dev) return sf_set_err(SF_ERR_INVALID, "%s: a lo plane needs its hi plane", who);
-  if (F < 1 || Q < 1 || HW < 1 || heads < 1) return sf_set_err(SF_ERR_INVALID, "%s: bad shape F=%d Q=%d HW=%d heads=%d", who, F, Q, HW, heads);
-  if (head_dim < 8 || head_dim > 128 || head_dim % 8) return sf_set_err(SF_ERR_INVALID, "%s: head_dim must be a multiple of 8 in 8..128", who);
-  const int D = heads * head_dim;
-  if (q_pitch < D || kv_pitch < D || (k_pos_dev && pos_pitch < D) || ((q_pitch | kv_pitch | pos_pitch) & 3))
-    return sf_set_err(SF_ERR_INVALID, "%s: row pitches must be multiples of 4 and at least heads * head_dim = %d", who, D);
-  if ((int64_t)F * (Q > HW ? Q : HW) * std::max(q_pitch, kv_pitch) > (int64_t)0x7fffffff) return sf_set_err(SF_ERR_CAPACITY, "%s: more than 2^31 - 1 elements", who);
-  if (((uintptr_t)q_dev | (uintptr_t)k_dev | (uintptr_t)v_dev | (uintptr_t)k_pos_dev | (uintptr_t)mask_dev | (uintptr_t)ctx_dev | (uintptr_t)ctx_hi_dev |
-       (uintptr_t)ctx_lo_dev) & 15)
-    return sf_set_err(SF_ERR_INVALID, "%s: buffers must be 16-byte aligned", who);
-  SfMkdAttn a;
-  memset(&a, 0, sizeof(a));
-  a.q = q_dev; a.k = k_dev; a.v = v_dev; a.kpos = k_pos_dev; a.mask = mask_dev;
-  a.ctx = ctx_dev; a.ctx_hi = ctx_hi_dev; a.ctx_lo = ctx_lo_dev;
-  a.q_pitch = q_pitch; a.k_pitch = kv_pitch; a.v_pitch = kv_pitch; a.pos_pitch = k_pos_dev ? pos_pitch : 0;
-  a.F = F; a.Tq = Q; a.Tk = HW; a.heads = heads; a.hd = head_dim; a.words = (HW + 31) / 32; a.no_skip = no_skip ? 1 : 0;
-  a.scale = 1.0f / sqrtf((float)head_dim);
-  HIP_TRY(mkd_launch_attention(a, (hipStream_t)stream));
-  return SF_OK;
-}
-
-// The same kernel as the training forward of streamformer_amd/masked_attention.py: the row statistics the backward (sf_maskattn.hip)
-// recomputes the probabilities from, and a mask that may differ between the heads.  Without both it is sf_op_maskdec_attention.
-extern "C" int sf_op_maskattn_forward(const float* q_dev, int q_pitch, const float* k_dev, const float* v_dev, int kv_pitch, const uint32_t* mask_dev,
-                                      int mask_per_head, float* ctx_dev, float* stats_dev, int F, int Q, int HW, int heads, int head_dim, int no_skip,
-                                      sf_stream stream) {
-  const char* who = "sf_op_maskattn_forward";
-  if (!q_dev || !k_dev || !v_dev || !ctx_dev) return sf_set_err(SF_ERR_INVALID, "%s: null buffer", who);
-  if (F < 1 || F > 65535 || Q < 1 || Q > 65535 || HW < 1 || HW > (1 << 24) || heads < 1 || heads > 65535)
-    return sf_set_err(SF_ERR_INVALID, "%s: bad shape F=%d Q=%d HW=%d heads=%d", who, F, Q, HW, heads);
-  if (head_dim < 8 || head_dim > 128 || head_dim % 8) return sf_set_err(SF_ERR_INVALID, "%s: head_dim must be a multiple of 8 in 8..128", who);
-  const int D = heads * head_dim;
-  if (q_pitch < D || kv_pitch < D || ((q_pitch | kv_pitch) & 3))
-    return sf_set_err(SF_ERR_INVALID, "%s: row pitches must be multiples of 4 and at least heads * head_dim = %d", who, D);
-  if ((int64_t)F * (Q > HW ? Q : HW) * std::max(q_pitch, kv_pitch) > (int64_t)0x7fffffff) return sf_set_err(SF_ERR_CAPACITY, "%s: more than 2^31 - 1 elements", who);
-  if (((uintptr_t)q_dev | (uintptr_t)k_dev | (uintptr_t)v_dev | (uintptr_t)mask_dev | (uintptr_t)ctx_dev | (uintptr_t)stats_dev) & 15)
-    return sf_set_err(SF_ERR_INVALID, "%s: buffers must be 16-byte aligned", who);
-  SfMkdAttn a;
-  memset(&a, 0, sizeof(a));
-  a.q = q_dev; a.k = k_dev; a.v = v_dev; a.mask = mask_dev; a.ctx = ctx_dev; a.stats = stats_dev; a.mask_per_head = mask_dev && mask_per_head ? 1 : 0;
-  a.q_pitch = q_pitch; a.k_pitch = kv_pitch; a.v_pitch = kv_pitch;
-  a.F = F; a.Tq = Q; a.Tk = HW; a.heads = heads; a.hd = head_dim; a.words = (HW + 31) / 32; a.no_skip = no_skip ? 1 : 0;
-  a.scale = 1.0f / sqrtf((float)head_dim);
-  HIP_TRY(mkd_launch_attention(a, (hipStream_t)stream));
-  return SF_OK;
-}
-
 // the box kernel alone, over masks some other kernel made (the training path's full-resolution logits)
 extern "C" int sf_op_maskdec_boxes(const float* masks_dev, float* boxes_dev, int rows, int H, int W, sf_stream stream) {
   const char* who = "sf_op_maskdec_boxes";

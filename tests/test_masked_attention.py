@@ -159,6 +159,14 @@ def test_kernel_refusals():
         assert bwd(**kw) == nat.SF_ERR_INVALID, kw
         assert b"sf_op_maskattn_backward" in nat.lib.sf_last_error()
     assert nat.lib.sf_op_maskattn_forward(p + 4, 16, p, p, 16, None, 0, p, p, 2, 4, 8, 2, 8, 0, _stream()) == nat.SF_ERR_INVALID
+
+    def dec(F=2, Q=4, HW=8, heads=2):                        # the decoder's entry point has the bounds of the other two
+        return nat.lib.sf_op_maskdec_attention(p, 16, p, p, 16, None, 0, None, p, None, None, F, Q, HW, heads, 8, 0, _stream())
+
+    assert dec() == nat.SF_OK
+    for kw in (dict(F=65536), dict(Q=65536), dict(HW=(1 << 24) + 1), dict(heads=65536), dict(F=0), dict(Q=0), dict(HW=0), dict(heads=0)):
+        assert dec(**kw) == nat.SF_ERR_INVALID, kw
+        assert b"sf_op_maskdec_attention" in nat.lib.sf_last_error()
     assert nat.lib.sf_op_maskattn_pack(None, p, 4, 8, _stream()) == nat.SF_ERR_INVALID
     assert nat.lib.sf_op_maskattn_pack(p, p, 4, 0, _stream()) == nat.SF_ERR_INVALID
     torch.cuda.synchronize()

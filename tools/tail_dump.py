@@ -3,6 +3,7 @@
     python tools/tail_dump.py --case pixdec_fpn_enc2 --out a.pt [--root OTHER_TREE]
     python tools/tail_dump.py --case maskdec --out a.pt          # a model's name: every case of that model, one after the other
     python tools/tail_dump.py --case encoder --out a.pt          # enc_forward, enc_stream, enc_ops: the encoder's host code (below)
+    python tools/tail_dump.py --case maskattn --out a.pt         # masked attention's entry points alone: forward, planes, stats, backward
     python tools/tail_dump.py --compare a.pt b.pt
 
 A case builds one model (the smallest widths the GEMM k-step allows, a handful of rows), fills its parameters from a seeded generator,
@@ -13,6 +14,7 @@ import argparse
 import os
 import sys
 
+import numpy as np
 import torch
 
 MODES = ("fp32", "bf16")
@@ -225,7 +227,57 @@ def run_enc_ops(sa, mode, g, dev):
     return res
 
 
+# ---------------------------------------------------------------------------------------------------- masked attention, the operator alone
+MASKATTN_SHAPES = ((8, 1, 1), (72, 17, 17), (32, 16, 31), (32, 100, 63), (128, 33, 130))      # (head width, Q, HW): one lane, a ragged last
+# query tile, a ragged last key tile, a mask word boundary, more key tiles than waves, the widest head
+
+
+def maskattn_mask(g, lead, Q, HW):
+    """bool [*lead, Q, HW], True = hidden, and its packed words.  About half the bits; in the first [Q, HW] plane the last query is fully
+    hidden and the last 16-key tile is hidden from the whole last 16-query tile (the skip path).  The properties are asserted."""
+    m = torch.rand(*lead, Q, HW, generator=g) < 0.5
+    first, q0, k0 = m.reshape(-1, Q, HW)[0], (Q - 1) // 16 * 16, (HW - 1) // 16 * 16
+    first[Q - 1] = True
+    first[q0:, k0:] = True
+    assert bool(first[Q - 1].all()) and bool(first[q0:, k0:].all()) and first.data_ptr() == m.data_ptr()
+    if m.numel() >= 512:
+        assert 0.4 < float(m.float().mean()) < 0.75, float(m.float().mean())
+    padded = torch.cat([m, torch.ones(*lead, Q, (-HW) % 32, dtype=torch.bool)], -1).numpy()      # the padding bits are set
+    return m, torch.from_numpy(np.packbits(padded, axis=-1, bitorder="little").view(np.int32))      # uint32 bit patterns
+
+
+def run_maskattn(sa, mode, g, dev):
+    """sf_op_maskdec_attention (with and without k_pos, fp32 ctx and hi / lo planes), sf_op_maskattn_forward and sf_op_maskattn_backward."""
+    nat = sa._native
+    lib, stream, F, heads = nat.lib, nat.current_stream_handle(dev), 2, 2
+    res = {}
+    for hd, Q, HW in MASKATTN_SHAPES:
+        D = heads * hd
+        rnd = lambda *shape: torch.randn(*shape, generator=g).to(dev)      # noqa: E731
+        q, k, v, kpos, d_ctx = rnd(F * Q, D), rnd(F * HW, D), rnd(F * HW, D), rnd(HW, D), rnd(F * Q, D)
+        for kind, lead in (("null", None), ("shared", (F,)), ("per_head", (F, heads))):
+            words = None
+            if lead is not None:
+                words = maskattn_mask(g, lead, Q, HW)[1].to(dev)
+            tag, mp, per_head = f"hd{hd}.q{Q}.hw{HW}.{kind}", nat.ptr(words), int(kind == "per_head")
+            if kind != "per_head":      # the decoder's entry point takes one mask for all heads
+                for name, pos in (("plain", None), ("kpos", kpos)):
+                    ctx, hi, lo = torch.zeros(F * Q, D, device=dev), torch.zeros(F * Q, D, dtype=torch.int16, device=dev), torch.zeros(F * Q, D, dtype=torch.int16, device=dev)
+                    nat.check(lib.sf_op_maskdec_attention(q.data_ptr(), D, k.data_ptr(), v.data_ptr(), D, nat.ptr(pos), D if pos is not None else 0, mp,
+                                                          ctx.data_ptr(), hi.data_ptr(), lo.data_ptr(), F, Q, HW, heads, hd, 0, stream))
+                    res[f"{tag}.maskdec.{name}"] = {"ctx": ctx, "hi": hi, "lo": lo}
+            ctx, stats = torch.zeros(F * Q, D, device=dev), torch.zeros(F, heads, Q, device=dev)
+            nat.check(lib.sf_op_maskattn_forward(q.data_ptr(), D, k.data_ptr(), v.data_ptr(), D, mp, per_head, ctx.data_ptr(), stats.data_ptr(), F, Q, HW,
+                                                 heads, hd, 0, stream))
+            dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+            nat.check(lib.sf_op_maskattn_backward(q.data_ptr(), D, k.data_ptr(), v.data_ptr(), D, mp, per_head, ctx.data_ptr(), stats.data_ptr(),
+                                                  d_ctx.data_ptr(), dq.data_ptr(), D, dk.data_ptr(), dv.data_ptr(), D, F, Q, HW, heads, hd, 0, stream))
+            res[f"{tag}.train"] = {"ctx": ctx, "stats": stats, "dq": dq, "dk": dk, "dv": dv}
+    return res
+
+
 CASES = {
+    "maskattn": (run_maskattn, {}),
     "text": (run_text, {}),
     "connector_depth1": (run_connector, dict(projector="linear")),
     "connector_depth2": (run_connector, dict(projector="mlp2x_gelu")),
