@@ -427,7 +427,7 @@ class PackedHandle:
         ws = self.workspaces.get(key)
         if ws is None or ws.numel() < nbytes or ws.device != device:
             self.workspaces.pop(key, None)       # before the new one is made: both need not fit at once
-            ws = self.workspaces[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+            ws = self.workspaces[key] = scratch(nbytes, device)
         return ws
 
     def release(self) -> None:
@@ -455,3 +455,45 @@ class PackedHandle:
 
 def current_stream_handle(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
+
+
+_ABSENT = object()
+WORKSPACE_FLOOR = 256      # bytes: the least any byte buffer handed to the library has, so that its address is never null
+
+
+# Written out at their call sites, not through ``launch``: sf_forward_profile and the sf_bench_* family (a result pointer follows the
+# stream), and a call whose code the caller reads instead of raising (the refusal probes).  Everything else that takes a stream goes
+# through ``launch``.
+def launch(device, fn, *args, workspace=_ABSENT) -> None:
+    """``fn(*args[, workspace address, workspace bytes], stream)`` with ``device`` current and its current stream last; raises NativeError
+    on a non-zero code.  ``fn`` is the entry point itself (``nat.lib.sf_op_x`` at the call site); ``workspace`` is a byte tensor or
+    None (0, 0)."""
+    if workspace is not _ABSENT:
+        args += (ptr(workspace), 0 if workspace is None else workspace.numel())
+    if device.index in (None, torch.cuda.current_device()):      # current already (a one-GPU process, a caller's own guard): no guard entry
+        check(fn(*args, current_stream_handle(device)))
+    else:
+        with torch.cuda.device(device):
+            check(fn(*args, current_stream_handle(device)))
+
+
+def sized(fn, *args) -> int:
+    """What a sizer that answers through a trailing ``size_t*`` wrote."""
+    n = C.c_size_t()
+    check(fn(*args, C.byref(n)))
+    return n.value
+
+
+def scratch(nbytes: int, device) -> torch.Tensor:
+    """A one-shot byte buffer of at least ``nbytes``; the caller keeps it until its launch is enqueued."""
+    return torch.empty(max(int(nbytes), WORKSPACE_FLOOR), dtype=torch.uint8, device=device)
+
+
+def ptr_array(tensors):
+    """ctypes array of the tensors' addresses (None -> 0), at least one element long."""
+    return (C.c_void_p * max(len(tensors), 1))(*[ptr(t) for t in tensors])
+
+
+def i32_array(values):
+    """ctypes int32 array of the values, at least one element long."""
+    return (C.c_int32 * max(len(values), 1))(*[int(v) for v in values])

@@ -267,8 +267,8 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
     # ------------------------------------------------------------------------------- native pieces
     def _layernorm(self, x: torch.Tensor, ln: nn.LayerNorm) -> torch.Tensor:
         y = torch.empty_like(x)
-        nat.check(nat.lib.sf_op_layernorm(x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), y.data_ptr(), x.numel() // x.shape[-1], x.shape[-1],
-                                          float(ln.eps), nat.current_stream_handle(x.device)))
+        nat.launch(x.device, nat.lib.sf_op_layernorm, x.data_ptr(), ln.weight.data_ptr(), ln.bias.data_ptr(), y.data_ptr(), x.numel() // x.shape[-1],
+                   x.shape[-1], float(ln.eps))
         return y
 
     def _linear(self, x: torch.Tensor, w: torch.Tensor, b, resid=None) -> torch.Tensor:
@@ -276,8 +276,8 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         N = w.shape[0]
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         ws = self._native.workspace(nat.lib.sf_op_linear_workspace_bytes(M, N, K), x.device)
-        nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), nat.ptr(b), nat.ptr(resid), 1.0, 0, y.data_ptr(), M, N, K, self._compute,
-                                       ws.data_ptr(), ws.numel(), nat.current_stream_handle(x.device)))
+        nat.launch(x.device, nat.lib.sf_op_linear, x.data_ptr(), w.data_ptr(), nat.ptr(b), nat.ptr(resid), 1.0, 0, y.data_ptr(), M, N, K, self._compute,
+                   workspace=ws)
         return y
 
     def _extract(self, ex: Extractor, c: torch.Tensor, feat: torch.Tensor, ref: torch.Tensor, lv: _Levels, Hg: int, Wg: int) -> torch.Tensor:
@@ -289,8 +289,8 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         ffn = ex.ffn
         u = self._linear(self._layernorm(c, ex.ffn_norm).view(Fr * Lq, D), ffn.fc1.weight, ffn.fc1.bias)
         v = torch.empty_like(u)
-        nat.check(nat.lib.sf_op_adapter_dwconv_gelu(u.data_ptr(), ffn.dwconv.dwconv.weight.data_ptr(), ffn.dwconv.dwconv.bias.data_ptr(), v.data_ptr(),
-                                                    Fr, Hg, Wg, u.shape[1], nat.current_stream_handle(c.device)))
+        nat.launch(c.device, nat.lib.sf_op_adapter_dwconv_gelu, u.data_ptr(), ffn.dwconv.dwconv.weight.data_ptr(), ffn.dwconv.dwconv.bias.data_ptr(),
+                   v.data_ptr(), Fr, Hg, Wg, u.shape[1])
         return self._linear(v, ffn.fc2.weight, ffn.fc2.bias, resid=c.view(Fr * Lq, D)).view(Fr, Lq, D)
 
     def _folded_tail(self, dev) -> Tuple[torch.Tensor, List[torch.Tensor], List[torch.Tensor]]:
@@ -354,7 +354,6 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         Fr, Hg, Wg = B * T, H // 16, W // 16
         n = (Hg // 2) * (Wg // 2)
         with torch.no_grad(), torch.cuda.device(dev):
-            stream = nat.current_stream_handle(dev)
             x = pixel_values.to(dev, torch.float32).contiguous()
             self._mark("start")
             # spatial prior module (torch): c1 NCHW, c2..c4 as tokens with their level embedding
@@ -371,15 +370,14 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             ws = enc._stage_ws(B, T, H, W)
             handle = enc._handle
             h = torch.empty(B, T, Hg * Wg, D, dtype=torch.float32, device=dev)
-            nat.check(nat.lib.sf_embed(handle, x.data_ptr(), nat.SF_F32, B, T, H, W, h.data_ptr(), nat.ptr(enc._pos_table(H, W)), ws.data_ptr(), ws.numel(),
-                                       stream))
+            nat.launch(dev, nat.lib.sf_embed, handle, x.data_ptr(), nat.SF_F32, B, T, H, W, h.data_ptr(), nat.ptr(enc._pos_table(H, W)), workspace=ws)
             self._mark("embed")
             ref, lv = self._geometry_for(Fr, Hg, Wg, dev)
             feat = h.view(Fr, Hg * Wg, D)
             kept: List[torch.Tensor] = []
             last = len(self.interactions) - 1
             for i, (block, (la, lb)) in enumerate(zip(self.interactions, self.interaction_indexes)):
-                nat.check(nat.lib.sf_layers(handle, h.data_ptr(), B, T, H, W, la, lb + 1, None, ws.data_ptr(), ws.numel(), stream))
+                nat.launch(dev, nat.lib.sf_layers, handle, h.data_ptr(), B, T, H, W, la, lb + 1, None, workspace=ws)
                 self._mark("layers")
                 for ex in block.extractors():
                     c = self._extract(ex, c, feat, ref, lv, Hg, Wg)
@@ -394,9 +392,8 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             for level, (name, tok, stride) in enumerate(zip(_OUTPUTS, (up.data_ptr(), c.data_ptr(), c.data_ptr() + 4 * 16 * n * D,
                                                                        c.data_ptr() + 4 * 20 * n * D), (16 * n * 4 * D, frame, frame, frame))):
                 out = torch.empty(Fr, D, *Ho_Wo(level, Hg, Wg), dtype=torch.float32, device=dev)
-                nat.check(nat.lib.sf_op_adapter_fuse(level, tok, stride, nat.ptr(kept[level]) if self.add_vit_feature else None,
-                                                     c1.data_ptr() if level == 0 else None, scales[level].data_ptr(), shifts[level].data_ptr(),
-                                                     out.data_ptr(), Fr, Hg, Wg, D, stream))
+                nat.launch(dev, nat.lib.sf_op_adapter_fuse, level, tok, stride, nat.ptr(kept[level]) if self.add_vit_feature else None,
+                           c1.data_ptr() if level == 0 else None, scales[level].data_ptr(), shifts[level].data_ptr(), out.data_ptr(), Fr, Hg, Wg, D)
                 outs[name] = out
             self._mark("tail")
         return outs, c

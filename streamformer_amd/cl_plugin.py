@@ -148,18 +148,15 @@ class _Step:
         self.sg = sg if sg is not None else torch.empty(max(p.T, 1), p.F, self.C, dtype=torch.float32, device=dev)
         self.stats = stats if stats is not None else torch.empty(max(p.T, 1), p.F, 2, dtype=torch.float32, device=dev)
         if p.T:
-            with torch.cuda.device(dev):
-                nat.check(nat.lib.sf_op_clp_tracks(e.data_ptr(), p.R, self.C, self.p_track_rows, p.T, p.F, self.sg.data_ptr(), self.stats.data_ptr(),
-                                                   nat.current_stream_handle(dev)))
+            nat.launch(dev, nat.lib.sf_op_clp_tracks, e.data_ptr(), p.R, self.C, self.p_track_rows, p.T, p.F, self.sg.data_ptr(), self.stats.data_ptr())
 
     def losses(self, e: torch.Tensor, out: Optional[torch.Tensor] = None, item_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """(loss_reid, loss_aux_reid) [2]; item_out [I, 4] = (contras, aux, d_pos, 1 / |anchor|) per item."""
         p, dev = self.plan, e.device
         out = out if out is not None else torch.empty(2, dtype=torch.float32, device=dev)
         self.item_out = item_out if item_out is not None else torch.empty(max(p.I, 1), 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_op_clp_items(e.data_ptr(), p.R, self.C, self.sg.data_ptr(), p.T, p.F, self.p_items, p.I, self.p_neg, p.NE, p.max_neg,
-                                              out.data_ptr(), self.item_out.data_ptr(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_op_clp_items, e.data_ptr(), p.R, self.C, self.sg.data_ptr(), p.T, p.F, self.p_items, p.I, self.p_neg, p.NE, p.max_neg,
+                   out.data_ptr(), self.item_out.data_ptr())
         return out
 
     def forward(self, e: torch.Tensor) -> torch.Tensor:
@@ -171,12 +168,10 @@ class _Step:
         p, dev = self.plan, e.device
         grad = grad if grad is not None else torch.empty(p.R, self.C, dtype=torch.float32, device=dev)
         upstream = upstream.to(torch.float32).contiguous()
-        ws = torch.empty(max(int(nat.lib.sf_op_clp_backward_workspace_bytes(p.I, p.T, p.F, self.C)), 256), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_op_clp_backward(e.data_ptr(), p.R, self.C, self.sg.data_ptr(), self.stats.data_ptr(), self.p_track_rows, self.p_track_items,
-                                                 p.T, p.F, self.p_items, p.I, self.p_neg, p.NE, p.max_neg, self.p_row_start, self.p_row_items,
-                                                 self.item_out.data_ptr(), upstream.data_ptr(), grad.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_op_clp_backward, e.data_ptr(), p.R, self.C, self.sg.data_ptr(), self.stats.data_ptr(), self.p_track_rows,
+                   self.p_track_items, p.T, p.F, self.p_items, p.I, self.p_neg, p.NE, p.max_neg, self.p_row_start, self.p_row_items,
+                   self.item_out.data_ptr(), upstream.data_ptr(), grad.data_ptr(),
+                   workspace=nat.scratch(nat.lib.sf_op_clp_backward_workspace_bytes(p.I, p.T, p.F, self.C), dev))
         return grad
 
 

@@ -160,9 +160,7 @@ class VideoTokenConnector(nn.Module):
                                 lambda: [(k, p) for k, p in params if not (k == "image_newline" and key[2] == 0)], key)
 
     def _workspace(self, h, F: int, P: int) -> torch.Tensor:
-        n = C.c_size_t()
-        nat.check(nat.lib.sf_connector_workspace_bytes(h, F, P, C.byref(n)))
-        return self._native.workspace(n.value, self.device)
+        return self._native.workspace(nat.sized(nat.lib.sf_connector_workspace_bytes, h, F, P), self.device)
 
     def _run(self, key: Tuple[int, int, int], feats: torch.Tensor, P: int, out_dtype: torch.dtype) -> torch.Tensor:
         h = self._handle(key)
@@ -173,9 +171,7 @@ class VideoTokenConnector(nn.Module):
         nat.check(nat.lib.sf_connector_num_tokens(h, F, P, C.byref(rows)))
         out = torch.empty(rows.value, self.out_dim, dtype=out_dtype, device=dev)
         ws = self._workspace(h, F, P)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_connector_forward(h, x.data_ptr(), F, P, out.data_ptr(), _OUT_DTYPES[out_dtype], ws.data_ptr(), ws.numel(),
-                                                   nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_connector_forward, h, x.data_ptr(), F, P, out.data_ptr(), _OUT_DTYPES[out_dtype], workspace=ws)
         return out
 
     # ------------------------------------------------------------------------------------ weights
@@ -269,9 +265,8 @@ class VideoTokenConnector(nn.Module):
         x = frame_tokens.to(device=dev, dtype=torch.float32).contiguous()
         newline = self.image_newline.detach().to(device=dev, dtype=torch.float32).contiguous() if nl else None
         out = torch.empty(rows.value, D, dtype=self.out_dtype, device=dev)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_op_connector_pool(x.data_ptr(), None, None, F, Po, D, 0, 1, nl, nat.ptr(newline), out.data_ptr(),
-                                                   _OUT_DTYPES[self.out_dtype], None, None, nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_op_connector_pool, x.data_ptr(), None, None, F, Po, D, 0, 1, nl, nat.ptr(newline), out.data_ptr(),
+                   _OUT_DTYPES[self.out_dtype], None, None)
         return out
 
 

@@ -19,7 +19,6 @@ natively.  There is no CPU fallback.  Chosen points: the ``int(importance_sample
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -77,14 +76,6 @@ def _num_masks(targets: Sequence[Dict[str, Any]], device) -> float:
     return max(n, 1.0)
 
 
-def _ptrs(tensors: Sequence[Optional[torch.Tensor]]):
-    return (C.c_void_p * max(len(tensors), 1))(*[nat.ptr(t) for t in tensors])
-
-
-def _i32(values: Sequence[int]):
-    return (C.c_int32 * max(len(values), 1))(*values)
-
-
 class _Batch:
     """What the entry points take of one step: the layers' tensors (fp32, contiguous, one shape), the targets (masks as fp32, labels as
     int64, on the device) and their host tables.  Every refusal that needs no launch is made here."""
@@ -119,14 +110,10 @@ class _Batch:
             raise RuntimeError(f"{who}: capacity limit: {self.L} layers (up to {MAX_LAYERS}), {self.B} images (up to {MAX_IMAGES}), "
                                f"{max(self.G, default=0)} targets in an image (up to {MAX_TARGETS})")
         self.G_max = max(max(self.G, default=0), 1)
-        self.c_logits, self.c_masks = _ptrs(self.logits), _ptrs(self.masks)
-        self.c_tgt_masks, self.c_tgt_labels = _ptrs(self.tgt_masks), _ptrs(self.tgt_labels)
-        self.c_G = _i32(self.G)
-        self.c_H, self.c_W = _i32([int(m.shape[1]) for m in self.tgt_masks]), _i32([int(m.shape[2]) for m in self.tgt_masks])
-        self.stream = nat.current_stream_handle(self.device)
-
-    def workspace(self, nbytes: int) -> torch.Tensor:
-        return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+        self.c_logits, self.c_masks = nat.ptr_array(self.logits), nat.ptr_array(self.masks)
+        self.c_tgt_masks, self.c_tgt_labels = nat.ptr_array(self.tgt_masks), nat.ptr_array(self.tgt_labels)
+        self.c_G = nat.i32_array(self.G)
+        self.c_H, self.c_W = nat.i32_array([m.shape[1] for m in self.tgt_masks]), nat.i32_array([m.shape[2] for m in self.tgt_masks])
 
     def pairs_expected(self) -> int:
         return sum(min(self.Q, g) for g in self.G)
@@ -139,11 +126,10 @@ def _cost_matrices(batch: _Batch, coords: torch.Tensor, K: int, w_class: float, 
     coords = coords.to(torch.float32).contiguous()
     if tuple(coords.shape) != (batch.L, batch.B, K, 2):
         raise ValueError(f"point coordinates {tuple(coords.shape)} are not [L, B, K, 2] = {(batch.L, batch.B, K, 2)}")
-    ws = batch.workspace(nat.lib.sf_op_crit_costs_workspace_bytes(batch.L, batch.B, batch.Q, batch.G_max, K))
-    with torch.cuda.device(batch.device):
-        nat.check(nat.lib.sf_op_crit_costs(batch.c_logits, batch.c_masks, batch.L, batch.B, batch.Q, batch.C1, batch.H, batch.W, batch.c_tgt_masks,
-                                           batch.c_tgt_labels, batch.c_G, batch.c_H, batch.c_W, coords.data_ptr(), K, batch.G_max, float(w_class),
-                                           float(w_mask), float(w_dice), cost.data_ptr(), ws.data_ptr(), ws.numel(), batch.stream))
+    nat.launch(batch.device, nat.lib.sf_op_crit_costs, batch.c_logits, batch.c_masks, batch.L, batch.B, batch.Q, batch.C1, batch.H, batch.W,
+               batch.c_tgt_masks, batch.c_tgt_labels, batch.c_G, batch.c_H, batch.c_W, coords.data_ptr(), K, batch.G_max, float(w_class),
+               float(w_mask), float(w_dice), cost.data_ptr(),
+               workspace=nat.scratch(nat.lib.sf_op_crit_costs_workspace_bytes(batch.L, batch.B, batch.Q, batch.G_max, K), batch.device))
     return cost
 
 
@@ -236,7 +222,7 @@ class _Step:
         _check_pairs(pairs, batch)
         dev = batch.device
         self.pairs = torch.from_numpy(pairs).to(dev, non_blocking=True) if self.N else torch.zeros(1, 4, dtype=torch.int32, device=dev)
-        self.c_start = _i32(layer_start)
+        self.c_start = nat.i32_array(layer_start)
         self.empty_weight, self.over, self.rnd = empty_weight, over, rnd
         self.class_grad = self.coords = self.sums = self.chosen = self.target_classes = None
         self.debug = debug                                     # tests: keep the draws and write the chosen indices
@@ -244,27 +230,24 @@ class _Step:
     def forward(self, need_grad: bool = True) -> torch.Tensor:
         b, dev = self.batch, self.batch.device
         out = torch.zeros(b.L, 3, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            if self.want_labels:
-                w = self.empty_weight.to(device=dev, dtype=torch.float32).contiguous()
-                if w.numel() != b.C1:
-                    raise ValueError(f"empty_weight has {w.numel()} entries for {b.C1} class logits")
-                self.class_grad = torch.empty(b.L, b.B, b.Q, b.C1, dtype=torch.float32, device=dev) if need_grad else None
-                self.target_classes = torch.empty(b.L, b.B, b.Q, dtype=torch.int32, device=dev)
-                ws = b.workspace(nat.lib.sf_op_crit_class_loss_workspace_bytes(b.L, b.B, b.Q))
-                nat.check(nat.lib.sf_op_crit_class_loss(b.c_logits, b.L, b.B, b.Q, b.C1, self.pairs.data_ptr(), self.N, b.c_tgt_labels, b.c_G, w.data_ptr(),
-                                                        out.data_ptr(), 3, nat.ptr(self.class_grad), self.target_classes.data_ptr(), ws.data_ptr(),
-                                                        ws.numel(), b.stream))
-            if self.want_masks:
-                n = max(self.N, 1)
-                self.coords = torch.zeros(n, self.K, 2, dtype=torch.float32, device=dev)
-                self.sums = torch.zeros(n, 4, dtype=torch.float32, device=dev)
-                self.chosen = torch.zeros(n, max(self.K_uncertain, 1), dtype=torch.int32, device=dev) if self.debug else None
-                ws = b.workspace(nat.lib.sf_op_crit_losses_workspace_bytes(self.N))
-                nat.check(nat.lib.sf_op_crit_losses(b.c_masks, b.L, b.B, b.Q, b.H, b.W, b.c_tgt_masks, b.c_G, b.c_H, b.c_W, self.pairs.data_ptr(),
-                                                    self.c_start, self.N, nat.ptr(self.over), nat.ptr(self.rnd), self.K, self.K_over, self.K_uncertain,
-                                                    self.num_masks, out[:, 1:].data_ptr(), 3, self.coords.data_ptr(), self.sums.data_ptr(),
-                                                    nat.ptr(self.chosen), ws.data_ptr(), ws.numel(), b.stream))
+        if self.want_labels:
+            w = self.empty_weight.to(device=dev, dtype=torch.float32).contiguous()
+            if w.numel() != b.C1:
+                raise ValueError(f"empty_weight has {w.numel()} entries for {b.C1} class logits")
+            self.class_grad = torch.empty(b.L, b.B, b.Q, b.C1, dtype=torch.float32, device=dev) if need_grad else None
+            self.target_classes = torch.empty(b.L, b.B, b.Q, dtype=torch.int32, device=dev)
+            nat.launch(dev, nat.lib.sf_op_crit_class_loss, b.c_logits, b.L, b.B, b.Q, b.C1, self.pairs.data_ptr(), self.N, b.c_tgt_labels, b.c_G,
+                       w.data_ptr(), out.data_ptr(), 3, nat.ptr(self.class_grad), self.target_classes.data_ptr(),
+                       workspace=nat.scratch(nat.lib.sf_op_crit_class_loss_workspace_bytes(b.L, b.B, b.Q), dev))
+        if self.want_masks:
+            n = max(self.N, 1)
+            self.coords = torch.zeros(n, self.K, 2, dtype=torch.float32, device=dev)
+            self.sums = torch.zeros(n, 4, dtype=torch.float32, device=dev)
+            self.chosen = torch.zeros(n, max(self.K_uncertain, 1), dtype=torch.int32, device=dev) if self.debug else None
+            nat.launch(dev, nat.lib.sf_op_crit_losses, b.c_masks, b.L, b.B, b.Q, b.H, b.W, b.c_tgt_masks, b.c_G, b.c_H, b.c_W, self.pairs.data_ptr(),
+                       self.c_start, self.N, nat.ptr(self.over), nat.ptr(self.rnd), self.K, self.K_over, self.K_uncertain, self.num_masks,
+                       out[:, 1:].data_ptr(), 3, self.coords.data_ptr(), self.sums.data_ptr(), nat.ptr(self.chosen),
+                       workspace=nat.scratch(nat.lib.sf_op_crit_losses_workspace_bytes(self.N), dev))
         return out
 
     def backward_masks(self, upstream: torch.Tensor) -> torch.Tensor:
@@ -272,10 +255,8 @@ class _Step:
         b, dev = self.batch, self.batch.device
         grad = torch.empty(b.L, b.B, b.Q, b.H, b.W, dtype=torch.float32, device=dev)
         upstream = upstream.to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_op_crit_losses_backward(b.c_masks, b.L, b.B, b.Q, b.H, b.W, b.c_tgt_masks, b.c_G, b.c_H, b.c_W, self.pairs.data_ptr(), self.N,
-                                                         self.coords.data_ptr(), self.sums.data_ptr(), self.K, self.num_masks, upstream.data_ptr(),
-                                                         grad.data_ptr(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_op_crit_losses_backward, b.c_masks, b.L, b.B, b.Q, b.H, b.W, b.c_tgt_masks, b.c_G, b.c_H, b.c_W, self.pairs.data_ptr(),
+                   self.N, self.coords.data_ptr(), self.sums.data_ptr(), self.K, self.num_masks, upstream.data_ptr(), grad.data_ptr())
         return grad
 
 

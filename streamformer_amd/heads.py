@@ -10,7 +10,6 @@ The caption-driven heads sit on the same conventions: ``GroundingHead`` (``Times
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional, Tuple
 
@@ -31,7 +30,7 @@ def _scalar_on(dev: torch.device, v) -> torch.Tensor:
 
 
 def _workspace(dev: torch.device, B: int, T: int) -> torch.Tensor:
-    return torch.empty(nat.lib.sf_loss_workspace_bytes(B, T), dtype=torch.uint8, device=dev)
+    return nat.scratch(nat.lib.sf_loss_workspace_bytes(B, T), dev)
 
 
 class RetrievalHead:
@@ -59,10 +58,8 @@ class RetrievalHead:
         gp = torch.empty_like(p) if need_grad else None
         gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
         ls, lb, ws = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias), _workspace(dev, B, T)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_retrieval_loss(p.data_ptr(), t.data_ptr(), B, T, D, Bt, rank * B, ls.data_ptr(), lb.data_ptr(),
-                                                loss.data_ptr(), nat.ptr(gp), nat.ptr(gs), ws.data_ptr(), ws.numel(),
-                                                nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_retrieval_loss, p.data_ptr(), t.data_ptr(), B, T, D, Bt, rank * B, ls.data_ptr(), lb.data_ptr(), loss.data_ptr(),
+                   nat.ptr(gp), nat.ptr(gs), workspace=ws)
         return loss, gp, gs
 
 
@@ -86,10 +83,8 @@ class LocalizationHead:
         gp = torch.empty_like(p) if need_grad else None
         gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
         ls, lb, ws = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias), _workspace(dev, B, T)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_localization_loss(p.data_ptr(), e.data_ptr(), lab.data_ptr(), B, T, D, e.shape[0],
-                                                   ls.data_ptr(), lb.data_ptr(), loss.data_ptr(), nat.ptr(gp),
-                                                   nat.ptr(gs), ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_localization_loss, p.data_ptr(), e.data_ptr(), lab.data_ptr(), B, T, D, e.shape[0], ls.data_ptr(), lb.data_ptr(),
+                   loss.data_ptr(), nat.ptr(gp), nat.ptr(gs), workspace=ws)
         return loss, gp, gs
 
 
@@ -119,18 +114,14 @@ class MaskLossHead:
                 raise ValueError(f"clip {i}: label table must be [L, {D}], got {tuple(t.shape)}")
             if m.dim() != 3 or m.shape[0] != T or m.shape[1] != H:
                 raise ValueError(f"clip {i}: mask must be [{T}, {H}, W], got {tuple(m.shape)}")
-        nl = (C.c_int32 * B)(*[int(t.shape[0]) for t in tabs])
-        wd = (C.c_int32 * B)(*[int(m.shape[2]) for m in masks])
-        tp = (C.c_void_p * B)(*[t.data_ptr() for t in tabs])
-        mp = (C.c_void_p * B)(*[m.data_ptr() for m in masks])
+        nl, wd = nat.i32_array([t.shape[0] for t in tabs]), nat.i32_array([m.shape[2] for m in masks])
+        tp, mp = nat.ptr_array(tabs), nat.ptr_array(masks)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         gx = torch.empty_like(x) if need_grad else None
         gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
         ls, lb = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias)
-        ws = torch.empty(max(1, nat.lib.sf_mask_loss_workspace_bytes(B, T, N, max(1, max(nl)))), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_mask_loss(x.data_ptr(), B, T, N, D, tp, nl, mp, wd, H, ls.data_ptr(), lb.data_ptr(), loss.data_ptr(),
-                                           nat.ptr(gx), nat.ptr(gs), ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_mask_loss, x.data_ptr(), B, T, N, D, tp, nl, mp, wd, H, ls.data_ptr(), lb.data_ptr(), loss.data_ptr(), nat.ptr(gx),
+                   nat.ptr(gs), workspace=nat.scratch(nat.lib.sf_mask_loss_workspace_bytes(B, T, N, max(1, max(nl))), dev))
         return loss, gx, gs
 
 
@@ -165,10 +156,7 @@ class DenseHeadProjection:
         self.release()
         self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         out = torch.empty_like(x)
-        pp = (C.c_void_p * 10)(*[p.data_ptr() for p in ps])
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_dense_head_forward(x.data_ptr(), M, D, inter, self.eps, pp, out.data_ptr(), self._ws.data_ptr(),
-                                                    self._ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_dense_head_forward, x.data_ptr(), M, D, inter, self.eps, nat.ptr_array(ps), out.data_ptr(), workspace=self._ws)
         self._shape = (M, D, inter)
         self._params = ps
         return out
@@ -183,11 +171,8 @@ class DenseHeadProjection:
         ps = self._params
         dx = torch.empty_like(g)
         grads = [torch.empty_like(p) for p in ps]
-        pp = (C.c_void_p * 10)(*[p.data_ptr() for p in ps])
-        gp = (C.c_void_p * 10)(*[t.data_ptr() for t in grads])
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_dense_head_backward(g.data_ptr(), M, D, inter, self.eps, pp, dx.data_ptr(), gp, self._ws.data_ptr(),
-                                                     self._ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_dense_head_backward, g.data_ptr(), M, D, inter, self.eps, nat.ptr_array(ps), dx.data_ptr(), nat.ptr_array(grads),
+                   workspace=self._ws)
         self.release()         # stream-ordered: torch's allocator reuses the block only behind the launches above
         return dx, grads
 
@@ -222,10 +207,8 @@ class GroundingHead:
         gs = torch.empty(2, dtype=torch.float32, device=dev) if need_grad else None
         logits = torch.empty(B, T, dtype=torch.float32, device=dev) if return_logits else None
         ls, lb, ws = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias), _workspace(dev, B, T)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_grounding_loss(p.data_ptr(), t.data_ptr(), lab.data_ptr(), B, T, D, ls.data_ptr(), lb.data_ptr(),
-                                                loss.data_ptr(), nat.ptr(gp), nat.ptr(gs), nat.ptr(logits), ws.data_ptr(), ws.numel(),
-                                                nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_grounding_loss, p.data_ptr(), t.data_ptr(), lab.data_ptr(), B, T, D, ls.data_ptr(), lb.data_ptr(), loss.data_ptr(),
+                   nat.ptr(gp), nat.ptr(gs), nat.ptr(logits), workspace=ws)
         return (loss, gp, gs, logits) if return_logits else (loss, gp, gs)
 
     def logits(self, pooler_output: torch.Tensor, text_features: torch.Tensor) -> torch.Tensor:
@@ -259,7 +242,5 @@ class DenseTextLogits:
         M = x.numel() // D
         out = torch.empty(tuple(x.shape[:-1]) + (n,), dtype=torch.float32, device=dev)
         ls, lb = _scalar_on(dev, self.logit_scale), _scalar_on(dev, self.logit_bias)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_dense_text_logits(x.data_ptr(), t.data_ptr(), M, D, n, ls.data_ptr(), lb.data_ptr(), out.data_ptr(),
-                                                   nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_dense_text_logits, x.data_ptr(), t.data_ptr(), M, D, n, ls.data_ptr(), lb.data_ptr(), out.data_ptr())
         return out

@@ -91,9 +91,7 @@ class _MaskLogitsFunction(Function):
         H, W = feat.shape[2:]
         me = me.contiguous()
         out = torch.empty(Fr, Q, H, W, device=me.device, dtype=torch.float32)
-        with torch.cuda.device(me.device):
-            nat.check(nat.lib.sf_op_masklogits_forward(me.data_ptr(), feat.data_ptr(), out.data_ptr(), Fr, Q, Dm, H * W,
-                                                       nat.current_stream_handle(me.device)))
+        nat.launch(me.device, nat.lib.sf_op_masklogits_forward, me.data_ptr(), feat.data_ptr(), out.data_ptr(), Fr, Q, Dm, H * W)
         ctx.save_for_backward(me, feat)
         ctx.shared = shared
         return out
@@ -117,11 +115,9 @@ class _MaskLogitsFunction(Function):
             return None, None, None
         ws = None
         if d_me is not None:
-            ws = torch.empty(max(nat.lib.sf_op_masklogits_backward_workspace_bytes(Fr, Q, Dm, P), 256), dtype=torch.uint8, device=me.device)
-        with torch.cuda.device(me.device):
-            nat.check(nat.lib.sf_op_masklogits_backward(grad.data_ptr(), me.data_ptr(), feat.data_ptr(), nat.ptr(d_me), nat.ptr(d_feat), accumulate,
-                                                        Fr, Q, Dm, P, nat.ptr(ws), 0 if ws is None else ws.numel(),
-                                                        nat.current_stream_handle(me.device)))
+            ws = nat.scratch(nat.lib.sf_op_masklogits_backward_workspace_bytes(Fr, Q, Dm, P), me.device)
+        nat.launch(me.device, nat.lib.sf_op_masklogits_backward, grad.data_ptr(), me.data_ptr(), feat.data_ptr(), nat.ptr(d_me), nat.ptr(d_feat),
+                   accumulate, Fr, Q, Dm, P, workspace=ws)
         return d_me, None, None               # the hub returns the gradient of the features
 
 
@@ -330,7 +326,6 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         F, Dm, H, W = mf.shape
         Q, Cd, L = self.num_queries, self.hidden_dim, self.num_layers
         cl = self._reid_layers >= 0
-        stream = nat.current_stream_handle(dev)
         shared = _SharedGrad()
         feat = _MaskFeatureHub.apply(mf, shared)
         mf_plain = mf.detach()
@@ -370,9 +365,8 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
                 h, w = size
                 bits = torch.empty(F, Q, (h * w + 31) // 32, dtype=torch.int32, device=dev)
                 ws = self._native.workspace(nat.lib.sf_op_maskdec_mask_workspace_bytes(F, Dm, h, w), dev, key="train mask")
-                with torch.cuda.device(dev):
-                    nat.check(nat.lib.sf_op_maskdec_mask(me.detach().data_ptr(), mf_plain.data_ptr(), F, Q, Dm, H, W, h, w, bits.data_ptr(), None, None,
-                                                         ws.data_ptr(), ws.numel(), stream))
+                nat.launch(dev, nat.lib.sf_op_maskdec_mask, me.detach().data_ptr(), mf_plain.data_ptr(), F, Q, Dm, H, W, h, w, bits.data_ptr(), None, None,
+                           workspace=ws)
             return pred, bits
 
         preds, masks = [], []
@@ -391,8 +385,7 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
         res: Dict[str, Any] = dict(preds[-1])
         if cl:
             boxes = torch.empty(F, Q, 4, dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                nat.check(nat.lib.sf_op_maskdec_boxes(res["pred_masks"].detach().data_ptr(), boxes.data_ptr(), F * Q, H, W, stream))
+            nat.launch(dev, nat.lib.sf_op_maskdec_boxes, res["pred_masks"].detach().data_ptr(), boxes.data_ptr(), F * Q, H, W)
             res.update(pred_bboxes=boxes, query_pos_embeds=self.query_embed.weight.detach().unsqueeze(0).repeat(F, 1, 1))
         res["aux_outputs"] = preds[:-1]
         if return_attn_masks:
@@ -435,14 +428,9 @@ class MultiScaleMaskedTransformerDecoder(nn.Module):
             t["attn_masks"] = torch.empty(F * Q * sum(words), dtype=torch.int32, device=dev)
         for k, v in t.items():
             setattr(out, k, v.data_ptr())
-        shapes = (C.c_int32 * 6)(*[d for v in xs for d in v.shape[2:]])
-        nbytes = C.c_size_t()
-        nat.check(nat.lib.sf_maskdec_workspace_bytes(h, F, shapes, H, W, C.byref(nbytes)))
-        ws = self._native.workspace(nbytes.value, dev)
-        ptrs = (C.c_void_p * 3)(*[v.data_ptr() for v in xs])
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_maskdec_forward(h, ptrs, mf.data_ptr(), F, shapes, H, W, C.byref(out), ws.data_ptr(), ws.numel(),
-                                                 nat.current_stream_handle(dev)))
+        shapes = nat.i32_array([d for v in xs for d in v.shape[2:]])
+        ws = self._native.workspace(nat.sized(nat.lib.sf_maskdec_workspace_bytes, h, F, shapes, H, W), dev)
+        nat.launch(dev, nat.lib.sf_maskdec_forward, h, nat.ptr_array(xs), mf.data_ptr(), F, shapes, H, W, C.byref(out), workspace=ws)
         res: Dict[str, Any] = {"pred_logits": t["pred_logits"], "pred_masks": t["pred_masks"]}
         if cl:
             res.update(pred_queries=t["pred_queries"], pred_embeds=t["pred_embeds"], pred_bboxes=t["pred_bboxes"],

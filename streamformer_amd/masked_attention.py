@@ -75,8 +75,7 @@ def pack_attention_mask(mask_bool: torch.Tensor, heads: Optional[int] = None) ->
     m = mask_bool.contiguous()
     HW = m.shape[-1]
     words = torch.empty(*m.shape[:-1], (HW + 31) // 32, device=m.device, dtype=torch.int32)
-    with torch.cuda.device(m.device):
-        nat.check(nat.lib.sf_op_maskattn_pack(m.data_ptr(), words.data_ptr(), m.numel() // HW, HW, nat.current_stream_handle(m.device)))
+    nat.launch(m.device, nat.lib.sf_op_maskattn_pack, m.data_ptr(), words.data_ptr(), m.numel() // HW, HW)
     return PackedAttentionMask(words, HW, per_head=m.dim() == 4)
 
 
@@ -122,10 +121,9 @@ class MaskedAttentionFunction(Function):
             k, v, kp = k.contiguous(), v.contiguous(), C
         out = torch.empty(Fr, Tq, C, device=q.device, dtype=torch.float32)
         stats = torch.empty(Fr, heads, Tq, device=q.device, dtype=torch.float32)
-        with torch.cuda.device(q.device):
-            nat.check(nat.lib.sf_op_maskattn_forward(q.data_ptr(), qp, k.data_ptr(), v.data_ptr(), kp, nat.ptr(mask.words if mask is not None else None),
-                                                     int(mask is not None and mask.per_head), out.data_ptr(), stats.data_ptr(), Fr, Tq, Tk, heads,
-                                                     C // heads, 0, nat.current_stream_handle(q.device)))
+        nat.launch(q.device, nat.lib.sf_op_maskattn_forward, q.data_ptr(), qp, k.data_ptr(), v.data_ptr(), kp,
+                   nat.ptr(mask.words if mask is not None else None), int(mask is not None and mask.per_head), out.data_ptr(), stats.data_ptr(),
+                   Fr, Tq, Tk, heads, C // heads, 0)
         ctx.save_for_backward(q, k, v, out, stats)
         ctx.mask, ctx.heads, ctx.pitches = mask, heads, (qp, kp)
         return out
@@ -140,11 +138,9 @@ class MaskedAttentionFunction(Function):
         grad_out = grad_out.float().contiguous()
         dq = torch.empty(Fr, Tq, C, device=q.device, dtype=torch.float32)
         dkv = torch.empty(2, Fr, Tk, C, device=q.device, dtype=torch.float32)
-        with torch.cuda.device(q.device):
-            nat.check(nat.lib.sf_op_maskattn_backward(q.data_ptr(), qp, k.data_ptr(), v.data_ptr(), kp, nat.ptr(mask.words if mask is not None else None),
-                                                      int(mask is not None and mask.per_head), out.data_ptr(), stats.data_ptr(), grad_out.data_ptr(),
-                                                      dq.data_ptr(), C, dkv[0].data_ptr(), dkv[1].data_ptr(), C, Fr, Tq, Tk, heads, C // heads, 0,
-                                                      nat.current_stream_handle(q.device)))
+        nat.launch(q.device, nat.lib.sf_op_maskattn_backward, q.data_ptr(), qp, k.data_ptr(), v.data_ptr(), kp,
+                   nat.ptr(mask.words if mask is not None else None), int(mask is not None and mask.per_head), out.data_ptr(), stats.data_ptr(),
+                   grad_out.data_ptr(), dq.data_ptr(), C, dkv[0].data_ptr(), dkv[1].data_ptr(), C, Fr, Tq, Tk, heads, C // heads, 0)
         return dq, dkv[0], dkv[1], None, None
 
 

@@ -245,14 +245,12 @@ class StreamCache:
         h = self._require()
         model = self._model()
         stream = self._check_stream(stream)
-        nbytes = nat.C.c_size_t()
-        nat.check(nat.lib.sf_cache_stream_blob_bytes(h, stream, nat.C.byref(nbytes)))
+        nbytes = nat.sized(nat.lib.sf_cache_stream_blob_bytes, h, stream)
         meta = nat.SfCacheStreamMeta()
         dev = model.device
         with torch.cuda.device(dev):
-            blob = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-            nat.check(nat.lib.sf_cache_export_stream(model._handle, h, stream, blob.data_ptr(), nbytes.value, nat.C.byref(meta),
-                                                     nat.current_stream_handle(dev)))
+            blob = torch.empty(nbytes, dtype=torch.uint8, device=dev)        # the snapshot keeps it: exactly the blob, no floor
+            nat.launch(dev, nat.lib.sf_cache_export_stream, model._handle, h, stream, blob.data_ptr(), nbytes, nat.C.byref(meta))
         snap = StreamSnapshot(blob, {k: int(getattr(meta, k)) for k in _SNAPSHOT_FIELDS}, (weakref.ref(model), model._pack_epoch))
         return snap if device is None else snap.to(device)
 
@@ -280,8 +278,7 @@ class StreamCache:
             with torch.cuda.device(dev):
                 blob = snapshot.blob.to(dev, non_blocking=True)
                 meta = nat.SfCacheStreamMeta(**snapshot.meta)
-                nat.check(nat.lib.sf_cache_import_stream(model._handle, h, sid, blob.data_ptr(), blob.numel(), nat.C.byref(meta),
-                                                         nat.current_stream_handle(dev)))
+                nat.launch(dev, nat.lib.sf_cache_import_stream, model._handle, h, sid, blob.data_ptr(), blob.numel(), nat.C.byref(meta))
         except Exception:
             if own:
                 _slab_release(self._free, sid)
@@ -454,9 +451,7 @@ class TimesformerEmbeddingsSigLIP(_Node):
         N = (H // c.patch_size) * (W // c.patch_size)
         h = torch.empty(B, T, N, c.hidden_size, dtype=torch.float32, device=dev)
         pos = m._pos_table(H, W)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_embed(m._handle, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, h.data_ptr(), nat.ptr(pos),
-                                       ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_embed, m._handle, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, h.data_ptr(), nat.ptr(pos), workspace=ws)
         return _to_patch_major(h)
 
 
@@ -483,9 +478,7 @@ class TimesformerEncoder(_Node):
         h = _to_frame_major(hidden_states.to(dev), T)
         N = NT // T
         att = torch.empty(lb - la, B * T, m.config.num_attention_heads, N, N, dtype=torch.float32, device=dev) if want_attn else None
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_layers(m._handle, h.data_ptr(), B, T, H, W, la, lb, nat.ptr(att), ws.data_ptr(), ws.numel(),
-                                        nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_layers, m._handle, h.data_ptr(), B, T, H, W, la, lb, nat.ptr(att), workspace=ws)
         return _to_patch_major(h), (tuple(att[i] for i in range(lb - la)) if want_attn else None)
 
     def forward(self, hidden_states: torch.Tensor, num_frames: int, output_attentions: bool = False,
@@ -518,9 +511,8 @@ class _PostLayerNorm(_Node):
         y = torch.empty_like(xf)
         g = self.weight.detach().to(dev, torch.float32).contiguous()
         b = self.bias.detach().to(dev, torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_op_layernorm(xf.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), xf.numel() // xf.shape[-1],
-                                              xf.shape[-1], float(m.config.layer_norm_eps), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_op_layernorm, xf.data_ptr(), g.data_ptr(), b.data_ptr(), y.data_ptr(), xf.numel() // xf.shape[-1], xf.shape[-1],
+                   float(m.config.layer_norm_eps))
         return y
 
 
@@ -535,9 +527,7 @@ class TimesformerSiglipMultiheadAttentionPoolingHead(_Node):
         dev = m.device
         xf = x.to(dev, torch.float32).contiguous()
         pool = torch.empty(Fr, D, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_post_head(m._handle, xf.data_ptr(), Fr, 1, H, W, None, pool.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_post_head, m._handle, xf.data_ptr(), Fr, 1, H, W, None, pool.data_ptr(), workspace=ws)
         return pool
 
 
@@ -952,8 +942,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             return t if (t is None or out_dtype is None) else t.to(out_dtype)
 
         with torch.cuda.device(dev):
-            stream = nat.current_stream_handle(dev)
-            skey = int(stream or 0)          # one workspace per HIP stream: concurrent forwards never share scratch
+            skey = int(nat.current_stream_handle(dev) or 0)          # one workspace per HIP stream: concurrent forwards never share scratch
             lhs = torch.empty(B, T, N, D, dtype=torch.float32, device=dev)
             pool = torch.empty(B, T, D, dtype=torch.float32, device=dev)
             hs = torch.empty(L + 1, B, T, N, D, dtype=torch.float32, device=dev) if output_hidden_states else None
@@ -961,19 +950,16 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             # reference materialises these anyway (modeling:703-705), here only on request
             att = torch.empty(L, B * T, c.num_attention_heads, N, N, dtype=torch.float32, device=dev) if output_attentions else None
             if streaming:
-                cache = self._forward_stream(x, pos, past_key_values, cache_position, stream_ids, lhs, pool, hs, att, stream, skey)
+                cache = self._forward_stream(x, pos, past_key_values, cache_position, stream_ids, lhs, pool, hs, att, skey)
             else:
-                nbytes = nat.C.c_size_t()
                 h = self._native.handles[None]
-                nat.check(nat.lib.sf_workspace_bytes(h, B, T, H, W, nat.C.byref(nbytes)))
-                ws = self._native.workspace(nbytes.value, dev, ("f", B, T, H, W, skey))
+                ws = self._native.workspace(nat.sized(nat.lib.sf_workspace_bytes, h, B, T, H, W), dev, ("f", B, T, H, W, skey))
                 if att is not None:
-                    nat.check(nat.lib.sf_forward_attentions(h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W,
-                                                            lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(),
-                                                            nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
+                    nat.launch(dev, nat.lib.sf_forward_attentions, h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, lhs.data_ptr(), pool.data_ptr(),
+                               nat.ptr(hs), att.data_ptr(), nat.ptr(pos), workspace=ws)
                 else:
-                    nat.check(nat.lib.sf_forward(h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, lhs.data_ptr(),
-                                                 pool.data_ptr(), nat.ptr(hs), nat.ptr(pos), ws.data_ptr(), ws.numel(), stream))
+                    nat.launch(dev, nat.lib.sf_forward, h, x.data_ptr(), _TORCH2SF[x.dtype], B, T, H, W, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs),
+                               nat.ptr(pos), workspace=ws)
         hidden = None
         if hs is not None:
             # the reference hands back patch-major (B, N*T, D) tensors (modeling:1352): permuted views
@@ -986,7 +972,7 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             return (lhs,) + ((hidden,) if hidden is not None else ()) + ((attentions,) if attentions is not None else ())
         return BaseModelOutputWithPooling(lhs, pool, hidden_states=hidden, attentions=attentions)
 
-    def _forward_stream(self, x, pos, cache, cache_position, stream_ids, lhs, pool, hs, att, stream, skey):
+    def _forward_stream(self, x, pos, cache, cache_position, stream_ids, lhs, pool, hs, att, skey):
         """One streaming call into the caller's output tensors: every stream of ``cache`` in lockstep, or the streams that
         ``stream_ids`` names.  Returns the cache (a new one when the caller passed none)."""
         B, T, _, H, W = x.shape
@@ -1016,19 +1002,18 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
             raise ValueError("past_key_values was created for a different resolution")
         if not ragged and (cache.batch, cache.H, cache.W) != (B, H, W):
             raise ValueError("past_key_values was created for a different batch size / resolution")
-        nbytes = nat.C.c_size_t()
         h = self._native.handles[None]
-        nat.check(nat.lib.sf_stream_workspace_bytes(h, ch, T, nat.C.byref(nbytes)))
-        ws = self._native.workspace(nbytes.value, x.device, ("s", cache.batch, T, H, W, skey))      # (a lockstep call has B == cache.batch)
+        # (a lockstep call has B == cache.batch)
+        ws = self._native.workspace(nat.sized(nat.lib.sf_stream_workspace_bytes, h, ch, T), x.device, ("s", cache.batch, T, H, W, skey))
         frames = (h, ch, x.data_ptr(), _TORCH2SF[x.dtype], T)
-        tail = (nat.ptr(pos), ws.data_ptr(), ws.numel(), stream)
         if ragged:
-            ids = (nat.C.c_int * max(B, 1))(*stream_ids)
-            nat.check(nat.lib.sf_forward_stream_slots(*frames, ids, B, lhs.data_ptr(), pool.data_ptr(), *tail))
+            nat.launch(x.device, nat.lib.sf_forward_stream_slots, *frames, nat.i32_array(stream_ids), B, lhs.data_ptr(), pool.data_ptr(), nat.ptr(pos),
+                       workspace=ws)
         elif att is not None:
-            nat.check(nat.lib.sf_forward_stream_attentions(*frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(), *tail))
+            nat.launch(x.device, nat.lib.sf_forward_stream_attentions, *frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), att.data_ptr(),
+                       nat.ptr(pos), workspace=ws)
         else:
-            nat.check(nat.lib.sf_forward_stream(*frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), *tail))
+            nat.launch(x.device, nat.lib.sf_forward_stream, *frames, lhs.data_ptr(), pool.data_ptr(), nat.ptr(hs), nat.ptr(pos), workspace=ws)
         return cache
 
     @staticmethod
@@ -1046,9 +1031,8 @@ class TimesformerMultiTaskingModelSigLIP(nn.Module):
     # permuted to the library's frame-major layout around each native call.
     def _stage_ws(self, B: int, T: int, H: int, W: int):
         self._sync()
-        n = nat.C.c_size_t()
-        nat.check(nat.lib.sf_workspace_bytes(self._handle, B, T, H, W, nat.C.byref(n)))
-        return self._native.workspace(n.value, self.device, ("f", B, T, H, W, int(nat.current_stream_handle(self.device) or 0)))
+        return self._native.workspace(nat.sized(nat.lib.sf_workspace_bytes, self._handle, B, T, H, W), self.device,
+                                      ("f", B, T, H, W, int(nat.current_stream_handle(self.device) or 0)))
 
     def _grid(self, n_tokens: int, T: int) -> Tuple[int, int]:
         """(H, W) of a frame whose patch grid has n_tokens / T cells (square, or the config's aspect)."""

@@ -14,7 +14,6 @@ Everything is fp32; tensors are made contiguous; kernels run on torch's current 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import types
 import weakref
@@ -67,8 +66,7 @@ class _Levels:
             if len(start) != self.L:
                 raise ValueError(f"level_start_index has {len(start)} entries for {self.L} levels")
         self.hw, self.start = hw, tuple(start)
-        self.c_hw = (C.c_int32 * len(hw))(*hw)
-        self.c_start = (C.c_int32 * self.L)(*start)
+        self.c_hw, self.c_start = nat.i32_array(hw), nat.i32_array(start)
 
 
 def _need_gpu(t: torch.Tensor, what: str) -> None:
@@ -98,9 +96,8 @@ def _forward(value, lv: _Levels, loc, w) -> torch.Tensor:
     value, loc, w = _f32(value, "value"), _f32(loc, "sampling_locations"), _f32(w, "attention_weights")
     N, S, M, D, Lq, L, P = _dims(value, loc, w, lv)
     out = torch.empty(N, Lq, M * D, device=value.device, dtype=torch.float32)
-    with torch.cuda.device(value.device):
-        nat.check(nat.lib.sf_op_msda_forward(value.data_ptr(), lv.c_hw, lv.c_start, loc.data_ptr(), w.data_ptr(), out.data_ptr(),
-                                             N, S, M, D, Lq, L, P, nat.current_stream_handle(value.device)))
+    nat.launch(value.device, nat.lib.sf_op_msda_forward, value.data_ptr(), lv.c_hw, lv.c_start, loc.data_ptr(), w.data_ptr(), out.data_ptr(),
+               N, S, M, D, Lq, L, P)
     return out
 
 
@@ -111,10 +108,8 @@ def _backward(value, lv: _Levels, loc, w, grad_out):
     if tuple(grad_out.shape) != (N, Lq, M * D):
         raise ValueError(f"grad_output {tuple(grad_out.shape)} is not [N, Lq, M * D] = {(N, Lq, M * D)}")
     gv, gl, gw = torch.empty_like(value), torch.empty_like(loc), torch.empty_like(w)
-    with torch.cuda.device(value.device):
-        nat.check(nat.lib.sf_op_msda_backward(value.data_ptr(), lv.c_hw, lv.c_start, loc.data_ptr(), w.data_ptr(), grad_out.data_ptr(),
-                                              gv.data_ptr(), gl.data_ptr(), gw.data_ptr(), N, S, M, D, Lq, L, P,
-                                              nat.current_stream_handle(value.device)))
+    nat.launch(value.device, nat.lib.sf_op_msda_backward, value.data_ptr(), lv.c_hw, lv.c_start, loc.data_ptr(), w.data_ptr(), grad_out.data_ptr(),
+               gv.data_ptr(), gl.data_ptr(), gw.data_ptr(), N, S, M, D, Lq, L, P)
     return gv, gl, gw
 
 
@@ -214,8 +209,8 @@ class MSDeformAttn(nn.Module):
         y = torch.empty(M, N, device=x.device, dtype=torch.float32)
         nbytes = nat.lib.sf_op_linear_workspace_bytes(M, N, K)
         ws = self._native.workspace(nbytes, x.device)
-        nat.check(nat.lib.sf_op_linear(x.data_ptr(), w.data_ptr(), b.data_ptr(), nat.ptr(resid), 1.0, 0, y.data_ptr(), M, N, K, self._compute,
-                                       ws.data_ptr(), ws.numel(), nat.current_stream_handle(x.device)))
+        nat.launch(x.device, nat.lib.sf_op_linear, x.data_ptr(), w.data_ptr(), b.data_ptr(), nat.ptr(resid), 1.0, 0, y.data_ptr(), M, N, K, self._compute,
+                   workspace=ws)
         return y
 
     def _front_weights(self, dev) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -251,9 +246,8 @@ class MSDeformAttn(nn.Module):
                 if tuple(pad.shape) != (N, S):
                     raise ValueError(f"input_padding_mask {tuple(pad.shape)} is not [N, S] = {(N, S)}")
             ctx = torch.empty(N * Lq, self.d_model, device=dev, dtype=torch.float32)
-            nat.check(nat.lib.sf_op_msda_forward_fused(
-                value.data_ptr(), nat.ptr(pad), lv.c_hw, lv.c_start, front.data_ptr(), front.shape[1], front.data_ptr() + 4 * n_off, front.shape[1],
-                ref.data_ptr(), ref.shape[-1], ctx.data_ptr(), N, S, Mh, D, Lq, L, P, nat.current_stream_handle(dev)))
+            nat.launch(dev, nat.lib.sf_op_msda_forward_fused, value.data_ptr(), nat.ptr(pad), lv.c_hw, lv.c_start, front.data_ptr(), front.shape[1],
+                       front.data_ptr() + 4 * n_off, front.shape[1], ref.data_ptr(), ref.shape[-1], ctx.data_ptr(), N, S, Mh, D, Lq, L, P)
             return self._linear(ctx, self.output_proj.weight.detach(), self.output_proj.bias.detach(), resid).view(N, Lq, self.d_model)
 
     # ---- grad path ---------------------------------------------------------------------------------

@@ -208,9 +208,8 @@ class DetectorState:
     def clone(self) -> "DetectorState":
         other = DetectorState(self.detector, self.streams)
         dev = self.detector.device
-        with torch.cuda.device(dev):
-            for i in range(self.streams):
-                nat.check(nat.lib.sf_oad_state_copy(other._h, i, self._h, i, nat.current_stream_handle(dev)))
+        for i in range(self.streams):
+            nat.launch(dev, nat.lib.sf_oad_state_copy, other._h, i, self._h, i)
         return other
 
 
@@ -310,9 +309,7 @@ class OnlineActionDetector(nn.Module):
         return DetectorState(self, streams)
 
     def _workspace(self, h, n: int) -> torch.Tensor:
-        size = C.c_size_t()
-        nat.check(nat.lib.sf_oad_workspace_bytes(h, n, C.byref(size)))
-        return self._native.workspace(size.value, self.device)
+        return self._native.workspace(nat.sized(nat.lib.sf_oad_workspace_bytes, h, n), self.device)
 
     @torch.no_grad()
     def step(self, work_features: torch.Tensor, long_features: Any = None, memory_key_padding_mask: Any = None, state: DetectorState = None,
@@ -388,11 +385,8 @@ class OnlineActionDetector(nn.Module):
         work = work.contiguous()
         long_dev = torch.cat(rows).contiguous() if rows else None
         out = torch.empty(n, W, self.num_classes, dtype=torch.float32, device=dev)
-        ws = self._workspace(h, n)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_oad_step(h, state._h, (C.c_int32 * n)(*ids), n, work.data_ptr(), nat.ptr(long_dev), (C.c_int32 * n)(*counts),
-                                          nat.ptr(mask), out.data_ptr(), int(bool(probs)), ws.data_ptr(), ws.numel(),
-                                          nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_oad_step, h, state._h, nat.i32_array(ids), n, work.data_ptr(), nat.ptr(long_dev), nat.i32_array(counts),
+                   nat.ptr(mask), out.data_ptr(), int(bool(probs)), workspace=self._workspace(h, n))
         return out
 
 

@@ -209,21 +209,15 @@ class MSDeformAttnPixelDecoder(nn.Module):
             raise ValueError("the levels of `features` hold different numbers of frames")
         h = self._handle()
         n = len(xs)
-        shapes = (C.c_int32 * (2 * n))(*[d for x in xs for d in ((x.shape[2], x.shape[3]) if x is not None else (1, 1))])
+        shapes = nat.i32_array([d for x in xs for d in ((x.shape[2], x.shape[3]) if x is not None else (1, 1))])
         n_ms = C.c_int()
         nat.check(nat.lib.sf_pixdec_num_outputs(h, C.byref(n_ms), None))
         out_levels = self.transformer_in_features[::-1] + self.in_features[:self.num_fpn_levels][::-1]
         by_name = dict(zip(self.in_features, xs))
         ms = [torch.empty(F, self.conv_dim, *by_name[k].shape[2:], dtype=torch.float32, device=dev) for k in out_levels[:n_ms.value]]
         mask = torch.empty(F, self.mask_dim, *by_name[out_levels[-1]].shape[2:], dtype=torch.float32, device=dev)
-        nbytes = C.c_size_t()
-        nat.check(nat.lib.sf_pixdec_workspace_bytes(h, F, shapes, n, C.byref(nbytes)))
-        ws = self._native.workspace(nbytes.value, dev)
-        feats = (C.c_void_p * n)(*[nat.ptr(x) or None for x in xs])
-        outs = (C.c_void_p * len(ms))(*[t.data_ptr() for t in ms])
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_pixdec_forward(h, feats, F, shapes, n, mask.data_ptr(), outs, len(ms), ws.data_ptr(), ws.numel(),
-                                                nat.current_stream_handle(dev)))
+        ws = self._native.workspace(nat.sized(nat.lib.sf_pixdec_workspace_bytes, h, F, shapes, n), dev)
+        nat.launch(dev, nat.lib.sf_pixdec_forward, h, nat.ptr_array(xs), F, shapes, n, mask.data_ptr(), nat.ptr_array(ms), len(ms), workspace=ws)
         return mask, ms[0], ms
 
     def forward(self, features: Dict[str, torch.Tensor], targets=None):

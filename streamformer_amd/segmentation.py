@@ -73,9 +73,8 @@ def semantic_inference(mask_cls: torch.Tensor, mask_pred: torch.Tensor, geometry
     (Q, h, w), C = src.shape, probs.shape[1]
     first_crop, first_out = (crop, out) if postprocess_before_inference else (padded, padded)
     sem = torch.empty((C,) + first_out, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib.sf_op_seg_semantic(src.data_ptr(), probs.data_ptr(), Q, C, h, w, padded[0], padded[1], first_crop[0], first_crop[1],
-                                             first_out[0], first_out[1], sem.data_ptr(), nat.current_stream_handle(dev)))
+    nat.launch(dev, nat.lib.sf_op_seg_semantic, src.data_ptr(), probs.data_ptr(), Q, C, h, w, padded[0], padded[1], first_crop[0], first_crop[1],
+               first_out[0], first_out[1], sem.data_ptr())
     if postprocess_before_inference:
         return sem
     index = torch.arange(C, dtype=torch.int32, device=dev).view(C, 1)
@@ -132,10 +131,8 @@ def panoptic_argmax(mask_cls: torch.Tensor, mask_pred: torch.Tensor, geometry: G
     Q, h, w = src.shape
     code = torch.empty(out, dtype=torch.int32, device=dev)
     counts = torch.empty(Q, 3, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib.sf_op_seg_panoptic_argmax(src.data_ptr(), max_scores.data_ptr(), labels.data_ptr(), Q, int(num_classes), float(object_mask_threshold),
-                                                    h, w, padded[0], padded[1], crop[0], crop[1], out[0], out[1], code.data_ptr(), counts.data_ptr(),
-                                                    nat.current_stream_handle(dev)))
+    nat.launch(dev, nat.lib.sf_op_seg_panoptic_argmax, src.data_ptr(), max_scores.data_ptr(), labels.data_ptr(), Q, int(num_classes),
+               float(object_mask_threshold), h, w, padded[0], padded[1], crop[0], crop[1], out[0], out[1], code.data_ptr(), counts.data_ptr())
     return code, max_scores, labels, counts
 
 
@@ -146,9 +143,8 @@ def panoptic_relabel(code: torch.Tensor, segment_of_query: torch.Tensor, out: Op
     if code.dtype != torch.int32 or segment_of_query.dtype != torch.int32 or not code.is_contiguous() or not segment_of_query.is_contiguous():
         raise ValueError("code and segment_of_query must be contiguous int32 tensors")
     out = torch.empty_like(code) if out is None else out
-    with torch.cuda.device(dev):
-        nat.check(nat.lib.sf_op_seg_panoptic_relabel(code.data_ptr(), segment_of_query.data_ptr(), segment_of_query.numel(), code.numel(), out.data_ptr(),
-                                                     nat.current_stream_handle(dev)))
+    nat.launch(dev, nat.lib.sf_op_seg_panoptic_relabel, code.data_ptr(), segment_of_query.data_ptr(), segment_of_query.numel(), code.numel(),
+               out.data_ptr())
     return out
 
 

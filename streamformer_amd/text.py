@@ -216,10 +216,9 @@ class SiglipTextModel(nn.Module):
     def _workspace(self, h, B: int, L: int) -> torch.Tensor:
         ws = self._native.workspaces.get((B, L))
         if ws is None:
-            n = C.c_size_t()
-            nat.check(nat.lib.sf_text_workspace_bytes(h, B, L, C.byref(n)))
+            n = nat.sized(nat.lib.sf_text_workspace_bytes, h, B, L)
             self._native.workspaces.clear()      # one shape at a time: class tables are large
-            ws = self._native.workspace(n.value, self.device, (B, L))
+            ws = self._native.workspace(n, self.device, (B, L))
         return ws
 
     # ------------------------------------------------------------------------------------ forward
@@ -266,10 +265,8 @@ class SiglipTextModel(nn.Module):
         ids_d, mask_d = self._device_inputs(ids, mask)
         last = torch.empty(B, L, c.hidden_size, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, c.projection_size, dtype=torch.float32, device=dev)
-        ws = self._workspace(h, B, L)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_text_forward(h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, last.data_ptr(), pooled.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_text_forward, h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, last.data_ptr(), pooled.data_ptr(),
+                   workspace=self._workspace(h, B, L))
         last = last.reshape(*input_ids.shape, c.hidden_size)
         out = TextModelOutput(last, pooled)
         return out if return_dict else out.to_tuple()
@@ -286,10 +283,8 @@ class SiglipTextModel(nn.Module):
         dev = self.device
         ids_d, mask_d = self._device_inputs(ids, mask)
         table = torch.empty(B // group, self.config.projection_size, dtype=torch.float32, device=dev)
-        ws = self._workspace(h, B, L)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib.sf_text_forward_groups(h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, group, table.data_ptr(),
-                                                     ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev)))
+        nat.launch(dev, nat.lib.sf_text_forward_groups, h, ids_d.data_ptr(), nat.ptr(mask_d), B, L, group, table.data_ptr(),
+                   workspace=self._workspace(h, B, L))
         return table
 
 

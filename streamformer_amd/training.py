@@ -537,19 +537,14 @@ class StreamformerTrainer:
                                "must schedule the same task per micro-step (sampler.py:218-337), or its collectives do not match")
 
     # ---- the step ---------------------------------------------------------------------------------------
-    def _stream(self) -> int:
-        return nat.current_stream_handle(self.device)
-
     def sync_weights(self) -> None:
-        with torch.cuda.device(self.device):
-            nat.check(nat.lib.sf_trainer_sync_weights(self._h, self.params.data_ptr(), self._stream()))
+        nat.launch(self.device, nat.lib.sf_trainer_sync_weights, self._h, self.params.data_ptr())
 
     def _workspace(self, B: int, T: int) -> torch.Tensor:
         if self._ws_key != (B, T):
-            n = C.c_size_t()
-            nat.check(nat.lib.sf_trainer_workspace_bytes(self._h, B, T, C.byref(n)))
+            n = nat.sized(nat.lib.sf_trainer_workspace_bytes, self._h, B, T)
             self._ws = None
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)      # held from the forward to the backward: the saved activations
             self._ws_key = (B, T)
         return self._ws
 
@@ -583,9 +578,8 @@ class StreamformerTrainer:
             nat.check(nat.lib.sf_trainer_set_dropout(self._h, 0.0, 0.0, 0))
         lhs = torch.empty(B, T, N, c.hidden_size, dtype=torch.float32, device=self.device)
         pool = torch.empty(B, T, c.hidden_size, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            nat.check(nat.lib.sf_trainer_forward(self._h, x.data_ptr(), {torch.bfloat16: nat.SF_BF16, torch.uint8: nat.SF_U8}.get(x.dtype, nat.SF_F32),
-                                                 B, T, lhs.data_ptr(), pool.data_ptr(), ws.data_ptr(), ws.numel(), self._stream()))
+        nat.launch(self.device, nat.lib.sf_trainer_forward, self._h, x.data_ptr(),
+                   {torch.bfloat16: nat.SF_BF16, torch.uint8: nat.SF_U8}.get(x.dtype, nat.SF_F32), B, T, lhs.data_ptr(), pool.data_ptr(), workspace=ws)
         self._lhs, self._pooler = lhs, pool
         return lhs, pool
 
@@ -603,8 +597,7 @@ class StreamformerTrainer:
             reduce = reduce and self._collectives and self.comm_enabled
             plan = self.buckets if reduce else [(nst - 1, 0, 0)]
             for last, off, n in plan:
-                nat.check(nat.lib.sf_trainer_backward(self._h, dp.data_ptr(), nat.ptr(dl), self.grads.data_ptr(), first, last,
-                                                      ws.data_ptr(), ws.numel(), self._stream()))
+                nat.launch(self.device, nat.lib.sf_trainer_backward, self._h, dp.data_ptr(), nat.ptr(dl), self.grads.data_ptr(), first, last, workspace=ws)
                 first = last + 1
                 if reduce:
                     sl = self.grads[off: off + n]
@@ -729,8 +722,7 @@ class StreamformerTrainer:
         return loss
 
     def grad_norm(self) -> torch.Tensor:
-        with torch.cuda.device(self.device):
-            nat.check(nat.lib.sf_trainer_grad_sumsq(self._h, self.grads.data_ptr(), self._scratch.data_ptr(), self._stream()))
+        nat.launch(self.device, nat.lib.sf_trainer_grad_sumsq, self._h, self.grads.data_ptr(), self._scratch.data_ptr())
         return self._scratch[0].sqrt() / self.world
 
     def optimizer_step(self, lr: Optional[float] = None, weight_decay: Optional[float] = None,
@@ -752,7 +744,7 @@ class StreamformerTrainer:
                 if t in active:
                     self.head_steps[t] += 1
                 steps += [self.head_steps[t] if t in active else 0] * 2
-            nat.check(nat.lib.sf_trainer_set_extra_steps(self._h, (C.c_int32 * len(steps))(*steps), len(steps)))
+            nat.check(nat.lib.sf_trainer_set_extra_steps(self._h, nat.i32_array(steps), len(steps)))
             self._touched = set()
         with torch.cuda.device(self.device):
             if self._guard is not None:
@@ -760,13 +752,13 @@ class StreamformerTrainer:
                 nat.check(nat.lib.sf_trainer_set_nonfinite_guard(
                     self._h, self._guard_row(active).data_ptr(), ll.data_ptr() if (ll is not None and ll.dtype == torch.float32 and ll.is_cuda) else None))
             if clip_grad is not None:
-                nat.check(nat.lib.sf_trainer_grad_sumsq(self._h, self.grads.data_ptr(), self._scratch.data_ptr(), self._stream()))
+                nat.launch(self.device, nat.lib.sf_trainer_grad_sumsq, self._h, self.grads.data_ptr(), self._scratch.data_ptr())
                 sumsq = self._scratch.data_ptr()
-            nat.check(nat.lib.sf_trainer_adamw_step(
-                self._h, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.step_count, self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps,
-                self.weight_decay if weight_decay is None else weight_decay, scale, sumsq,
-                float(clip_grad) if clip_grad is not None else 0.0, 1, self._stream()))
+            nat.launch(self.device, nat.lib.sf_trainer_adamw_step,
+                       self._h, self.params.data_ptr(), self.grads.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                       self.step_count, self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps,
+                       self.weight_decay if weight_decay is None else weight_decay, scale, sumsq,
+                       float(clip_grad) if clip_grad is not None else 0.0, 1)
         # the guard has read its loss: a later optimizer_step() without a micro_step() must not re-check a stale one
         self._last_loss = None
         if self._loss_acc_used:

@@ -34,7 +34,6 @@ returns ``pred_masks=[]`` next to ``pred_logits=[]``; ``num_topk`` above the num
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -79,8 +78,7 @@ def vis_scores(pred_logits: torch.Tensor, full: bool = False):
     mx = torch.empty(lead, dtype=torch.float32, device=dev)
     lab = torch.empty(lead, dtype=torch.int32, device=dev)
     sc = torch.empty(lead + (c1 - 1,), dtype=torch.float32, device=dev) if full else None
-    with torch.cuda.device(dev):
-        nat.check(nat.lib.sf_op_vis_scores(x.data_ptr(), rows, c1, mx.data_ptr(), lab.data_ptr(), nat.ptr(sc), nat.current_stream_handle(dev)))
+    nat.launch(dev, nat.lib.sf_op_vis_scores, x.data_ptr(), rows, c1, mx.data_ptr(), lab.data_ptr(), nat.ptr(sc))
     return mx, lab, sc
 
 
@@ -103,12 +101,10 @@ def resample_masks(det_masks: torch.Tensor, index: torch.Tensor, padded: Tuple[i
         res["denominator"] = torch.empty(K, dtype=torch.int64, device=dev)
         need = nat.lib.sf_op_vis_postprocess_workspace_bytes(K, Fr, H, W)
         if workspace is None or workspace.numel() < need or workspace.device != dev:
-            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib.sf_op_vis_postprocess(src.data_ptr(), R, h, w, idx.data_ptr(), K, Fr, padded[0], padded[1], crop[0], crop[1], H, W,
-                                                nat.ptr(res.get("masks")), nat.ptr(res.get("logits")), nat.ptr(res.get("numerator")),
-                                                nat.ptr(res.get("denominator")), nat.ptr(workspace) if sums else None,
-                                                workspace.numel() if sums else 0, nat.current_stream_handle(dev)))
+            workspace = nat.scratch(need, dev)
+    nat.launch(dev, nat.lib.sf_op_vis_postprocess, src.data_ptr(), R, h, w, idx.data_ptr(), K, Fr, padded[0], padded[1], crop[0], crop[1], H, W,
+               nat.ptr(res.get("masks")), nat.ptr(res.get("logits")), nat.ptr(res.get("numerator")), nat.ptr(res.get("denominator")),
+               workspace=workspace if sums else None)
     return res
 
 
@@ -212,10 +208,8 @@ class SimpleTracker(nn.Module):
         bits = torch.empty(Fr, Q, (pixels + 31) // 32, dtype=torch.int32, device=dev)
         area = torch.empty(Fr, Q, dtype=torch.int32, device=dev)
         inter = torch.empty(Fr, Q, Q, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            s = nat.current_stream_handle(dev)
-            nat.check(nat.lib.sf_op_vis_pack_masks(mk.data_ptr(), Fr * Q, pixels, bits.data_ptr(), area.data_ptr(), s))
-            nat.check(nat.lib.sf_op_vis_mask_iou(bits.data_ptr(), Fr, Q, pixels, inter.data_ptr(), s))
+        nat.launch(dev, nat.lib.sf_op_vis_pack_masks, mk.data_ptr(), Fr * Q, pixels, bits.data_ptr(), area.data_ptr())
+        nat.launch(dev, nat.lib.sf_op_vis_mask_iou, bits.data_ptr(), Fr, Q, pixels, inter.data_ptr())
         parts = dict(zip(HOST_KEYS, (mx, lab, lg, inter, area, _f32(det["pred_embeds"]), _f32(det["pred_queries"]))))
         flat = torch.cat([(t if t.dtype == torch.float32 else t.view(torch.float32)).reshape(-1) for t in parts.values()])
         host_flat = _device_to_host(flat)

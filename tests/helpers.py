@@ -62,6 +62,53 @@ def read_guarded(buf, view):
     return host[:view.numel()].view(view.shape)
 
 
+def guarded_ints(dev, n, fill=0x5a5a5a5a):
+    """An int32 buffer of n elements with 64 guard words behind it."""
+    return torch.full((n + 64,), fill, dtype=torch.int32, device=dev)
+
+
+def read_guarded_ints(buf, n, fill=0x5a5a5a5a):
+    host = buf.cpu()
+    assert (host[n:] == fill).all(), "the guard words were written"
+    return host[:n]
+
+
+# ---------------------------------------------------------------------------------------------------
+# the native library as the tests reach it
+# ---------------------------------------------------------------------------------------------------
+def native():
+    """streamformer_amd._native, imported on first use: collecting a test file must not need the built library."""
+    import streamformer_amd._native as nat
+    return nat
+
+
+def stream():
+    return native().current_stream_handle(gpu_device())
+
+
+class NoLaunch:
+    """Stands in for the module's view of streamformer_amd._native: size and capacity queries pass, every other entry point of the
+    library is recorded in ``calls`` and refused, so a refusal that came after a launch cannot pass for one that came before."""
+
+    def __init__(self, real):
+        self._real, self.calls = real, []
+
+    def __getattr__(self, name):
+        return getattr(self._real, name)
+
+    @property
+    def lib(self):
+        outer = self
+
+        class Lib:
+            def __getattr__(self, name):
+                if name.endswith(("_workspace_bytes", "_capacity")) or name == "sf_last_error":
+                    return getattr(outer._real.lib, name)
+                outer.calls.append(name)
+                raise AssertionError(f"{name} was reached")
+        return Lib()
+
+
 # ---------------------------------------------------------------------------------------------------
 # metrics (fp64, on CPU copies) and small helpers
 # ---------------------------------------------------------------------------------------------------
@@ -83,6 +130,11 @@ def rel_max(got, want):
 
 def randn(seed, *shape):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
+
+
+def draw(rs, *shape):
+    """fp32 standard normals of a numpy RandomState."""
+    return torch.from_numpy(rs.standard_normal(shape).astype(np.float32))
 
 
 def bf16_bits(t):

@@ -13,7 +13,7 @@ from streamformer_amd import cl_plugin as CP
 from streamformer_amd import criterion as K
 from tests import cl_plugin_oracle as PO
 from tests import criterion_oracle as CO
-from tests.helpers import check_against_floor, gpu_device, guarded, load_npz, read_guarded
+from tests.helpers import NoLaunch, check_against_floor, gpu_device, guarded, load_npz, read_guarded
 
 pytestmark = pytest.mark.gpu
 
@@ -58,29 +58,6 @@ def per_item(items):
     c = [torch.logsumexp(torch.nn.functional.pad(d[1:, 0] - d[0, 0], (0, 1)), 0) for d, _, _ in items]
     a = [((cos[:, 0] - y) ** 2).mean() for _, cos, y in items]
     return torch.stack(c).detach(), torch.stack(a).detach()
-
-
-class NoLaunch:
-    """Stands in for the module's view of streamformer_amd._native: size and capacity queries pass, every other entry point of the
-    library is recorded in ``calls`` and refused, so a refusal that came after a launch cannot pass for one that came before."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        return getattr(self._real, name)
-
-    @property
-    def lib(self):
-        outer = self
-
-        class Lib:
-            def __getattr__(self, name):
-                if name.endswith(("_workspace_bytes", "_capacity")) or name == "sf_last_error":
-                    return getattr(outer._real.lib, name)
-                outer.calls.append(name)
-                raise AssertionError(f"{name} was reached")
-        return Lib()
 
 
 @pytest.mark.parametrize("name", WITH_ITEMS)

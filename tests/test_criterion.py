@@ -12,7 +12,7 @@ import streamformer_amd as sa
 from streamformer_amd import _native as nat
 from streamformer_amd import criterion as K
 from tests import criterion_oracle as CO
-from tests.helpers import check_against_floor, gpu_device, load_npz, maxabs
+from tests.helpers import NoLaunch, check_against_floor, gpu_device, load_npz, maxabs
 
 pytestmark = pytest.mark.gpu
 
@@ -44,29 +44,6 @@ def want_indices(f27, name, l, b):
     if name in CO.CASES:
         return f27[f"{name}_src_{l}_{b}"], f27[f"{name}_tgt_{l}_{b}"]
     return tuple(t.numpy() for t in oracle(name, torch.float64)["indices"][l][b])
-
-
-class NoLaunch:
-    """Stands in for the module's view of streamformer_amd._native: size and capacity queries pass, every other entry point of the
-    library is recorded in ``calls`` and refused, so a refusal that came after a launch cannot pass for one that came before."""
-
-    def __init__(self, real):
-        self._real, self.calls = real, []
-
-    def __getattr__(self, name):
-        return getattr(self._real, name)
-
-    @property
-    def lib(self):
-        outer = self
-
-        class Lib:
-            def __getattr__(self, name):
-                if name.endswith(("_workspace_bytes", "_capacity")) or name == "sf_last_error":
-                    return getattr(outer._real.lib, name)
-                outer.calls.append(name)
-                raise AssertionError(f"{name} was reached")
-        return Lib()
 
 
 def split_draws(case, dev):
@@ -186,11 +163,11 @@ def test_capacity_is_refused_before_any_launch(monkeypatch):
     assert cap >= 37632 and (cap + 1352) * 4 <= 160 * 1024      # values + histogram, scan and partials: inside the CU's LDS
     step, _ = native_step("q_lt_g", dev)
     b = step.batch
-    ws = b.workspace(nat.lib.sf_op_crit_losses_workspace_bytes(step.N))
+    ws = nat.scratch(nat.lib.sf_op_crit_losses_workspace_bytes(step.N), dev)
     out = torch.full((3,), float("nan"), device=dev)
     args = lambda ko: (b.c_masks, b.L, b.B, b.Q, b.H, b.W, b.c_tgt_masks, b.c_G, b.c_H, b.c_W, step.pairs.data_ptr(), step.c_start, step.N,      # noqa: E731
                        step.over.data_ptr(), nat.ptr(step.rnd), step.K, ko, step.K_uncertain, 1.0, out.data_ptr(), 3, step.coords.data_ptr(),
-                       step.sums.data_ptr(), 0, ws.data_ptr(), ws.numel(), b.stream)
+                       step.sums.data_ptr(), 0, ws.data_ptr(), ws.numel(), nat.current_stream_handle(dev))
     assert nat.lib.sf_op_crit_losses(*args(cap + 1)) == nat.SF_ERR_CAPACITY and b"LDS" in nat.lib.sf_last_error()
     torch.cuda.synchronize()
     assert torch.isnan(out.cpu()).all(), "something was launched"

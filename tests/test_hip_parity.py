@@ -76,6 +76,28 @@ def test_op_layernorm(sa, rows, D):
     assert maxabs(y, want) <= 5e-6
 
 
+def test_launch_helper_runs_on_the_current_stream(sa):
+    """``nat.launch`` inside ``torch.cuda.stream(side)`` hands the entry point the side stream, not the default one, and its result is
+    bit-equal to the same call written out on that stream (3 rows x 64 columns of sf_op_layernorm)."""
+    nat, dev = sa._native, torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(364)
+    x, w, b = (torch.randn(*s, generator=g).to(dev) for s in ((3, 64), (64,), (64,)))
+    got, want = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+    side, seen = torch.cuda.Stream(dev), []
+
+    def entry(*args):
+        seen.append(args[-1])
+        return nat.lib.sf_op_layernorm(*args)
+
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        nat.launch(dev, entry, x.data_ptr(), w.data_ptr(), b.data_ptr(), got.data_ptr(), 3, 64, 1e-6)
+        nat.check(nat.lib.sf_op_layernorm(x.data_ptr(), w.data_ptr(), b.data_ptr(), want.data_ptr(), 3, 64, 1e-6, side.cuda_stream))
+    side.synchronize()
+    assert seen == [side.cuda_stream] and side.cuda_stream != torch.cuda.default_stream(dev).cuda_stream
+    assert not torch.isnan(got).any() and torch.equal(got.cpu().view(torch.int32), want.cpu().view(torch.int32))
+
+
 def _linear(sa, x, w, b, resid, alpha, gelu, mode):
     nat = sa._native
     M, K = x.shape

@@ -28,24 +28,12 @@ import torch.nn.functional as F
 
 from tests import mask_decoder_oracle as DO
 from tests.helpers import EPS32, MARGIN, check_against_floor, gpu_device, guarded, maxabs, read_guarded
+from tests.helpers import native as _nat, stream as _stream, draw as _draw
 
 pytestmark = pytest.mark.gpu
 
 MODES = {"fp32": "x3", "bf16": True}
 CAP = 0.05
-
-
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
-
-
-def _draw(rs, *shape):
-    return torch.from_numpy(rs.standard_normal(shape).astype(np.float32))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -21,6 +21,7 @@ import torch
 
 from tests import mask_decoder_oracle as DO
 from tests.helpers import EPS32, MARGIN, check_against_floor, fp32_floor, gpu_device, guarded, maxabs, read_guarded
+from tests.helpers import native as _nat, stream as _stream, draw as _draw
 from tests.test_mask_decoder import CAP, _accept_masks
 
 pytestmark = pytest.mark.gpu
@@ -29,19 +30,6 @@ TILE = 64
 FR = 2
 QS = (1, 5, 16, 17, 100)
 PS = (1, TILE - 1, TILE, TILE + 1, 2 * TILE + 3)
-
-
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
-
-
-def _draw(rs, *shape):
-    return torch.from_numpy(rs.standard_normal(shape).astype(np.float32))
 
 
 def _ratio(got, floor32, want):

@@ -18,6 +18,7 @@ from torch import nn
 from tests import mask_decoder_oracle as DO
 from tests import masked_attention_oracle as MO
 from tests.helpers import MARGIN, check_against_floor, fp32_floor, gpu_device, guarded, maxabs, read_guarded
+from tests.helpers import native as _nat, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
@@ -27,18 +28,9 @@ CASES = [(8, 1, 1), (32, 15, 15), (32, 16, 16), (72, 17, 17), (32, 16, 31), (8, 
          (128, 17, 65), (72, 100, 100), (128, 100, 784)]
 
 
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
 def _ma():
     import streamformer_amd as ma      # the package exports the whole interface (its attribute masked_attention is the function)
     return ma
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
 
 
 def _ratio(what, got, floor32, want):

@@ -246,6 +246,104 @@ def test_owned_handle():
     assert log == [0x1234, 7]
 
 
+class EntryPoint:
+    """A fake library entry point: records its arguments, answers ``code``; ``size`` is what a sizer writes through its last argument."""
+
+    def __init__(self, code=nat.SF_OK, size=None):
+        self.code, self.size, self.calls = code, size, []
+
+    def __call__(self, *args):
+        self.calls.append(args)
+        if self.size is not None:
+            args[-1]._obj.value = self.size
+        return self.code
+
+
+@pytest.fixture
+def guard_log(monkeypatch):
+    """``torch.cuda.device`` records ("enter" | "exit", device); cuda:0 is the current device; the stream of a device is 0x5000 + its
+    index."""
+    log = []
+
+    class Guard:
+        def __init__(self, device):
+            self.device = device
+
+        def __enter__(self):
+            log.append(("enter", self.device))
+
+        def __exit__(self, *exc):
+            log.append(("exit", self.device))
+            return False
+
+    monkeypatch.setattr(torch.cuda, "device", Guard)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    monkeypatch.setattr(nat, "current_stream_handle", lambda device: 0x5000 + (device.index or 0))
+    return log
+
+
+def test_launch_passes_arguments_through_with_the_stream_last(guard_log):
+    fn, t = EntryPoint(), torch.zeros(3)
+    assert nat.launch(CUDA1, fn, 7, None, 2.5, t) is None
+    assert len(fn.calls) == 1 and len(fn.calls[0]) == 5
+    assert fn.calls[0][:3] == (7, None, 2.5) and fn.calls[0][3] is t and fn.calls[0][4] == 0x5001
+    assert guard_log == [("enter", CUDA1), ("exit", CUDA1)]
+
+
+def test_launch_enters_no_guard_when_the_device_is_current(guard_log):
+    fn = EntryPoint()
+    nat.launch(CUDA0, fn)
+    nat.launch(torch.device("cuda"), fn, 3)                           # no index: the current device
+    assert fn.calls == [(0x5000,), (3, 0x5000)] and guard_log == []
+
+
+def test_launch_workspace_tail(guard_log):
+    fn, ws = EntryPoint(), torch.empty(300, dtype=torch.uint8)
+    nat.launch(CUDA0, fn, 1, 2, workspace=ws)
+    nat.launch(CUDA0, fn, 1, 2, workspace=None)
+    assert fn.calls == [(1, 2, ws.data_ptr(), 300, 0x5000), (1, 2, 0, 0, 0x5000)]
+
+
+def test_launch_raises_the_code_and_leaves_the_guard(guard_log):
+    with pytest.raises(nat.NativeError) as e:
+        nat.launch(CUDA1, EntryPoint(nat.SF_ERR_WORKSPACE), 1, workspace=None)
+    assert e.value.code == nat.SF_ERR_WORKSPACE
+    assert guard_log == [("enter", CUDA1), ("exit", CUDA1)]
+
+    def broken(*args):
+        raise KeyError("inside the call")
+
+    with pytest.raises(KeyError):
+        nat.launch(CUDA1, broken)
+    assert guard_log[2:] == [("enter", CUDA1), ("exit", CUDA1)]
+
+
+def test_sized():
+    fn = EntryPoint(size=12345)
+    assert nat.sized(fn, 4, 5) == 12345
+    assert len(fn.calls[0]) == 3 and fn.calls[0][:2] == (4, 5) and isinstance(fn.calls[0][2]._obj, C.c_size_t)
+    with pytest.raises(nat.NativeError) as e:
+        nat.sized(EntryPoint(nat.SF_ERR_INVALID, size=1), 4)
+    assert e.value.code == nat.SF_ERR_INVALID
+
+
+def test_scratch_has_the_workspace_floor():
+    cpu = torch.device("cpu")
+    s = nat.scratch(0, cpu)
+    assert s.dtype == torch.uint8 and s.device == cpu and s.numel() == 256 == nat.WORKSPACE_FLOOR
+    assert nat.scratch(255, cpu).numel() == 256 and nat.scratch(257, cpu).numel() == 257
+    assert nat.PackedHandle().workspace(0, cpu).numel() == s.numel()            # the two allocators agree
+
+
+def test_ctypes_arrays():
+    a, b = torch.zeros(2), torch.ones(5)
+    p = nat.ptr_array([a, None, b])
+    assert isinstance(p, C.Array) and p._type_ is C.c_void_p and list(p) == [a.data_ptr(), None, b.data_ptr()]
+    i = nat.i32_array([3, torch.Size([9])[0], -1])
+    assert i._type_ is C.c_int32 and list(i) == [3, 9, -1]
+    assert len(nat.ptr_array([])) == 1 and len(nat.i32_array([])) == 1          # never a zero-length array: its address is passed
+
+
 PARENT_TABLES = {       # what each module's own table took before there was one
     "text": {"bf16": 0, "fp32": 1, "bf16x3": 1},
     "connector": {"bf16": 0, "fp32": 1, "bf16x3": 1},

@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from tests import pixel_decoder_oracle as PO
 from tests import vit_adapter_oracle as VO
 from tests.helpers import bf16_bits, check_against_floor, gpu_device, guarded, read_guarded
+from tests.helpers import native as _nat, stream as _stream, draw as _draw
 from tests.oracle_ops import layernorm, operand_linear
 
 pytestmark = pytest.mark.gpu
@@ -29,19 +30,6 @@ pytestmark = pytest.mark.gpu
 MODES = {"fp32": "x3", "bf16": True}
 FRAMES = 2
 SENTINEL = -1            # 0xffff: a bf16 NaN no kernel writes
-
-
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
-
-
-def _draw(rs, *shape):
-    return torch.from_numpy(rs.standard_normal(shape).astype(np.float32))
 
 
 def guarded_bits(dev, *shape):

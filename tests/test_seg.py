@@ -17,29 +17,10 @@ import torch
 from tests import seg_oracle as SO
 from tests import vis_oracle as VO
 from tests.helpers import check_against_floor, gpu_device, guarded, read_guarded
+from tests.helpers import native as _nat, stream as _stream, guarded_ints as _ints, read_guarded_ints as _read_ints
 
 pytestmark = pytest.mark.gpu
 CAP = 0.01
-FILL = 0x5a5a5a5a
-
-
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
-
-
-def _ints(dev, n):
-    return torch.full((n + 64,), FILL, dtype=torch.int32, device=dev)
-
-
-def _read_ints(buf, n):
-    host = buf.cpu()
-    assert (host[n:] == FILL).all(), "the guard words were written"
-    return host[:n]
 
 
 def _geo_args(src, g):

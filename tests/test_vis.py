@@ -16,29 +16,10 @@ import torch.nn.functional as F
 
 from tests import vis_oracle as VO
 from tests.helpers import EPS32, MARGIN, check_against_floor, gpu_device, guarded, maxabs, read_guarded
+from tests.helpers import native as _nat, stream as _stream, guarded_ints as _ints, read_guarded_ints as _read_ints
 
 pytestmark = pytest.mark.gpu
 CAP = 0.01
-
-
-def _nat():
-    import streamformer_amd._native as nat
-    return nat
-
-
-def _stream():
-    return _nat().current_stream_handle(gpu_device())
-
-
-def _ints(dev, n, fill=0x5a5a5a5a):
-    """An int32 buffer of n elements with 64 guard words behind it."""
-    return torch.full((n + 64,), fill, dtype=torch.int32, device=dev)
-
-
-def _read_ints(buf, n, fill=0x5a5a5a5a):
-    host = buf.cpu()
-    assert (host[n:] == fill).all(), "the guard words were written"
-    return host[:n]
 
 
 # ------------------------------------------------------------------------------------------------

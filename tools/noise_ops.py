@@ -34,7 +34,7 @@ nst = len(tr.stage_ranges)
 
 
 def stages(first, last):
-    nat.check(nat.lib.sf_trainer_backward(tr._h, gp.data_ptr(), None, tr.grads.data_ptr(), first, last, tr._ws.data_ptr(), tr._ws.numel(), tr._stream()))
+    nat.check(nat.lib.sf_trainer_backward(tr._h, gp.data_ptr(), None, tr.grads.data_ptr(), first, last, tr._ws.data_ptr(), tr._ws.numel(), nat.current_stream_handle(tr.device)))
 
 
 def one(mode):

@@ -71,7 +71,7 @@ def main():
     if args.staged:
         for st in range(len(tr.stage_ranges)):
             nat.check(nat.lib.sf_trainer_backward(tr._h, gp.data_ptr(), None, tr.grads.data_ptr(), st, st, tr._ws.data_ptr(), tr._ws.numel(),
-                                                  tr._stream()))
+                                                  nat.current_stream_handle(tr.device)))
     else:
         tr.backward(gp)
     torch.cuda.synchronize()
