@@ -273,6 +273,15 @@ int sf_op_attention(const float* qkv_dev, float* ctx_dev, int groups, int L, int
                     int causal, int temporal_layout, int N_tokens, int compute,
                     void* workspace_dev, size_t workspace_bytes, sf_stream stream);
 size_t sf_op_attention_workspace_bytes(int groups, int L, int heads, int head_dim);
+/* Which spatial-attention kernel sf_op_attention(frames, N, heads, head_dim, ..., temporal_layout = 0, compute) runs, without running
+ * it; `probs` / `dropout` > 0 ask the same for a call that also wants the probabilities (output_attentions) / dropout on them, which
+ * the encoder and the training step make.  Nothing is launched and no device memory is touched.
+ * *route: 0 no kernel takes the call, 1 the generic kernel (head_dim != 64), 2 / 3 N > 224 on bf16 / fp32 rows, 4 DMA-staged bf16 rows,
+ * 5 the same with 13 key tiles at compile time (193 .. 208 tokens), 6 the same with dropout, 7 / 8 DMA-staged hi + lo planes / with 13
+ * tiles, 9 / 10 register-staged bf16 / fp32 rows.  *qsplit: workgroups per (frame, head).  *lds: dynamic LDS bytes of the launch.
+ * Any of the three may be NULL.                                                                                                      */
+int sf_op_spatial_attention_plan(int frames, int N, int heads, int head_dim, int compute, int probs, float dropout,
+                                 int* route, int* qsplit, size_t* lds);
 /* Temporal attention over a KV-cache the CALLER built: the streaming step (Tq = 1), chunked prefill (Tq > 1 behind a past), the position
  * read from device memory and the table of a ragged call — the kernels of a stream, without an encoder around them.
  * cache fp32 [slabs, cap, N_tokens, 3*D], q | k | v per row (the encoder's cache layout); it is converted to what `compute` keeps in a real

@@ -145,6 +145,7 @@ SIGNATURES = {
     "sf_op_gemm": (_I, [C.POINTER(SfGemmDesc), _I, C.POINTER(_I), _P]),
     "sf_op_attention": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _SZ, _P]),
     "sf_op_attention_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_spatial_attention_plan": (_I, [_I, _I, _I, _I, _I, _I, _F, C.POINTER(_I), C.POINTER(_I), C.POINTER(_SZ)]),
     "sf_op_attention_cached": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, C.POINTER(_I), C.POINTER(_I), _P, _SZ, _P]),
     "sf_op_attention_cached_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
     "sf_loss_workspace_bytes": (_SZ, [_I, _I]),

@@ -19,70 +19,32 @@
 // Spatial: one 8-wave workgroup per (frame, head), L <= 224.  Temporal: one WAVE per (batch, patch,
 // head) sequence with wave-private images, L <= 32.
 #include "sf_train.h"
+#include "sf_attn_image.h"       // the images' swizzle and readers, shared with the forward DMA kernels
 #include "sf_switches.h"
 #include <cstdlib>
-
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
 
 #define LOG2E 1.4426950408889634f
 #define NEG_BIG (-1.0e30f)
 
-SF_DEVICE f32x4_t ab_mfma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
-  typedef __attribute__((ext_vector_type(8))) __bf16 v8bf;
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
-}
-// chunk swizzle: bijective in row bits 1..3 (row fragments of 16 rows conflict-free), and its upper
-// two bits bijective in row bits 1..2 (the 8 rows of a half-wave transposed read conflict-free)
-// (round 6) gfx950 serves a ds_read_b128 in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32), not in contiguous sixteens: a row
-// fragment's group holds rows 0-3 and 12-15 at chunk c and rows 4-11 at chunk c ^ 1.  With 128-byte rows the even rows share one half of the
-// 256-byte bank row, so {s(0), s(2), s(12), s(14)} and {s(4), s(6), s(8), s(10)} ^ 1 must partition the 8 slots: s = 2 * ((row >> 1) & 3)
-// gives {0, 2, 4, 6} and {5, 7, 1, 3}.  Rounds 2-5 also folded row bit 3 in (| ((row >> 3) & 1)): bijective over 16 contiguous rows, 2-way
-// conflicted on the real groups (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.24-0.28 on these kernels).  SF_ATTN_SWZ_LEGACY: the old function (A/B builds).
-#ifdef SF_ATTN_SWZ_LEGACY
-SF_DEVICE int bswz(int row) { return (((row >> 1) & 3) << 1) | ((row >> 3) & 1); }
-#else
-SF_DEVICE int bswz(int row) { return ((row >> 1) & 3) << 1; }
-#endif
-SF_DEVICE int img_off(int row, int chunk) { return row * 128 + ((chunk ^ bswz(row)) << 4); }
-
-SF_DEVICE bf16x8_t row_frag(const char* img, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8_t*>(img + img_off(row, chunk));
-}
+// token-major fragments of this file: the shared tr_frag, or in the lab library (SF_TBWD_LAB=6) plain 8-byte reads of the same
+// addresses in its place (results invalid)
 #ifdef SF_LAB
-__device__ int g_tbwd_plain_reads;       // lab (SF_TBWD_LAB=6): plain 8-byte reads in place of the transposed ones (results invalid)
-#endif
-// token-major fragment: lane (l15 = column e of tile et, g) gets rows {r0+4g..+3} and {r0+16+4g..+3}
+__device__ int g_tbwd_plain_reads;
 template <bool TWO>
-SF_DEVICE bf16x8_t tr_frag(const char* img, int r0, int et, int lane) {
+SF_DEVICE bf16x8_t bwd_tr_frag(const char* img, int r0, int et, int lane) {
+  if (!g_tbwd_plain_reads) return tr_frag<TWO>(img, r0, et, lane);
   const int t16 = lane & 15, g = lane >> 4;
-  const int row = r0 + 4 * g + (t16 >> 2);
-  const int off = img_off(row, 2 * et + ((t16 & 3) >> 1)) + ((t16 & 1) << 3);
-#ifdef SF_LAB
-  if (g_tbwd_plain_reads) {
-    const s16x4_t lo = *reinterpret_cast<const s16x4_t*>(img + off);
-    bf16x8_t f;
-    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-    if (TWO) {
-      const s16x4_t hi = *reinterpret_cast<const s16x4_t*>(img + off + 16 * 128);
-      f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-    } else {
-      f[4] = f[5] = f[6] = f[7] = 0;
-    }
-    return f;
-  }
-#endif
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + off));
+  const int off = img_off(r0 + 4 * g + (t16 >> 2), 2 * et + ((t16 & 3) >> 1)) + ((t16 & 1) << 3);
+  const s16x4_t lo = *reinterpret_cast<const s16x4_t*>(img + off);
+  const s16x4_t hi = TWO ? *reinterpret_cast<const s16x4_t*>(img + off + 16 * 128) : (s16x4_t){0, 0, 0, 0};
   bf16x8_t f;
   f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-  if (TWO) {
-    const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + off + 16 * 128));
-    f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-  } else {
-    f[4] = f[5] = f[6] = f[7] = 0;
-  }
+  f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
   return f;
 }
+#else
+#define bwd_tr_frag tr_frag
+#endif
 SF_DEVICE bf16x8_t pack_a(const f32x4_t lo, const f32x4_t hi) {
   u32x4_t u = {pack_bf2(lo[0], lo[1]), pack_bf2(lo[2], lo[3]), pack_bf2(hi[0], hi[1]), pack_bf2(hi[2], hi[3])};
   return __builtin_bit_cast(bf16x8_t, u);
@@ -117,7 +79,7 @@ SF_DEVICE void phase_a_tile(const BwdView& w, int it, int nt, int lane) {
   for (int jt = 0; jt < nt; ++jt) {
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) acc = ab_mfma(row_frag(w.k, jt * 16 + l15, ks * 4 + g), qf[ks], acc);
+    for (int ks = 0; ks < 2; ++ks) acc = mfma16(row_frag(w.k, jt * 16 + l15, ks * 4 + g), qf[ks], acc);
     float s[4];
     float tm = NEG_BIG;
 #pragma unroll
@@ -200,8 +162,8 @@ SF_DEVICE void phase_b_block(const BwdView& w, int jb, int nb, f32x4_t (&dk)[2][
             f32x4_t s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              s = ab_mfma(qf[ks], kf[jt2][ks], s);
-              dp = ab_mfma(gf[ks], vf[jt2][ks], dp);
+              s = mfma16(qf[ks], kf[jt2][ks], s);
+              dp = mfma16(gf[ks], vf[jt2][ks], dp);
             }
             const int kj = jb * 32 + jt2 * 16 + l15;
 #pragma unroll
@@ -223,12 +185,12 @@ SF_DEVICE void phase_b_block(const BwdView& w, int jb, int nb, f32x4_t (&dk)[2][
     }
 #pragma unroll
     for (int et = 0; et < 4; ++et) {
-      const bf16x8_t gt = tr_frag<TWO>(w.d_o, ib * 32, et, lane);
-      const bf16x8_t qt = tr_frag<TWO>(w.q, ib * 32, et, lane);
+      const bf16x8_t gt = bwd_tr_frag<TWO>(w.d_o, ib * 32, et, lane);
+      const bf16x8_t qt = bwd_tr_frag<TWO>(w.q, ib * 32, et, lane);
 #pragma unroll
       for (int jt2 = 0; jt2 < NT2; ++jt2) {
-        dv[jt2][et] = ab_mfma(pack_a(p[0][jt2], p[1][jt2]), gt, dv[jt2][et]);
-        dk[jt2][et] = ab_mfma(pack_a(ds[0][jt2], ds[1][jt2]), qt, dk[jt2][et]);
+        dv[jt2][et] = mfma16(pack_a(p[0][jt2], p[1][jt2]), gt, dv[jt2][et]);
+        dk[jt2][et] = mfma16(pack_a(ds[0][jt2], ds[1][jt2]), qt, dk[jt2][et]);
       }
     }
   }
@@ -275,8 +237,8 @@ SF_DEVICE void phase_c_block(const BwdView& w, int ib, int nb, f32x4_t (&dq)[2][
             f32x4_t s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-              s = ab_mfma(kf[ks], qf[it2][ks], s);
-              dp = ab_mfma(vf[ks], gf[it2][ks], dp);
+              s = mfma16(kf[ks], qf[it2][ks], s);
+              dp = mfma16(vf[ks], gf[it2][ks], dp);
             }
             const int qi = ib * 32 + it2 * 16 + l15;
 #pragma unroll
@@ -296,9 +258,9 @@ SF_DEVICE void phase_c_block(const BwdView& w, int ib, int nb, f32x4_t (&dq)[2][
     }
 #pragma unroll
     for (int et = 0; et < 4; ++et) {
-      const bf16x8_t kt = tr_frag<TWO>(w.k, jb * 32, et, lane);
+      const bf16x8_t kt = bwd_tr_frag<TWO>(w.k, jb * 32, et, lane);
 #pragma unroll
-      for (int it2 = 0; it2 < NT2; ++it2) dq[it2][et] = ab_mfma(pack_a(ds[0][it2], ds[1][it2]), kt, dq[it2][et]);
+      for (int it2 = 0; it2 < NT2; ++it2) dq[it2][et] = mfma16(pack_a(ds[0][it2], ds[1][it2]), kt, dq[it2][et]);
     }
   }
 }
@@ -418,8 +380,8 @@ SF_DEVICE void phase_b_tile16(const BwdView& w, int jt, int nb_rt, f32x4_t (&dk)
       f32x4_t sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        sc = ab_mfma(row_frag(w.q, q0 + l15, ks * 4 + g), kf[ks], sc);
-        dp = ab_mfma(row_frag(w.d_o, q0 + l15, ks * 4 + g), vf[ks], dp);
+        sc = mfma16(row_frag(w.q, q0 + l15, ks * 4 + g), kf[ks], sc);
+        dp = mfma16(row_frag(w.d_o, q0 + l15, ks * 4 + g), vf[ks], dp);
       }
       const f32x4_t lse = *reinterpret_cast<const f32x4_t*>(w.lse2 + q0 + 4 * g);
       const f32x4_t dl = *reinterpret_cast<const f32x4_t*>(w.delta + q0 + 4 * g);
@@ -436,8 +398,8 @@ SF_DEVICE void phase_b_tile16(const BwdView& w, int jt, int nb_rt, f32x4_t (&dk)
     const bf16x8_t pa = pack_a(p[0], p[1]), dsa = pack_a(ds[0], ds[1]);
 #pragma unroll
     for (int et = 0; et < 4; ++et) {
-      dv[et] = ab_mfma(pa, tr_frag<true>(w.d_o, ib * 32, et, lane), dv[et]);
-      dk[et] = ab_mfma(dsa, tr_frag<true>(w.q, ib * 32, et, lane), dk[et]);
+      dv[et] = mfma16(pa, bwd_tr_frag<true>(w.d_o, ib * 32, et, lane), dv[et]);
+      dk[et] = mfma16(dsa, bwd_tr_frag<true>(w.q, ib * 32, et, lane), dk[et]);
     }
   }
 }
@@ -468,8 +430,8 @@ SF_DEVICE void phase_c_tile16(const BwdView& w, int it, int nb_rt, f32x4_t (&dq)
       f32x4_t sc = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        sc = ab_mfma(row_frag(w.k, k0 + l15, ks * 4 + g), qf[ks], sc);
-        dp = ab_mfma(row_frag(w.v, k0 + l15, ks * 4 + g), gf[ks], dp);
+        sc = mfma16(row_frag(w.k, k0 + l15, ks * 4 + g), qf[ks], sc);
+        dp = mfma16(row_frag(w.v, k0 + l15, ks * 4 + g), gf[ks], dp);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -481,7 +443,7 @@ SF_DEVICE void phase_c_tile16(const BwdView& w, int it, int nb_rt, f32x4_t (&dq)
     }
     const bf16x8_t dsa = pack_a(ds[0], ds[1]);
 #pragma unroll
-    for (int et = 0; et < 4; ++et) dq[et] = ab_mfma(dsa, tr_frag<true>(w.k, jb * 32, et, lane), dq[et]);
+    for (int et = 0; et < 4; ++et) dq[et] = mfma16(dsa, bwd_tr_frag<true>(w.k, jb * 32, et, lane), dq[et]);
   }
 }
 
@@ -571,8 +533,8 @@ hipError_t sf_launch_spatial_attention_bwd(const SfAttnBwdArgs& a, hipStream_t s
   const int nt = (a.L + 15) >> 4;
   const dim3 grid(a.nseq * a.heads), block(SB_THREADS);
   if (b.drop.on) return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<true>, grid, block, lds, s, b);
-  if (nt == 13 && !a.causal && !ntc_off)      // 224^2 frames: 196 patches = 13 tiles, block loops unrolled
-    return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<false, 13>, grid, block, lds, s, b);
+  if (nt == SF_SPATIAL_NTC && !a.causal && !ntc_off)      // 224^2 frames: 196 patches = 13 tiles, block loops unrolled
+    return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<false, SF_SPATIAL_NTC>, grid, block, lds, s, b);
   return sf_launch_big_lds(sf_spatial_attn_bwd_kernel<false>, grid, block, lds, s, b);
 }
 

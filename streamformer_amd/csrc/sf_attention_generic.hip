@@ -1,4 +1,4 @@
-// Attention for head widths the tuned kernels of sf_attention.hip (head_dim 64) do not cover — the reference's config takes any
+// Attention for head widths the tuned kernels of sf_attention_{spatial,temporal,decode}.hip (head_dim 64) do not cover — the reference's config takes any
 // hidden_size / num_attention_heads (models/configuration_streamformer.py:90-135; SigLIP-so400m: 1152 / 16 = 72).  Same contracts as
 // sf_launch_spatial_attention / sf_launch_temporal_attention (modeling:688-717 / 575-615, cache + single query: vqa_enc:491-560), any
 // head_dim that is a multiple of 8 up to 128, bf16 / fp32 / hi + lo plane inputs, both compute modes.

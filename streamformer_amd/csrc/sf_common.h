@@ -64,12 +64,16 @@ SF_DEVICE void store_planes4(f32x4_t v, bf16_t* hi, bf16_t* lo, size_t o) {
   *reinterpret_cast<u32x2_t*>(hi + o) = (u32x2_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16)};
   if (lo) *reinterpret_cast<u32x2_t*>(lo + o) = (u32x2_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16)};
 }
+// eight bf16 bit patterns (one per word, as split_bf / f2bf return them) -> the 16 bytes of eight consecutive elements
+SF_DEVICE u32x4_t pack_bf8(const unsigned int (&b)[8]) {
+  return (u32x4_t){b[0] | (b[1] << 16), b[2] | (b[3] << 16), b[4] | (b[5] << 16), b[6] | (b[7] << 16)};
+}
 SF_DEVICE void store_planes8(const float v[8], bf16_t* hi, bf16_t* lo, size_t o) {
   unsigned int hb[8], lb[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) split_bf(v[j], hb[j], lb[j]);
-  *reinterpret_cast<u32x4_t*>(hi + o) = (u32x4_t){hb[0] | (hb[1] << 16), hb[2] | (hb[3] << 16), hb[4] | (hb[5] << 16), hb[6] | (hb[7] << 16)};
-  if (lo) *reinterpret_cast<u32x4_t*>(lo + o) = (u32x4_t){lb[0] | (lb[1] << 16), lb[2] | (lb[3] << 16), lb[4] | (lb[5] << 16), lb[6] | (lb[7] << 16)};
+  *reinterpret_cast<u32x4_t*>(hi + o) = pack_bf8(hb);
+  if (lo) *reinterpret_cast<u32x4_t*>(lo + o) = pack_bf8(lb);
 }
 
 // LayerNorm folded into the consumer at small M (LNF): A = bf16(x) of the residual stream, W' = W * gamma.  The wave adds
@@ -475,7 +479,7 @@ struct SfAttnArgs {
                                       // tab[b].stream; its context row stays row b of the call
   bf16_t* ctx_hi; bf16_t* ctx_lo;     // [rows, D] output (lo only in accurate mode)
   int D;
-  int head_dim;                       // 0 or 64: the tuned kernels of sf_attention.hip; any other multiple of 8 up to 128: sf_attention_generic.hip
+  int head_dim;                       // 0 or 64: the tuned kernels of sf_attention_{spatial,temporal,decode}.hip; any other multiple of 8 up to 128: sf_attention_generic.hip
   float* lse2_out;                    // spatial only, optional: base-2 log-sum-exp of the scaled scores per query,
                                       // [frames, heads, N] fp32 (kept by the training forward for the backward kernel)
   float* probs;                       // spatial only, optional: softmax probabilities [frames, heads, N, N] fp32
@@ -483,8 +487,6 @@ struct SfAttnArgs {
   SfDrop drop;                        // training forward: dropout on the probabilities (on = 0: none); element ((seq * heads + h) * Lq + q) * Lk + k,
                                       // seq = frame (spatial) / b * N + n (temporal).  DMA-staged bf16 kernels only.
 };
-hipError_t sf_launch_spatial_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);
-bool sf_spatial_planes_ok(int N, bool probs);
 bool sf_temporal_planes_ok(int Tq, int Tk);
 // the kernels of the temporal attention and their instances; the values are the `route` of sf_op_attention_cached (include/streamformer_hip.h)
 enum SfTemporalRoute {
@@ -497,10 +499,32 @@ enum SfTemporalRoute {
   SF_TROUTE_MFMA_BF16_NT1 = 15, SF_TROUTE_MFMA_BF16_NT2 = 16, SF_TROUTE_MFMA_BF16_NT4 = 17, SF_TROUTE_MFMA_BF16_NT8 = 18,
   SF_TROUTE_GENERIC = 19,                                                        // head_dim != 64: sf_attention_generic.hip
 };
-SfTemporalRoute sf_temporal_route(const SfAttnArgs& a, bool accurate);          // sf_attention.hip: what sf_launch_temporal_attention will run (no launch)
+SfTemporalRoute sf_temporal_route(const SfAttnArgs& a, bool accurate);          // sf_attention_temporal.hip: what sf_launch_temporal_attention will run (no launch)
 int sf_temporal_route_waves(SfTemporalRoute r, const SfAttnArgs& a);            // waves per workgroup of that launch (the MFMA routes shrink it when the LDS patch is large)
 hipError_t sf_launch_temporal_route(SfTemporalRoute r, const SfAttnArgs& a, hipStream_t s);
 hipError_t sf_launch_temporal_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);      // = sf_launch_temporal_route(sf_temporal_route(a, accurate), ...)
+// the kernels of the spatial attention and their instances; the values are the `route` of sf_op_spatial_attention_plan (include/streamformer_hip.h)
+enum SfSpatialRoute {
+  SF_SROUTE_NONE = 0,                                                            // no kernel takes the call
+  SF_SROUTE_GENERIC = 1,                                                         // head_dim != 64: sf_attention_generic.hip
+  SF_SROUTE_LARGE_BF16 = 2, SF_SROUTE_LARGE_ACC = 3,                             // N > 224: keys stream through LDS; bf16 / fp32 rows
+  SF_SROUTE_DMA_BF16 = 4, SF_SROUTE_DMA_BF16_NT13 = 5, SF_SROUTE_DMA_DROP = 6,   // N <= 224, bf16 rows by LDS-DMA; 13 tiles at compile time; dropout
+  SF_SROUTE_DMA_PLANES = 7, SF_SROUTE_DMA_PLANES_NT13 = 8,                       // the same on hi + lo planes (accurate mode)
+  SF_SROUTE_STAGED_BF16 = 9, SF_SROUTE_STAGED_ACC = 10,                          // N <= 224, register-staged: probabilities, fp32 rows, A/B switches
+#ifdef SF_LAB
+  SF_SROUTE_PERS = 11,                                                           // lab library: persistent kernel (tools/lab/sf_spatial_pers.inc)
+#endif
+};
+#define SF_SPATIAL_NTC 13     // 193 .. 208 tokens per frame (the 196 patches of a 224^2 frame): 13 key tiles, which forward and backward have as compile-time instances
+struct SfSpatialPlan {
+  SfSpatialRoute route;
+  int qsplit;                 // workgroups per (frame, head): shares of the query tiles (N <= 224) / blocks of 128 queries (N > 224)
+  size_t lds;                 // dynamic LDS bytes of the launch
+};
+SfSpatialPlan sf_spatial_plan(const SfAttnArgs& a, bool accurate);              // sf_attention_spatial.hip: what sf_launch_spatial_attention will run (no launch)
+hipError_t sf_launch_spatial_plan(const SfSpatialPlan& pl, const SfAttnArgs& a, hipStream_t s);
+hipError_t sf_launch_spatial_attention(const SfAttnArgs& a, bool accurate, hipStream_t s);       // = sf_launch_spatial_plan(sf_spatial_plan(a, accurate), ...)
+bool sf_spatial_planes_ok(int N, bool probs);                                   // accurate mode: does the plan send hi + lo planes to a DMA kernel?
 bool sf_attention_generic_supported(const SfAttnArgs& a, int head_dim);            // sf_attention_generic.hip: head_dim % 8 == 0, <= 128
 hipError_t sf_launch_attention_generic(const SfAttnArgs& a, int head_dim, bool temporal, hipStream_t s);
 

@@ -146,6 +146,52 @@ extern "C" size_t sf_op_attention_workspace_bytes(int groups, int L, int heads, 
   return rows * 3 * D * 2 * 2 + rows * D * 2 * 2 + 4096;     // qkv hi (+ lo) planes, ctx hi + lo
 }
 
+// The arguments of sf_op_attention's kernel call and where its workspace pieces lie: shared with sf_op_spatial_attention_plan, which
+// passes no buffers (every pointer is then null, the offsets between them as in a real call), so the query cannot drift from the call.
+struct OpAttn {
+  SfAttnArgs a;               // everything but the layout's own fields (spatial: N, frames; temporal: the T* fields)
+  bf16_t *qb, *ql;            // bf16 rows / lo plane of qkv, filled by sf_launch_split when `split`
+  bool split;
+};
+static OpAttn op_attention_args(const float* qkv, void* workspace, int groups, int L, int heads, int head_dim, bool acc, bool temporal_layout,
+                                bool probs) {
+  const int D = heads * head_dim;
+  const size_t rows = (size_t)groups * L;
+  SfCarver c(workspace, acc, true);      // ctx: hi + lo bytes in both modes, the lo plane handed out in the accurate mode
+  const SfPlanes cp = c.planes(rows * D);
+  OpAttn o;
+  o.qb = c.take<bf16_t>(rows * 3 * D);
+  const size_t qb_off = c.off;
+  const bool planes = acc && head_dim == 64 && (temporal_layout ? sf_temporal_planes_ok(L, L) : sf_spatial_planes_ok(L, probs));
+  o.ql = planes ? c.lo(rows * 3 * D) : nullptr;      // (planes: accurate mode only)
+  o.split = !acc || planes;
+  const void* base = o.split ? (const void*)o.qb : (const void*)qkv;
+  const size_t esz = o.split ? 2 : 4;
+  SfAttnArgs& a = o.a;
+  memset(&a, 0, sizeof(a));
+  a.q = base; a.k = (const char*)base + (size_t)D * esz; a.v = (const char*)base + (size_t)2 * D * esz;
+  a.in_is_f32 = acc && !planes; a.lo_plane_off = planes ? (long long)((c.off - qb_off) / sizeof(bf16_t)) : 0;      // = ql - qb: two pieces of one size, ends as far apart as starts
+  a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = 1.0f / sqrtf((float)head_dim);
+  a.ctx_hi = cp.hi; a.ctx_lo = cp.lo; a.D = D; a.head_dim = head_dim;
+  return o;
+}
+
+extern "C" int sf_op_spatial_attention_plan(int frames, int N, int heads, int head_dim, int compute, int probs, float dropout, int* route,
+                                            int* qsplit, size_t* lds) {
+  if (head_dim < 8 || head_dim > 128 || head_dim % 8) return sf_set_err(SF_ERR_INVALID, "head_dim must be a multiple of 8 in 8..128");
+  static float probs_wanted;             // the plan only asks whether a.probs is null
+  const bool acc = compute == SF_COMPUTE_BF16X3;
+  SfAttnArgs a = op_attention_args(nullptr, nullptr, frames, N, heads, head_dim, acc, false, probs != 0).a;
+  a.N = N; a.frames = frames;
+  if (probs) a.probs = &probs_wanted;
+  a.drop = sf_drop_make(dropout, 0u, 0u);
+  const SfSpatialPlan pl = sf_spatial_plan(a, acc);
+  if (route) *route = (int)pl.route;
+  if (qsplit) *qsplit = pl.qsplit;
+  if (lds) *lds = pl.lds;
+  return SF_OK;
+}
+
 extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, int heads, int head_dim, int causal,
                                int temporal_layout, int N_tokens, int compute, void* workspace, size_t workspace_bytes,
                                sf_stream stream) {
@@ -153,27 +199,10 @@ extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, 
   if (workspace_bytes < sf_op_attention_workspace_bytes(groups, L, heads, head_dim)) return sf_set_err(SF_ERR_WORKSPACE, "workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const bool acc = compute == SF_COMPUTE_BF16X3;
-  const int D = heads * head_dim;
   const size_t rows = (size_t)groups * L;
-  SfCarver c(workspace, acc, true);      // ctx: hi + lo bytes in both modes, the lo plane handed out in the accurate mode
-  const SfPlanes cp = c.planes(rows * D);
-  bf16_t* qb = c.take<bf16_t>(rows * 3 * D);
-  const void* base = qkv;
-  size_t esz = 4;
-  const bool planes = acc && head_dim == 64 && (temporal_layout ? sf_temporal_planes_ok(L, L) : sf_spatial_planes_ok(L, false));
-  bf16_t* ql = nullptr;
-  if (!acc || planes) {
-    if (planes) ql = c.lo(rows * 3 * D);      // (planes: accurate mode only)
-    HIP_TRY(sf_launch_split(qkv, qb, ql, rows * 3 * D, s));
-    base = qb;
-    esz = 2;
-  }
-  SfAttnArgs a;
-  memset(&a, 0, sizeof(a));
-  a.q = base; a.k = (const char*)base + (size_t)D * esz; a.v = (const char*)base + (size_t)2 * D * esz;
-  a.in_is_f32 = acc && !planes; a.lo_plane_off = planes ? (long long)(ql - qb) : 0;
-  a.row_pitch_q = 3 * D; a.row_pitch_kv = 3 * D; a.heads = heads; a.scale = 1.0f / sqrtf((float)head_dim);
-  a.ctx_hi = cp.hi; a.ctx_lo = cp.lo; a.D = D; a.head_dim = head_dim;
+  const OpAttn o = op_attention_args(qkv, workspace, groups, L, heads, head_dim, acc, temporal_layout != 0, false);
+  if (o.split) HIP_TRY(sf_launch_split(qkv, o.qb, o.ql, rows * 3 * o.a.D, s));
+  SfAttnArgs a = o.a;
   if (temporal_layout) {
     // rows are [B, L, N_tokens, 3D] with groups = B * N_tokens sequences of length L
     if (N_tokens <= 0 || groups % N_tokens) return sf_set_err(SF_ERR_INVALID, "groups must be a multiple of N_tokens");
@@ -185,7 +214,7 @@ extern "C" int sf_op_attention(const float* qkv, float* ctx, int groups, int L, 
     a.N = L; a.frames = groups;
     HIP_TRY(sf_launch_spatial_attention(a, acc, s));
   }
-  HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, cp.hi, cp.lo, ctx, rows * D));
+  HIP_TRY(sf_launch(sf_combine_kernel, dim3(1024), dim3(256), 0, s, a.ctx_hi, a.ctx_lo, ctx, rows * a.D));
   return SF_OK;
 }
 

@@ -269,6 +269,81 @@ def test_compile_time_tile_count_is_bit_identical(sa):
     assert digests[0] == digests[1], digests
 
 
+def test_spatial_attention_plan_is_pinned(sa, switches):
+    """Which spatial kernel a call takes, how many workgroups share a (frame, head) problem and how much LDS the launch asks for:
+    sf_op_spatial_attention_plan answers without launching.  The numeric tests pass whichever kernel runs; this table keeps the
+    dispatch (csrc/sf_attention_spatial.hip, sf_spatial_plan) where it is."""
+    import ctypes
+    lib = sa._native.lib
+    (NONE, GENERIC, LARGE_BF16, LARGE_ACC, DMA_BF16, DMA_BF16_NT13, DMA_DROP, DMA_PLANES, DMA_PLANES_NT13, STAGED_BF16,
+     STAGED_ACC) = range(11)
+
+    def plan(N, mode=0, frames_=8, heads=12, head_dim=64, probs=0, dropout=0.0):
+        r, q, l = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_size_t(0)
+        sa._native.check(lib.sf_op_spatial_attention_plan(frames_, N, heads, head_dim, mode, probs, dropout, ctypes.byref(r),
+                                                          ctypes.byref(q), ctypes.byref(l)))
+        return r.value, q.value, l.value
+
+    def lds(route, N):
+        nkp = (N + 31) & ~31
+        if route in (DMA_BF16, DMA_BF16_NT13, DMA_DROP):
+            return nkp * 256 + 8 * 2048
+        if route in (DMA_PLANES, DMA_PLANES_NT13):
+            return nkp * 512 + 8 * 4096
+        if route in (STAGED_BF16, STAGED_ACC):
+            return (nkp * 128 + 64 * ((2 * nkp + 255) & ~255) + 8 * 2048) * (2 if route == STAGED_ACC else 1)
+        if route in (LARGE_BF16, LARGE_ACC):
+            return (128 * 128 + 64 * 2 * 128 + 8 * 2048) * (2 if route == LARGE_ACC else 1)
+        return 0
+
+    def check(want, N, **kw):
+        route, _, got_lds = plan(N, **kw)
+        assert route == want, (N, kw, route, want)
+        assert got_lds == lds(want, N), (N, kw, got_lds)
+
+    check(DMA_BF16_NT13, 196)
+    check(DMA_PLANES_NT13, 196, mode=1)
+    for N, bf16, acc in ((193, DMA_BF16_NT13, DMA_PLANES_NT13), (208, DMA_BF16_NT13, DMA_PLANES_NT13),      # both edges of the 13-tile instance
+                         (192, DMA_BF16, DMA_PLANES), (209, DMA_BF16, DMA_PLANES), (9, DMA_BF16, DMA_PLANES),
+                         (224, DMA_BF16, DMA_PLANES), (225, LARGE_BF16, LARGE_ACC)):
+        check(bf16, N)
+        check(acc, N, mode=1)
+    assert plan(225)[1] == 2 and plan(1024)[1] == 8           # N > 224: one workgroup per 128 queries
+    check(STAGED_BF16, 196, probs=1)
+    check(STAGED_ACC, 196, mode=1, probs=1)
+    assert plan(196, frames_=1, probs=1)[1] == 1              # the probabilities leave from one workgroup per problem
+    check(GENERIC, 196, head_dim=72, heads=16)
+    check(GENERIC, 196, head_dim=72, heads=16, mode=1)
+    check(DMA_DROP, 196, dropout=0.1)
+    check(NONE, 196, mode=1, dropout=0.1)
+    check(NONE, 225, dropout=0.1)
+    check(NONE, 196, probs=1, dropout=0.1)
+
+    # few problems: the query tiles of each are split over several workgroups
+    for frames_, heads, want in ((1, 12, 7), (4, 12, 4), (8, 12, 2), (128, 12, 1)):
+        for mode in (0, 1):
+            assert plan(196, mode=mode, frames_=frames_, heads=heads)[1] == want, (frames_, heads, mode)
+    for frames_ in (1, 4, 8, 128):
+        assert plan(16, frames_=frames_)[1] == 1
+    switches("SF_SPATIAL_TPW", 13)
+    assert plan(196, frames_=1)[1] == 1
+    switches("SF_SPATIAL_TPW", 2)
+    assert plan(196, frames_=128)[1] == 7
+
+    switches("SF_DISABLE_SPATIAL_NTC")
+    check(DMA_BF16, 196)
+    check(DMA_PLANES, 196, mode=1)
+    switches("SF_DISABLE_SPATIAL_DMA")
+    check(STAGED_BF16, 196)
+    check(STAGED_BF16, 9)
+    check(DMA_PLANES, 196, mode=1)                            # the planes form has its own switch
+    check(NONE, 196, dropout=0.1)                             # dropout lives in the DMA kernel only
+    switches("SF_DISABLE_SPATIAL_DMA_ACC")
+    check(STAGED_ACC, 196, mode=1)
+    check(STAGED_ACC, 9, mode=1)
+    check(LARGE_ACC, 225, mode=1)
+
+
 def _spatial_attention_case(sa, frames_, N, heads, mode, head_dim=64):
     g = torch.Generator().manual_seed(N * 13 + heads)
     qkv = torch.randn(frames_, N, 3 * heads * head_dim, generator=g) * 1.5

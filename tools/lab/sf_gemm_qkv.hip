@@ -47,7 +47,7 @@ SF_DEVICE void q_wait_vm() {
 SF_DEVICE bf16x8_t q_rd32(const char* piece, int row, int kc) {
   return *reinterpret_cast<const bf16x8_t*>(piece + row * 64 + ((kc ^ sf_swz64(row)) << 4));
 }
-// head-block swizzle (same as sf_attention.hip): row fragments of 16 rows and the 8 rows of a half-wave transposed read are conflict-free
+// head-block swizzle (the rounds 2-5 swizzle of csrc/sf_attn_image.h, SF_ATTN_SWZ_LEGACY): row fragments of 16 rows and the 8 rows of a half-wave transposed read are conflict-free
 SF_DEVICE int q_bswz(int row) { return (((row >> 1) & 3) << 1) | ((row >> 3) & 1); }
 SF_DEVICE int q_img_off(int row, int chunk) { return row * 128 + ((chunk ^ q_bswz(row)) << 4); }
 SF_DEVICE bf16x8_t q_row_frag(const char* img, int row, int chunk) {

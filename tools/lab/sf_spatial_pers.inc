@@ -1,5 +1,14 @@
+// Round 4: the same (frame, head) problem on a PERSISTENT workgroup with explicit double buffering.  The kernel above leaves
+// the overlap of one problem's K / V load with another's arithmetic to two independent workgroups per CU that start in
+// phase (0.43 of the HBM roofline at 8 clips: each problem pays its own load latency).  Here one workgroup of 16 waves walks
+// its problems p = blockIdx.x, + gridDim.x, ... with TWO K / V image pairs in LDS: the LDS-DMA of problem i + 1 and the Q
+// fragment loads of its tile are issued before the arithmetic of problem i starts, so a problem costs max(load, compute).
+// A wave owns ONE 16-query tile (13 of 16 waves busy at 196 tokens; all 16 issue the DMA pieces).  Two barriers per problem:
+// A = every wave's pieces of problem i have landed (counted vmcnt: the pieces of problem i + 1 stay in flight), B = every
+// wave has finished reading image i & 1 before the pieces of problem i + 2 may overwrite it.
+// bf16 mode, N <= 224, no probabilities; the tile arithmetic is the one of sf_spatial_attn_dma_kernel.
 // Persistent, double-buffered spatial attention (round 4, VERDICT r3 item 5): bit-identical to the product kernel, 76-79 us against
-// 43-44 us (profiles/r04_spatial_pers_lab.txt).  Lab library only: included by sf_attention.hip under -DSF_LAB (build.py --lab).
+// 43-44 us (profiles/r04_spatial_pers_lab.txt).  Lab library only: included by sf_attention_spatial.hip under -DSF_LAB (build.py --lab).
 #define SPP_WAVES 8
 #define SPP_QT 2       // query tiles per wave (16 x 8 x 2 = 256 >= 224 queries)
 template <int MAXNT>
@@ -28,11 +37,11 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void sf_spatial_attn_pers_kernel(Sf
     char* v_img = k_img + nkp * 128;
     for (int j = wave; j < nrg; j += SPP_WAVES) {
       const int row = j * 8 + (lane >> 3);
-      const int chunk = (lane & 7) ^ sp_bswz(row);
+      const int chunk = img_dma_chunk(lane, row);
       const int key = row < N ? row : N - 1;
       const size_t src = (row0 + key) * (size_t)p.row_pitch_kv + chunk * 8;
-      __builtin_amdgcn_global_load_lds((sp_gptr_t)(kbase + src), (sp_lptr_t)(k_img + j * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((sp_gptr_t)(vbase + src), (sp_lptr_t)(v_img + j * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((dma_gptr_t)(kbase + src), (dma_lptr_t)(k_img + j * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((dma_gptr_t)(vbase + src), (dma_lptr_t)(v_img + j * 1024), 16, 0, 0);
     }
 #pragma unroll
     for (int u = 0; u < SPP_QT; ++u) {
@@ -53,7 +62,7 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void sf_spatial_attn_pers_kernel(Sf
   auto tr_issue = [&](const char* img, int r0, int et, s16x4_t& lo, s16x4_t& hi) {
     const int t16 = lane & 15;
     const int row = r0 + 4 * g + (t16 >> 2);
-    const unsigned off = (unsigned)(size_t)(img - smem) + sp_img_off(row, 2 * et + ((t16 & 3) >> 1)) + ((t16 & 1) << 3);
+    const unsigned off = (unsigned)(size_t)(img - smem) + img_off(row, 2 * et + ((t16 & 3) >> 1)) + ((t16 & 1) << 3);
     asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(off) : "memory");
     asm volatile("ds_read_b64_tr_b16 %0, %1 offset:2048" : "=v"(hi) : "v"(off) : "memory");
   };
@@ -74,7 +83,7 @@ __global__ __launch_bounds__(SPP_WAVES * 64) void sf_spatial_attn_pers_kernel(Sf
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         if (jt * 16 < N) {
 #pragma unroll
-          for (int ks = 0; ks < 2; ++ks) acc = mfma16(sp_row_frag(k_img, jt * 16 + l15, ks * 4 + g), qh[u][ks], acc);
+          for (int ks = 0; ks < 2; ++ks) acc = mfma16(row_frag(k_img, jt * 16 + l15, ks * 4 + g), qh[u][ks], acc);
         }
         s[jt] = acc;
       }
