@@ -697,7 +697,8 @@ int sf_op_adapter_fuse(int level, const float* tokens_dev, long long tokens_fram
  * embedding), FPN levels (lateral 1 x 1, bilinear upsample + add, 3 x 3, GroupNorm, ReLU) for the finer ones and the 1 x 1 mask_features
  * convolution.  Same protocol as the connector: create (the width rules are checked there, the field named), stage the weights under
  * the reference's state-dict names (a leading "sem_seg_head.pixel_decoder." is dropped), finalize in a compute mode (weights rounded /
- * split once; the convolution weights re-laid out for the GEMMs there).  Inference only, no padding masks.  Kernels: csrc/sf_pixdec.hip. */
+ * split once; the convolution weights re-laid out for the GEMMs there).  The handle is inference only (training runs on the Python
+ * module's autograd graph and the two backward entries below), no padding masks.  Kernels: csrc/sf_pixdec.hip, csrc/sf_pixdec_bwd.hip. */
 typedef struct sf_pixdec sf_pixdec;
 #define SF_PIXDEC_MAX_LEVELS 4
 #define SF_PIXDEC_NORM_GN 0
@@ -761,6 +762,22 @@ size_t sf_op_pixdec_conv3x3_workspace_bytes(int F, int H, int W, int C, int chun
 int sf_op_pixdec_conv3x3(const uint16_t* in_hi_dev, const uint16_t* in_lo_dev, const uint16_t* w_hi_dev, const uint16_t* w_lo_dev, int F,
                          int H, int W, int C, int N, int chunk_rows, float* out_dev, void* workspace_dev, size_t workspace_bytes,
                          sf_stream stream);
+/* GroupNorm's backward for training (streamformer_amd/pixel_decoder.py with trainable=True; csrc/sf_pixdec_bwd.hip).  x_dev, dy_dev and
+ * dx_dev are rows [F, H W, C]; stats_dev is what sf_op_pixdec_groupnorm wrote for x_dev and is not recomputed; relu as in that call (the
+ * gradient is zeroed where the forward clipped, decided by the forward's own expression).  Outputs, any subset (not none): dx_dev,
+ * dgamma_dev [C], dbeta_dev [C]; each equals what the joint call writes, bit for bit.  A workgroup sums a span of whole pixel rows of one
+ * frame, the spans (a function of F and H W alone) are added in ascending order by a second launch: no atomics, bit-reproducible.  The
+ * caller's stream, no allocation, no host synchronisation.  Refused before anything is launched: a NULL or not 16-byte aligned buffer,
+ * C no positive multiple of 64, F outside 1..65535, H or W < 1 (SF_ERR_INVALID), more than 2^31 - 1 elements (SF_ERR_CAPACITY), a short
+ * workspace (SF_ERR_WORKSPACE; 256-byte aligned).                                                                                    */
+size_t sf_op_pixdec_groupnorm_backward_workspace_bytes(int F, int H, int W, int C);
+int sf_op_pixdec_groupnorm_backward(const float* x_dev, const float* stats_dev, const float* gamma_dev, const float* beta_dev, int relu,
+                                    const float* dy_dev, float* dx_dev, float* dgamma_dev, float* dbeta_dev, int F, int H, int W, int C,
+                                    void* workspace_dev, size_t workspace_bytes, sf_stream stream);
+/* The adjoint of sf_op_pixdec_groupnorm's `+ bilinear upsample of prev_dev`: d_prev_dev rows [F, Hp Wp, C] from dy_dev rows [F, H W, C],
+ * at any ratio.  Gather form: each coarse pixel adds the fine pixels whose taps land on it in ascending (y, x) order; no atomics,
+ * bit-reproducible.  The same refusals (no workspace).                                                                               */
+int sf_op_pixdec_upsample_backward(const float* dy_dev, float* d_prev_dev, int F, int H, int W, int Hp, int Wp, int C, sf_stream stream);
 
 /* ---- Mask2Former masked-attention decoder: queries -> class logits, masks, re-identification embeddings ----------------------------
  * The reference's MultiScaleMaskedTransformerDecoder (downstream/OVIS/mask2former/modeling/transformer_decoder/

@@ -235,6 +235,9 @@ SIGNATURES = {
     "sf_op_pixdec_im2col": (_I, [_P, _P, _I, _I, _I, _I, C.c_longlong, _I, _P, _P, _P]),
     "sf_op_pixdec_conv3x3_workspace_bytes": (_SZ, [_I, _I, _I, _I, _I]),
     "sf_op_pixdec_conv3x3": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    "sf_op_pixdec_groupnorm_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_pixdec_groupnorm_backward": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
+    "sf_op_pixdec_upsample_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "sf_maskdec_create": (_I, [C.POINTER(SfMaskdecConfig), _I, C.POINTER(_P)]),
     "sf_maskdec_destroy": (None, [_P]),
     "sf_maskdec_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),

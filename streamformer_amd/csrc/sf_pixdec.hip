@@ -34,13 +34,9 @@
 //
 // The 3 x 3 convolution is that gather followed by ONE GEMM with K = 9 C, in chunks of im2col_chunk_rows pixels so that the gathered
 // planes stay bounded (SfGemmArgs has no A row pitch; a chunk is a contiguous [rows, 9 C] operand).
-#include "sf_handle.h"
-#include "sf_nchw_tile.h"
+#include "sf_pixdec.h"
 
-#define PXD_THREADS 256
 #define PXD_MAX_LEVELS 4
-#define PXD_GROUPS 32
-#define PXD_GN_EPS 1e-5f
 #define PXD_LN_EPS 1e-5f
 #define PXD_DEFAULT_CHUNK_ROWS 16384
 
@@ -150,12 +146,6 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_stats_kernel(SfPxdGn
   }
 }
 
-SF_DEVICE void pxd_load8(const float* q, float v[8]) {
-  const f32x4_t a = *reinterpret_cast<const f32x4_t*>(q), b = *reinterpret_cast<const f32x4_t*>(q + 4);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[4 + j] = b[j]; }
-}
-
 __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn p) {
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < p.total; i += gridDim.x * blockDim.x) {
     const unsigned r = i / (unsigned)p.C8;
@@ -168,7 +158,7 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float* st = p.stats + ((size_t)f * p.G + (c + j) / p.cg) * 4;
-      v[j] = ((v[j] - st[0]) - st[1]) * st[2] * gm[j] + bt[j];      // (x - shift) - (mean - shift): the mean itself is never rounded
+      v[j] = pxd_gn_value(v[j], st, gm[j], bt[j]);
       if (p.relu) v[j] = fmaxf(v[j], 0.f);
     }
     if (p.prev) {
@@ -201,13 +191,7 @@ __global__ __launch_bounds__(PXD_THREADS) void sf_pixdec_gn_apply_kernel(SfPxdGn
   }
 }
 
-static unsigned pxd_stream_grid(unsigned total, unsigned* block) {
-  *block = total < 65536u ? 64u : 256u;
-  const unsigned grid = (total + *block - 1) / *block;
-  return grid > 2048u ? 2048u : (grid ? grid : 1u);
-}
-
-// x, gamma, beta, prev, pos and every output 16-byte aligned, C % (8 * G / gcd) ...: checked by the callers (pxd_gn_check)
+// x, gamma, beta, prev, pos and every output 16-byte aligned, C % (8 * G / gcd) ...: checked by the callers (pxd_gn_check, sf_pixdec.h)
 static hipError_t pxd_launch_groupnorm(const SfPxdGn& q, hipStream_t s) {
   SfPxdGn p = q;
   p.HW = p.H * p.W; p.G = PXD_GROUPS; p.cg = p.C / PXD_GROUPS; p.C8 = p.C / 8; p.eps = PXD_GN_EPS;
@@ -218,13 +202,6 @@ static hipError_t pxd_launch_groupnorm(const SfPxdGn& q, hipStream_t s) {
   unsigned block;
   const unsigned grid = pxd_stream_grid(p.total, &block);
   return sf_launch(sf_pixdec_gn_apply_kernel, dim3(grid), dim3(block), 0, s, p);
-}
-
-static int pxd_gn_check(const char* who, int F, int H, int W, int C) {
-  if (F < 1 || F > 65535 || H < 1 || W < 1) return sf_set_err(SF_ERR_INVALID, "%s: F = %d (1..65535), H = %d, W = %d", who, F, H, W);
-  if (C < 64 || C % 64) return sf_set_err(SF_ERR_INVALID, "%s: C = %d must be a positive multiple of 64 (GroupNorm(32, C) in 16-byte vectors)", who, C);
-  if ((long long)F * H * W * C > 0x7fffffffLL) return sf_set_err(SF_ERR_CAPACITY, "%s: %d frames of %d x %d x %d exceed 2^31 - 1 elements", who, F, H, W, C);
-  return SF_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -5,12 +5,20 @@ of ``adapter.py``'s pyramid and of ``msda.py``'s operator in every shipped OVIS 
 constructor, parameter tree, state-dict keys and initialisation, so ``load_state_dict(strict=True)`` of the
 ``sem_seg_head.pixel_decoder.*`` slice of a CTVIS checkpoint works (the prefix is accepted and dropped); detectron2's ``Conv2d(norm=...)``
 is restated as ``ConvNorm`` (``adapter_1.weight``, ``adapter_1.norm.weight``).  The forward runs in ``libstreamformer_hip.so``
-(``sf_pixdec_forward``, kernels in ``csrc/sf_pixdec.hip``): inference only, no padding masks, no CPU fallback.
+(``sf_pixdec_forward``, kernels in ``csrc/sf_pixdec.hip``): no padding masks, no CPU fallback.
 
     dec = MSDeformAttnPixelDecoder({"res2": ShapeSpec(768, 4), ...}, transformer_dropout=0.0, transformer_nheads=8,
                                    transformer_dim_feedforward=1024, transformer_enc_layers=6, conv_dim=256, mask_dim=256, norm="GN",
                                    transformer_in_features=["res3", "res4", "res5"], common_stride=4).cuda().eval()
     mask_features, transformer_encoder_features, multi_scale_features = dec.forward_features(pyramid)
+
+Training is an opt-in: ``trainable=True`` (constructor keyword or attribute, fp32 only) makes ``.train()`` run an autograd graph on the
+module's own parameters instead of the refusal.  The graph stays in the rows layout [F, H W, C]: the 1 x 1 convolutions are ``F.linear``,
+the 3 x 3 convolution is ``F.conv2d`` on the channels-last view of the rows, every GroupNorm (plain, with ReLU, with the FPN's
+upsample-and-add) is one ``autograd.Function`` on ``sf_op_pixdec_groupnorm`` and its two backward entries (``csrc/sf_pixdec_bwd.hip``),
+the sine table and the reference points are constants from ``sf_op_pixdec_pos_ref``, and each encoder layer calls its ``MSDeformAttn``
+child (torch Linears around ``MSDeformAttnFunction``).  ``.eval()`` is the same native path either way; without the opt-in ``.train()``
+is refused as before.
 """
 from __future__ import annotations
 
@@ -20,7 +28,10 @@ from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
+import torch.nn.functional as TF
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .msda import MSDeformAttn
@@ -88,12 +99,71 @@ class _EncoderOnly(nn.Module):
         nn.init.normal_(self.level_embed)
 
 
+class _GroupNormFunction(Function):
+    """GroupNorm(32, C) of rows ``x`` [F, H W, C] [+ ReLU] [+ the bilinear upsample of ``prev`` rows [F, Hp Wp, C]] on the HIP kernels.
+    Saves ``x``, the statistics the forward wrote and the two parameters; not ``y``."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, relu, size, prev, prev_size):
+        Fr, HW, Cd = x.shape
+        H, W = size
+        Hp, Wp = prev_size if prev is not None else (0, 0)
+        x, gamma, beta = x.contiguous(), gamma.contiguous(), beta.contiguous()
+        prev_c = prev.contiguous() if prev is not None else None
+        stats = torch.empty(Fr, 32, 4, device=x.device, dtype=torch.float32)
+        y = torch.empty_like(x)
+        nat.launch(x.device, nat.lib.sf_op_pixdec_groupnorm, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(relu), nat.ptr(prev_c), Hp, Wp, None,
+                   stats.data_ptr(), y.data_ptr(), None, None, None, None, Fr, H, W, Cd)
+        ctx.save_for_backward(x, stats, gamma, beta)
+        ctx.meta = (bool(relu), H, W, Hp, Wp, prev is not None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, stats, gamma, beta = ctx.saved_tensors
+        relu, H, W, Hp, Wp, has_prev = ctx.meta
+        Fr, _, Cd = x.shape
+        dev = x.device
+        dy = dy.float().contiguous()
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        dx = torch.empty_like(x) if need_x else None
+        dg = torch.empty_like(gamma) if need_g else None
+        db = torch.empty_like(beta) if need_b else None
+        if need_x or need_g or need_b:
+            ws = nat.scratch(nat.lib.sf_op_pixdec_groupnorm_backward_workspace_bytes(Fr, H, W, Cd), dev)
+            nat.launch(dev, nat.lib.sf_op_pixdec_groupnorm_backward, x.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(relu),
+                       dy.data_ptr(), nat.ptr(dx), nat.ptr(dg), nat.ptr(db), Fr, H, W, Cd, workspace=ws)
+        d_prev = None
+        if has_prev and ctx.needs_input_grad[5]:
+            d_prev = torch.empty(Fr, Hp * Wp, Cd, device=dev, dtype=torch.float32)
+            nat.launch(dev, nat.lib.sf_op_pixdec_upsample_backward, dy.data_ptr(), d_prev.data_ptr(), Fr, H, W, Hp, Wp, Cd)
+        return dx, dg, db, None, None, d_prev, None
+
+
+def _rows(x: torch.Tensor) -> torch.Tensor:
+    """NCHW -> rows [F, H W, C], a view."""
+    return x.flatten(2).transpose(1, 2)
+
+
+def _nchw(rows: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    return rows.transpose(1, 2).reshape(rows.shape[0], rows.shape[2], H, W)
+
+
 class MSDeformAttnPixelDecoder(nn.Module):
+    """The reference's constructor plus ``compute_dtype`` ("fp32": bf16x3 operands, fp32-accurate; "bf16"), ``im2col_chunk_rows`` (pixels
+    per gathered 3 x 3 operand, 0: the library's default) and ``trainable`` (also an attribute): with it ``.train()`` runs the autograd
+    path of the module header (fp32 only, ``transformer_dropout`` must be 0), without it ``.train()`` is refused.  ``.eval()`` is the
+    native forward in both cases."""
+
     def __init__(self, input_shape: Dict[str, Any], *, transformer_dropout: float, transformer_nheads: int, transformer_dim_feedforward: int,
                  transformer_enc_layers: int, conv_dim: int, mask_dim: int, norm: Any = None, transformer_in_features: List[str],
-                 common_stride: int, compute_dtype: Any = "fp32", im2col_chunk_rows: int = 0):
+                 common_stride: int, compute_dtype: Any = "fp32", im2col_chunk_rows: int = 0, trainable: bool = False):
         super().__init__()
         self._compute = nat.compute_mode(compute_dtype)
+        self.compute_dtype = compute_dtype
+        self._trainable = False
+        self.trainable = trainable
         if norm != "GN":
             raise NotImplementedError(f"norm {norm!r}: only norm=\"GN\" (GroupNorm(32, conv_dim)) runs natively")
         shapes = sorted(input_shape.items(), key=lambda kv: kv[1].stride)
@@ -121,9 +191,8 @@ class MSDeformAttnPixelDecoder(nn.Module):
             raise ValueError(f"mask_dim = {mask_dim} must be a positive multiple of 4")
         self.conv_dim, self.mask_dim, self.common_stride = int(conv_dim), int(mask_dim), int(common_stride)
         self.nheads, self.dim_feedforward, self.enc_layers = int(transformer_nheads), int(transformer_dim_feedforward), int(transformer_enc_layers)
-        self.transformer_dropout = float(transformer_dropout)            # inference only: never applied
+        self.transformer_dropout = float(transformer_dropout)            # never applied: the training path refuses a non-zero value
         self.im2col_chunk_rows = int(im2col_chunk_rows)
-        self.compute_dtype = compute_dtype
         self.maskformer_num_feature_levels = 3
         self.num_fpn_levels = int(math.log2(min(self.transformer_feature_strides)) - math.log2(self.common_stride))
         nat.OwnedHandle.release(self._create(0, nat.OwnedHandle(nat.lib.sf_pixdec_destroy, "pixel decoder probe")))      # the library's own rules, before any weight exists
@@ -183,13 +252,36 @@ class MSDeformAttnPixelDecoder(nn.Module):
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
     # ------------------------------------------------------------------------------------ forward
-    @torch.no_grad()
+    @property
+    def trainable(self) -> bool:
+        """Whether ``.train()`` runs the autograd path (fp32 only) instead of refusing."""
+        return self._trainable
+
+    @trainable.setter
+    def trainable(self, value: bool) -> None:
+        if value and self._compute != nat.compute_mode("fp32"):
+            raise ValueError(f"trainable=True needs compute_dtype='fp32', got compute_dtype={self.compute_dtype!r} (there is no bf16 training mode)")
+        self._trainable = bool(value)
+
     def forward_features(self, features: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, List[torch.Tensor]]:
         """``features``: name -> fp32 (F, C_l, H_l, W_l) on the GPU.  Returns ``(mask_features, transformer_encoder_features,
         multi_scale_features)`` exactly as the reference's ``forward_features``: (F, mask_dim, H, W) of the finest level, the coarsest
-        transformer level, and the first three entries of its ``out`` list."""
+        transformer level, and the first three entries of its ``out`` list.
+
+        In ``.train()`` with ``trainable=True`` the three are differentiable in the module's parameters and in every level of
+        ``features`` the decoder reads."""
+        if self.training and not self._trainable:
+            raise RuntimeError("the native pixel decoder is inference only: call .eval(), or opt in to the autograd path with trainable=True")
         if self.training:
-            raise RuntimeError("the native pixel decoder is inference only: call .eval() (training and gradients through it are not part of it)")
+            if self.transformer_dropout > 0:
+                raise NotImplementedError(f"transformer_dropout = {self.transformer_dropout}: the training path applies no dropout (the shipped "
+                                          "configs train with DROPOUT 0.0)")
+            return self._forward_train(self._checked(features))
+        with torch.no_grad():
+            return self._forward_eval(self._checked(features))
+
+    def _checked(self, features: Dict[str, torch.Tensor]) -> List[Optional[torch.Tensor]]:
+        """Per input level the fp32 contiguous feature map on the module's device, None for a level the decoder does not read."""
         used = [k for i, k in enumerate(self.in_features) if k in self.transformer_in_features or i < self.num_fpn_levels]
         xs: List[Optional[torch.Tensor]] = []
         dev = self.device
@@ -204,9 +296,55 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 raise ValueError(f"features[{k!r}] must be (F, {ch}, H, W), got {tuple(x.shape)}")
             xs.append(x.to(device=dev, dtype=torch.float32).contiguous())
         live = [x for x in xs if x is not None]
-        F = live[0].shape[0]
-        if any(x.shape[0] != F for x in live):
+        if any(x.shape[0] != live[0].shape[0] for x in live):
             raise ValueError("the levels of `features` hold different numbers of frames")
+        return xs
+
+    def _forward_train(self, xs: List[Optional[torch.Tensor]]) -> Tuple[torch.Tensor, torch.Tensor, List[torch.Tensor]]:
+        dev = self.device
+        Cd = self.conv_dim
+        F = next(x for x in xs if x is not None).shape[0]
+        tr = [i for i in range(len(xs) - 1, -1, -1) if self.in_features[i] in self.transformer_in_features]      # coarsest first
+        L = len(tr)
+        shapes = [tuple(xs[i].shape[2:]) for i in tr]
+        starts = [sum(h * w for h, w in shapes[:j]) for j in range(L)]
+        S = sum(h * w for h, w in shapes)
+
+        def group_norm(rows, norm: nn.GroupNorm, size, relu=False, prev=None, prev_size=None):
+            return _GroupNormFunction.apply(rows, norm.weight, norm.bias, relu, size, prev, prev_size)
+
+        # the sine table and the reference points: constants, formed in fp64 and rounded once by the kernel (a zero level_embed)
+        table = torch.empty(S, Cd, device=dev, dtype=torch.float32)
+        ref = torch.empty(F, S, L, 2, device=dev, dtype=torch.float32)
+        no_embed = torch.zeros(L, Cd, device=dev, dtype=torch.float32)      # level_embed[l] is added below, in torch, for its gradient
+        nat.launch(dev, nat.lib.sf_op_pixdec_pos_ref, no_embed.data_ptr(), nat.i32_array([d for s in shapes for d in s]), L, F, Cd, table.data_ptr(),
+                   ref.data_ptr())
+        srcs, poss = [], []
+        for j, l in enumerate(tr):
+            conv, norm = self.input_proj[j][0], self.input_proj[j][1]
+            srcs.append(group_norm(TF.linear(_rows(xs[l]), conv.weight.flatten(1), conv.bias), norm, shapes[j]))
+            poss.append(table[starts[j]:starts[j] + shapes[j][0] * shapes[j][1]] + self.transformer.level_embed[j])
+        src, pos = torch.cat(srcs, 1), torch.cat(poss, 0)
+        for layer in self.transformer.encoder.layers:
+            src = layer.norm1(src + layer.self_attn(src + pos, ref, src, shapes, starts))
+            src = layer.norm2(src + layer.linear2(torch.relu(layer.linear1(src))))
+        out = [(src[:, starts[j]:starts[j] + h * w], (h, w)) for j, (h, w) in enumerate(shapes)]
+        for k in range(self.num_fpn_levels - 1, -1, -1):
+            lateral, output = getattr(self, f"adapter_{k + 1}"), getattr(self, f"layer_{k + 1}")
+            H, W = xs[k].shape[2:]
+            prev, prev_size = out[-1]
+            y = group_norm(TF.linear(_rows(xs[k]), lateral.weight.flatten(1)), lateral.norm, (H, W), prev=prev, prev_size=prev_size)
+            y = TF.conv2d(y.view(F, H, W, Cd).permute(0, 3, 1, 2), output.weight, None, 1, 1)      # the rows ARE the channels-last image
+            y = y.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(F, H * W, Cd)
+            out.append((group_norm(y, output.norm, (H, W), relu=True), (H, W)))
+        rows, (H, W) = out[-1]
+        mask = _nchw(TF.linear(rows, self.mask_features.weight.flatten(1), self.mask_features.bias), H, W).contiguous()
+        ms = [_nchw(r, h, w).contiguous() for r, (h, w) in out[:self.maskformer_num_feature_levels]]
+        return mask, ms[0], ms
+
+    def _forward_eval(self, xs: List[Optional[torch.Tensor]]) -> Tuple[torch.Tensor, torch.Tensor, List[torch.Tensor]]:
+        dev = self.device
+        F = next(x for x in xs if x is not None).shape[0]
         h = self._handle()
         n = len(xs)
         shapes = nat.i32_array([d for x in xs for d in ((x.shape[2], x.shape[3]) if x is not None else (1, 1))])
