@@ -691,6 +691,29 @@ int sf_op_adapter_dwconv_gelu(const float* x_dev, const float* w_dev, const floa
 int sf_op_adapter_fuse(int level, const float* tokens_dev, long long tokens_frame_stride, const float* vit_dev, const float* c1_dev,
                        const float* scale_dev, const float* shift_dev, float* out_dev, int F, int H, int W, int D, sf_stream stream);
 
+/* The two backward entries of the adapter's training path (streamformer_amd/adapter.py with trainable=True; csrc/sf_adapter_bwd.hip).
+ * Backward of sf_op_adapter_dwconv_gelu: x_dev is the forward's input (z = dwconv(x) + b is recomputed, y is not needed), dy_dev the
+ * gradient of its output, both [F, 21 * (H/2 * W/2), C].  Outputs, any subset (not none): dx_dev like x_dev, dw_dev [C, 3, 3], db_dev [C];
+ * an output that is not asked for stays unwritten and each equals what the joint call writes, bit for bit.  g = dy gelu'(z) (the exact
+ * derivative of the erf form) goes to the workspace; a workgroup keeps the sums of dw and db over its strip of tokens and writes one
+ * partial row, the rows are added in ascending order by a second launch, dx is a gather over the token's own level grid: no atomics,
+ * bit-reproducible, three launches at most, the caller's stream, no allocation.  The workspace is the g tensor rounded up to 256 bytes
+ * followed by one row of 10 C floats per workgroup (a function of F, H, W, C alone).  Refused before anything is launched: a NULL
+ * buffer, F < 1, H or W odd or < 2, C no multiple of 4 in 4..1024, x, b, dy or dx not 16-byte aligned, dx aliasing x or dy
+ * (SF_ERR_INVALID), more than 2^31 - 1 elements (SF_ERR_CAPACITY; the sizer then returns 0), a short workspace (SF_ERR_WORKSPACE;
+ * 256-byte aligned).                                                                                                                  */
+size_t sf_op_adapter_dwconv_gelu_backward_workspace_bytes(int F, int H, int W, int C);
+int sf_op_adapter_dwconv_gelu_backward(const float* x_dev, const float* w_dev, const float* b_dev, const float* dy_dev, float* dx_dev,
+                                       float* dw_dev, float* db_dev, int F, int H, int W, int C, void* workspace_dev, size_t workspace_bytes,
+                                       sf_stream stream);
+/* The adjoint of sf_op_adapter_fuse in its token operand, a re-layout: dy_dev fp32 NCHW [F, D, Ho, Wo] of level 0..3 -> d_tokens_dev in
+ * the layout sf_op_adapter_fuse reads its tokens in (levels 1..3: rows of D floats, frame f at d_tokens_dev + f * tokens_frame_stride
+ * floats, so a level's slice of a [F, 21 n, D] tensor can be the target and the other slices stay untouched; level 0: [F, 2H * 2W, 4 D]
+ * through the inverse 2 x 2 pixel shuffle).  Every output element is written exactly once.  The ViT term is constant under a frozen
+ * backbone and c1's gradient is dy itself.  The refusals of sf_op_adapter_fuse; d_tokens_dev 16-byte aligned.                        */
+int sf_op_adapter_fuse_backward(int level, const float* dy_dev, float* d_tokens_dev, long long tokens_frame_stride, int F, int H, int W, int D,
+                                sf_stream stream);
+
 /* ---- Mask2Former pixel decoder: mask features and multi-scale features from res2..res5 -------------------------------------------
  * The reference's MSDeformAttnPixelDecoder (downstream/OVIS/mask2former/modeling/pixel_decoder/msdeformattn.py): 1 x 1 input projections
  * + GroupNorm(32), a deformable-attention transformer encoder over the chosen levels (post-norm, ReLU, sine position table + level

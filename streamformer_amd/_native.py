@@ -219,6 +219,9 @@ SIGNATURES = {
     "sf_op_msda_backward": (_I, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "sf_op_adapter_dwconv_gelu": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "sf_op_adapter_fuse": (_I, [_I, _P, C.c_longlong, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "sf_op_adapter_dwconv_gelu_backward_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "sf_op_adapter_dwconv_gelu_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
+    "sf_op_adapter_fuse_backward": (_I, [_I, _P, _P, C.c_longlong, _I, _I, _I, _I, _P]),
     "sf_pixdec_create": (_I, [C.POINTER(SfPixdecConfig), _I, C.POINTER(_P)]),
     "sf_pixdec_destroy": (None, [_P]),
     "sf_pixdec_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),

@@ -1,5 +1,5 @@
 """The ViT-Adapter backbone on the MI355X: ``TimesformerMultiTaskingModelSigLIPViTAdapter``, a drop-in for the reference's class of the
-same name (models/modeling_timesformer_siglip_adapter.py), for inference.
+same name (models/modeling_timesformer_siglip_adapter.py), for inference and, as an opt-in, for training under a frozen backbone.
 
 It wraps the native encoder and returns the ``res2 .. res5`` feature pyramid (strides 4, 8, 16, 32) that the dense-prediction consumers
 read (CTVIS / Mask2Former under downstream/OVIS).  Same constructor, parameter and buffer tree, state-dict keys and initialisation as the
@@ -18,8 +18,21 @@ block): ``sf_op_layernorm`` on query and feature, ``MSDeformAttn``'s no-grad pat
 GEMM for ``ConvTranspose2d(D, D, 2, 2)`` and ``sf_op_adapter_fuse`` per level (tokens + bilinear ViT feature [+ c1] + eval BatchNorm,
 written NCHW).  The spatial prior module (the 3 x 3 convolution stem, about 5 % of the FLOPs at SigLIP-base) stays torch.
 
-Inference only: ``eval()`` mode, ``SyncBatchNorm`` as its running-statistics affine, outputs carry no graph; ``forward`` in training mode
-raises.  ``conv_inplane`` and ``deform_ratio`` are accepted and ignored exactly as the reference does (it builds
+Inference by default: ``eval()`` mode, ``SyncBatchNorm`` as its running-statistics affine, outputs carry no graph; ``forward`` in training
+mode raises unless the module was built (or later marked) ``trainable=True``.
+
+Training is an opt-in: ``trainable=True`` (constructor keyword or attribute, fp32 only) makes ``.train()`` run an autograd graph on the
+module's own parameters under a FROZEN backbone, which is how the reference trains this module (``freeze_backbone=True``).  The spatial
+prior module runs in torch with its ``SyncBatchNorm`` layers in training mode (batch statistics, running statistics updated, synchronised
+across ranks by torch when a process group exists), ``sf_embed`` / ``sf_layers`` run without a graph exactly as in ``eval()`` (``feat`` and
+the kept ViT maps are constants, no gradient passes through an encoder layer), every extractor is ``F.layer_norm`` / ``F.linear`` /
+``MSDeformAttn``'s autograd path plus one ``autograd.Function`` for DWConv + GELU (forward: the inference kernel, backward:
+``sf_op_adapter_dwconv_gelu_backward``; saves x, w, b, not y), and the tail is ``F.linear`` on a view of ``up.weight``, one
+``autograd.Function`` per level on ``sf_op_adapter_fuse`` (unit scale, zero shift) and ``sf_op_adapter_fuse_backward``, and ``norm1..4``
+as the torch modules they are.  A parameter of the backbone that requires a gradient, a non-zero dropout or drop-path rate in the config
+and ``with_cp=True`` are refused by name before anything runs.  ``eval()`` of a ``trainable=True`` module is the inference path, bit for bit.
+
+``conv_inplane`` and ``deform_ratio`` are accepted and ignored exactly as the reference does (it builds
 ``SpatialPriorModule(inplanes=64)`` and its live ``MSDeformAttn`` ignores ``ratio``); ``init_values``, ``finetune`` and
 ``finetune_indexes`` are unused there too (the injector they belonged to is commented out).  The reference's adapter has no ``head``: the
 inner native encoder keeps a default-initialised one that is never run and is not part of this module's ``state_dict()``.
@@ -31,7 +44,10 @@ from collections import OrderedDict
 from typing import Any, Dict, List, Sequence, Tuple
 
 import torch
+import torch.nn.functional as F
 from torch import nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _native as nat
 from .configuration import StreamformerConfig
@@ -112,6 +128,68 @@ class InteractionBlock(nn.Module):
         return [self.extractor] + (list(self.extra_extractors) if self.extra_extractors is not None else [])
 
 
+class _DWConvGeluFunction(Function):
+    """ConvFFN's DWConv + GELU on the three-level tokens ``x`` [F, 21 n, C] on the HIP kernels.  Saves ``x``, ``w`` and ``b``, not ``y``: the
+    backward recomputes the convolution."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, Hg, Wg):
+        x, w, b = x.contiguous(), w.contiguous(), b.contiguous()
+        y = torch.empty_like(x)
+        nat.launch(x.device, nat.lib.sf_op_adapter_dwconv_gelu, x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), x.shape[0], Hg, Wg, x.shape[2])
+        ctx.save_for_backward(x, w, b)
+        ctx.grid = (Hg, Wg)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, w, b = ctx.saved_tensors
+        Hg, Wg = ctx.grid
+        Fr, _, Cd = x.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None
+        dy = dy.float().contiguous()
+        dx = torch.empty_like(x) if need_x else None
+        dw = torch.empty_like(w) if need_w else None
+        db = torch.empty_like(b) if need_b else None
+        ws = nat.scratch(nat.lib.sf_op_adapter_dwconv_gelu_backward_workspace_bytes(Fr, Hg, Wg, Cd), x.device)
+        nat.launch(x.device, nat.lib.sf_op_adapter_dwconv_gelu_backward, x.data_ptr(), w.data_ptr(), b.data_ptr(), dy.data_ptr(), nat.ptr(dx), nat.ptr(dw),
+                   nat.ptr(db), Fr, Hg, Wg, Cd, workspace=ws)
+        return dx, dw, db, None, None
+
+
+class _FuseFunction(Function):
+    """One level of the tail without its BatchNorm: ``tokens`` (level 0: the transposed convolution's GEMM output [F, 16 n, 4 D]; levels
+    1..3: the level's slice of ``c``, [F, pixels, D] with any frame stride) + the bilinear resampling of the constant ViT map ``vit`` [+ c1],
+    written NCHW by ``sf_op_adapter_fuse`` with the unit scale ``one`` and the zero shift ``zero``.  The backward is a re-layout of dy
+    (``sf_op_adapter_fuse_backward``), and dy itself for c1."""
+
+    @staticmethod
+    def forward(ctx, tokens, c1, vit, one, zero, level, Hg, Wg):
+        Fr, D = tokens.shape[0], one.shape[0]
+        if tokens.stride(2) != 1 or tokens.stride(1) != tokens.shape[2] or tokens.stride(0) % 4 or tokens.data_ptr() % 16:
+            tokens = tokens.contiguous()
+        c1 = c1.contiguous() if c1 is not None else None
+        out = torch.empty(Fr, D, *Ho_Wo(level, Hg, Wg), dtype=torch.float32, device=tokens.device)
+        nat.launch(tokens.device, nat.lib.sf_op_adapter_fuse, level, tokens.data_ptr(), tokens.stride(0), nat.ptr(vit), nat.ptr(c1), one.data_ptr(),
+                   zero.data_ptr(), out.data_ptr(), Fr, Hg, Wg, D)
+        ctx.meta = (level, Hg, Wg, D, tuple(tokens.shape))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        level, Hg, Wg, D, shape = ctx.meta
+        dy = dy.float().contiguous()
+        d_tok = None
+        if ctx.needs_input_grad[0]:
+            d_tok = torch.empty(shape, dtype=torch.float32, device=dy.device)
+            nat.launch(dy.device, nat.lib.sf_op_adapter_fuse_backward, level, dy.data_ptr(), d_tok.data_ptr(), shape[1] * shape[2], shape[0], Hg, Wg, D)
+        return d_tok, (dy if level == 0 and ctx.needs_input_grad[1] else None), None, None, None, None, None, None
+
+
 def _check_partition(indexes: Sequence[Sequence[int]], layers: int) -> None:
     nxt = 0
     for pair in indexes:
@@ -133,7 +211,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
                  deform_num_heads: int = 12, init_values: float = 1e-6, interaction_indexes=[[0, 2], [3, 5], [6, 8], [9, 11]],
                  with_cffn: bool = True, cffn_ratio: float = 0.25, deform_ratio: float = 0.5, add_vit_feature: bool = True,
                  use_extra_extractor: bool = True, with_cp: bool = False, freeze_backbone: bool = True, finetune: bool = False,
-                 finetune_indexes=[0], compute_dtype: Any = "fp32"):
+                 finetune_indexes=[0], compute_dtype: Any = "fp32", trainable: bool = False):
         super().__init__()
         config = StreamformerConfig() if config is None else config
         D = config.hidden_size
@@ -142,7 +220,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             raise NotImplementedError(f"patch_size={config.patch_size}: the adapter views the stride-16 level as the patch grid (adapter:656), which "
                                       "needs patch_size 16")
         if with_cp:
-            raise NotImplementedError("with_cp=True: activation checkpointing belongs to training; this module is inference only")
+            raise NotImplementedError("with_cp=True: activation checkpointing is not implemented, neither for inference nor for the trainable=True path")
         if D % 64:
             raise ValueError(f"hidden_size={D} must be a multiple of 64 (the GEMM kernels' k-step)")
         if with_cffn and (int(D * cffn_ratio) < 64 or int(D * cffn_ratio) % 64):
@@ -159,6 +237,8 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
                              "(adapter:661)")
         self._compute = nat.compute_mode(compute_dtype)
         self.compute_dtype = compute_dtype
+        self._trainable = False
+        self.trainable = trainable
         self.config = config
         self.add_vit_feature, self.freeze_backbone = bool(add_vit_feature), bool(freeze_backbone)
         self.interaction_indexes = [[int(a), int(b)] for a, b in interaction_indexes]
@@ -185,6 +265,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             if isinstance(m, MSDeformAttn):
                 m._native = self._native
         self._tail, self._tail_token = None, None
+        self._unit = None                    # the training path's (unit scale, zero shift) of sf_op_adapter_fuse
         self._geometry: Dict[tuple, tuple] = {}
         self._marks = None                   # tools/vit_adapter_bench.py: a list that receives (stage, HIP event) pairs during a forward
 
@@ -232,6 +313,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         self._enc._apply(fn)                 # the head the encoder keeps, and its own bookkeeping (packed weights, workspaces)
         self._native.workspaces.clear()
         self._tail_token = None
+        self._unit = None
         self._geometry.clear()
         return out
 
@@ -248,6 +330,32 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         self._enc.training = mode
         return self
 
+    @property
+    def trainable(self) -> bool:
+        """Whether ``.train()`` runs the autograd path (fp32 only, frozen backbone) instead of refusing."""
+        return self._trainable
+
+    @trainable.setter
+    def trainable(self, value: bool) -> None:
+        if value and self._compute != nat.SF_COMPUTE_BF16X3:
+            raise ValueError(f"trainable=True needs compute_dtype='fp32', got compute_dtype={self.compute_dtype!r} (there is no bf16 training mode)")
+        self._trainable = bool(value)
+
+    def _check_trainable(self) -> None:
+        """What ``.train()`` refuses, by name, before anything runs."""
+        if not self._trainable:
+            raise NotImplementedError("the native ViT-Adapter is inference only (SyncBatchNorm as its running statistics, no gradients): call .eval(), "
+                                      "or opt in to the autograd path under a frozen backbone with trainable=True")
+        for part in ("embeddings", "encoder", "post_layernorm"):
+            for k, p in getattr(self, part).named_parameters():
+                if p.requires_grad:
+                    raise NotImplementedError(f"{part}.{k} requires a gradient (freeze_backbone={self.freeze_backbone}): the trainable=True path trains the "
+                                              "adapter under a frozen backbone, no gradient passes through an encoder layer")
+        for field in ("hidden_dropout_prob", "attention_probs_dropout_prob", "drop_path_rate"):
+            if float(getattr(self.config, field, 0.0) or 0.0) != 0.0:
+                raise NotImplementedError(f"config.{field}={getattr(self.config, field)}: the frozen encoder runs its inference kernels, which have no "
+                                          "dropout or drop path; set it to 0")
+
     def get_input_embeddings(self):
         return self.embeddings.patch_embeddings
 
@@ -256,7 +364,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
         return self.level_embed.device
 
     def __getstate__(self):
-        return dict(self.__dict__, _tail=None, _tail_token=None, _geometry={}, _marks=None)
+        return dict(self.__dict__, _tail=None, _tail_token=None, _unit=None, _geometry={}, _marks=None)
 
     def _mark(self, stage: str) -> None:
         if self._marks is not None:
@@ -330,6 +438,62 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             hit = self._geometry[key] = (ref, _Levels([(Hg, Wg)]))
         return hit
 
+    # ------------------------------------------------------------------------ the training path
+    def _extract_train(self, ex: Extractor, c: torch.Tensor, feat: torch.Tensor, ref: torch.Tensor, lv: _Levels, Hg: int, Wg: int) -> torch.Tensor:
+        """``_extract`` as a graph of torch operators on the extractor's parameters; ``feat`` is a constant."""
+        c = c + ex.attn._forward_autograd(ex.query_norm(c), ref, ex.feat_norm(feat), lv, None)
+        if not ex.with_cffn:
+            return c
+        ffn = ex.ffn
+        u = ffn.fc1(ex.ffn_norm(c))
+        v = _DWConvGeluFunction.apply(u, ffn.dwconv.dwconv.weight, ffn.dwconv.dwconv.bias, Hg, Wg)
+        return c + ffn.fc2(v)
+
+    def _forward_train(self, pixel_values: torch.Tensor) -> Tuple["OrderedDict[str, torch.Tensor]", torch.Tensor]:
+        dev, enc, D = self.device, self._enc, self.config.hidden_size
+        B, T, _, H, W = pixel_values.shape
+        Fr, Hg, Wg = B * T, H // 16, W // 16
+        n = (Hg // 2) * (Wg // 2)
+        x = pixel_values.detach().to(dev, torch.float32).contiguous()
+        self._mark("start")
+        cd = torch.backends.cudnn              # the deterministic convolution algorithms, as in eval()
+        with cd.flags(enabled=cd.enabled, benchmark=cd.benchmark, deterministic=True, allow_tf32=cd.allow_tf32):
+            c1, c2, c3, c4 = self.spm(x.view(Fr, 3, H, W))
+        le = self.level_embed
+        c = torch.cat([t.flatten(2).transpose(1, 2) + le[i] for i, t in enumerate((c2, c3, c4))], 1)
+        self._mark("spm")
+        ref, lv = self._geometry_for(Fr, Hg, Wg, dev)
+        kept: List[torch.Tensor] = []
+        last = len(self.interactions) - 1
+        with torch.no_grad():
+            ws = enc._stage_ws(B, T, H, W)
+            handle = enc._handle
+            h = torch.empty(B, T, Hg * Wg, D, dtype=torch.float32, device=dev)
+            nat.launch(dev, nat.lib.sf_embed, handle, x.data_ptr(), nat.SF_F32, B, T, H, W, h.data_ptr(), nat.ptr(enc._pos_table(H, W)), workspace=ws)
+        self._mark("embed")
+        for i, (block, (la, lb)) in enumerate(zip(self.interactions, self.interaction_indexes)):
+            with torch.no_grad():
+                nat.launch(dev, nat.lib.sf_layers, handle, h.data_ptr(), B, T, H, W, la, lb + 1, None, workspace=ws)
+                # the graph keeps this block's stream (LayerNorm's input), and sf_layers goes on in place: every block but the last gets a copy
+                feat = h.view(Fr, Hg * Wg, D) if i == last else h.view(Fr, Hg * Wg, D).clone()
+            self._mark("layers")
+            for ex in block.extractors():
+                c = self._extract_train(ex, c, feat, ref, lv, Hg, Wg)
+            kept.append(feat)
+            self._mark("extractors")
+        if self._unit is None or self._unit[0].device != dev or self._unit[0].shape[0] != D:
+            self._unit = (torch.ones(D, dtype=torch.float32, device=dev), torch.zeros(D, dtype=torch.float32, device=dev))
+        one, zero = self._unit
+        up_w = self.up.weight.permute(2, 3, 1, 0).reshape(4 * D, D)
+        up = F.linear(c[:, :16 * n], up_w, self.up.bias.repeat(4))                # [F, 16 n, 4 D]: columns (dy, dx, c_out)
+        toks = (up, c[:, :16 * n], c[:, 16 * n:20 * n], c[:, 20 * n:])
+        outs = OrderedDict()
+        for level, (name, norm) in enumerate(zip(_OUTPUTS, (self.norm1, self.norm2, self.norm3, self.norm4))):
+            pre = _FuseFunction.apply(toks[level], c1 if level == 0 else None, kept[level] if self.add_vit_feature else None, one, zero, level, Hg, Wg)
+            outs[name] = norm(pre)
+        self._mark("tail")
+        return outs, c
+
     # ------------------------------------------------------------------------------------ forward
     def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, return_dict=None) -> "OrderedDict[str, torch.Tensor]":
         """pixel_values [B, T, 3, H, W] (H, W multiples of 32) -> {"res2", "res3", "res4", "res5"}: fp32 NCHW [B * T, D, H / s, W / s] at
@@ -339,7 +503,7 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
     def forward_with_tokens(self, pixel_values: torch.Tensor) -> Tuple["OrderedDict[str, torch.Tensor]", torch.Tensor]:
         """``forward`` and the extractors' final tokens ``c`` [B * T, 21 n, D] (the three levels at strides 8, 16, 32, before the tail)."""
         if self.training:
-            raise NotImplementedError("the native ViT-Adapter is inference only (SyncBatchNorm as its running statistics, no gradients): call .eval()")
+            self._check_trainable()
         if pixel_values.dim() != 5 or pixel_values.shape[2] != self.config.num_channels:
             raise ValueError(f"pixel_values must be (B, T, {self.config.num_channels}, H, W), got {tuple(pixel_values.shape)}")
         B, T, _, H, W = pixel_values.shape
@@ -350,6 +514,9 @@ class TimesformerMultiTaskingModelSigLIPViTAdapter(nn.Module):
             raise RuntimeError("the ViT-Adapter runs on the MI355X: move the module and its input with .to('cuda') (there is no CPU fallback)")
         if self.level_embed.dtype != torch.float32:
             raise TypeError(f"the ViT-Adapter keeps fp32 parameters (compute_dtype picks the GEMM precision), got {self.level_embed.dtype}")
+        if self.training:
+            with torch.cuda.device(dev):
+                return self._forward_train(pixel_values)
         enc, D = self._enc, self.config.hidden_size
         Fr, Hg, Wg = B * T, H // 16, W // 16
         n = (Hg // 2) * (Wg // 2)

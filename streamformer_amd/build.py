@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstreamformer_hip.so")
 SOURCES = ["sf_gemm.hip", "sf_gemm256.hip", "sf_gemm_panel.hip", "sf_gemm_skinny.hip", "sf_gemm_tile.hip", "sf_switches.hip", "sf_rowwise.hip", "sf_attention_spatial.hip", "sf_attention_temporal.hip", "sf_attention_decode.hip", "sf_attention_generic.hip", "sf_pool_head.hip", "sf_loss.hip", "sf_mask_loss.hip", "sf_text_heads.hip", "sf_text.hip", "sf_connector.hip", "sf_oad.hip", "sf_cache_park.hip", "sf_encoder.hip", "sf_stream.hip", "sf_ops.hip", "sf_bench.hip",
-           "sf_train_kernels.hip", "sf_wgrad.hip", "sf_attention_bwd.hip", "sf_attention_generic_bwd.hip", "sf_pool_generic_bwd.hip", "sf_train.hip", "sf_dense_head.hip", "sf_msda.hip", "sf_adapter.hip", "sf_pixdec.hip", "sf_pixdec_bwd.hip", "sf_maskdec.hip", "sf_maskattn.hip", "sf_masklogits.hip", "sf_vis.hip", "sf_seg.hip", "sf_criterion.hip", "sf_cl_plugin.hip"]
+           "sf_train_kernels.hip", "sf_wgrad.hip", "sf_attention_bwd.hip", "sf_attention_generic_bwd.hip", "sf_pool_generic_bwd.hip", "sf_train.hip", "sf_dense_head.hip", "sf_msda.hip", "sf_adapter.hip", "sf_adapter_bwd.hip", "sf_pixdec.hip", "sf_pixdec_bwd.hip", "sf_maskdec.hip", "sf_maskattn.hip", "sf_masklogits.hip", "sf_vis.hip", "sf_seg.hip", "sf_criterion.hip", "sf_cl_plugin.hip"]
 # lab library only (build.py --lab): round-4 kernels that were built to parity and did not beat the product path on the wall clock —
 # the two epilogue-overlap variants of the panel kernel, the qkv projection with the temporal attention as its epilogue (clip form, round 4;
 # streamed-frame form, round 6).

@@ -1,5 +1,5 @@
 // The transpose tile between channel-contiguous rows [F, HW, C] and pixel-contiguous NCHW [F, C, HW], shared by sf_pixdec.hip's two
-// move kernels and sf_adapter.hip's fuse kernel: 64 pixels x 64 channels of fp32 in LDS, rows padded to 65 floats so that a column read
+// move kernels, sf_adapter.hip's fuse kernel and its adjoint in sf_adapter_bwd.hip: 64 pixels x 64 channels of fp32 in LDS, rows padded to 65 floats so that a column read
 // touches 64 different banks, 256 threads.  The rows side moves 16 lanes x float4 along the channels of a pixel (256 B), the NCHW side
 // 64 lanes along the pixels of a channel row (256 B).  A kernel declares `__shared__ float tile[SF_TILE_CELLS]`, takes its tile from
 // blockIdx (x: pixels, y: channels, z: frame; sf_tile_grid) and puts __syncthreads() between the two sides.  Also here: the bilinear
@@ -22,6 +22,18 @@ SF_DEVICE void sf_tile_gather_rows(float* tile, int p0, int c0, int HW, int C, L
     const f32x4_t v = load(p0 + pp, c0 + lane_c);
     float* row = tile + pp * SF_TILE_LD + lane_c;
     row[0] = v[0]; row[1] = v[1]; row[2] = v[2]; row[3] = v[3];
+  }
+}
+
+// tile -> rows.  store(pix, c, v): the four values of channels c .. c + 3 of pixel pix (both inside HW x C, C % 4 == 0)
+template <typename Store>
+SF_DEVICE void sf_tile_scatter_rows(const float* tile, int p0, int c0, int HW, int C, Store store) {
+  const int lane_c = ((int)threadIdx.x % 16) * 4, lane_p = (int)threadIdx.x / 16;
+  if (c0 + lane_c >= C) return;
+  for (int pp = lane_p; pp < SF_TILE; pp += SF_TILE_THREADS / 16) {
+    if (p0 + pp >= HW) break;
+    const float* row = tile + pp * SF_TILE_LD + lane_c;
+    store(p0 + pp, c0 + lane_c, (f32x4_t){row[0], row[1], row[2], row[3]});
   }
 }
 
