@@ -55,6 +55,36 @@ __device__ unsigned long long panel_trace[16];
 #define PT_OFF(bit) 0
 #endif
 
+// Plane-form residual row, one lane's eight columns:  x = bf(h) + bf(l) + alpha v  ->  hi = bf16(x), lo = bf16(x - hi), and the lane's share of
+// the row's {sum x, sum x^2}.  h / l: the 16 bytes of the residual planes, v0 / v1: the two staged fp32 chunks.
+// Every rounding is written out (fp contraction off, explicit fma).  Until here the source said `x = h + l + alpha * v` once and left the
+// contraction to the compiler, which kept two values of x per element: the planes took h + l + round(alpha v), the statistics partly
+// fma(alpha, v, h + l) (the same choice in every unrolled copy; read from the ISA).  With alpha = tanh(gate) != 1 in the temporal branch the
+// two differ in the last bit, so the forward's bits depended on a vectoriser decision.  The choices below are the ones the forward has
+// always computed with; written on register pairs they take 78 VALU instructions per row where the compiler's took 117, and the
+// forward is byte-equal and 0.16 ms faster (profiles/panel_epilogue_ab.txt).
+SF_DEVICE void plane_row8(u32x4_t h, u32x4_t l, f32x4_t v0, f32x4_t v1, float alpha, u32x4_t& ho, u32x4_t& lo, float& s1, float& s2) {
+#pragma clang fp contract(off)
+  typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+  auto unpk = [](unsigned int w) { return (f32x2_t){__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)}; };
+  const f32x2_t a2 = {alpha, alpha};
+  const f32x2_t v[4] = {{v0[0], v0[1]}, {v0[2], v0[3]}, {v1[0], v1[1]}, {v1[2], v1[3]}};
+  f32x2_t hl[4], x[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    hl[w] = unpk(h[w]) + unpk(l[w]);
+    x[w] = hl[w] + a2 * v[w];                        // the value the planes are split from
+    ho[w] = pack_bf2(x[w][0], x[w][1]);
+    const f32x2_t d = x[w] - unpk(ho[w]);
+    lo[w] = pack_bf2(d[0], d[1]);
+  }
+  const f32x2_t f0 = __builtin_elementwise_fma(a2, v[0], hl[0]), f1 = __builtin_elementwise_fma(a2, v[1], hl[1]),
+                f2 = __builtin_elementwise_fma(a2, v[2], hl[2]);
+  s1 = ((x[2][0] + x[2][1]) + (x[3][0] + x[3][1])) + (((f0[0] + f0[1]) + (f1[0] + f1[1])) + 0.f);
+  const f32x2_t q0 = x[0] * x[0], q1 = x[1] * x[1], q2 = f2 * f2;
+  s2 = ((q0[0] + q0[1]) + (q1[0] + q1[1])) + ((q2[0] + q2[1]) + __builtin_fmaf(x[3][1], x[3][1], x[3][0] * x[3][0]));
+}
+
 template <int P_MT>
 __global__ __launch_bounds__(P_THREADS) void sf_gemm_panel_kernel(SfGemmArgs p, int rows_per_tile, int ntiles, int stagger_ticks, int pad_clamp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -255,21 +285,13 @@ __global__ __launch_bounds__(P_THREADS) void sf_gemm_panel_kernel(SfGemmArgs p, 
           if (elane < 48) {
             const u32x4_t h = __builtin_bit_cast(u32x4_t, res[j][0]), l = __builtin_bit_cast(u32x4_t, res[j][1]);
             u32x4_t ho, lo;
+            f32x4_t v[2];
 #pragma unroll
             for (int hf = 0; hf < 2; ++hf) {
               const int c = 2 * elane + hf;
-              const f32x4_t v = *reinterpret_cast<const f32x4_t*>(smem + r * 1536 + (((c & ~31) | ((c ^ r) & 31)) << 4));
-              f32x4_t x;
-              x[0] = bf2f(h[2 * hf] & 0xffffu) + bf2f(l[2 * hf] & 0xffffu) + p.alpha * v[0];
-              x[1] = bf2f(h[2 * hf] >> 16) + bf2f(l[2 * hf] >> 16) + p.alpha * v[1];
-              x[2] = bf2f(h[2 * hf + 1] & 0xffffu) + bf2f(l[2 * hf + 1] & 0xffffu) + p.alpha * v[2];
-              x[3] = bf2f(h[2 * hf + 1] >> 16) + bf2f(l[2 * hf + 1] >> 16) + p.alpha * v[3];
-              ho[2 * hf] = pack_bf2(x[0], x[1]); ho[2 * hf + 1] = pack_bf2(x[2], x[3]);
-              lo[2 * hf] = pack_bf2(x[0] - bf2f(ho[2 * hf] & 0xffffu), x[1] - bf2f(ho[2 * hf] >> 16));
-              lo[2 * hf + 1] = pack_bf2(x[2] - bf2f(ho[2 * hf + 1] & 0xffffu), x[3] - bf2f(ho[2 * hf + 1] >> 16));
-              s1 += (x[0] + x[1]) + (x[2] + x[3]);
-              s2 += (x[0] * x[0] + x[1] * x[1]) + (x[2] * x[2] + x[3] * x[3]);
+              v[hf] = *reinterpret_cast<const f32x4_t*>(smem + r * 1536 + (((c & ~31) | ((c ^ r) & 31)) << 4));
             }
+            plane_row8(h, l, v[0], v[1], p.alpha, ho, lo, s1, s2);
             const size_t o = (size_t)m * (size_t)p.ldc + n0 + elane * 8;
             if (!PT_OFF(4) || s1 == 12345.678f) {
               *reinterpret_cast<u32x4_t*>(p.out_hi + o) = ho;
